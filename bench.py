@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: validated RRT edges/sec on the Franka 7-DoF 16-obstacle scene.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (the edge kernel: endpoint + interior waypoints of
@@ -45,6 +45,8 @@ CLOCK_WARM_STEPS = 300       # untimed launches before anything is measured (~60
 SHORT_REGION_STEPS = 64      # a timed region shorter than this carries no HIP events (they come from untimed launches)
 IN_TURNS_MIN_STEPS = 600     # the three-engine `in_turns` figure is only taken in runs at least this long
 FP64_VECTOR_PEAK = 78.6e12   # MI355X_MICROARCH.md: FP64 vector 78.6 TFLOP/s
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all, over every rank's files
+DEFAULT_STEPS = {"rrt": 5, "plan": 15}  # --steps when it is not given (every other workload: 2000)
 
 
 class World:
@@ -227,6 +229,26 @@ def make_edges(model, qidx, n, seed):
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     qb = np.clip(qa + EPS * d, lo, hi)
     return qa, qb
+
+
+def dump_outputs(path, arrays, world):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array (float64 stays
+    float64, everything else is written as float32); ranks other than 0 write DIR/<name>_rank<r>.npy.  The inputs are
+    seeded, so two runs with the same arguments compare output for output.  Above DUMP_BYTES in all, every array keeps
+    the same fraction of its rows: a sample drawn by default_rng(0), in row order, identical from run to run."""
+    if not path:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    budget = DUMP_BYTES // world.world - 4096 * len(arrays)  # (less the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    suffix = "" if world.rank == 0 else f"_rank{world.rank}"
+    for name, a in arrays.items():
+        if total > budget and a.ndim > 0 and len(a) > 0:
+            keep = max(1, int(len(a) * (budget / total)))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def host_cpu():
@@ -426,6 +448,7 @@ def bench_configs(args, world):
     elapsed = time.perf_counter() - t0
     value, slowest = aggregate(world, N, args.steps, elapsed)
     valid = dv.download(np.uint8, N)
+    dump_outputs(args.dump_outputs, {"valid": valid}, world)
     if world.rank == 0:
         out = {"metric": "validated configurations/sec, Franka-P self-collision (BASELINE configs[1])",
                "value": value, "unit": "configs/s", "n_gpus": world.world, "steps": args.steps,
@@ -500,8 +523,10 @@ def bench_next_rows(args, world):
         elapsed = time.perf_counter() - t0
         value, slowest = aggregate(world, n, args.steps, elapsed)
         out = None
-        if world.rank == 0:
+        if world.rank == 0 or args.dump_outputs:
             out_q, ok, iters = dout.download(np.float64, n * model.nq).reshape(n, -1), dok.download(np.uint8, n), dit.download(np.int32, n)
+            dump_outputs(args.dump_outputs, {"q": out_q, "ok": ok, "iterations": iters}, world)
+        if world.rank == 0:
             inv = frame.inverse()
             po = pyoracle.PoseOracle(model, "ee_site", (inv.wxyz_xyz[:4], inv.wxyz_xyz[4:]),
                                      [(-np.inf, np.inf)] * 3 + [(-0.1, 0.1)] * 2 + [(-np.inf, np.inf)], q_step=0.5)
@@ -548,6 +573,7 @@ def bench_next_rows(args, world):
         world.barrier()
         elapsed = time.perf_counter() - t0
         value, slowest = aggregate(world, len(Q0), args.steps, elapsed)
+        dump_outputs(args.dump_outputs, {"q": Qs, "ok": ok, "iterations": its, "collision_free": free}, world)
         out = None
         if world.rank == 0:
             orc = pyoracle.Oracle(model)
@@ -607,7 +633,7 @@ def bench_rrt(args, world):
     from mjpl_amd import scenes
     from oracle import pyoracle
     L = args.lanes
-    rounds = args.steps if args.steps != 2000 else 5
+    rounds = args.steps
     m = scenes.franka_p(obstacles=True)
     joints = scenes.FRANKA_ARM_JOINTS
     qidx = scenes.planning_index(m, joints)
@@ -772,7 +798,7 @@ def bench_plan(args, world):
     import benchmark as harness
     from mjpl_amd import scenes
     from mjpl_amd.constraint import Constraint
-    attempts = 15 if args.steps == 2000 else args.steps
+    attempts = args.steps
     model = scenes.franka_p(obstacles=True)
     orc = pyoracle.Oracle(model)
 
@@ -833,8 +859,9 @@ def time_variant(eng, engine, dqa, dqb, E, layout, dvalid, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000,
-                    help="timed steps; the default keeps the timed region near one second")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (>= 1); by default 2000, which keeps the edges' timed region near one second "
+                         "(rrt: 5 rounds, plan: 15 attempts)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--edges", type=int, default=EDGES_PER_GPU)
     ap.add_argument("--layout", choices=["soa", "aos"], default="soa")
@@ -858,7 +885,18 @@ def main():
                          "rrt = configs[3] as the planner runs it: rounds of the device-resident frontier bi-RRT, "
                          "131 072 samples per rank each, [PoseConstraint, JointLimit, Collision], new nodes exchanged "
                          "over RCCL (--steps = timed rounds, default 5); plan = examples/benchmark.py's 15 attempts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all): edges and configs the verdicts (valid), pose and ik the "
+                         "rows (q) with their ok / iterations (ik also collision_free of the converged rows).  Not for rrt or "
+                         "plan, whose timed steps grow trees")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = DEFAULT_STEPS.get(args.workload, 2000)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload in ("rrt", "plan"):
+        ap.error(f"--dump-outputs: the {args.workload} workload has no fixed output per step")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args.gpus)  # (this process never touches a GPU)
@@ -986,6 +1024,7 @@ def main():
     for k in range(1, S):
         if share[k] > 0 and not np.array_equal(outs[k].download(np.uint8, E), valid):
             sys.exit(f"bench.py: engine {k} of {S} returned other verdicts than engine 0 for the same batch")
+    dump_outputs(args.dump_outputs, {"valid": valid}, world)  # (one verdict per edge of make_edges(seed=2 + rank))
     one_stream = None
     if S > 1:  # ... and the same K steps on ONE stream (not the measurement: the figure of rounds 1-3, and the kernels alone)
         eng.sync()

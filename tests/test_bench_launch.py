@@ -72,6 +72,59 @@ def test_planner_workload_through_a_one_rank_communicator():
     assert d["n_gpus"] == 1 and d["config"]["rccl_ranks"] == 1 and d["config"]["nodes"][0] > 1
 
 
+def test_dump_outputs_types_names_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays float64, everything else is float32; ranks beyond 0 carry a suffix; above the byte
+    budget every array keeps the same seeded rows from run to run, and the files stay within it."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class W:
+        rank, world = 0, 1
+    valid = (np.arange(1000) % 3 == 0).astype(np.uint8)
+    q = np.arange(3000, dtype=np.float64).reshape(1000, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"valid": valid, "q": q}, W)
+    a_valid, a_q = np.load(tmp_path / "a" / "valid.npy"), np.load(tmp_path / "a" / "q.npy")
+    assert a_valid.dtype == np.float32 and np.array_equal(a_valid, valid)
+    assert a_q.dtype == np.float64 and np.array_equal(a_q, q)
+    W.rank, W.world = 1, 2
+    bench.dump_outputs(str(tmp_path / "a"), {"valid": valid}, W)
+    assert np.array_equal(np.load(tmp_path / "a" / "valid_rank1.npy"), valid)
+    W.rank, W.world = 0, 1
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16384)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"valid": valid, "q": q}, W)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 16384
+    b_q, c_q = np.load(tmp_path / "b" / "q.npy"), np.load(tmp_path / "c" / "q.npy")
+    assert 0 < len(b_q) < len(q) and np.array_equal(b_q, c_q)
+    assert np.all(np.diff(b_q[:, 0]) > 0) and np.all(b_q[:, 0] % 3 == 0)  # whole rows, in row order
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_verdicts_of_the_timed_steps(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`: the line says K steps and its ms_per_step, and DIR/valid.npy holds the verdict
+    of every edge of the seeded batch -- the oracle's on a sample of them."""
+    import numpy as np
+    E = 8192
+    res = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--edges", str(E), "--no-cpu-baseline",
+                          "--no-variants", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stderr[-3000:]
+    d = _json_line(res.stdout)
+    assert d["steps"] == 7 and d["ms_per_step"] > 0
+    got = np.load(tmp_path / "valid.npy")
+    assert got.dtype == np.float32 and got.shape == (E,) and abs(float(got.astype(np.float64).mean()) - d["config"]["valid_fraction"]) < 1e-12
+    sys.path.insert(0, ROOT)
+    import bench
+    from mjpl_amd import scenes
+    from oracle import pyoracle
+    m = scenes.franka_p(obstacles=True)
+    qidx = scenes.planning_index(m, scenes.FRANKA_ARM_JOINTS)
+    qa, qb = bench.make_edges(m, qidx, E, seed=2)
+    want = pyoracle.Oracle(m, planning_qidx=qidx, qpos_base=m.keyframe("home").qpos.copy()).valid_edges(
+        qa[:1024], qb[:1024], bench.STEP, nthreads=4)
+    assert np.array_equal(got[:1024], want.astype(np.float32))
+
+
 def test_a_failing_rank_ends_the_launch():
     """Without a GPU every rank fails when it creates its engine ("no CPU fallback"); the launcher must pass that on
     at once instead of leaving ranks at the rendezvous (here: no GPU in the container; on the GPU box: skipped)."""
