@@ -202,6 +202,32 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
 int mjpl_fk(mjpl_engine *e, const double *Q, int64_t N, int32_t layout,
             double *xpos, double *xquat, double *geom_xpos, double *geom_xmat);
 
+/* ---- contacts: which geom pairs touch (data.contact.geom after mj_kinematics + mj_collision,
+ * collision_constraint.py:26-30) -------------------------------------------------------------
+ * Candidate pairs of mj_collision: every geom pair that passes contype/conaffinity, the weld-body
+ * and parent-child filters, and has a collision function (all but plane-plane, plane-hfield).
+ * Pairs the CollisionRuleset allows are INCLUDED, with allowed[p] = 1.  Order = the oracle's
+ * enumeration order: g1 < g2 ascending, g2 ascending.  Each row is written smaller-geom-type first,
+ * as orc_collision writes it.  The table is built at mjpl_create from the model alone;
+ * mjpl_set_planning leaves it as it is.  mjpl_contact_pair_count returns P (>= 0) or < 0;
+ * mjpl_contact_pairs fails with MJPL_E_ARG if cap < P or an output is NULL while P > 0. */
+int32_t mjpl_contact_pair_count(mjpl_engine *e);
+int mjpl_contact_pairs(mjpl_engine *e, int32_t *geom1, int32_t *geom2, uint8_t *allowed, int32_t cap);
+
+/* bits[i * W + w] (W = (P + 63) / 64): bit (p % 64) of word p / 64 is set iff candidate pair p is
+ * in contact at configuration i.  Exact float64 verdict with margin = max of the two margins: the
+ * bound cull and narrowphase routine the collision check runs for that pair, so that
+ * valid[i] of mjpl_check_configs == no set bit outside the allowed pairs.  Q as mjpl_check_configs
+ * reads it: same layouts, same planning-joint selection.  P = 0: nothing is launched, MJPL_OK.
+ * Non-finite entries of Q are not rejected, as in mjpl_check_configs: every pair is decided by the
+ * same comparisons on the NaN / inf poses they produce (a comparison with NaN counts as contact
+ * where the routine tests "not farther than", so such a configuration reports contacts and the
+ * check calls it invalid).  MJPL_E_PAIRTYPE if a candidate pair has a geom type without a routine
+ * here (only possible for allowed pairs: mjpl_create refuses the others).  The host-buffer form
+ * synchronises; the device form is asynchronous on the engine's stream. */
+int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, uint64_t *bits);
+int mjpl_contacts_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, uint64_t *dbits);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

@@ -17,6 +17,27 @@ from .. import engine as _engine
 from .constraint_interface import Constraint
 
 
+def contact_hits(bits: np.ndarray, npairs: int) -> np.ndarray:
+    """Contact words [N, W] (uint64; bit p % 64 of word p // 64 = candidate pair p touches) -> bool [N, npairs]."""
+    bits = np.ascontiguousarray(bits, dtype="<u8")
+    if bits.ndim != 2 or bits.shape[1] != (npairs + 63) // 64:
+        raise ValueError(f"contact words must be [N, {(npairs + 63) // 64}] for {npairs} candidate pairs, got {bits.shape}")
+    flat = np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little") if bits.size else \
+        np.zeros((bits.shape[0], 64 * bits.shape[1]), np.uint8)
+    return flat[:, :npairs].astype(bool)
+
+
+def contact_csr(bits: np.ndarray, pairs: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Contact words [N, W] and the candidate table pairs [P, 2] -> (offsets int64 [N + 1], rows int32 [M, 2]):
+    configuration i's contacts are rows[offsets[i]:offsets[i + 1]], in candidate-table order."""
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    hit = contact_hits(bits, len(pairs))
+    offsets = np.zeros(hit.shape[0] + 1, np.int64)
+    np.cumsum(hit.sum(axis=1), out=offsets[1:])
+    _, p = np.nonzero(hit)  # row-major: configuration by configuration, pairs in table order
+    return offsets, pairs[p]
+
+
 class CollisionRuleset:
     """Which body pairs may touch (reference collision_constraint.py:36-95).
 
@@ -102,6 +123,44 @@ class CollisionConstraint(Constraint):
         """Full-nq configurations [N, nq] -> bool [N]."""
         self._ensure_full()
         return self.engine.check_configs(np.asarray(Q, dtype=np.float64), _engine.AOS).astype(bool)
+
+    # ---- contacts (``data.contact.geom``) ---------------------------------------------
+    # Invariant: CollisionRuleset(model, allowed).obeys_ruleset(c.contacts(q)) == c.valid_config(q) for every q --
+    # a pair's contact bit is the per-pair decision the collision check makes.
+    def contacts(self, q: np.ndarray) -> np.ndarray:
+        """The rows ``data.contact.geom`` holds after mj_kinematics + mj_collision at the full-nq ``q``:
+        int32 [ncon, 2], one row per touching geom pair (allowed pairs included, as in MuJoCo's list),
+        smaller geom type first, in the oracle's order.  Invariant:
+        ``CollisionRuleset(model, allowed).obeys_ruleset(c.contacts(q)) == c.valid_config(q)``."""
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape != (self.model.nq,):
+            raise ValueError(f"q must have shape ({self.model.nq},)")
+        return self.contacts_batch(q[None, :])[1]
+
+    def contacts_batch(self, Q: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """``contacts`` for every row of full-nq configurations [N, nq], one launch -> CSR (offsets int64 [N + 1],
+        pairs int32 [M, 2]): row i's contacts are pairs[offsets[i]:offsets[i + 1]].  The same invariant holds row by
+        row against ``valid_configs``."""
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[1] != self.model.nq:
+            raise ValueError(f"Q must have shape (N, {self.model.nq})")
+        self._ensure_full()
+        bits = self.engine.contacts(Q, _engine.AOS)
+        return contact_csr(bits, self.engine.contact_pairs()[0])
+
+    def colliding_bodies(self, q: np.ndarray, include_allowed: bool = False) -> list[tuple[str, str]]:
+        """Which bodies touch at ``q``: sorted, distinct body-name pairs (each pair sorted by name).  Pairs of
+        ``allowed_collision_bodies`` are left out unless ``include_allowed``: what remains is why ``valid_config(q)``
+        is False (empty iff it is True)."""
+        rows = self.contacts(q)
+        bid = np.asarray(self.model.geom_bodyid)
+        out = set()
+        for g1, g2 in rows:
+            b1, b2 = sorted((int(bid[g1]), int(bid[g2])))
+            if not include_allowed and (b1, b2) in self.cr._allowed_set:
+                continue
+            out.add(tuple(sorted((self.model.body(b1).name, self.model.body(b2).name))))
+        return sorted(out)
 
     def valid_interval(self, start: np.ndarray, end: np.ndarray, step_dist: float) -> bool:
         """``_valid_collision_interval(start, end, step_dist, self)`` in one launch

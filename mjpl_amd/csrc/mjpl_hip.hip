@@ -31,6 +31,7 @@
 #include "mjpl_project.h"
 #include "mjpl_nearest.h"
 #include "mjpl_nearest_cells.h"
+#include "mjpl_contacts.h"
 
 namespace {
 
@@ -398,6 +399,16 @@ struct mjpl_engine {
   // (one H2D and one D2H per call instead of five copies from / to pageable memory)
   void *h_pin = nullptr;
   size_t h_pin_bytes = 0;
+  // candidate pairs of mj_collision for mjpl_contacts* (build_contact_table): made once at create from the model
+  // alone, so mjpl_set_planning leaves them be.  Rows as the caller sees them (smaller geom type first) and the
+  // kernel's records (mjpl_contacts.h: CI_* / CD_*)
+  std::vector<int32_t> ct_g1, ct_g2;
+  std::vector<uint8_t> ct_allowed;
+  int ct_unsupported = -1;  // index of a candidate pair no narrowphase routine here decides (-1: none)
+  int *d_ct_ip = nullptr;
+  double *d_ct_dp = nullptr;
+  double *d_ct_scratch = nullptr;  // FK scratch rows of one launch (grow-only)
+  size_t ct_scratch_bytes = 0;
 };
 
 namespace {
@@ -1200,6 +1211,88 @@ int compile_program(mjpl_engine *e) {
   return MJPL_OK;
 }
 
+// The candidate pairs of mj_collision (oracle/mjpl_oracle.c: orc_collision's enumeration): every pair g1 < g2 that
+// passes the contype/conaffinity, same-weld-body and weld parent-child filters and has a collision function (all but
+// plane-plane and plane-hfield), allowed body pairs INCLUDED.  The kernel's record of each pair restates what
+// run_config tests for it: cur = the moving geom it places later, its partner, pfirst, margin and cull bound
+// (compile_program: pair_bound).  Depends on the model only: called once, at mjpl_create.
+int build_contact_table(mjpl_engine *e) {
+  const HostModel &m = e->m;
+  const int ng = m.ngeom;
+  constexpr int kGeomHfield = 1;
+  std::vector<int> world_row(ng, -1);
+  for (int g = 0, w = 0; g < ng; g++)
+    if (e->geom_static[g]) world_row[g] = w++;
+  // processing order of the moving geoms: bodies in id order, a body's geoms in id order
+  auto later = [&](int a, int b) {
+    const int ba = m.geom_bodyid[a], bb = m.geom_bodyid[b];
+    return ba != bb ? ba > bb : a > b;
+  };
+  std::vector<int> ip;
+  std::vector<double> dp;
+  e->ct_g1.clear(); e->ct_g2.clear(); e->ct_allowed.clear();
+  e->ct_unsupported = -1;
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int g1 = 0; g1 < ng; g1++)
+    for (int g2 = g1 + 1; g2 < ng; g2++) {
+      const int ct1 = m.geom_contype[g1], ca1 = m.geom_conaffinity[g1];
+      const int ct2 = m.geom_contype[g2], ca2 = m.geom_conaffinity[g2];
+      if (!(ct1 & ca2) && !(ct2 & ca1)) continue;
+      const int b1 = m.geom_bodyid[g1], b2 = m.geom_bodyid[g2];
+      const int w1 = m.body_weldid[b1], w2 = m.body_weldid[b2];
+      if (w1 == w2) continue;
+      const int wp1 = m.body_weldid[m.body_parentid[w1]], wp2 = m.body_weldid[m.body_parentid[w2]];
+      if (w1 != 0 && w2 != 0 && (w1 == wp2 || w2 == wp1)) continue;
+      const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
+      const int tlo = std::min(t1, t2), thi = std::max(t1, t2);
+      if (tlo == GT_PLANE && (thi == GT_PLANE || thi == kGeomHfield)) continue;  // no collision function
+      const int p = (int)e->ct_g1.size();
+      e->ct_g1.push_back(t1 > t2 ? g2 : g1);
+      e->ct_g2.push_back(t1 > t2 ? g1 : g2);
+      e->ct_allowed.push_back(e->allowed.count({std::min(b1, b2), std::max(b1, b2)}) ? 1 : 0);
+      // (one geom is moving: both static means both welded to the world, filtered above)
+      const bool s1 = e->geom_static[g1], s2 = e->geom_static[g2];
+      int cur, par;
+      if (s1 || s2) { cur = s1 ? g2 : g1; par = s1 ? g1 : g2; }
+      else { cur = later(g1, g2) ? g1 : g2; par = cur == g1 ? g2 : g1; }
+      const int tcur = m.geom_type[cur], tpar = m.geom_type[par];
+      if (!type_supported(tcur) || !type_supported(tpar) || tcur == GT_PLANE) {
+        if (e->ct_unsupported < 0) e->ct_unsupported = p;
+      }
+      const bool pstatic = e->geom_static[par] != 0;
+      const bool pfirst = (tpar < tcur) || (tpar == tcur && par < cur);
+      int rec[CI_LEN] = {0};
+      rec[CI_CUR] = cur;
+      rec[CI_PAR] = pstatic ? world_row[par] : par;
+      rec[CI_TCUR] = tcur;
+      rec[CI_TPAR] = tpar;
+      rec[CI_FLAGS] = (pfirst ? CF_PFIRST : 0) | (pstatic ? CF_STATIC : 0);
+      rec[CI_PARID] = par;
+      ip.insert(ip.end(), rec, rec + CI_LEN);
+      double d[CD_LEN] = {0};
+      d[CD_MARGIN] = std::fmax(m.geom_margin[g1], m.geom_margin[g2]);
+      const double r1 = m.geom_rbound[g1], r2 = m.geom_rbound[g2];
+      d[CD_BOUND] = inf;
+      if (r1 > 0 && r2 > 0) {
+        const double bsum = r1 + r2 + d[CD_MARGIN];
+        d[CD_BOUND] = bsum * bsum;
+      } else if (tpar == GT_PLANE && m.geom_rbound[cur] > 0) {
+        d[CD_BOUND] = d[CD_MARGIN] + m.geom_rbound[cur];
+      }
+      for (int k = 0; k < 3; k++) {
+        d[CD_SCUR + k] = m.geom_size[3 * cur + k];
+        d[CD_SPAR + k] = m.geom_size[3 * par + k];
+      }
+      dp.insert(dp.end(), d, d + CD_LEN);
+    }
+  if (ip.empty()) return MJPL_OK;
+  HIP_TRY(hipMalloc(&e->d_ct_ip, ip.size() * sizeof(int)));
+  HIP_TRY(hipMalloc(&e->d_ct_dp, dp.size() * sizeof(double)));
+  HIP_TRY(hipMemcpy(e->d_ct_ip, ip.data(), ip.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->d_ct_dp, dp.data(), dp.size() * sizeof(double), hipMemcpyHostToDevice));
+  return MJPL_OK;
+}
+
 size_t lds_bytes(const mjpl_engine *e, int ncolsets, size_t scalar = sizeof(double), int block = kBlock,
                  bool queued = false, size_t colscalar = sizeof(double)) {
   const size_t nplan = e->qidx.size();
@@ -1880,6 +1973,40 @@ int launch_edges(mjpl_engine *e, const double *dQA, const double *dQB, int64_t E
   return MJPL_OK;
 }
 
+// One k_contacts launch per kContactRows configurations (the FK scratch holds that many rows).
+int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, unsigned long long *dbits) {
+  const int P = (int)e->ct_g1.size();
+  const int W = (P + 63) / 64;
+  if (N == 0 || P == 0) return MJPL_OK;
+  if (e->ct_unsupported >= 0) {
+    const int p = e->ct_unsupported;
+    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no narrowphase routine here decides it",
+                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
+  }
+  const int ng = e->m.ngeom;
+  const int64_t rows = std::min<int64_t>(N, kContactRows);
+  const size_t need = (size_t)rows * (size_t)ng * 12 * sizeof(double);
+  if (need > e->ct_scratch_bytes) {
+    if (e->d_ct_scratch) HIP_TRY(hipFree(e->d_ct_scratch));
+    e->d_ct_scratch = nullptr;
+    e->ct_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&e->d_ct_scratch, need));
+    e->ct_scratch_bytes = need;
+  }
+  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
+  const size_t lds = lds_bytes(e, 1);
+  int rc = allow_lds(k_contacts, lds);
+  if (rc != MJPL_OK) return rc;
+  for (int64_t i0 = 0; i0 < N; i0 += rows) {
+    const int64_t n = std::min<int64_t>(rows, N - i0);
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_contacts, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
+                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, P, W, dQ, N, i0, n, layout, gx, gm, ng, dbits);
+    HIP_TRY(hipGetLastError());
+  }
+  return MJPL_OK;
+}
+
 int check_common(const mjpl_engine *e, const void *a, int64_t n, int layout) {
   if (!e) return fail(MJPL_E_ARG, "engine is NULL");
   if (n < 0) return fail(MJPL_E_ARG, "negative batch size");
@@ -1987,6 +2114,8 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
   apply_debug_environment(e);
   rc = compile_program(e);
   if (rc != MJPL_OK) return bail(rc);
+  rc = build_contact_table(e);
+  if (rc != MJPL_OK) return bail(rc);
   *out = e;
   return MJPL_OK;
 }
@@ -2032,6 +2161,9 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->d_ucedge) (void)hipFree(e->d_ucedge);
   if (e->d_ucidx) (void)hipFree(e->d_ucidx);
   if (e->d_status) (void)hipFree(e->d_status);
+  if (e->d_ct_ip) (void)hipFree(e->d_ct_ip);
+  if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
+  if (e->d_ct_scratch) (void)hipFree(e->d_ct_scratch);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3063,6 +3195,53 @@ int mjpl_fk(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double *
       if (geom_xmat) memcpy(geom_xmat + (i * m.ngeom + g) * 9, &e->st_gxmat[9 * g], 9 * sizeof(double));
     }
   }
+  return MJPL_OK;
+}
+
+// ---- contacts: which candidate pairs touch (mjpl_contacts.h)
+
+int32_t mjpl_contact_pair_count(mjpl_engine *e) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  return (int32_t)e->ct_g1.size();
+}
+
+int mjpl_contact_pairs(mjpl_engine *e, int32_t *geom1, int32_t *geom2, uint8_t *allowed, int32_t cap) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  const int32_t P = (int32_t)e->ct_g1.size();
+  if (cap < P) return fail(MJPL_E_ARG, "mjpl_contact_pairs: cap %d < %d candidate pairs", cap, P);
+  if (P > 0 && (!geom1 || !geom2 || !allowed)) return fail(MJPL_E_ARG, "mjpl_contact_pairs: NULL output pointer");
+  for (int32_t p = 0; p < P; p++) {
+    geom1[p] = e->ct_g1[p];
+    geom2[p] = e->ct_g2[p];
+    allowed[p] = e->ct_allowed[p];
+  }
+  return MJPL_OK;
+}
+
+int mjpl_contacts_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, uint64_t *dbits) {
+  int rc = check_common(e, dQ, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if (N > 0 && !e->ct_g1.empty() && !dbits) return fail(MJPL_E_ARG, "NULL output pointer");
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_contacts(e, dQ, N, layout, reinterpret_cast<unsigned long long *>(dbits));
+}
+
+int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, uint64_t *bits) {
+  int rc = check_common(e, Q, N, layout);
+  if (rc != MJPL_OK) return rc;
+  const int64_t W = ((int64_t)e->ct_g1.size() + 63) / 64;
+  if (N == 0 || W == 0) return MJPL_OK;
+  if (!bits) return fail(MJPL_E_ARG, "NULL output pointer");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  const size_t bb = (size_t)N * (size_t)W * sizeof(uint64_t);
+  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
+  if ((rc = stage_reserve(e, 1, bb)) != MJPL_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
+  if ((rc = launch_contacts(e, (const double *)e->stage[0], N, layout, (unsigned long long *)e->stage[1])) != MJPL_OK)
+    return rc;
+  HIP_TRY(hipMemcpyAsync(bits, e->stage[1], bb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return MJPL_OK;
 }
 

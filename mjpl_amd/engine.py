@@ -21,6 +21,7 @@ EDGE_INTERIOR_ONLY = 1
 _I32P = C.POINTER(C.c_int32)
 _F64P = C.POINTER(C.c_double)
 _U8P = C.POINTER(C.c_uint8)
+_U64P = C.POINTER(C.c_uint64)
 
 
 class MjplError(RuntimeError):
@@ -118,6 +119,10 @@ ABI = {
                                        _VP]),
     "mjpl_take_status": (C.c_int, [_VP, _I32P]),
     "mjpl_check_configs_bits_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP]),
+    "mjpl_contact_pair_count": (C.c_int32, [_VP]),
+    "mjpl_contact_pairs": (C.c_int, [_VP, _I32P, _I32P, _U8P, C.c_int32]),
+    "mjpl_contacts": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, _U64P]),
+    "mjpl_contacts_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -467,6 +472,36 @@ class Engine:
 
     def check_configs_bits_dev(self, dQ, n, layout, dbits):
         self._ok(self.lib.mjpl_check_configs_bits_dev(self.h, dQ, n, layout, dbits))
+
+    # -- contacts: which candidate geom pairs touch (include/mjpl_hip.h, mjpl_contacts*)
+    def contact_pairs(self):
+        """Candidate pairs of mj_collision -> (pairs int32 [P, 2], allowed bool [P]): the oracle's enumeration
+        order, each row smaller geom type first; pairs of allowed bodies included (allowed[p] = True)."""
+        if getattr(self, "_contact_pairs", None) is None:
+            P = int(self.lib.mjpl_contact_pair_count(self.h))
+            if P < 0:
+                self._ok(P)
+            g1, g2, allowed = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.uint8)
+            self._ok(self.lib.mjpl_contact_pairs(self.h, g1.ctypes.data_as(_I32P), g2.ctypes.data_as(_I32P),
+                                                 allowed.ctypes.data_as(_U8P), P))
+            self._contact_pairs = (np.stack([g1, g2], axis=1), allowed.astype(bool))
+        pairs, allowed = self._contact_pairs
+        return pairs.copy(), allowed.copy()
+
+    def contact_words(self) -> int:
+        """W = (P + 63) // 64: 64-bit words per configuration of a contacts() result."""
+        return (len(self.contact_pairs()[1]) + 63) // 64
+
+    def contacts(self, Q, layout=AOS) -> np.ndarray:
+        """Bit p % 64 of word p // 64 of row i: candidate pair p touches at configuration i -> uint64 [N, W]."""
+        Q, n = self._batch(Q, layout)
+        out = np.zeros((n, self.contact_words()), np.uint64)
+        self._ok(self.lib.mjpl_contacts(self.h, Q.ctypes.data_as(_F64P), n, layout, out.ctypes.data_as(_U64P)))
+        return out
+
+    def contacts_dev(self, dQ, n, layout, dbits):
+        """contacts() on device pointers: dbits receives n * W uint64 words (asynchronous on the engine's stream)."""
+        self._ok(self.lib.mjpl_contacts_dev(self.h, dQ, n, layout, dbits))
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,
