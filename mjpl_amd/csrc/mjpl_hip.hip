@@ -531,8 +531,8 @@ const SpecLib *find_spec(uint64_t hash, bool generic, const char *subdir = nullp
 void load_spec(mjpl_engine *e, bool generic_ok = false, int nstage = 0) {
   e->spec = nullptr;
   e->spec_generic = false;
+  e->spec_cert = nullptr;  // (before the early return: a certificate build never outlives the default library it was found beside)
   if (e->spec_off || e->immediate() || (e->exact_general() && !e->filter_mbox()) || !e->filter_usable) return;  // (the generator covers the queued builds)
-  e->spec_cert = nullptr;
   if (!e->spec_generic_only) e->spec = find_spec(e->program_hash, false);
   // (round 6: the certificate pays from about a million edges per launch on -- +7 ... 11 % -- and costs 4 % at 262 144,
   //  profiles/README.md round 5: both builds are loaded, launch_edges picks by the batch's size)
@@ -1593,8 +1593,8 @@ int launch_edges(mjpl_engine *e, const double *dQA, const double *dQB, int64_t E
     ItemBuffers ib = {};
     int fwaves = 0, fring = 0;
     size_t flds = 0;
-    // (a big batch goes to the model's certificate build, if the engine found one: load_spec)
-    const SpecLib *flib = (e->spec_cert && e->fused_cert && e->fused_cert_min_edges > 0 && E >= e->fused_cert_min_edges &&
+    // (a big batch goes to the model's certificate build, if the engine found one beside the program's own library: load_spec)
+    const SpecLib *flib = (e->spec && !e->spec_generic && e->spec_cert && e->fused_cert && e->fused_cert_min_edges > 0 && E >= e->fused_cert_min_edges &&
                            E > (int64_t)e->fused_single_max) ? e->spec_cert : e->spec;
     const bool fused = expand && !e->fused_skip_once && fused_plan(e, &fwaves, &flds, &fring, flib);
     e->fused_skip_once = false;  // (set by the host-pointer entry point for the launch that follows it)

@@ -1,0 +1,372 @@
+"""History independence: an engine brought into a state by any sequence of calls must return exactly what a fresh
+engine made directly in that state returns -- verdicts, first-bad indices, contact bits and the introspection getters
+-- and the fresh engine must equal the float64 oracle on a sample.
+
+Every other parity test builds a fresh engine for the state it tests.  A long-lived planner does not: it calls
+set_planning again for every base pose or joint subset, flips set_spec / set_filter / set_option on a live engine, and
+sends batches whose sizes cross the dispatch thresholds of launch_edges (fused_single_max, fused_cert_min_edges) and
+grow the scratch buffers, which never shrink.  Each of those leaves state behind in mjpl_engine; this file checks it.
+
+A small driver runs a list of steps on one engine.  After each launch it makes the reference engine from scratch with
+the same effective state.  Options go in through Engine(options=...) and are read back with get_option, and no MJPL_*
+variable of the caller's shell reaches either engine."""
+import os
+
+import numpy as np
+import pytest
+
+from mjpl_amd import engine as eng_mod
+from mjpl_amd import scenes
+from mjpl_amd.constraint.collision_constraint import contact_csr
+from helpers import random_edges
+from spec_models import generic_scenes
+from test_gpu_contacts import assert_same_contacts, oracle_csr
+
+pytestmark = pytest.mark.gpu
+
+STEP = 0.01
+SAMPLE = 20000          # rows of every launch compared with the oracle
+CONTACT_SAMPLE = 1000   # ... of a contacts launch (the oracle walks those one configuration at a time)
+# options that shape the compiled program: they take effect at the next compile (set_planning / set_spec / set_filter),
+# the others at the next launch (the comment above kEngineOptions in mjpl_hip.hip)
+COMPILE_TIME = {"force_immediate", "filter_tol"}
+
+
+@pytest.fixture(autouse=True)
+def _no_shell_options(monkeypatch):
+    """Neither engine of a comparison may pick anything up from the caller: no MJPL_* variables, no default options,
+    per-model libraries from their default directory."""
+    for k in list(os.environ):
+        if k.startswith("MJPL_"):
+            monkeypatch.delenv(k)
+    monkeypatch.setattr(eng_mod, "DEFAULT_OPTIONS", {})
+    monkeypatch.setattr(eng_mod.Engine, "_spec_dir_from_env", None, raising=False)
+    eng_mod.set_spec_dir(None)
+
+
+def _franka():
+    m = scenes.franka_p(obstacles=True)
+    return m, scenes.planning_index(m, scenes.FRANKA_ARM_JOINTS), m.keyframe("home").qpos.copy()
+
+
+def _narrow(base):
+    """The home keyframe with the fingers closed further (0.04 -> 0.01): same columns, another program."""
+    b = base.copy()
+    b[7] = 0.01
+    return b
+
+
+class Driver:
+    """One live engine and the state a fresh engine would need to be in to match it."""
+
+    def __init__(self, oracle_mod, m, qidx, base, allowed=(), options=None, spec=1, label=""):
+        self.orc_mod, self.m, self.allowed, self.label = oracle_mod, m, tuple(allowed), label
+        self.qidx, self.base = np.asarray(qidx, np.int32), np.asarray(base, float).copy()
+        self.spec, self.opts = spec, dict(options or {})
+        self.history = [f"Engine(options={self.opts}, spec={spec}) + set_planning({self.qidx.tolist()})"]
+        self.e = self._fresh()
+        self._batches, self._oracle = {}, {}
+        self.prev_program = None  # (qidx, base) before the last set_planning that changed the base
+
+    def close(self):
+        self.e.close()
+
+    # ---- engines
+    def _fresh(self):
+        opts = dict(self.opts)
+        if self.spec == 0:
+            opts["spec"] = 0
+        e = eng_mod.Engine(self.m, self.allowed, options=opts)
+        e.set_planning(self.qidx, self.base)
+        if self.spec == 2:
+            e.set_spec(2)
+        self._assert_options(e, "fresh")
+        return e
+
+    def _assert_options(self, e, who):
+        for k, v in self.opts.items():
+            assert e.get_option(k) == pytest.approx(float(v), rel=1e-6), (who, k, e.get_option(k), v)
+
+    # ---- steps
+    def run(self, steps):
+        for s in steps:
+            getattr(self, s[0])(*s[1:])
+        return self
+
+    def planning(self, qidx, base):
+        qidx, base = np.asarray(qidx, np.int32), np.asarray(base, float)
+        self.prev_program = (self.qidx, self.base) if len(qidx) == len(self.qidx) and not np.array_equal(base, self.base) else None
+        self.e.set_planning(qidx, base)
+        self.qidx, self.base = qidx, base.copy()
+        self.history.append(f"set_planning({qidx.tolist()}, base[7]={base[7] if len(base) > 7 else None})")
+
+    def set_spec(self, k):
+        self.e.set_spec(k)
+        self.spec = k
+        self.history.append(f"set_spec({k})")
+
+    def set_filter(self, on, tol=None):
+        if on:
+            self.e.set_filter(True, tol)
+            self.opts["filter_tol"] = tol
+        else:
+            self.e.set_filter(False)
+        self.opts["filter"] = 1 if on else 0
+        self.history.append(f"set_filter({on}, {tol})")
+
+    def option(self, name, v):
+        self.e.set_option(name, v)
+        if name in COMPILE_TIME:
+            self.e.set_planning(self.qidx, self.base)
+        self.opts[name] = v
+        self.history.append(f"set_option({name}, {v})" + (" + set_planning(same)" if name in COMPILE_TIME else ""))
+
+    # ---- batches (one per planning set and size) and the oracle's answers (one per program and batch)
+    def _edges(self, n):
+        key = ("edges", tuple(self.qidx.tolist()), n)
+        if key not in self._batches:
+            self._batches[key] = random_edges(self.m, self.qidx, n, seed=1000 + n % 997)
+        return self._batches[key]
+
+    def _configs(self, n):
+        key = ("configs", tuple(self.qidx.tolist()), n)
+        if key not in self._batches:
+            qa, _ = random_edges(self.m, self.qidx, n, seed=2000 + n % 997)
+            self._batches[key] = qa
+        return self._batches[key]
+
+    def _oracle_edges(self, qidx, base, n):
+        key = ("edges", tuple(qidx.tolist()), base.tobytes(), n)
+        if key not in self._oracle:
+            qa, qb = self._edges(n)
+            k = min(n, SAMPLE)
+            with self.orc_mod.portable_trig():
+                orc = self.orc_mod.Oracle(self.m, self.allowed, planning_qidx=qidx, qpos_base=base)
+                ov, ofb, _ = orc.valid_edges(qa[:k], qb[:k], STEP, nthreads=8, info=True)
+            self._oracle[key] = (ov, ofb)
+        return self._oracle[key]
+
+    # ---- launches
+    def _launch(self, e, kind, n, layout, interior_only, dev):
+        flags = eng_mod.EDGE_INTERIOR_ONLY if interior_only else 0
+        if kind == "edges":
+            qa, qb = self._edges(n)
+            if layout == eng_mod.SOA:
+                qa, qb = np.ascontiguousarray(qa.T), np.ascontiguousarray(qb.T)
+            if not dev:
+                return e.check_edges(qa, qb, STEP, layout=layout, first_bad=True, interior_only=interior_only)
+            dA, dB = e.alloc(max(qa.nbytes, 8)).upload(qa), e.alloc(max(qb.nbytes, 8)).upload(qb)
+            dv, dfb = e.alloc(max(n, 8)), e.alloc(max(4 * n, 8))
+            e.check_edges_dev(dA.ptr, dB.ptr, n, STEP, layout, dv.ptr, dfb.ptr, flags)
+            out = (dv.download(np.uint8, n), dfb.download(np.int32, n))
+            for b in (dA, dB, dv, dfb):
+                b.free()
+            return out
+        Q = self._configs(n)
+        if layout == eng_mod.SOA:
+            Q = np.ascontiguousarray(Q.T)
+        if kind == "configs":
+            return (e.check_configs(Q, layout=layout),)
+        assert kind == "contacts"
+        if not dev:
+            return (e.contacts(Q, layout=layout),)
+        W = e.contact_words()
+        dQ, dbits = e.alloc(max(Q.nbytes, 8)).upload(Q), e.alloc(max(8 * n * W, 8))
+        e.contacts_dev(dQ.ptr, n, layout, dbits.ptr)
+        out = (dbits.download(np.uint64, n * W).reshape(n, W),)
+        dQ.free()
+        dbits.free()
+        return out
+
+    def _meta(self, e, kind):
+        meta = {"spec_kind": e.spec_kind(), "spec_cert_loaded": e.get_option("spec_cert_loaded")}
+        if kind == "edges":
+            meta["certified"] = e.last_certified() > 0
+        return meta
+
+    def launch(self, kind, n, layout=eng_mod.AOS, interior_only=False, dev=False, expect=None):
+        """One launch on the live engine, then the same launch on a fresh engine, the other entry point (host or
+        device pointers) on the live engine, and the oracle on a sample.  `expect`: getters asserted outright."""
+        what = f"{kind}({n}, layout={layout}, interior_only={interior_only}, dev={dev})"
+        msg = f"{self.label}: {what} after " + " -> ".join(self.history)
+        got = self._launch(self.e, kind, n, layout, interior_only, dev)
+        meta = self._meta(self.e, kind)
+        self._assert_options(self.e, "live")
+        ref = self._fresh()
+        try:
+            want = self._launch(ref, kind, n, layout, interior_only, dev)
+            ref_meta = self._meta(ref, kind)
+        finally:
+            ref.close()
+        for x, y in zip(got, want):
+            np.testing.assert_array_equal(x, y, err_msg=msg)
+        assert meta == ref_meta, (msg, meta, ref_meta)
+        for k, v in (expect or {}).items():
+            assert meta[k] == v, (msg, k, meta[k], v)
+        if kind in ("edges", "contacts"):  # the other entry point, on the same engine
+            other = self._launch(self.e, kind, n, layout, interior_only, not dev)
+            for x, y in zip(other, got):
+                np.testing.assert_array_equal(x, y, err_msg="host vs device pointers: " + msg)
+        self._check_oracle(kind, n, got, msg, interior_only)
+        self.history.append(what)
+        return got
+
+    def _check_oracle(self, kind, n, got, msg, interior_only):
+        if n == 0:
+            return
+        if kind == "edges":
+            if interior_only:  # (endpoints are not looked at: the fresh engine is the reference of this launch)
+                return
+            ov, ofb = self._oracle_edges(self.qidx, self.base, n)
+            k = len(ov)
+            np.testing.assert_array_equal(got[0][:k], ov, err_msg="oracle: " + msg)
+            np.testing.assert_array_equal(got[1][:k], ofb, err_msg="oracle first-bad: " + msg)
+            if k >= 32:
+                assert 0 < ov.mean() < 1, ("oracle verdicts all alike", msg)
+            if self.prev_program is not None and n >= 32:  # a program change the batch can see
+                pv, _ = self._oracle_edges(*self.prev_program, n)
+                assert (pv != ov).any(), ("both programs give the same verdicts on this batch", msg)
+            return
+        Q = self._configs(n)
+        k = min(n, SAMPLE if kind == "configs" else CONTACT_SAMPLE)
+        with self.orc_mod.portable_trig():
+            orc = self.orc_mod.Oracle(self.m, self.allowed, planning_qidx=self.qidx, qpos_base=self.base)
+            if kind == "configs":
+                ov = orc.valid_configs(Q[:k], nthreads=8)
+                np.testing.assert_array_equal(got[0][:k], ov, err_msg="oracle: " + msg)
+                if k >= 32:
+                    assert 0 < ov.mean() < 1, ("oracle verdicts all alike", msg)
+                return
+            full = np.tile(self.base, (k, 1))
+            full[:, self.qidx] = Q[:k]
+            pairs, _ = self.e.contact_pairs()
+            assert_same_contacts(self.m, full, contact_csr(got[0][:k], pairs), oracle_csr(orc, full), msg)
+            rows = got[0][:k]
+            assert rows.any() and len({r.tobytes() for r in rows}) > 1, ("contact rows all alike", msg)
+
+
+def _cert_driver(oracle_mod, label):
+    m, qidx, base = _franka()
+    d = Driver(oracle_mod, m, qidx, base, options={"fused_cert_min_edges": 100000}, label=label)
+    if not d.e.get_option("spec_cert_loaded"):
+        d.close()
+        pytest.skip("no certificate build beside the default library (python -c 'import __graft_entry__ as g; g.build()')")
+    return d, qidx, base
+
+
+def test_certificate_after_spec_toggles(oracle_mod):
+    """(a) set_spec(0) must drop the certificate build with the default library: a big batch after it runs the
+    interpreter and certifies nothing; set_spec(1) brings both back, set_spec(2) leaves the certificate out."""
+    d, _, _ = _cert_driver(oracle_mod, "certificate after spec toggles")
+    on = {"spec_kind": 1, "spec_cert_loaded": 1, "certified": True}
+    d.run([("launch", "edges", 150000, eng_mod.AOS, False, False, on),
+           ("set_spec", 0),
+           ("launch", "edges", 150000, eng_mod.AOS, False, False, {"spec_kind": 0, "spec_cert_loaded": 0, "certified": False}),
+           ("set_spec", 1),
+           ("launch", "edges", 150000, eng_mod.AOS, False, False, on),
+           ("set_spec", 2),
+           ("launch", "edges", 150000, eng_mod.AOS, False, True, {"spec_cert_loaded": 0, "certified": False}),
+           ("set_spec", 1),
+           ("launch", "edges", 150000, eng_mod.AOS, False, True, on)])
+    d.close()
+
+
+def test_no_stale_library_on_a_new_program(oracle_mod):
+    """(b) With spec off, set_planning to another base pose (same columns, other float64 constants) must not keep the
+    old program's certificate build: a big batch equals a fresh engine for the new program and the oracle.  Back on
+    the home program with spec on, its own library and certificate are loaded again."""
+    d, qidx, base = _cert_driver(oracle_mod, "stale library on a new program")
+    d.run([("launch", "edges", 150000),
+           ("set_spec", 0),
+           ("planning", qidx, _narrow(base)),
+           ("launch", "edges", 150000, eng_mod.AOS, False, False, {"spec_kind": 0, "spec_cert_loaded": 0, "certified": False}),
+           ("launch", "edges", 150000, eng_mod.AOS, False, True),
+           ("planning", qidx, base),
+           ("set_spec", 1),
+           ("launch", "edges", 150000, eng_mod.AOS, False, False, {"spec_kind": 1, "spec_cert_loaded": 1, "certified": True})])
+    d.close()
+
+
+SIZES = (300000, 1, 0, 65, 32768, 32769, 100000, 150000, 63)
+
+
+@pytest.mark.parametrize("variant", [
+    # (options, spec): the fused kernel with the certificate build taking batches from 100 000 edges on ...
+    ({"fused_cert_min_edges": 100000}, 1),
+    # ... every launch in two rounds, on the interpreter ...
+    ({"fused_single": 0}, 0),
+    # ... and the two persistent kernels in place of the fused one
+    ({"fused": 0}, 1)], ids=["fused-cert", "fused_single0-interp", "unfused"])
+def test_sizes_across_the_thresholds_on_one_engine(oracle_mod, variant):
+    """(c) Batch sizes back and forth across fused_single_max (32 768), fused_cert_min_edges and the grow-only scratch
+    capacities; after the first (largest) batch the hand-over and item buffers are capped small, as the fresh engine
+    has them from the start.  One launch with only the interior waypoints, one in the SOA layout."""
+    opts, spec = variant
+    m, qidx, base = _franka()
+    d = Driver(oracle_mod, m, qidx, base, options=opts, spec=spec, label=f"sizes {opts} spec={spec}")
+    for i, n in enumerate(SIZES):
+        layout = eng_mod.SOA if n == 32769 else eng_mod.AOS
+        d.launch("edges", n, layout=layout, interior_only=(n == 65), dev=(i % 2 == 1))
+        if i == 0:
+            d.option("uc_cap", 16)
+            if "fused" in opts:
+                d.option("item_cap", 3000)
+    d.launch("configs", 65)
+    d.close()
+
+
+@pytest.mark.parametrize("spec", [0, 1])
+def test_recompiling_transitions(oracle_mod, spec):
+    """(d) Transitions that compile the program again: another filter tolerance, the filter off and on, the immediate
+    interpreter forced and released, a planning set of fewer columns and back."""
+    m, qidx, base = _franka()
+    d = Driver(oracle_mod, m, qidx, base, spec=spec, label=f"recompiling spec={spec}")
+    n = 20000
+    d.run([("launch", "edges", n),
+           ("set_filter", True, 2e-4), ("launch", "edges", n),
+           ("set_filter", False), ("launch", "edges", n), ("launch", "configs", n),
+           ("set_filter", True, 1e-4), ("launch", "edges", n, eng_mod.SOA),
+           ("option", "force_immediate", 1), ("launch", "edges", n), ("launch", "configs", n),
+           ("option", "force_immediate", 0), ("launch", "edges", n),
+           ("planning", qidx[:-1], base), ("launch", "edges", n), ("launch", "contacts", 4096),
+           ("planning", qidx, base), ("launch", "edges", n, eng_mod.AOS, False, True), ("launch", "contacts", 4096, eng_mod.AOS, False, True)])
+    if spec:
+        assert d.e.spec_kind() == 1
+    d.close()
+
+
+def test_moving_boxes_short_sequence(oracle_mod):
+    """(f) Franka-P with the finger-pad boxes (moving boxes: the exact path is the general one, so forcing the immediate
+    interpreter changes the program): spec toggles through every kind, a set_planning round trip."""
+    m = scenes.franka_p(True, True)
+    qidx, base = scenes.planning_index(m, scenes.FRANKA_ARM_JOINTS), m.keyframe("home").qpos.copy()
+    d = Driver(oracle_mod, m, qidx, base, label="moving boxes")
+    n = 20000
+    d.run([("launch", "edges", n),
+           ("set_spec", 0), ("launch", "edges", n),
+           ("set_spec", 2), ("launch", "edges", n),
+           ("set_spec", 1), ("launch", "edges", n, eng_mod.AOS, False, False, {"spec_kind": 1}),
+           ("option", "force_immediate", 1), ("launch", "edges", n),
+           ("option", "force_immediate", 0), ("launch", "configs", n),
+           ("planning", qidx, _narrow(base)), ("launch", "edges", n),
+           ("planning", qidx, base), ("launch", "edges", n, eng_mod.AOS, False, True, {"spec_kind": 1}),
+           ("launch", "contacts", 4096)])
+    d.close()
+
+
+def test_scene_generic_robot_short_sequence(oracle_mod):
+    """(f) A scene served by the robot's scene-generic library (spec kind 2): spec toggles, a planning set of fewer
+    columns and back."""
+    name, m, kind = generic_scenes()[2]
+    assert kind == 2, name
+    qidx, base = scenes.planning_index(m, scenes.FRANKA_ARM_JOINTS), m.keyframe("home").qpos.copy()
+    d = Driver(oracle_mod, m, qidx, base, label=name)
+    n = 20000
+    d.run([("launch", "edges", n, eng_mod.AOS, False, False, {"spec_kind": 2}),
+           ("set_spec", 0), ("launch", "edges", n),
+           ("set_spec", 1), ("launch", "edges", n, eng_mod.AOS, False, True, {"spec_kind": 2}),
+           ("planning", qidx[:-1], base), ("launch", "edges", n),
+           ("planning", qidx, base), ("launch", "edges", n, eng_mod.AOS, False, False, {"spec_kind": 2}),
+           ("launch", "contacts", 4096),
+           ("set_spec", 2), ("launch", "configs", n)])
+    d.close()
