@@ -228,6 +228,36 @@ int mjpl_contact_pairs(mjpl_engine *e, int32_t *geom1, int32_t *geom2, uint8_t *
 int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, uint64_t *bits);
 int mjpl_contacts_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, uint64_t *dbits);
 
+/* ---- distances and clearance: how far each configuration is from touching -------------------
+ * Pair distance.  For candidate pair p of the contacts table (same P, same order, allowed pairs
+ * included), d_p(q) is the exact geometric (Euclidean) signed distance of the two solids: the width
+ * of the gap when they are disjoint (> 0), minus the penetration depth when they overlap (the length
+ * of the shortest translation that separates them).  A plane is a half-space: d is the signed height
+ * above it of the geom's lowest point (sphere centre - r, lower capsule end point - r, lowest box
+ * corner).  Margins are NOT subtracted.  Float64 geometry, not the numbers of MuJoCo's convex solver.
+ *
+ * distmax (> 0, may be +inf): dist[i * P + p] = d_p(q_i) if d_p < distmax, else exactly distmax (the
+ * contract of mj_geomDistance), which lets the kernel skip a pair whose bounding spheres (or centre
+ * height above a plane minus geom_rbound) are distmax apart.
+ *
+ * Clearance.  clear[i] = min over NON-allowed p of (dist[i * P + p] - margin_p), margin_p =
+ * max(m1, m2) as the check uses it; pair[i] = the candidate-table index of the minimiser, the lowest
+ * on ties.  No non-allowed pair: clear = distmax, pair = -1.  With distmax > every margin,
+ * clear[i] <= 0 <=> mjpl_check_configs calls q_i invalid, up to rounding at the threshold.
+ *
+ * A configuration with a non-finite planning column gives NaN in every dist[i * P + .] and clear[i],
+ * and pair[i] = -1.  Q as mjpl_check_configs reads it: same layouts, same planning-joint selection.
+ * N = 0, or P = 0 for mjpl_distances*, launches nothing and returns MJPL_OK.  MJPL_E_ARG: distmax NaN
+ * or <= 0, a NULL output with N > 0, an unknown layout.  MJPL_E_PAIRTYPE as for mjpl_contacts.  The
+ * results depend on no option and no MJPL_* variable.  The host-buffer forms synchronise; the device
+ * forms are asynchronous on the engine's stream. */
+int mjpl_distances(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *dist);
+int mjpl_distances_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *ddist);
+int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax,
+                   double *clear, int32_t *pair);
+int mjpl_clearance_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax,
+                       double *dclear, int32_t *dpair);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

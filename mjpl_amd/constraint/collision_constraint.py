@@ -162,6 +162,46 @@ class CollisionConstraint(Constraint):
             out.add(tuple(sorted((self.model.body(b1).name, self.model.body(b2).name))))
         return sorted(out)
 
+    # ---- distances and clearance (``data.contact.dist``, ``mj_geomDistance``) ----------------
+    # Exact geometric signed distances (gap > 0, minus the penetration depth when overlapping, margins not
+    # subtracted), per candidate pair of ``engine.contact_pairs()``; entries not below ``distmax`` read distmax.
+    # Invariant: ``c.clearance(q)[0] > 0`` <=> ``c.valid_config(q)``, away from the threshold.
+    def _full_batch(self, Q: np.ndarray) -> np.ndarray:
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[1] != self.model.nq:
+            raise ValueError(f"Q must have shape (N, {self.model.nq})")
+        self._ensure_full()
+        return Q
+
+    def _full_q(self, q: np.ndarray) -> np.ndarray:
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape != (self.model.nq,):
+            raise ValueError(f"q must have shape ({self.model.nq},)")
+        return q[None, :]
+
+    def pair_distances(self, q: np.ndarray, distmax: float = np.inf) -> np.ndarray:
+        """Signed distance of every candidate pair at the full-nq ``q`` -> float64 [P] (allowed pairs included)."""
+        return self.distances_batch(self._full_q(q), distmax)[0]
+
+    def distances_batch(self, Q: np.ndarray, distmax: float = np.inf) -> np.ndarray:
+        """``pair_distances`` for every row of full-nq configurations [N, nq], one launch -> float64 [N, P]."""
+        return self.engine.distances(self._full_batch(Q), distmax, _engine.AOS)
+
+    def clearance(self, q: np.ndarray, distmax: float = np.inf) -> tuple[float, tuple[int, int] | None]:
+        """How far ``q`` is from being invalid: (min over non-allowed pairs of distance - margin, the geom pair
+        attaining it, smaller geom type first), or (distmax, None) if no pair counts.  Invariant:
+        ``clearance(q)[0] > 0`` <=> ``valid_config(q)``, away from the threshold."""
+        C, pair = self.clearance_batch(self._full_q(q), distmax)
+        if pair[0] < 0:
+            return float(C[0]), None
+        g1, g2 = self.engine.contact_pairs()[0][pair[0]]
+        return float(C[0]), (int(g1), int(g2))
+
+    def clearance_batch(self, Q: np.ndarray, distmax: float = np.inf) -> tuple[np.ndarray, np.ndarray]:
+        """``clearance`` for every row of [N, nq], one launch -> (C float64 [N], candidate-pair index int32 [N],
+        -1 for none).  The same invariant holds row by row against ``valid_configs``."""
+        return self.engine.clearance(self._full_batch(Q), distmax, _engine.AOS)
+
     def valid_interval(self, start: np.ndarray, end: np.ndarray, step_dist: float) -> bool:
         """``_valid_collision_interval(start, end, step_dist, self)`` in one launch
         (planning/utils.py:188-216): interior waypoints only."""

@@ -1,0 +1,410 @@
+// mjpl_distance.h -- signed geom distances and clearance per configuration (mjpl_distances*, mjpl_clearance*).
+//
+// What it adds: how far a configuration is from touching anything -- the quantity MuJoCo users read from
+// data.contact.dist or mj_geomDistance.  The numbers here are the exact Euclidean signed distance of the two
+// solids (gap width when disjoint, minus the penetration depth when they overlap; a plane is a half-space),
+// computed in float64 by the routines below.  They are geometry, not MuJoCo's solver output, and margins are
+// not subtracted.
+//
+// Shape: k_contacts's (mjpl_contacts.h), one lane per configuration.
+//   1. The lane runs the interpreter's float64 FK (run_config with EMIT) into the contacts scratch row.
+//   2. It walks the candidate table in order with a wave-uniform pair index.  Per pair: a bound cull against
+//      distmax (|c1 - c2| - rb1 - rb2, or the signed centre distance - rb for a plane), then -- if any lane of
+//      the wave still needs it -- the pair's distance routine.
+//   3. k_distance<false> (distances) stores D[i][p] = min(d_p, distmax); k_distance<true> (clearance) keeps
+//      (min over non-allowed pairs of D - margin, its pair index) in registers and stores 12 bytes per
+//      configuration.
+//
+// The routines reduce every non-plane pair to core distance minus radii (sphere = point, capsule = segment,
+// box = box).  Disjoint cores: the minimum over the feature pairs that can hold the closest points (end
+// points, the box's 8 vertices and 12 edges); every candidate is a distance between two points of the sets,
+// so the minimum is exact up to rounding.  Overlapping cores: the least normalised overlap over the separating
+// axes of the pair (3 face normals of a box, 3 segment x box-axis crosses, 15 axes for two boxes), which is
+// the penetration depth of two convex polytopes.
+#pragma once
+
+namespace mjpl {
+
+// per-pair record of the distance table (mjpl_hip.hip: build_distance_table), beside the candidate table of
+// mjpl_contacts.h: rb1 + rb2 (geom_rbound; a plane's is 0) and whether the ruleset allows the pair
+enum : int { DT_RBSUM = 0, DT_ALLOWED, DT_LEN = 2 };
+
+// A pair is culled only when its bound exceeds distmax by this much, so that rounding of the bound can never
+// hide a distance below distmax: a culled pair's exact distance is >= distmax + slack - (a few ulps).
+constexpr double kDistCullSlack = 1e-9;
+// squared lengths below this are degenerate segments (points)
+constexpr double kDistTiny = 1e-30;
+
+__device__ __forceinline__ double dist_clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
+
+// squared distance between the segments p1 + s d1 and p2 + t d2 (s, t in [0, 1]): closest points with each
+// parameter optimal for the other after clamping; parallel and degenerate segments included
+__device__ __forceinline__ double seg_seg_d2(const double *p1, const double *d1, const double *p2, const double *d2) {
+  const double r[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+  const double a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
+  double s, t;
+  if (e <= kDistTiny) {
+    t = 0.0;
+    s = a <= kDistTiny ? 0.0 : dist_clamp01(-c / a);
+  } else {
+    const double denom = a * e - b * b;
+    s = (a > kDistTiny && denom > 0) ? dist_clamp01((b * f - c * e) / denom) : 0.0;
+    t = (b * s + f) / e;
+    if (t < 0) {
+      t = 0.0;
+      s = a <= kDistTiny ? 0.0 : dist_clamp01(-c / a);
+    } else if (t > 1) {
+      t = 1.0;
+      s = a <= kDistTiny ? 0.0 : dist_clamp01((b - c) / a);
+    }
+  }
+  double w2 = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double w = (p1[k] + d1[k] * s) - (p2[k] + d2[k] * t);
+    w2 += w * w;
+  }
+  return w2;
+}
+
+// squared distance from the point p to the segment q + t d, t in [0, 1]
+__device__ __forceinline__ double pt_seg_d2(const double *p, const double *q, const double *d) {
+  const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  const double dd = dot3(d, d);
+  const double t = dd <= kDistTiny ? 0.0 : dist_clamp01(dot3(r, d) / dd);
+  const double w[3] = {r[0] - d[0] * t, r[1] - d[1] * t, r[2] - d[2] * t};
+  return dot3(w, w);
+}
+
+// squared distance from the point p (box frame) to the box |x_k| <= s_k; 0 inside
+__device__ __forceinline__ double pt_box_d2(const double *p, const double *s) {
+  double w2 = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double w = p[k] - fmin(fmax(p[k], -s[k]), s[k]);
+    w2 += w * w;
+  }
+  return w2;
+}
+
+// min over the box's 12 edges of the squared distance to the segment p + t d (all in the box frame)
+__device__ __forceinline__ double seg_box_edges_d2(const double *p, const double *d, const double *s) {
+  double best = INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int i = (k + 1) % 3, j = (k + 2) % 3;
+#pragma unroll 1
+    for (int q = 0; q < 4; q++) {
+      double a[3], e[3];
+      a[k] = -s[k];
+      a[i] = (q & 1) ? s[i] : -s[i];
+      a[j] = (q & 2) ? s[j] : -s[j];
+      e[k] = 2 * s[k];
+      e[i] = 0.0;
+      e[j] = 0.0;
+      best = fmin(best, seg_seg_d2(p, d, a, e));
+    }
+  }
+  return best;
+}
+
+// squared distance between the segment p + t d and the box (box frame), valid when they are disjoint: the
+// closest points are then an end point and the box, or the segment and one of the box's edges
+__device__ __forceinline__ double seg_box_disjoint_d2(const double *p, const double *d, const double *s) {
+  const double q[3] = {p[0] + d[0], p[1] + d[1], p[2] + d[2]};
+  return fmin(fmin(pt_box_d2(p, s), pt_box_d2(q, s)), seg_box_edges_d2(p, d, s));
+}
+
+// Segment m +- h (box frame) against the box |x_k| <= s_k on the separating axes: the 3 face normals and
+// h x e_k (skipped when h is nearly parallel to e_k, or zero).  Returns the least normalised overlap (the
+// penetration depth when >= 0); *sep = some axis has a gap.
+__device__ __forceinline__ double seg_box_sat(const double *m, const double *h, const double *s, bool *sep) {
+  double depth = INFINITY;
+  bool gap = false;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double o = s[k] + fabs(h[k]) - fabs(m[k]);
+    gap = gap || o < 0;
+    depth = fmin(depth, o);
+  }
+  const double hh = dot3(h, h);
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int i = (k + 1) % 3, j = (k + 2) % 3;
+    // n = h x e_k: n_k = 0, n_i = h_j, n_j = -h_i
+    const double nn = h[i] * h[i] + h[j] * h[j];
+    if (nn > 1e-12 * hh) {
+      const double rad = s[i] * fabs(h[j]) + s[j] * fabs(h[i]);
+      const double o = (rad - fabs(h[j] * m[i] - h[i] * m[j])) / sqrt(nn);
+      gap = gap || o < 0;
+      depth = fmin(depth, o);
+    }
+  }
+  *sep = gap;
+  return depth;
+}
+
+// core of a sphere (point: seg = false) or capsule (segment) against a box: signed distance of the cores
+__device__ __forceinline__ double core_box_distance(bool seg, const GeomT<double> &g, const double *sg,
+                                                    const GeomT<double> &box, const double *sb) {
+  const double tmp[3] = {g.pos[0] - box.pos[0], g.pos[1] - box.pos[1], g.pos[2] - box.pos[2]};
+  double m[3];
+  mul_matT_vec3(m, box.m, tmp);
+  if (!seg) {  // (wave-uniform)
+    const double d2 = pt_box_d2(m, sb);
+    if (d2 > 0) return sqrt(d2) - sg[0];
+    const double depth = fmin(fmin(sb[0] - fabs(m[0]), sb[1] - fabs(m[1])), sb[2] - fabs(m[2]));
+    return -depth - sg[0];
+  }
+  const double axis[3] = {g.m[2], g.m[5], g.m[8]};
+  double a[3], h[3];
+  mul_matT_vec3(a, box.m, axis);
+#pragma unroll
+  for (int k = 0; k < 3; k++) h[k] = a[k] * sg[1];
+  bool sep;
+  const double depth = seg_box_sat(m, h, sb, &sep);
+  if (!sep) return -depth - sg[0];
+  const double p[3] = {m[0] - h[0], m[1] - h[1], m[2] - h[2]};
+  const double d[3] = {2 * h[0], 2 * h[1], 2 * h[2]};
+  return sqrt(seg_box_disjoint_d2(p, d, sb)) - sg[0];
+}
+
+// point or segment cores of two spheres / capsules: distance of the cores minus both radii
+__device__ __forceinline__ double core_core_distance(const GeomT<double> &g1, const double *s1, bool seg1,
+                                                     const GeomT<double> &g2, const double *s2, bool seg2) {
+  const double h1 = seg1 ? s1[1] : 0.0, h2 = seg2 ? s2[1] : 0.0;
+  double p1[3], d1[3], p2[3], d2[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    d1[k] = 2 * h1 * g1.m[3 * k + 2];
+    d2[k] = 2 * h2 * g2.m[3 * k + 2];
+    p1[k] = g1.pos[k] - h1 * g1.m[3 * k + 2];
+    p2[k] = g2.pos[k] - h2 * g2.m[3 * k + 2];
+  }
+  double w2 = seg_seg_d2(p1, d1, p2, d2);
+  if (seg1 && seg2) {  // (wave-uniform) end points against the other segment: robust to near-parallel axes
+    const double q1[3] = {p1[0] + d1[0], p1[1] + d1[1], p1[2] + d1[2]};
+    const double q2[3] = {p2[0] + d2[0], p2[1] + d2[1], p2[2] + d2[2]};
+    w2 = fmin(w2, fmin(fmin(pt_seg_d2(p1, p2, d2), pt_seg_d2(q1, p2, d2)),
+                       fmin(pt_seg_d2(p2, p1, d1), pt_seg_d2(q2, p1, d1))));
+  }
+  return sqrt(w2) - (s1[0] + s2[0]);
+}
+
+// two boxes: 15-axis SAT decides overlap (least normalised overlap = depth; an edge-pair axis with
+// 1 - R_ij^2 < 1e-12 is skipped, as box_box does); disjoint boxes by feature enumeration: vertex against box
+// (8 + 8, b2's as the end points of its edges) and edge against edge (12 x 12)
+__device__ __forceinline__ double box_box_distance(const GeomT<double> &b1, const double *s1, const GeomT<double> &b2,
+                                                   const double *s2) {
+  const double dp[3] = {b2.pos[0] - b1.pos[0], b2.pos[1] - b1.pos[1], b2.pos[2] - b1.pos[2]};
+  double R[9], t[3];  // (|R| enters as operand modifiers: no array of its own)
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) R[3 * i + j] = b1.m[i] * b2.m[j] + b1.m[3 + i] * b2.m[3 + j] + b1.m[6 + i] * b2.m[6 + j];
+  mul_matT_vec3(t, b1.m, dp);
+  double depth = INFINITY;
+  bool sep = false;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double o = s1[i] + s2[0] * fabs(R[3 * i]) + s2[1] * fabs(R[3 * i + 1]) + s2[2] * fabs(R[3 * i + 2]) - fabs(t[i]);
+    sep = sep || o < 0;
+    depth = fmin(depth, o);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const double tj = t[0] * R[j] + t[1] * R[3 + j] + t[2] * R[6 + j];
+    const double o = s1[0] * fabs(R[j]) + s1[1] * fabs(R[3 + j]) + s1[2] * fabs(R[6 + j]) + s2[j] - fabs(tj);
+    sep = sep || o < 0;
+    depth = fmin(depth, o);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      const double len2 = 1 - R[3 * i + j] * R[3 * i + j];
+      if (!(len2 < 1e-12)) {
+        const double ra = s1[i1] * fabs(R[3 * i2 + j]) + s1[i2] * fabs(R[3 * i1 + j]);
+        const double rb = s2[j1] * fabs(R[3 * i + j2]) + s2[j2] * fabs(R[3 * i + j1]);
+        const double tl = t[i2] * R[3 * i1 + j] - t[i1] * R[3 * i2 + j];
+        const double o = (ra + rb - fabs(tl)) / sqrt(len2);
+        sep = sep || o < 0;
+        depth = fmin(depth, o);
+      }
+    }
+  }
+  if (!sep) return -depth;
+  double best = INFINITY;
+  // b2's 12 edges in b1's frame (axis k of b2 is column k of R) against b1: their end points are b2's vertices.
+  // One edge per trip, picked by selects between register copies (pinned: an indexed pick would put the
+  // arrays in scratch memory).
+  double c0 = R[0], c1 = R[3], c2 = R[6], c3 = R[1], c4 = R[4], c5 = R[7], c6 = R[2], c7 = R[5], c8 = R[8];
+  double h0 = s2[0], h1 = s2[1], h2 = s2[2];
+  pin(c0); pin(c1); pin(c2); pin(c3); pin(c4); pin(c5); pin(c6); pin(c7); pin(c8);
+  pin(h0); pin(h1); pin(h2);
+#pragma unroll 1
+  for (int e = 0; e < 12; e++) {
+    const int k = e >> 2;
+    const double sa = (e & 1) ? 1.0 : -1.0, sb = (e & 2) ? 1.0 : -1.0;
+    // v = -s2_k on axis k, sa s2_i on i = k + 1, sb s2_j on j = k + 2 (mod 3)
+    const double v0 = k == 0 ? -h0 : (k == 1 ? sb * h0 : sa * h0);
+    const double v1 = k == 1 ? -h1 : (k == 2 ? sb * h1 : sa * h1);
+    const double v2 = k == 2 ? -h2 : (k == 0 ? sb * h2 : sa * h2);
+    const double len = 2 * (k == 0 ? h0 : (k == 1 ? h1 : h2));
+    const double p[3] = {t[0] + c0 * v0 + c3 * v1 + c6 * v2, t[1] + c1 * v0 + c4 * v1 + c7 * v2,
+                         t[2] + c2 * v0 + c5 * v1 + c8 * v2};
+    const double d[3] = {len * (k == 0 ? c0 : (k == 1 ? c3 : c6)), len * (k == 0 ? c1 : (k == 1 ? c4 : c7)),
+                         len * (k == 0 ? c2 : (k == 1 ? c5 : c8))};
+    best = fmin(best, seg_box_disjoint_d2(p, d, s1));
+  }
+  // b1's vertices in b2's frame: u = R^T (v - t)
+#pragma unroll 1
+  for (int c = 0; c < 8; c++) {
+    const double v[3] = {(c & 1) ? s1[0] : -s1[0], (c & 2) ? s1[1] : -s1[1], (c & 4) ? s1[2] : -s1[2]};
+    const double w[3] = {v[0] - t[0], v[1] - t[1], v[2] - t[2]};
+    double u[3];
+    mul_matT_vec3(u, R, w);
+    best = fmin(best, pt_box_d2(u, s2));
+  }
+  return sqrt(best);
+}
+
+// a geom against a plane (half-space below the plane's z axis): signed height of the geom's lowest point
+__device__ __forceinline__ double plane_distance(const GeomT<double> &pl, int type, const GeomT<double> &g,
+                                                 const double *s) {
+  const double n[3] = {pl.m[2], pl.m[5], pl.m[8]};
+  const double dif[3] = {g.pos[0] - pl.pos[0], g.pos[1] - pl.pos[1], g.pos[2] - pl.pos[2]};
+  const double h = dot3(dif, n);
+  if (type == GT_SPHERE) return h - s[0];
+  if (type == GT_CAPSULE) {
+    const double axis[3] = {g.m[2], g.m[5], g.m[8]};
+    return h - s[1] * fabs(dot3(axis, n)) - s[0];
+  }
+  // box: its lowest corner sits sum_k s_k |axis_k . n| below the centre
+  double low = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double ak[3] = {g.m[k], g.m[3 + k], g.m[6 + k]};
+    low += s[k] * fabs(dot3(ak, n));
+  }
+  return h - low;
+}
+
+// signed distance of one candidate pair (cur moving, par its partner; the types are wave-uniform)
+__device__ __forceinline__ double pair_distance(int tcur, const GeomT<double> &cur, const double *scur, int tpar,
+                                                const GeomT<double> &par, const double *spar) {
+  if (tpar == GT_PLANE) return plane_distance(par, tcur, cur, scur);
+  if (tcur == GT_BOX && tpar == GT_BOX) return box_box_distance(cur, scur, par, spar);
+  if (tcur == GT_BOX) return core_box_distance(tpar == GT_CAPSULE, par, spar, cur, scur);
+  if (tpar == GT_BOX) return core_box_distance(tcur == GT_CAPSULE, cur, scur, par, spar);
+  return core_core_distance(cur, scur, tcur == GT_CAPSULE, par, spar, tpar == GT_CAPSULE);
+}
+
+// Configurations [i0, i0 + n) of the batch Q (N rows, `layout`), FK scratch rows as k_contacts uses them.
+// CLEAR = false: dist[i * P + p] = min(d_p, distmax).  CLEAR = true: clear[i] = min over non-allowed p of
+// (min(d_p, distmax) - margin_p), pair[i] = its lowest index (distmax, -1 without such a pair).  A row with a
+// non-finite planning column gives NaN (and pair -1).
+template <bool CLEAR>
+__global__ void __launch_bounds__(kBlock)
+k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp, int ndp,
+           const int *__restrict__ gct, const double *__restrict__ gcd, const double *__restrict__ gdt, int P,
+           const double *__restrict__ Q, int64_t N, int64_t i0, int64_t n, int layout, double distmax,
+           double *__restrict__ gx, double *__restrict__ gm, int ngeom, double *__restrict__ dist,
+           double *__restrict__ clear, int *__restrict__ pair) {
+  extern __shared__ double smem[];
+  const int B = blockDim.x;
+  const int nplan = gip[H_NPLAN];
+  Carve<double> c = carve_lds<double>(smem, gip, nip, gdp, ndp, nplan, 1, B);
+  const int64_t r = (int64_t)blockIdx.x * B + threadIdx.x;
+  const bool active = r < n;
+  const int64_t i = i0 + (active ? r : 0);
+  load_columns(c.col0 + threadIdx.x, B, Q, N, i, nplan, layout, active);
+  __syncthreads();
+  bool finite = true;
+  for (int k = 0; k < nplan; k++) finite = finite && __builtin_isfinite(c.col0[k * B + threadIdx.x]);
+  const bool live = active && finite;
+
+  // 1. forward kinematics into the scratch row
+  FkOut out = {};
+  out.geom_xpos = gx;
+  out.geom_xmat = gm;
+  out.ngeom = ngeom;
+  run_config<double, 1, true, true, true>(c.ip, c.tp, c.col0 + threadIdx.x, B, c.save + threadIdx.x, B, active, 0.0,
+                                          out, active ? r : 0);
+  const double *rx = gx + (active ? r : 0) * ngeom * 3;
+  const double *rm = gm + (active ? r : 0) * ngeom * 9;
+
+  // 2. every candidate pair, in table order
+  IP ct = (IP)gct;
+  DP cd = (DP)gcd;
+  DP dt = (DP)gdt;
+  DP wcull = c.tp + uni(c.ip[H_OFF_WCULL]);
+  DP wnarrow = c.tp + uni(c.ip[H_OFF_WNARROW]);
+  double best = distmax;  // CLEAR: least D - margin so far, at pair index bestp
+  int bestp = -1;
+  for (int p = 0; p < P; p++) {
+    IP e = ct + p * CI_LEN;
+    DP d = cd + p * CD_LEN;
+    if (CLEAR && uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;  // (uniform: allowed pairs take no part)
+    const int gcur = uni(e[CI_CUR]), gpar = uni(e[CI_PAR]);
+    const int tcur = uni(e[CI_TCUR]), tpar = uni(e[CI_TPAR]), flags = uni(e[CI_FLAGS]);
+    GeomT<double> cur, par;
+    double spar[3];
+    const double scur[3] = {d[CD_SCUR], d[CD_SCUR + 1], d[CD_SCUR + 2]};
+    if (active) contact_load_geom(cur, rx, rm, gcur, tcur);
+    else cur = GeomT<double>{};
+    if (flags & CF_STATIC) {
+      DP rw = wnarrow + gpar * WN_LEN;
+      par.pos[0] = wcull[wc_at(gpar, 0)]; par.pos[1] = wcull[wc_at(gpar, 1)]; par.pos[2] = wcull[wc_at(gpar, 2)];
+      par.m[2] = rw[WN_ZAXIS]; par.m[5] = rw[WN_ZAXIS + 1]; par.m[8] = rw[WN_ZAXIS + 2];
+      par.m[0] = rw[WN_XAXIS]; par.m[3] = rw[WN_XAXIS + 1]; par.m[6] = rw[WN_XAXIS + 2];
+      par.m[1] = rw[WN_YAXIS]; par.m[4] = rw[WN_YAXIS + 1]; par.m[7] = rw[WN_YAXIS + 2];
+      for (int k = 0; k < 3; k++) spar[k] = tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
+    } else {
+      if (active) contact_load_geom(par, rx, rm, gpar, tpar);
+      else par = GeomT<double>{};
+      for (int k = 0; k < 3; k++) spar[k] = d[CD_SPAR + k];
+    }
+    const double margin = d[CD_MARGIN];
+    // lower bound of the distance: bounding spheres, or the centre's height above a plane minus rb
+    double lb;
+    {
+      const double dif[3] = {cur.pos[0] - par.pos[0], cur.pos[1] - par.pos[1], cur.pos[2] - par.pos[2]};
+      const double rb = dt[p * DT_LEN + DT_RBSUM];
+      if (tpar == GT_PLANE) {
+        const double nrm[3] = {par.m[2], par.m[5], par.m[8]};
+        lb = dot3(dif, nrm) - rb;
+      } else {
+        lb = sqrt(dot3(dif, dif)) - rb;
+      }
+    }
+    const bool far = lb >= distmax + kDistCullSlack;  // D = distmax, no routine
+    bool need = live && !far;
+    // CLEAR: a pair whose D - margin must exceed the least so far cannot change (C, pair)
+    if (CLEAR) need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
+    double D = distmax;
+    if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
+      const double x = pair_distance(tcur, cur, scur, tpar, par, spar);
+      if (need) D = x < distmax ? x : distmax;
+    }
+    if constexpr (CLEAR) {
+      const double v = D - margin;
+      if (live && (need || far) && (bestp < 0 || v < best)) {
+        best = v;
+        bestp = p;
+      }
+    } else {
+      if (active) dist[i * P + p] = live ? D : NAN;
+    }
+  }
+  if constexpr (CLEAR) {
+    if (active) {
+      clear[i] = live ? best : NAN;
+      pair[i] = live ? bestp : -1;
+    }
+  }
+}
+
+}  // namespace mjpl

@@ -32,6 +32,7 @@
 #include "mjpl_nearest.h"
 #include "mjpl_nearest_cells.h"
 #include "mjpl_contacts.h"
+#include "mjpl_distance.h"
 
 namespace {
 
@@ -409,6 +410,8 @@ struct mjpl_engine {
   double *d_ct_dp = nullptr;
   double *d_ct_scratch = nullptr;  // FK scratch rows of one launch (grow-only)
   size_t ct_scratch_bytes = 0;
+  // distance table of mjpl_distances* / mjpl_clearance* (mjpl_distance.h: DT_*), made on first use from the model
+  double *d_dt = nullptr;
 };
 
 namespace {
@@ -1973,6 +1976,19 @@ int launch_edges(mjpl_engine *e, const double *dQA, const double *dQB, int64_t E
   return MJPL_OK;
 }
 
+// FK scratch of k_contacts / k_distance: `rows` rows of ngeom poses (grow-only)
+int contact_scratch(mjpl_engine *e, int64_t rows) {
+  const size_t need = (size_t)rows * (size_t)e->m.ngeom * 12 * sizeof(double);
+  if (need > e->ct_scratch_bytes) {
+    if (e->d_ct_scratch) HIP_TRY(hipFree(e->d_ct_scratch));
+    e->d_ct_scratch = nullptr;
+    e->ct_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&e->d_ct_scratch, need));
+    e->ct_scratch_bytes = need;
+  }
+  return MJPL_OK;
+}
+
 // One k_contacts launch per kContactRows configurations (the FK scratch holds that many rows).
 int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, unsigned long long *dbits) {
   const int P = (int)e->ct_g1.size();
@@ -1985,17 +2001,11 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
   }
   const int ng = e->m.ngeom;
   const int64_t rows = std::min<int64_t>(N, kContactRows);
-  const size_t need = (size_t)rows * (size_t)ng * 12 * sizeof(double);
-  if (need > e->ct_scratch_bytes) {
-    if (e->d_ct_scratch) HIP_TRY(hipFree(e->d_ct_scratch));
-    e->d_ct_scratch = nullptr;
-    e->ct_scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&e->d_ct_scratch, need));
-    e->ct_scratch_bytes = need;
-  }
+  int rc = contact_scratch(e, rows);
+  if (rc != MJPL_OK) return rc;
   double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
   const size_t lds = lds_bytes(e, 1);
-  int rc = allow_lds(k_contacts, lds);
+  rc = allow_lds(k_contacts, lds);
   if (rc != MJPL_OK) return rc;
   for (int64_t i0 = 0; i0 < N; i0 += rows) {
     const int64_t n = std::min<int64_t>(rows, N - i0);
@@ -2004,6 +2014,69 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
                        (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, P, W, dQ, N, i0, n, layout, gx, gm, ng, dbits);
     HIP_TRY(hipGetLastError());
   }
+  return MJPL_OK;
+}
+
+// The distance table beside the candidate table (mjpl_distance.h: DT_*): rb1 + rb2 and the allowed flag per
+// pair.  Depends on the model only, so it is made once, on first use.
+int build_distance_table(mjpl_engine *e) {
+  const int P = (int)e->ct_g1.size();
+  if (e->d_dt || P == 0) return MJPL_OK;
+  std::vector<double> dt((size_t)P * DT_LEN);
+  for (int p = 0; p < P; p++) {
+    const int g1 = e->ct_g1[p], g2 = e->ct_g2[p];
+    // (a plane partner's bound is the half-space itself: only the other geom's radius counts)
+    const double rb1 = e->m.geom_type[g1] == GT_PLANE ? 0.0 : e->m.geom_rbound[g1];
+    const double rb2 = e->m.geom_type[g2] == GT_PLANE ? 0.0 : e->m.geom_rbound[g2];
+    dt[(size_t)p * DT_LEN + DT_RBSUM] = rb1 + rb2;
+    dt[(size_t)p * DT_LEN + DT_ALLOWED] = e->ct_allowed[p] ? 1.0 : 0.0;
+  }
+  double *d = nullptr;
+  HIP_TRY(hipMalloc(&d, dt.size() * sizeof(double)));
+  const hipError_t err = hipMemcpy(d, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    HIP_TRY(err);
+  }
+  e->d_dt = d;
+  return MJPL_OK;
+}
+
+// One k_distance launch per kContactRows configurations: D [N][P] (dclear == nullptr), or (C, pair) [N].
+int launch_distance(mjpl_engine *e, const double *dQ, int64_t N, int layout, double distmax, double *ddist,
+                    double *dclear, int32_t *dpair) {
+  const bool clear = dclear != nullptr;
+  const int P = (int)e->ct_g1.size();
+  if (N == 0 || (!clear && P == 0)) return MJPL_OK;
+  if (e->ct_unsupported >= 0) {
+    const int p = e->ct_unsupported;
+    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no distance routine here measures it",
+                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
+  }
+  int rc = build_distance_table(e);
+  if (rc != MJPL_OK) return rc;
+  const int ng = e->m.ngeom;
+  const int64_t rows = std::min<int64_t>(N, kContactRows);
+  if ((rc = contact_scratch(e, rows)) != MJPL_OK) return rc;
+  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
+  const size_t lds = lds_bytes(e, 1);
+  auto kernel = clear ? k_distance<true> : k_distance<false>;
+  if ((rc = allow_lds(kernel, lds)) != MJPL_OK) return rc;
+  for (int64_t i0 = 0; i0 < N; i0 += rows) {
+    const int64_t n = std::min<int64_t>(rows, N - i0);
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
+                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, gx, gm, ng,
+                       ddist, dclear, dpair);
+    HIP_TRY(hipGetLastError());
+  }
+  return MJPL_OK;
+}
+
+// argument checks shared by the four distance entry points (after check_common)
+int check_distance_args(double distmax, int64_t N, const void *out1, const void *out2) {
+  if (!(distmax > 0)) return fail(MJPL_E_ARG, "distmax must be > 0 (NaN is refused), got %g", distmax);
+  if (N > 0 && (!out1 || !out2)) return fail(MJPL_E_ARG, "NULL output pointer");
   return MJPL_OK;
 }
 
@@ -2164,6 +2237,7 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->d_ct_ip) (void)hipFree(e->d_ct_ip);
   if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
   if (e->d_ct_scratch) (void)hipFree(e->d_ct_scratch);
+  if (e->d_dt) (void)hipFree(e->d_dt);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3241,6 +3315,68 @@ int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, ui
   if ((rc = launch_contacts(e, (const double *)e->stage[0], N, layout, (unsigned long long *)e->stage[1])) != MJPL_OK)
     return rc;
   HIP_TRY(hipMemcpyAsync(bits, e->stage[1], bb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MJPL_OK;
+}
+
+// ---- distances and clearance per configuration (mjpl_distance.h)
+
+int mjpl_distances_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *ddist) {
+  int rc = check_common(e, dQ, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if ((rc = check_distance_args(distmax, N, ddist, ddist)) != MJPL_OK) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_distance(e, dQ, N, layout, distmax, ddist, nullptr, nullptr);
+}
+
+int mjpl_distances(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *dist) {
+  int rc = check_common(e, Q, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if ((rc = check_distance_args(distmax, N, dist, dist)) != MJPL_OK) return rc;
+  const int64_t P = (int64_t)e->ct_g1.size();
+  if (N == 0 || P == 0) return MJPL_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  const size_t db = (size_t)N * (size_t)P * sizeof(double);
+  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
+  if ((rc = stage_reserve(e, 1, db)) != MJPL_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
+  if ((rc = launch_distance(e, (const double *)e->stage[0], N, layout, distmax, (double *)e->stage[1], nullptr,
+                            nullptr)) != MJPL_OK)
+    return rc;
+  HIP_TRY(hipMemcpyAsync(dist, e->stage[1], db, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MJPL_OK;
+}
+
+int mjpl_clearance_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *dclear,
+                       int32_t *dpair) {
+  int rc = check_common(e, dQ, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if ((rc = check_distance_args(distmax, N, dclear, dpair)) != MJPL_OK) return rc;
+  if (N == 0) return MJPL_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_distance(e, dQ, N, layout, distmax, nullptr, dclear, dpair);
+}
+
+int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *clear,
+                   int32_t *pair) {
+  int rc = check_common(e, Q, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if ((rc = check_distance_args(distmax, N, clear, pair)) != MJPL_OK) return rc;
+  if (N == 0) return MJPL_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  const size_t cb = (size_t)N * sizeof(double), pb = (size_t)N * sizeof(int32_t);
+  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
+  if ((rc = stage_reserve(e, 1, cb + pb)) != MJPL_OK) return rc;
+  double *dclear = (double *)e->stage[1];
+  int32_t *dpair = (int32_t *)((char *)e->stage[1] + cb);
+  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
+  if ((rc = launch_distance(e, (const double *)e->stage[0], N, layout, distmax, nullptr, dclear, dpair)) != MJPL_OK)
+    return rc;
+  HIP_TRY(hipMemcpyAsync(clear, dclear, cb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(pair, dpair, pb, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return MJPL_OK;
 }

@@ -123,6 +123,10 @@ ABI = {
     "mjpl_contact_pairs": (C.c_int, [_VP, _I32P, _I32P, _U8P, C.c_int32]),
     "mjpl_contacts": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, _U64P]),
     "mjpl_contacts_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP]),
+    "mjpl_distances": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P]),
+    "mjpl_distances_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP]),
+    "mjpl_clearance": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P, _I32P]),
+    "mjpl_clearance_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP, _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -502,6 +506,35 @@ class Engine:
     def contacts_dev(self, dQ, n, layout, dbits):
         """contacts() on device pointers: dbits receives n * W uint64 words (asynchronous on the engine's stream)."""
         self._ok(self.lib.mjpl_contacts_dev(self.h, dQ, n, layout, dbits))
+
+    # -- distances and clearance: exact signed geom distances per candidate pair (include/mjpl_hip.h, mjpl_distances*)
+    def distances(self, Q, distmax=float("inf"), layout=AOS) -> np.ndarray:
+        """Signed distance of every candidate pair (contact_pairs() order) at every configuration -> float64 [N, P]:
+        exact geometric distance of the two solids (gap > 0, minus the penetration depth < 0, margins not
+        subtracted), or exactly ``distmax`` where it is not below ``distmax``.  NaN rows: non-finite input."""
+        Q, n = self._batch(Q, layout)
+        out = np.zeros((n, len(self.contact_pairs()[1])), np.float64)
+        self._ok(self.lib.mjpl_distances(self.h, Q.ctypes.data_as(_F64P), n, layout, float(distmax),
+                                         out.ctypes.data_as(_F64P)))
+        return out
+
+    def distances_dev(self, dQ, n, layout, ddist, distmax=float("inf")):
+        """distances() on device pointers: ddist receives n * P float64 (asynchronous on the engine's stream)."""
+        self._ok(self.lib.mjpl_distances_dev(self.h, dQ, n, layout, float(distmax), ddist))
+
+    def clearance(self, Q, distmax=float("inf"), layout=AOS) -> tuple[np.ndarray, np.ndarray]:
+        """(C float64 [N], pair int32 [N]): C = min over non-allowed pairs of (distance - margin), pair = the
+        lowest candidate index attaining it; (distmax, -1) without such a pair, (NaN, -1) for non-finite input.
+        C > 0 iff check_configs calls the configuration valid, away from the threshold."""
+        Q, n = self._batch(Q, layout)
+        clear, pair = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        self._ok(self.lib.mjpl_clearance(self.h, Q.ctypes.data_as(_F64P), n, layout, float(distmax),
+                                         clear.ctypes.data_as(_F64P), pair.ctypes.data_as(_I32P)))
+        return clear, pair
+
+    def clearance_dev(self, dQ, n, layout, dclear, dpair, distmax=float("inf")):
+        """clearance() on device pointers: dclear receives n float64, dpair n int32 (asynchronous)."""
+        self._ok(self.lib.mjpl_clearance_dev(self.h, dQ, n, layout, float(distmax), dclear, dpair))
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,
