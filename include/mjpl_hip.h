@@ -258,6 +258,45 @@ int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, d
 int mjpl_clearance_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax,
                        double *dclear, int32_t *dpair);
 
+/* ---- clearance gradients and witness points ------------------------------------------------
+ * clear[i] and pair[i] are bit-identical to what mjpl_clearance returns for the same Q, layout and
+ * distmax.  Let p = pair[i] and (g1, g2) row p of mjpl_contact_pairs, in that row's orientation, and
+ * D = clear[i] + margin_p the pair's signed distance.
+ *   fromto[i*6 + 0..2] = w1, a point of g1; fromto[i*6 + 3..5] = w2, a point of g2 (world frame, the
+ *     layout of mj_geomDistance's fromto).  Disjoint: closest points.  Overlap: the two ends of the
+ *     shortest separating translation (along the separating axis that gave the depth).  Plane (always
+ *     g1): w2 is the geom's lowest point, w1 its projection on the plane.
+ *   normal[i*3 + 0..2] = n, the unit vector from g1 towards g2; w2 - w1 = D n up to rounding.
+ *   grad[i*nplan + j] = d clear / d q_j over the planning columns of mjpl_set_planning, in its order:
+ *     n . (v_j(w2 in body(g2)) - v_j(w1 in body(g1))), v_j(x) = axis_j x (x - anchor_j) for a hinge and
+ *     axis_j for a slide (world frame after FK, the frame the joint moves), and v_j(x) = 0 unless the
+ *     joint's body is the point's body or one of its ancestors (static geoms: 0).
+ * Ties between pairs resolve to the lowest index, as for clear.  Where the clearance is not
+ * differentiable (the closest pair or feature switches) the result is the one-sided gradient of the
+ * pair and feature the kernel picked; it need not equal a central difference there.
+ * status[i]:
+ *   MJPL_GRAD_OK          all outputs set.
+ *   MJPL_GRAD_FLAT        no non-allowed pair (pair = -1) or the winner is capped at distmax: grad
+ *                         exactly 0, fromto and normal NaN.
+ *   MJPL_GRAD_DEGENERATE  no normal can be formed: the disjoint core gap (closest points of the
+ *                         sphere points, capsule segments and boxes before the radii) is below 1e-10,
+ *                         e.g. crossing capsule axes: grad and normal NaN, fromto = the two core points.
+ *   MJPL_GRAD_NONFINITE   a planning column is non-finite: everything NaN, clear NaN, pair -1.
+ * fromto and normal may be NULL; every other output is required when N > 0.  N = 0 launches nothing.
+ * Argument errors as mjpl_clearance (MJPL_E_ARG, MJPL_E_PAIRTYPE).  The results depend on no option and
+ * no MJPL_* variable.  The host form synchronises; the device form is asynchronous on the engine's
+ * stream. */
+#define MJPL_GRAD_OK          0
+#define MJPL_GRAD_FLAT        1
+#define MJPL_GRAD_DEGENERATE  2
+#define MJPL_GRAD_NONFINITE   3
+int mjpl_clearance_grad(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax,
+                        double *clear, int32_t *pair, double *grad, double *fromto, double *normal,
+                        int32_t *status);
+int mjpl_clearance_grad_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax,
+                            double *dclear, int32_t *dpair, double *dgrad, double *dfromto, double *dnormal,
+                            int32_t *dstatus);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

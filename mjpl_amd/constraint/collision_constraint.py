@@ -11,6 +11,8 @@ device raises.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from .. import engine as _engine
@@ -36,6 +38,16 @@ def contact_csr(bits: np.ndarray, pairs: np.ndarray) -> tuple[np.ndarray, np.nda
     np.cumsum(hit.sum(axis=1), out=offsets[1:])
     _, p = np.nonzero(hit)  # row-major: configuration by configuration, pairs in table order
     return offsets, pairs[p]
+
+
+class ClearanceGradient(NamedTuple):
+    """One configuration's clearance with its gradient (``CollisionConstraint.clearance_gradient``)."""
+    clearance: float                   # min over non-allowed pairs of distance - margin (distmax if none)
+    pair: tuple[int, int] | None       # the geom pair attaining it (smaller geom type first), None if none
+    gradient: np.ndarray               # dC/dq, float64 [nq]
+    fromto: np.ndarray                 # witness points w1 (on pair[0]), w2 (on pair[1]), world frame, float64 [6]
+    normal: np.ndarray                 # unit vector from pair[0] towards pair[1], float64 [3]
+    status: int                        # engine.GRAD_OK / GRAD_FLAT / GRAD_DEGENERATE / GRAD_NONFINITE
 
 
 class CollisionRuleset:
@@ -201,6 +213,30 @@ class CollisionConstraint(Constraint):
         """``clearance`` for every row of [N, nq], one launch -> (C float64 [N], candidate-pair index int32 [N],
         -1 for none).  The same invariant holds row by row against ``valid_configs``."""
         return self.engine.clearance(self._full_batch(Q), distmax, _engine.AOS)
+
+    # ---- clearance gradients and witness points (``mj_geomDistance``'s fromto, dC/dq) ------------
+    def clearance_gradient(self, q: np.ndarray, distmax: float = np.inf) -> "ClearanceGradient":
+        """The clearance at the full-nq ``q`` with its gradient over nq, witness points and normal ->
+        :class:`ClearanceGradient`.  ``clearance_gradient(q).clearance == clearance(q)[0]`` bit for bit, and ``pair``
+        is ``clearance(q)[1]`` (g1, g2; fromto[:3] lies on g1, fromto[3:] on g2, normal points from g1 to g2).
+        Where the closest pair or feature switches, the gradient is the one-sided one of the pair picked."""
+        C, pair, grad, fromto, normal, status = self.clearance_gradient_batch(self._full_q(q), distmax)
+        geoms = None
+        if pair[0] >= 0:
+            g1, g2 = self.engine.contact_pairs()[0][pair[0]]
+            geoms = (int(g1), int(g2))
+        return ClearanceGradient(float(C[0]), geoms, grad[0], fromto[0], normal[0], int(status[0]))
+
+    def clearance_gradient_batch(self, Q: np.ndarray, distmax: float = np.inf):
+        """``clearance_gradient`` for every row of full-nq configurations [N, nq], one launch -> (C [N], candidate-pair
+        index [N], grad [N, nq], fromto [N, 6], normal [N, 3], status [N]); C and pair equal clearance_batch's."""
+        return self.engine.clearance_grad(self._full_batch(Q), distmax, _engine.AOS)
+
+    def clearance_gradient_planning(self, Qp: np.ndarray, distmax: float = np.inf, layout: int = _engine.AOS):
+        """``clearance_gradient_batch`` over the columns of ``set_planning`` (every other joint at its base value):
+        grad is [N, nplan], dC/dq over those columns; C and pair equal what a full-nq batch gives there."""
+        self._ensure_planning()
+        return self.engine.clearance_grad(Qp, distmax, layout)
 
     def valid_interval(self, start: np.ndarray, end: np.ndarray, step_dist: float) -> bool:
         """``_valid_collision_interval(start, end, step_dist, self)`` in one launch

@@ -33,6 +33,7 @@
 #include "mjpl_nearest_cells.h"
 #include "mjpl_contacts.h"
 #include "mjpl_distance.h"
+#include "mjpl_distance_grad.h"
 
 namespace {
 
@@ -412,6 +413,11 @@ struct mjpl_engine {
   size_t ct_scratch_bytes = 0;
   // distance table of mjpl_distances* / mjpl_clearance* (mjpl_distance.h: DT_*), made on first use from the model
   double *d_dt = nullptr;
+  // column / joint / geom tables of mjpl_clearance_grad* (mjpl_distance_grad.h: GC_*, JR_*), made at mjpl_create and
+  // remade by mjpl_set_planning; body pose scratch rows of one launch (grow-only)
+  double *d_gr = nullptr;
+  double *d_gr_scratch = nullptr;
+  size_t gr_scratch_bytes = 0;
 };
 
 namespace {
@@ -2073,6 +2079,126 @@ int launch_distance(mjpl_engine *e, const double *dQ, int64_t N, int layout, dou
   return MJPL_OK;
 }
 
+// The tables of k_clearance_grad (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
+// the number of later joints on that body and the body's subtree as DFS times; per model joint its type, axis,
+// position and where its dq comes from (as the FK program computes it); per geom the DFS entry time of its body.
+// Depends on the model and the planning selection: made at mjpl_create and by mjpl_set_planning.
+int build_grad_table(mjpl_engine *e) {
+  const HostModel &m = e->m;
+  const int nplan = (int)e->qidx.size(), nj = m.njnt, ng = m.ngeom, nb = m.nbody;
+  // DFS entry / exit times of the body tree (children in id order)
+  std::vector<std::vector<int>> kids(nb);
+  for (int b = 1; b < nb; b++) kids[m.body_parentid[b]].push_back(b);
+  std::vector<int> tin(nb, 0), tout(nb, 0), stack = {0};
+  std::vector<size_t> next(nb, 0);
+  int clock = 0;
+  tin[0] = clock++;
+  while (!stack.empty()) {
+    const int b = stack.back();
+    if (next[b] < kids[b].size()) {
+      const int k = kids[b][next[b]++];
+      tin[k] = clock++;
+      stack.push_back(k);
+    } else {
+      tout[b] = clock;
+      stack.pop_back();
+    }
+  }
+  std::vector<int> col_of(m.nq, -1);
+  for (int c = 0; c < nplan; c++) col_of[e->qidx[c]] = c;
+  std::vector<int> jnt_body(nj, 0);
+  for (int b = 0; b < nb; b++)
+    for (int j = 0; j < m.body_jntnum[b]; j++) jnt_body[m.body_jntadr[b] + j] = b;
+  std::vector<double> t((size_t)nplan * GC_LEN + (size_t)nj * JR_LEN + ng, 0.0);
+  double *gc = t.data(), *jr = gc + (size_t)nplan * GC_LEN, *gt = jr + (size_t)nj * JR_LEN;
+  for (int j = 0; j < nj; j++) {
+    const int qadr = m.jnt_qposadr[j];
+    double *r = jr + (size_t)j * JR_LEN;
+    r[JR_TYPE] = m.jnt_type[j];
+    for (int k = 0; k < 3; k++) {
+      r[JR_AXIS + k] = m.jnt_axis[3 * j + k];
+      r[JR_POS + k] = m.jnt_pos[3 * j + k];
+    }
+    r[JR_COL] = col_of[qadr];
+    r[JR_Q0] = col_of[qadr] >= 0 ? m.qpos0[qadr] : e->qbase[qadr] - m.qpos0[qadr];  // (the FK's qv - jd[6])
+  }
+  for (int c = 0; c < nplan; c++) {
+    int j = -1;
+    for (int k = 0; k < nj; k++)
+      if (m.jnt_qposadr[k] == e->qidx[c]) j = k;
+    if (j < 0) return fail(MJPL_E_JOINT, "planning column %d names qpos %d, which no joint owns", c, e->qidx[c]);
+    const int b = jnt_body[j];
+    double *r = gc + (size_t)c * GC_LEN;
+    r[GC_BODY] = b;
+    r[GC_JNT] = j;
+    r[GC_NLATER] = m.body_jntadr[b] + m.body_jntnum[b] - 1 - j;
+    r[GC_TIN] = tin[b];
+    r[GC_TOUT] = tout[b];
+  }
+  for (int g = 0; g < ng; g++) gt[g] = tin[m.geom_bodyid[g]];
+  if (e->d_gr) HIP_TRY(hipFree(e->d_gr));
+  e->d_gr = nullptr;
+  double *d = nullptr;
+  HIP_TRY(hipMalloc(&d, std::max<size_t>(t.size(), 1) * sizeof(double)));
+  const hipError_t err = hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    HIP_TRY(err);
+  }
+  e->d_gr = d;
+  return MJPL_OK;
+}
+
+// One k_clearance_grad launch per kContactRows configurations (the scratch holds that many rows of geom and
+// body poses).  dfromto / dnormal may be null.
+int launch_clearance_grad(mjpl_engine *e, const double *dQ, int64_t N, int layout, double distmax, double *dclear,
+                          int32_t *dpair, double *dgrad, double *dfromto, double *dnormal, int32_t *dstatus) {
+  const int P = (int)e->ct_g1.size();
+  if (N == 0) return MJPL_OK;
+  if (e->ct_unsupported >= 0) {
+    const int p = e->ct_unsupported;
+    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no distance routine here measures it",
+                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
+  }
+  int rc = build_distance_table(e);
+  if (rc != MJPL_OK) return rc;
+  const int ng = e->m.ngeom, nb = e->m.nbody, nplan = (int)e->qidx.size();
+  const int64_t rows = std::min<int64_t>(N, kContactRows);
+  if ((rc = contact_scratch(e, rows)) != MJPL_OK) return rc;
+  const size_t need = (size_t)rows * (size_t)nb * 7 * sizeof(double);
+  if (need > e->gr_scratch_bytes) {
+    if (e->d_gr_scratch) HIP_TRY(hipFree(e->d_gr_scratch));
+    e->d_gr_scratch = nullptr;
+    e->gr_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&e->d_gr_scratch, need));
+    e->gr_scratch_bytes = need;
+  }
+  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
+  GradOut go = {};
+  go.xpos = e->d_gr_scratch;
+  go.xquat = e->d_gr_scratch + (size_t)rows * nb * 3;
+  go.nbody = nb;
+  go.gcol = e->d_gr;
+  go.gjnt = e->d_gr + (size_t)nplan * GC_LEN;
+  go.gtin = go.gjnt + (size_t)e->m.njnt * JR_LEN;
+  go.status = dstatus;
+  const size_t lds = lds_bytes(e, 1);
+  if ((rc = allow_lds(k_clearance_grad, lds)) != MJPL_OK) return rc;
+  for (int64_t i0 = 0; i0 < N; i0 += rows) {
+    const int64_t n = std::min<int64_t>(rows, N - i0);
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    // (the epilogue indexes its outputs by the batch row i: whole arrays, as clear / pair)
+    go.grad = dgrad;
+    go.fromto = dfromto;
+    go.normal = dnormal;
+    hipLaunchKernelGGL(k_clearance_grad, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
+                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, gx, gm, ng,
+                       dclear, dpair, go);
+    HIP_TRY(hipGetLastError());
+  }
+  return MJPL_OK;
+}
+
 // argument checks shared by the four distance entry points (after check_common)
 int check_distance_args(double distmax, int64_t N, const void *out1, const void *out2) {
   if (!(distmax > 0)) return fail(MJPL_E_ARG, "distmax must be > 0 (NaN is refused), got %g", distmax);
@@ -2189,6 +2315,8 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
   if (rc != MJPL_OK) return bail(rc);
   rc = build_contact_table(e);
   if (rc != MJPL_OK) return bail(rc);
+  rc = build_grad_table(e);
+  if (rc != MJPL_OK) return bail(rc);
   *out = e;
   return MJPL_OK;
 }
@@ -2238,6 +2366,8 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
   if (e->d_ct_scratch) (void)hipFree(e->d_ct_scratch);
   if (e->d_dt) (void)hipFree(e->d_dt);
+  if (e->d_gr) (void)hipFree(e->d_gr);
+  if (e->d_gr_scratch) (void)hipFree(e->d_gr_scratch);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2310,7 +2440,9 @@ int mjpl_set_planning(mjpl_engine *e, const int32_t *qidx, int32_t nplan, const 
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->qidx = q;
   if (qpos_base) e->qbase.assign(qpos_base, qpos_base + e->m.nq);
-  return compile_program(e);
+  const int rc = compile_program(e);
+  if (rc != MJPL_OK) return rc;
+  return build_grad_table(e);
 }
 
 int mjpl_set_filter(mjpl_engine *e, int32_t enable, double tol) {
@@ -3377,6 +3509,58 @@ int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, d
     return rc;
   HIP_TRY(hipMemcpyAsync(clear, dclear, cb, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(pair, dpair, pb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MJPL_OK;
+}
+
+// ---- clearance gradients and witness points per configuration (mjpl_distance_grad.h)
+
+namespace {
+int check_grad_args(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, const double *clear,
+                    const int32_t *pair, const double *grad, const int32_t *status) {
+  int rc = check_common(e, Q, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if ((rc = check_distance_args(distmax, N, clear, pair)) != MJPL_OK) return rc;
+  if (N > 0 && (!grad || !status)) return fail(MJPL_E_ARG, "NULL output pointer");
+  return MJPL_OK;
+}
+}  // namespace
+
+int mjpl_clearance_grad_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *dclear,
+                            int32_t *dpair, double *dgrad, double *dfromto, double *dnormal, int32_t *dstatus) {
+  int rc = check_grad_args(e, dQ, N, layout, distmax, dclear, dpair, dgrad, dstatus);
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_clearance_grad(e, dQ, N, layout, distmax, dclear, dpair, dgrad, dfromto, dnormal, dstatus);
+}
+
+int mjpl_clearance_grad(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *clear,
+                        int32_t *pair, double *grad, double *fromto, double *normal, int32_t *status) {
+  int rc = check_grad_args(e, Q, N, layout, distmax, clear, pair, grad, status);
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t nplan = e->qidx.size();
+  const size_t qb = (size_t)N * nplan * sizeof(double);
+  // one staging block: grad, fromto, normal, clear (float64), then pair, status (int32)
+  const size_t gb = (size_t)N * nplan * sizeof(double), fb = fromto ? (size_t)N * 6 * sizeof(double) : 0,
+               nb = normal ? (size_t)N * 3 * sizeof(double) : 0, cb = (size_t)N * sizeof(double),
+               ib = (size_t)N * sizeof(int32_t);
+  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
+  if ((rc = stage_reserve(e, 1, gb + fb + nb + cb + 2 * ib)) != MJPL_OK) return rc;
+  char *o = (char *)e->stage[1];
+  double *dgrad = (double *)o, *dfromto = fromto ? (double *)(o + gb) : nullptr,
+         *dnormal = normal ? (double *)(o + gb + fb) : nullptr, *dclear = (double *)(o + gb + fb + nb);
+  int32_t *dpair = (int32_t *)(o + gb + fb + nb + cb), *dstatus = (int32_t *)(o + gb + fb + nb + cb + ib);
+  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
+  if ((rc = launch_clearance_grad(e, (const double *)e->stage[0], N, layout, distmax, dclear, dpair, dgrad, dfromto,
+                                  dnormal, dstatus)) != MJPL_OK)
+    return rc;
+  if (gb) HIP_TRY(hipMemcpyAsync(grad, dgrad, gb, hipMemcpyDeviceToHost, e->stream));
+  if (fb) HIP_TRY(hipMemcpyAsync(fromto, dfromto, fb, hipMemcpyDeviceToHost, e->stream));
+  if (nb) HIP_TRY(hipMemcpyAsync(normal, dnormal, nb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(clear, dclear, cb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(pair, dpair, ib, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(status, dstatus, ib, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return MJPL_OK;
 }

@@ -16,6 +16,8 @@ from . import build as _build
 from .model import Model
 
 SOA, AOS = 0, 1
+# mjpl_clearance_grad* status values (include/mjpl_hip.h: MJPL_GRAD_*)
+GRAD_OK, GRAD_FLAT, GRAD_DEGENERATE, GRAD_NONFINITE = 0, 1, 2, 3
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -127,6 +129,9 @@ ABI = {
     "mjpl_distances_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP]),
     "mjpl_clearance": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P, _I32P]),
     "mjpl_clearance_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP, _VP]),
+    "mjpl_clearance_grad": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P, _I32P, _F64P, _F64P, _F64P,
+                                      _I32P]),
+    "mjpl_clearance_grad_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -535,6 +540,30 @@ class Engine:
     def clearance_dev(self, dQ, n, layout, dclear, dpair, distmax=float("inf")):
         """clearance() on device pointers: dclear receives n float64, dpair n int32 (asynchronous)."""
         self._ok(self.lib.mjpl_clearance_dev(self.h, dQ, n, layout, float(distmax), dclear, dpair))
+
+    # -- clearance gradients and witness points (include/mjpl_hip.h, mjpl_clearance_grad*)
+    def clearance_grad(self, Q, distmax=float("inf"), layout=AOS):
+        """(C float64 [N], pair int32 [N], grad float64 [N, nplan], fromto float64 [N, 6], normal float64 [N, 3],
+        status int32 [N]).  C and pair are clearance()'s, bit for bit; grad = dC/dq over the planning columns;
+        fromto = (w1 on g1, w2 on g2) of contact_pairs()[0][pair] in the world frame; normal = unit vector from g1
+        towards g2.  status: GRAD_OK, GRAD_FLAT (no pair or capped at distmax: grad 0), GRAD_DEGENERATE (no normal:
+        grad and normal NaN), GRAD_NONFINITE (non-finite input: all NaN)."""
+        Q, n = self._batch(Q, layout)
+        C_, pair = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        grad, fromto = np.zeros((n, self.nplan), np.float64), np.zeros((n, 6), np.float64)
+        normal, status = np.zeros((n, 3), np.float64), np.zeros(n, np.int32)
+        self._ok(self.lib.mjpl_clearance_grad(self.h, Q.ctypes.data_as(_F64P), n, layout, float(distmax),
+                                              C_.ctypes.data_as(_F64P), pair.ctypes.data_as(_I32P),
+                                              grad.ctypes.data_as(_F64P), fromto.ctypes.data_as(_F64P),
+                                              normal.ctypes.data_as(_F64P), status.ctypes.data_as(_I32P)))
+        return C_, pair, grad, fromto, normal, status
+
+    def clearance_grad_dev(self, dQ, n, layout, dclear, dpair, dgrad, dstatus, dfromto=None, dnormal=None,
+                           distmax=float("inf")):
+        """clearance_grad() on device pointers: dclear n float64, dpair n int32, dgrad n * nplan float64, dstatus n
+        int32, dfromto n * 6 and dnormal n * 3 float64 (either may be None).  Asynchronous on the engine's stream."""
+        self._ok(self.lib.mjpl_clearance_grad_dev(self.h, dQ, n, layout, float(distmax), dclear, dpair, dgrad, dfromto,
+                                                  dnormal, dstatus))
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,
