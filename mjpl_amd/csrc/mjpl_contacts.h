@@ -51,6 +51,47 @@ __device__ __forceinline__ void contact_load_geom(GeomT<double> &g, const double
   }
 }
 
+// Candidate pair p, its geoms placed as the check places them: cur from the lane's scratch row, par from it (moving)
+// or from the world tables (static: cull table position, narrow table axes and size).  Inactive lanes get zero poses.
+// UNI: p is wave-uniform and the record is read as such (the walks); the epilogue's p differs per lane.
+struct PairGeoms {
+  int gcur, gparid, tcur, tpar, flags;  // model geom ids of cur and par, CI_TCUR, CI_TPAR, CI_FLAGS
+  GeomT<double> cur, par;
+  double scur[3], spar[3];
+};
+
+template <bool UNI>
+__device__ __forceinline__ PairGeoms contact_load_pair(IP ct, DP cd, int p, const double *rx, const double *rm,
+                                                       DP wcull, DP wnarrow, bool active) {
+  IP e = ct + p * CI_LEN;
+  DP d = cd + p * CD_LEN;
+  auto rec = [](int v) { return UNI ? uni(v) : v; };
+  PairGeoms g;
+  const int gpar = rec(e[CI_PAR]);
+  g.gcur = rec(e[CI_CUR]);
+  g.gparid = rec(e[CI_PARID]);
+  g.tcur = rec(e[CI_TCUR]);
+  g.tpar = rec(e[CI_TPAR]);
+  g.flags = rec(e[CI_FLAGS]);
+  for (int k = 0; k < 3; k++) g.scur[k] = d[CD_SCUR + k];
+  if (active) contact_load_geom(g.cur, rx, rm, g.gcur, g.tcur);
+  else g.cur = GeomT<double>{};
+  if (g.flags & CF_STATIC) {
+    DP rw = wnarrow + gpar * WN_LEN;
+    g.par.pos[0] = wcull[wc_at(gpar, 0)]; g.par.pos[1] = wcull[wc_at(gpar, 1)]; g.par.pos[2] = wcull[wc_at(gpar, 2)];
+    g.par.m[2] = rw[WN_ZAXIS]; g.par.m[5] = rw[WN_ZAXIS + 1]; g.par.m[8] = rw[WN_ZAXIS + 2];
+    g.par.m[0] = rw[WN_XAXIS]; g.par.m[3] = rw[WN_XAXIS + 1]; g.par.m[6] = rw[WN_XAXIS + 2];
+    g.par.m[1] = rw[WN_YAXIS]; g.par.m[4] = rw[WN_YAXIS + 1]; g.par.m[7] = rw[WN_YAXIS + 2];
+    // (a plane's narrowphase size is no input of the plane routines; the check passes zeros)
+    for (int k = 0; k < 3; k++) g.spar[k] = g.tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
+  } else {
+    if (active) contact_load_geom(g.par, rx, rm, gpar, g.tpar);
+    else g.par = GeomT<double>{};
+    for (int k = 0; k < 3; k++) g.spar[k] = d[CD_SPAR + k];
+  }
+  return g;
+}
+
 // Configurations [i0, i0 + n) of the batch Q (N rows, `layout`); scratch row r = i - i0 holds
 // configuration i's moving geom poses: gx [n][ngeom][3], gm [n][ngeom][9].
 __global__ void __launch_bounds__(kBlock)
@@ -87,35 +128,15 @@ k_contacts(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
     unsigned long long word = 0;
     const int pend = P < 64 * (w + 1) ? P : 64 * (w + 1);
     for (int p = 64 * w; p < pend; p++) {
-      IP e = ct + p * CI_LEN;
+      const PairGeoms g = contact_load_pair<true>(ct, cd, p, rx, rm, wcull, wnarrow, active);
       DP d = cd + p * CD_LEN;
-      const int gcur = uni(e[CI_CUR]), gpar = uni(e[CI_PAR]);
-      const int tcur = uni(e[CI_TCUR]), tpar = uni(e[CI_TPAR]), flags = uni(e[CI_FLAGS]);
-      GeomT<double> cur, par;
-      double spar[3];
-      const double scur[3] = {d[CD_SCUR], d[CD_SCUR + 1], d[CD_SCUR + 2]};
-      if (active) contact_load_geom(cur, rx, rm, gcur, tcur);
-      else cur = GeomT<double>{};
-      if (flags & CF_STATIC) {
-        DP rw = wnarrow + gpar * WN_LEN;
-        par.pos[0] = wcull[wc_at(gpar, 0)]; par.pos[1] = wcull[wc_at(gpar, 1)]; par.pos[2] = wcull[wc_at(gpar, 2)];
-        par.m[2] = rw[WN_ZAXIS]; par.m[5] = rw[WN_ZAXIS + 1]; par.m[8] = rw[WN_ZAXIS + 2];
-        par.m[0] = rw[WN_XAXIS]; par.m[3] = rw[WN_XAXIS + 1]; par.m[6] = rw[WN_XAXIS + 2];
-        par.m[1] = rw[WN_YAXIS]; par.m[4] = rw[WN_YAXIS + 1]; par.m[7] = rw[WN_YAXIS + 2];
-        // (a plane's narrowphase size is no input of the plane routines; the check passes zeros)
-        for (int k = 0; k < 3; k++) spar[k] = tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
-      } else {
-        if (active) contact_load_geom(par, rx, rm, gpar, tpar);
-        else par = GeomT<double>{};
-        for (int k = 0; k < 3; k++) spar[k] = d[CD_SPAR + k];
-      }
       // the check's bound cull: plane partners by signed distance, all others by centre distance
       const double bound = d[CD_BOUND];
       bool pass;
       {
-        const double dif[3] = {cur.pos[0] - par.pos[0], cur.pos[1] - par.pos[1], cur.pos[2] - par.pos[2]};
-        if (tpar == GT_PLANE) {
-          const double nrm[3] = {par.m[2], par.m[5], par.m[8]};
+        const double dif[3] = {g.cur.pos[0] - g.par.pos[0], g.cur.pos[1] - g.par.pos[1], g.cur.pos[2] - g.par.pos[2]};
+        if (g.tpar == GT_PLANE) {
+          const double nrm[3] = {g.par.m[2], g.par.m[5], g.par.m[8]};
           pass = !(dot3(dif, nrm) > bound);
         } else {
           pass = !(dif[0] * dif[0] + dif[1] * dif[1] + dif[2] * dif[2] > bound);
@@ -123,8 +144,8 @@ k_contacts(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
       }
       pass = pass && active;
       if (__builtin_amdgcn_ballot_w64(pass) == 0ull) continue;
-      const int code = pair_contact<double, true, true>(tcur, cur, scur, tpar, par, spar, (flags & CF_PFIRST) != 0,
-                                                        d[CD_MARGIN], 0.0);
+      const int code = pair_contact<double, true, true>(g.tcur, g.cur, g.scur, g.tpar, g.par, g.spar,
+                                                        (g.flags & CF_PFIRST) != 0, d[CD_MARGIN], 0.0);
       if (pass && code == V_CONTACT) word |= 1ull << (p & 63);
     }
     if (active) bits[i * W + w] = word;

@@ -11,9 +11,11 @@
 //   2. It walks the candidate table in order with a wave-uniform pair index.  Per pair: a bound cull against
 //      distmax (|c1 - c2| - rb1 - rb2, or the signed centre distance - rb for a plane), then -- if any lane of
 //      the wave still needs it -- the pair's distance routine.
-//   3. k_distance<false> (distances) stores D[i][p] = min(d_p, distmax); k_distance<true> (clearance) keeps
+//   3. k_distance<DM_DIST> (distances) stores D[i][p] = min(d_p, distmax); k_distance<DM_CLEAR> (clearance) keeps
 //      (min over non-allowed pairs of D - margin, its pair index) in registers and stores 12 bytes per
-//      configuration.
+//      configuration; k_distance<DM_GRAD> (clearance gradients) does the same, then runs the epilogue of
+//      mjpl_distance_grad.h once per lane.
+// The walks of all three modes and of k_contacts load a pair's geoms with contact_load_pair (mjpl_contacts.h).
 //
 // The routines reduce every non-plane pair to core distance minus radii (sphere = point, capsule = segment,
 // box = box).  Disjoint cores: the minimum over the feature pairs that can hold the closest points (end
@@ -38,8 +40,10 @@ constexpr double kDistTiny = 1e-30;
 __device__ __forceinline__ double dist_clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
 
 // squared distance between the segments p1 + s d1 and p2 + t d2 (s, t in [0, 1]): closest points with each
-// parameter optimal for the other after clamping; parallel and degenerate segments included
-__device__ __forceinline__ double seg_seg_d2(const double *p1, const double *d1, const double *p2, const double *d2) {
+// parameter optimal for the other after clamping; parallel and degenerate segments included.  c1, c2 (both or
+// neither): the closest points, for the witness routines of mjpl_distance_grad.h.
+__device__ __forceinline__ double seg_seg_d2(const double *p1, const double *d1, const double *p2, const double *d2,
+                                             double *c1 = nullptr, double *c2 = nullptr) {
   const double r[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
   const double a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
   double s, t;
@@ -61,28 +65,39 @@ __device__ __forceinline__ double seg_seg_d2(const double *p1, const double *d1,
   double w2 = 0;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const double w = (p1[k] + d1[k] * s) - (p2[k] + d2[k] * t);
+    const double x1 = p1[k] + d1[k] * s, x2 = p2[k] + d2[k] * t;
+    const double w = x1 - x2;
     w2 += w * w;
+    if (c1) {
+      c1[k] = x1;
+      c2[k] = x2;
+    }
   }
   return w2;
 }
 
-// squared distance from the point p to the segment q + t d, t in [0, 1]
-__device__ __forceinline__ double pt_seg_d2(const double *p, const double *q, const double *d) {
+// squared distance from the point p to the segment q + t d, t in [0, 1]; c: the segment's closest point
+__device__ __forceinline__ double pt_seg_d2(const double *p, const double *q, const double *d, double *c = nullptr) {
   const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
   const double dd = dot3(d, d);
   const double t = dd <= kDistTiny ? 0.0 : dist_clamp01(dot3(r, d) / dd);
   const double w[3] = {r[0] - d[0] * t, r[1] - d[1] * t, r[2] - d[2] * t};
+  if (c) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = q[k] + d[k] * t;
+  }
   return dot3(w, w);
 }
 
-// squared distance from the point p (box frame) to the box |x_k| <= s_k; 0 inside
-__device__ __forceinline__ double pt_box_d2(const double *p, const double *s) {
+// squared distance from the point p (box frame) to the box |x_k| <= s_k, 0 inside; c: the box's closest point
+__device__ __forceinline__ double pt_box_d2(const double *p, const double *s, double *c = nullptr) {
   double w2 = 0;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const double w = p[k] - fmin(fmax(p[k], -s[k]), s[k]);
+    const double x = fmin(fmax(p[k], -s[k]), s[k]);
+    const double w = p[k] - x;
     w2 += w * w;
+    if (c) c[k] = x;
   }
   return w2;
 }
@@ -302,17 +317,35 @@ __device__ __forceinline__ double pair_distance(int tcur, const GeomT<double> &c
   return core_core_distance(cur, scur, tcur == GT_CAPSULE, par, spar, tpar == GT_CAPSULE);
 }
 
+// The kernel's three modes: distances, clearance, and clearance with the gradient epilogue.
+enum : int { DM_DIST = 0, DM_CLEAR, DM_GRAD };
+
+// DM_GRAD's scratch, tables and outputs (mjpl_distance_grad.h)
+struct GradOut {
+  double *xpos, *xquat;  // body pose scratch rows (nbody per row), written by the FK
+  int nbody;
+  const double *gcol, *gjnt, *gtin;  // column table [nplan][GC_LEN], joint table [njnt][JR_LEN], tin per geom
+  double *grad, *fromto, *normal;    // [N][nplan], [N][6] (may be null), [N][3] (may be null)
+  int *status;
+};
+
+// DM_GRAD's epilogue (mjpl_distance_grad.h)
+__device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<double> &c, IP ct, DP cd, DP wcull,
+                                              DP wnarrow, const double *rx, const double *rm, int64_t i, int64_t row,
+                                              int nplan, bool live, int bestp, bool bestcap);
+
 // Configurations [i0, i0 + n) of the batch Q (N rows, `layout`), FK scratch rows as k_contacts uses them.
-// CLEAR = false: dist[i * P + p] = min(d_p, distmax).  CLEAR = true: clear[i] = min over non-allowed p of
-// (min(d_p, distmax) - margin_p), pair[i] = its lowest index (distmax, -1 without such a pair).  A row with a
+// DM_DIST: dist[i * P + p] = min(d_p, distmax).  DM_CLEAR: clear[i] = min over non-allowed p of
+// (min(d_p, distmax) - margin_p), pair[i] = its lowest index (distmax, -1 without such a pair).  DM_GRAD: clear and
+// pair as DM_CLEAR, the body poses also written to go's scratch rows, then go's outputs at row i.  A row with a
 // non-finite planning column gives NaN (and pair -1).
-template <bool CLEAR>
+template <int MODE>
 __global__ void __launch_bounds__(kBlock)
 k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp, int ndp,
            const int *__restrict__ gct, const double *__restrict__ gcd, const double *__restrict__ gdt, int P,
            const double *__restrict__ Q, int64_t N, int64_t i0, int64_t n, int layout, double distmax,
            double *__restrict__ gx, double *__restrict__ gm, int ngeom, double *__restrict__ dist,
-           double *__restrict__ clear, int *__restrict__ pair) {
+           double *__restrict__ clear, int *__restrict__ pair, GradOut go) {
   extern __shared__ double smem[];
   const int B = blockDim.x;
   const int nplan = gip[H_NPLAN];
@@ -326,11 +359,16 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
   for (int k = 0; k < nplan; k++) finite = finite && __builtin_isfinite(c.col0[k * B + threadIdx.x]);
   const bool live = active && finite;
 
-  // 1. forward kinematics into the scratch row
+  // 1. forward kinematics into the scratch row (DM_GRAD: the body poses too, for the epilogue)
   FkOut out = {};
   out.geom_xpos = gx;
   out.geom_xmat = gm;
   out.ngeom = ngeom;
+  if (MODE == DM_GRAD) {
+    out.xpos = go.xpos;
+    out.xquat = go.xquat;
+    out.nbody = go.nbody;
+  }
   run_config<double, 1, true, true, true>(c.ip, c.tp, c.col0 + threadIdx.x, B, c.save + threadIdx.x, B, active, 0.0,
                                           out, active ? r : 0);
   const double *rx = gx + (active ? r : 0) * ngeom * 3;
@@ -342,39 +380,21 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
   DP dt = (DP)gdt;
   DP wcull = c.tp + uni(c.ip[H_OFF_WCULL]);
   DP wnarrow = c.tp + uni(c.ip[H_OFF_WNARROW]);
-  double best = distmax;  // CLEAR: least D - margin so far, at pair index bestp
+  double best = distmax;  // DM_CLEAR / DM_GRAD: least D - margin so far, at pair index bestp
   int bestp = -1;
+  bool bestcap = true;  // DM_GRAD: the winner's D is distmax (a cap: no geometry to differentiate)
   for (int p = 0; p < P; p++) {
-    IP e = ct + p * CI_LEN;
-    DP d = cd + p * CD_LEN;
-    if (CLEAR && uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;  // (uniform: allowed pairs take no part)
-    const int gcur = uni(e[CI_CUR]), gpar = uni(e[CI_PAR]);
-    const int tcur = uni(e[CI_TCUR]), tpar = uni(e[CI_TPAR]), flags = uni(e[CI_FLAGS]);
-    GeomT<double> cur, par;
-    double spar[3];
-    const double scur[3] = {d[CD_SCUR], d[CD_SCUR + 1], d[CD_SCUR + 2]};
-    if (active) contact_load_geom(cur, rx, rm, gcur, tcur);
-    else cur = GeomT<double>{};
-    if (flags & CF_STATIC) {
-      DP rw = wnarrow + gpar * WN_LEN;
-      par.pos[0] = wcull[wc_at(gpar, 0)]; par.pos[1] = wcull[wc_at(gpar, 1)]; par.pos[2] = wcull[wc_at(gpar, 2)];
-      par.m[2] = rw[WN_ZAXIS]; par.m[5] = rw[WN_ZAXIS + 1]; par.m[8] = rw[WN_ZAXIS + 2];
-      par.m[0] = rw[WN_XAXIS]; par.m[3] = rw[WN_XAXIS + 1]; par.m[6] = rw[WN_XAXIS + 2];
-      par.m[1] = rw[WN_YAXIS]; par.m[4] = rw[WN_YAXIS + 1]; par.m[7] = rw[WN_YAXIS + 2];
-      for (int k = 0; k < 3; k++) spar[k] = tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
-    } else {
-      if (active) contact_load_geom(par, rx, rm, gpar, tpar);
-      else par = GeomT<double>{};
-      for (int k = 0; k < 3; k++) spar[k] = d[CD_SPAR + k];
-    }
-    const double margin = d[CD_MARGIN];
+    // (uniform: allowed pairs take no part in the clearance)
+    if (MODE != DM_DIST && uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;
+    const PairGeoms g = contact_load_pair<true>(ct, cd, p, rx, rm, wcull, wnarrow, active);
+    const double margin = cd[p * CD_LEN + CD_MARGIN];
     // lower bound of the distance: bounding spheres, or the centre's height above a plane minus rb
     double lb;
     {
-      const double dif[3] = {cur.pos[0] - par.pos[0], cur.pos[1] - par.pos[1], cur.pos[2] - par.pos[2]};
+      const double dif[3] = {g.cur.pos[0] - g.par.pos[0], g.cur.pos[1] - g.par.pos[1], g.cur.pos[2] - g.par.pos[2]};
       const double rb = dt[p * DT_LEN + DT_RBSUM];
-      if (tpar == GT_PLANE) {
-        const double nrm[3] = {par.m[2], par.m[5], par.m[8]};
+      if (g.tpar == GT_PLANE) {
+        const double nrm[3] = {g.par.m[2], g.par.m[5], g.par.m[8]};
         lb = dot3(dif, nrm) - rb;
       } else {
         lb = sqrt(dot3(dif, dif)) - rb;
@@ -382,28 +402,31 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
     }
     const bool far = lb >= distmax + kDistCullSlack;  // D = distmax, no routine
     bool need = live && !far;
-    // CLEAR: a pair whose D - margin must exceed the least so far cannot change (C, pair)
-    if (CLEAR) need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
+    // a pair whose D - margin must exceed the least so far cannot change (C, pair)
+    if (MODE != DM_DIST) need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
     double D = distmax;
     if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
-      const double x = pair_distance(tcur, cur, scur, tpar, par, spar);
+      const double x = pair_distance(g.tcur, g.cur, g.scur, g.tpar, g.par, g.spar);
       if (need) D = x < distmax ? x : distmax;
     }
-    if constexpr (CLEAR) {
+    if constexpr (MODE == DM_DIST) {
+      if (active) dist[i * P + p] = live ? D : NAN;
+    } else {
       const double v = D - margin;
       if (live && (need || far) && (bestp < 0 || v < best)) {
         best = v;
         bestp = p;
+        bestcap = !(D < distmax);
       }
-    } else {
-      if (active) dist[i * P + p] = live ? D : NAN;
     }
   }
-  if constexpr (CLEAR) {
-    if (active) {
-      clear[i] = live ? best : NAN;
-      pair[i] = live ? bestp : -1;
-    }
+  if constexpr (MODE != DM_DIST) {
+    if (!active) return;
+    clear[i] = live ? best : NAN;
+    pair[i] = live ? bestp : -1;
+    // 3. DM_GRAD: the epilogue (lanes diverge from here on)
+    if constexpr (MODE == DM_GRAD)
+      grad_epilogue(go, c, ct, cd, wcull, wnarrow, rx, rm, i, r, nplan, live, bestp, bestcap);
   }
 }
 

@@ -1,10 +1,9 @@
 // mjpl_distance_grad.h -- clearance gradients and witness points per configuration (mjpl_clearance_grad*).
 //
-// k_clearance_grad is k_distance<true> (mjpl_distance.h) with an epilogue:
-//   1. Phase 1 is k_distance<true>'s body statement for statement: FK into the scratch rows (here also the body
-//      poses), the table walk, the cull and the winner's comparisons, so clear and pair come out bit-identical to
-//      mjpl_clearance (tests/test_gpu_clearance_grad.py compares the bytes).  k_distance itself is left alone:
-//      sharing its body through a function changed its machine code.
+// The clearance gradients are k_distance<DM_GRAD> (mjpl_distance.h): the clearance kernel's walk itself, with the
+// body poses also written to scratch and this file's epilogue after it.
+//   1. The walk is DM_CLEAR's (same FK, table walk, cull and winner's comparisons), so clear and pair come out
+//      bit-identical to mjpl_clearance (tests/test_gpu_clearance_grad.py compares the bytes).
 //   2. Once per lane, the winner's pair is measured again by a witness variant of its routine, which keeps the
 //      argmin feature beside each minimum: (w_cur, w_par, n) with n the unit vector from cur towards par and
 //      w_par - w_cur = D n.  The pair types differ per lane, so this step diverges once per lane.
@@ -33,14 +32,6 @@ constexpr double kGradDegenerate = 1e-10;
 enum : int { GC_BODY = 0, GC_JNT, GC_NLATER, GC_TIN, GC_TOUT, GC_LEN };
 enum : int { JR_TYPE = 0, JR_AXIS, JR_POS = 4, JR_COL = 7, JR_Q0, JR_LEN };  // dq = q[col] - q0, or q0 (col < 0)
 
-struct GradOut {
-  double *xpos, *xquat;  // body pose scratch rows (nbody per row), written by the FK
-  int nbody;
-  const double *gcol, *gjnt, *gtin;  // column table [nplan][GC_LEN], joint table [njnt][JR_LEN], tin per geom
-  double *grad, *fromto, *normal;    // [N][nplan], [N][6] (may be null), [N][3] (may be null)
-  int *status;
-};
-
 __device__ __forceinline__ void set3(double *o, const double *a) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
 __device__ __forceinline__ void cross3(double *o, const double *a, const double *b) {
   o[0] = a[1] * b[2] - a[2] * b[1];
@@ -48,69 +39,15 @@ __device__ __forceinline__ void cross3(double *o, const double *a, const double 
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// seg_seg_d2 with its closest points (same operations, same value)
-__device__ __forceinline__ double seg_seg_cp(const double *p1, const double *d1, const double *p2, const double *d2,
-                                             double *c1, double *c2) {
-  const double r[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-  const double a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
-  double s, t;
-  if (e <= kDistTiny) {
-    t = 0.0;
-    s = a <= kDistTiny ? 0.0 : dist_clamp01(-c / a);
-  } else {
-    const double denom = a * e - b * b;
-    s = (a > kDistTiny && denom > 0) ? dist_clamp01((b * f - c * e) / denom) : 0.0;
-    t = (b * s + f) / e;
-    if (t < 0) {
-      t = 0.0;
-      s = a <= kDistTiny ? 0.0 : dist_clamp01(-c / a);
-    } else if (t > 1) {
-      t = 1.0;
-      s = a <= kDistTiny ? 0.0 : dist_clamp01((b - c) / a);
-    }
-  }
-  double w2 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    c1[k] = p1[k] + d1[k] * s;
-    c2[k] = p2[k] + d2[k] * t;
-    const double w = c1[k] - c2[k];
-    w2 += w * w;
-  }
-  return w2;
-}
-
-// pt_seg_d2 with the segment's closest point
-__device__ __forceinline__ double pt_seg_cp(const double *p, const double *q, const double *d, double *c) {
-  const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-  const double dd = dot3(d, d);
-  const double t = dd <= kDistTiny ? 0.0 : dist_clamp01(dot3(r, d) / dd);
-  const double w[3] = {r[0] - d[0] * t, r[1] - d[1] * t, r[2] - d[2] * t};
-#pragma unroll
-  for (int k = 0; k < 3; k++) c[k] = q[k] + d[k] * t;
-  return dot3(w, w);
-}
-
-// pt_box_d2 with the box's closest point
-__device__ __forceinline__ double pt_box_cp(const double *p, const double *s, double *c) {
-  double w2 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    c[k] = fmin(fmax(p[k], -s[k]), s[k]);
-    const double w = p[k] - c[k];
-    w2 += w * w;
-  }
-  return w2;
-}
-
-// seg_box_disjoint_d2 with the closest points: cs on the segment p + t d, cb on the box (box frame)
+// seg_box_disjoint_d2 with the closest points: cs on the segment p + t d, cb on the box (box frame).  (An enumeration
+// of its own, as box_box_cp's: `x < best` keeps a NaN that comes first where seg_box_disjoint_d2's fmin drops it.)
 __device__ __forceinline__ double seg_box_cp(const double *p, const double *d, const double *s, double *cs, double *cb) {
   const double q[3] = {p[0] + d[0], p[1] + d[1], p[2] + d[2]};
-  double best = pt_box_cp(p, s, cb);
+  double best = pt_box_d2(p, s, cb);
   set3(cs, p);
   {
     double c[3];
-    const double x = pt_box_cp(q, s, c);
+    const double x = pt_box_d2(q, s, c);
     if (x < best) { best = x; set3(cs, q); set3(cb, c); }
   }
 #pragma unroll
@@ -125,7 +62,7 @@ __device__ __forceinline__ double seg_box_cp(const double *p, const double *d, c
       e[k] = 2 * s[k];
       e[i] = 0.0;
       e[j] = 0.0;
-      const double x = seg_seg_cp(p, d, a, e, c1, c2);
+      const double x = seg_seg_d2(p, d, a, e, c1, c2);
       if (x < best) { best = x; set3(cs, c1); set3(cb, c2); }
     }
   }
@@ -156,18 +93,18 @@ __device__ __forceinline__ int core_core_witness(const GeomT<double> &g1, const 
     p2[k] = g2.pos[k] - h2 * g2.m[3 * k + 2];
   }
   double c1[3], c2[3];
-  double w2 = seg_seg_cp(p1, d1, p2, d2, c1, c2);
+  double w2 = seg_seg_d2(p1, d1, p2, d2, c1, c2);
   if (seg1 && seg2) {  // the end points against the other segment, as core_core_distance takes them
     const double q1[3] = {p1[0] + d1[0], p1[1] + d1[1], p1[2] + d1[2]};
     const double q2[3] = {p2[0] + d2[0], p2[1] + d2[1], p2[2] + d2[2]};
     double c[3], x;
-    x = pt_seg_cp(p1, p2, d2, c);
+    x = pt_seg_d2(p1, p2, d2, c);
     if (x < w2) { w2 = x; set3(c1, p1); set3(c2, c); }
-    x = pt_seg_cp(q1, p2, d2, c);
+    x = pt_seg_d2(q1, p2, d2, c);
     if (x < w2) { w2 = x; set3(c1, q1); set3(c2, c); }
-    x = pt_seg_cp(p2, p1, d1, c);
+    x = pt_seg_d2(p2, p1, d1, c);
     if (x < w2) { w2 = x; set3(c1, c); set3(c2, p2); }
-    x = pt_seg_cp(q2, p1, d1, c);
+    x = pt_seg_d2(q2, p1, d1, c);
     if (x < w2) { w2 = x; set3(c1, c); set3(c2, q2); }
   }
   if (!unit_from_to(c1, c2, n)) {  // (the core points themselves)
@@ -243,7 +180,7 @@ __device__ __forceinline__ int core_box_witness(bool seg, const GeomT<double> &g
   if (seg) {
     (void)seg_box_cp(p, d, sb, cs, cb);
   } else {
-    (void)pt_box_cp(p, sb, cb);
+    (void)pt_box_d2(p, sb, cb);
     set3(cs, p);
   }
   int st = GS_OK;
@@ -305,7 +242,7 @@ __device__ __forceinline__ void box_box_cp(const double *R, const double *t, con
     const double w[3] = {v[0] - t[0], v[1] - t[1], v[2] - t[2]};
     double uu[3], cl[3];
     mul_matT_vec3(uu, R, w);
-    const double x = pt_box_cp(uu, s2, cl);
+    const double x = pt_box_d2(uu, s2, cl);
     if (x < best) {
       best = x;
       set3(c1, v);
@@ -498,36 +435,31 @@ __device__ __forceinline__ void column_frame(const GradOut &go, DP col, const do
   for (int m = 0; m < 3; m++) anchor[m] += p[m];
 }
 
-// the epilogue, once per live lane that has a winner: witnesses, normal, status and the gradient
-__device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<double> &c, IP ct, DP cd, DP wcull, DP wnarrow,
-                                              const double *rx, const double *rm, int64_t i, int64_t row, int nplan,
-                                              int bestp) {
+// The epilogue, once per active lane after the walk: FLAT / NONFINITE rows when there is nothing to differentiate,
+// otherwise the winner's witnesses, normal, status and gradient.
+__device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<double> &c, IP ct, DP cd, DP wcull,
+                                              DP wnarrow, const double *rx, const double *rm, int64_t i, int64_t row,
+                                              int nplan, bool live, int bestp, bool bestcap) {
+  if (!live || bestp < 0 || bestcap) {
+    for (int j = 0; j < nplan; j++) go.grad[i * nplan + j] = live ? 0.0 : NAN;
+    if (go.fromto)
+      for (int k = 0; k < 6; k++) go.fromto[i * 6 + k] = NAN;
+    if (go.normal)
+      for (int k = 0; k < 3; k++) go.normal[i * 3 + k] = NAN;
+    go.status[i] = live ? GS_FLAT : GS_NONFINITE;
+    return;
+  }
   const int B = blockDim.x;
   double *grad = go.grad + i * nplan;
   // the winner, loaded as the walk loads it (the index differs per lane here)
-  IP e = ct + bestp * CI_LEN;
-  DP d = cd + bestp * CD_LEN;
-  const int gcur = e[CI_CUR], gpar = e[CI_PAR], gparid = e[CI_PARID];
-  const int tcur = e[CI_TCUR], tpar = e[CI_TPAR], flags = e[CI_FLAGS];
-  GeomT<double> cur, par;
-  double spar[3];
-  const double scur[3] = {d[CD_SCUR], d[CD_SCUR + 1], d[CD_SCUR + 2]};
-  contact_load_geom(cur, rx, rm, gcur, tcur);
-  if (flags & CF_STATIC) {
-    DP rw = wnarrow + gpar * WN_LEN;
-    par.pos[0] = wcull[wc_at(gpar, 0)]; par.pos[1] = wcull[wc_at(gpar, 1)]; par.pos[2] = wcull[wc_at(gpar, 2)];
-    par.m[2] = rw[WN_ZAXIS]; par.m[5] = rw[WN_ZAXIS + 1]; par.m[8] = rw[WN_ZAXIS + 2];
-    par.m[0] = rw[WN_XAXIS]; par.m[3] = rw[WN_XAXIS + 1]; par.m[6] = rw[WN_XAXIS + 2];
-    par.m[1] = rw[WN_YAXIS]; par.m[4] = rw[WN_YAXIS + 1]; par.m[7] = rw[WN_YAXIS + 2];
-    for (int k = 0; k < 3; k++) spar[k] = tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
-  } else {
-    contact_load_geom(par, rx, rm, gpar, tpar);
-    for (int k = 0; k < 3; k++) spar[k] = d[CD_SPAR + k];
-  }
+  const PairGeoms g = contact_load_pair<false>(ct, cd, bestp, rx, rm, wcull, wnarrow, true);
+  // (copies of their own: pair_witness picks between the two geoms per lane, which would keep g out of registers)
+  const GeomT<double> cur = g.cur, par = g.par;
+  const double scur[3] = {g.scur[0], g.scur[1], g.scur[2]}, spar[3] = {g.spar[0], g.spar[1], g.spar[2]};
   double wc[3], wp[3], n[3];
-  const int st = pair_witness(tcur, cur, scur, tpar, par, spar, wc, wp, n);
+  const int st = pair_witness(g.tcur, cur, scur, g.tpar, par, spar, wc, wp, n);
   // the candidate table's orientation: g1 = par when CF_PFIRST
-  const bool pfirst = (flags & CF_PFIRST) != 0;
+  const bool pfirst = (g.flags & CF_PFIRST) != 0;
   double w1[3], w2[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
@@ -544,7 +476,7 @@ __device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<dou
     for (int k = 0; k < 3; k++) go.normal[i * 3 + k] = n[k];
   go.status[i] = st;
   // dclear/dq_j = n . (v_j(w2) [g2 moved by j] - v_j(w1) [g1 moved by j])
-  const double tin1 = go.gtin[pfirst ? gparid : gcur], tin2 = go.gtin[pfirst ? gcur : gparid];
+  const double tin1 = go.gtin[pfirst ? g.gparid : g.gcur], tin2 = go.gtin[pfirst ? g.gcur : g.gparid];
   const double *q = c.col0 + threadIdx.x;
   for (int j = 0; j < nplan; j++) {
     DP col = (DP)go.gcol + j * GC_LEN;
@@ -569,116 +501,6 @@ __device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<dou
     }
     grad[j] = st != GS_OK ? NAN : gj;
   }
-}
-
-// Configurations [i0, i0 + n) of the batch Q: clear[i], pair[i] as k_distance<true> computes them (its body, with
-// the body poses also written to go's scratch rows), then the epilogue's outputs at row i.
-__global__ void __launch_bounds__(kBlock)
-k_clearance_grad(const int *__restrict__ gip, int nip, const double *__restrict__ gdp, int ndp,
-                 const int *__restrict__ gct, const double *__restrict__ gcd, const double *__restrict__ gdt, int P,
-                 const double *__restrict__ Q, int64_t N, int64_t i0, int64_t n, int layout, double distmax,
-                 double *__restrict__ gx, double *__restrict__ gm, int ngeom, double *__restrict__ clear,
-                 int *__restrict__ pair, GradOut go) {
-  extern __shared__ double smem[];
-  const int B = blockDim.x;
-  const int nplan = gip[H_NPLAN];
-  Carve<double> c = carve_lds<double>(smem, gip, nip, gdp, ndp, nplan, 1, B);
-  const int64_t r = (int64_t)blockIdx.x * B + threadIdx.x;
-  const bool active = r < n;
-  const int64_t i = i0 + (active ? r : 0);
-  load_columns(c.col0 + threadIdx.x, B, Q, N, i, nplan, layout, active);
-  __syncthreads();
-  bool finite = true;
-  for (int k = 0; k < nplan; k++) finite = finite && __builtin_isfinite(c.col0[k * B + threadIdx.x]);
-  const bool live = active && finite;
-
-  // 1. forward kinematics into the scratch row: geom poses as k_distance, body poses for the epilogue
-  FkOut out = {};
-  out.geom_xpos = gx;
-  out.geom_xmat = gm;
-  out.ngeom = ngeom;
-  out.xpos = go.xpos;
-  out.xquat = go.xquat;
-  out.nbody = go.nbody;
-  run_config<double, 1, true, true, true>(c.ip, c.tp, c.col0 + threadIdx.x, B, c.save + threadIdx.x, B, active, 0.0,
-                                          out, active ? r : 0);
-  const double *rx = gx + (active ? r : 0) * ngeom * 3;
-  const double *rm = gm + (active ? r : 0) * ngeom * 9;
-
-  // 2. every non-allowed candidate pair, in table order (k_distance<true>'s walk)
-  IP ct = (IP)gct;
-  DP cd = (DP)gcd;
-  DP dt = (DP)gdt;
-  DP wcull = c.tp + uni(c.ip[H_OFF_WCULL]);
-  DP wnarrow = c.tp + uni(c.ip[H_OFF_WNARROW]);
-  double best = distmax;  // least D - margin so far, at pair index bestp
-  int bestp = -1;
-  bool bestcap = true;  // the winner's D is distmax (a cap: no geometry to differentiate)
-  for (int p = 0; p < P; p++) {
-    IP e = ct + p * CI_LEN;
-    DP d = cd + p * CD_LEN;
-    if (uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;  // (uniform: allowed pairs take no part)
-    const int gcur = uni(e[CI_CUR]), gpar = uni(e[CI_PAR]);
-    const int tcur = uni(e[CI_TCUR]), tpar = uni(e[CI_TPAR]), flags = uni(e[CI_FLAGS]);
-    GeomT<double> cur, par;
-    double spar[3];
-    const double scur[3] = {d[CD_SCUR], d[CD_SCUR + 1], d[CD_SCUR + 2]};
-    if (active) contact_load_geom(cur, rx, rm, gcur, tcur);
-    else cur = GeomT<double>{};
-    if (flags & CF_STATIC) {
-      DP rw = wnarrow + gpar * WN_LEN;
-      par.pos[0] = wcull[wc_at(gpar, 0)]; par.pos[1] = wcull[wc_at(gpar, 1)]; par.pos[2] = wcull[wc_at(gpar, 2)];
-      par.m[2] = rw[WN_ZAXIS]; par.m[5] = rw[WN_ZAXIS + 1]; par.m[8] = rw[WN_ZAXIS + 2];
-      par.m[0] = rw[WN_XAXIS]; par.m[3] = rw[WN_XAXIS + 1]; par.m[6] = rw[WN_XAXIS + 2];
-      par.m[1] = rw[WN_YAXIS]; par.m[4] = rw[WN_YAXIS + 1]; par.m[7] = rw[WN_YAXIS + 2];
-      for (int k = 0; k < 3; k++) spar[k] = tpar == GT_PLANE ? 0.0 : rw[WN_SIZE + k];
-    } else {
-      if (active) contact_load_geom(par, rx, rm, gpar, tpar);
-      else par = GeomT<double>{};
-      for (int k = 0; k < 3; k++) spar[k] = d[CD_SPAR + k];
-    }
-    const double margin = d[CD_MARGIN];
-    double lb;
-    {
-      const double dif[3] = {cur.pos[0] - par.pos[0], cur.pos[1] - par.pos[1], cur.pos[2] - par.pos[2]};
-      const double rb = dt[p * DT_LEN + DT_RBSUM];
-      if (tpar == GT_PLANE) {
-        const double nrm[3] = {par.m[2], par.m[5], par.m[8]};
-        lb = dot3(dif, nrm) - rb;
-      } else {
-        lb = sqrt(dot3(dif, dif)) - rb;
-      }
-    }
-    const bool far = lb >= distmax + kDistCullSlack;
-    bool need = live && !far;
-    need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
-    double D = distmax;
-    if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
-      const double x = pair_distance(tcur, cur, scur, tpar, par, spar);
-      if (need) D = x < distmax ? x : distmax;
-    }
-    const double v = D - margin;
-    if (live && (need || far) && (bestp < 0 || v < best)) {
-      best = v;
-      bestp = p;
-      bestcap = !(D < distmax);
-    }
-  }
-  if (!active) return;
-  clear[i] = live ? best : NAN;
-  pair[i] = live ? bestp : -1;
-
-  // 3. the epilogue (lanes diverge from here on)
-  if (!live || bestp < 0 || bestcap) {
-    for (int j = 0; j < nplan; j++) go.grad[i * nplan + j] = live ? 0.0 : NAN;
-    if (go.fromto)
-      for (int k = 0; k < 6; k++) go.fromto[i * 6 + k] = NAN;
-    if (go.normal)
-      for (int k = 0; k < 3; k++) go.normal[i * 3 + k] = NAN;
-    go.status[i] = live ? GS_FLAT : GS_NONFINITE;
-    return;
-  }
-  grad_epilogue(go, c, ct, cd, wcull, wnarrow, rx, rm, i, r, nplan, bestp);
 }
 
 }  // namespace mjpl

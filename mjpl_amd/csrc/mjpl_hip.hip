@@ -411,7 +411,7 @@ struct mjpl_engine {
   double *d_ct_dp = nullptr;
   double *d_ct_scratch = nullptr;  // FK scratch rows of one launch (grow-only)
   size_t ct_scratch_bytes = 0;
-  // distance table of mjpl_distances* / mjpl_clearance* (mjpl_distance.h: DT_*), made on first use from the model
+  // distance table of mjpl_distances* / mjpl_clearance* (mjpl_distance.h: DT_*), made at mjpl_create from the model
   double *d_dt = nullptr;
   // column / joint / geom tables of mjpl_clearance_grad* (mjpl_distance_grad.h: GC_*, JR_*), made at mjpl_create and
   // remade by mjpl_set_planning; body pose scratch rows of one launch (grow-only)
@@ -1982,17 +1982,46 @@ int launch_edges(mjpl_engine *e, const double *dQA, const double *dQB, int64_t E
   return MJPL_OK;
 }
 
-// FK scratch of k_contacts / k_distance: `rows` rows of ngeom poses (grow-only)
-int contact_scratch(mjpl_engine *e, int64_t rows) {
-  const size_t need = (size_t)rows * (size_t)e->m.ngeom * 12 * sizeof(double);
-  if (need > e->ct_scratch_bytes) {
-    if (e->d_ct_scratch) HIP_TRY(hipFree(e->d_ct_scratch));
-    e->d_ct_scratch = nullptr;
-    e->ct_scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&e->d_ct_scratch, need));
-    e->ct_scratch_bytes = need;
-  }
+// A grow-only device buffer of at least `need` bytes
+int grow_device(double *&buf, size_t &have, size_t need) {
+  if (need <= have) return MJPL_OK;
+  if (buf) HIP_TRY(hipFree(buf));
+  buf = nullptr;
+  have = 0;
+  HIP_TRY(hipMalloc(&buf, need));
+  have = need;
   return MJPL_OK;
+}
+
+// Every pair query refuses a model whose candidate table holds a pair no routine here handles.
+int check_pair_types(const mjpl_engine *e) {
+  if (e->ct_unsupported < 0) return MJPL_OK;
+  const int g1 = e->ct_g1[e->ct_unsupported], g2 = e->ct_g2[e->ct_unsupported];
+  return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no pair routine here handles it", g1,
+              g2, e->m.geom_type[g1], e->m.geom_type[g2]);
+}
+
+// Rows per launch of a pair-query kernel (min(N, kContactRows)), its dynamic LDS and its FK scratch rows:
+// gx [rows][ngeom][3], gm [rows][ngeom][9]
+struct PairLaunch {
+  int64_t rows;
+  size_t lds;
+  double *gx, *gm;
+};
+
+// What every pair-query launch needs first: the pair-type check, the FK scratch and the kernel's LDS grant.
+template <class K>
+int pair_query_prologue(mjpl_engine *e, K kernel, int64_t N, PairLaunch *pl) {
+  int rc = check_pair_types(e);
+  if (rc != MJPL_OK) return rc;
+  const size_t ng = e->m.ngeom;
+  pl->rows = std::min<int64_t>(N, kContactRows);
+  rc = grow_device(e->d_ct_scratch, e->ct_scratch_bytes, (size_t)pl->rows * ng * 12 * sizeof(double));
+  if (rc != MJPL_OK) return rc;
+  pl->gx = e->d_ct_scratch;
+  pl->gm = e->d_ct_scratch + (size_t)pl->rows * ng * 3;
+  pl->lds = lds_bytes(e, 1);
+  return allow_lds(kernel, pl->lds);
 }
 
 // One k_contacts launch per kContactRows configurations (the FK scratch holds that many rows).
@@ -2000,34 +2029,25 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
   const int P = (int)e->ct_g1.size();
   const int W = (P + 63) / 64;
   if (N == 0 || P == 0) return MJPL_OK;
-  if (e->ct_unsupported >= 0) {
-    const int p = e->ct_unsupported;
-    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no narrowphase routine here decides it",
-                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
-  }
-  const int ng = e->m.ngeom;
-  const int64_t rows = std::min<int64_t>(N, kContactRows);
-  int rc = contact_scratch(e, rows);
+  PairLaunch pl;
+  int rc = pair_query_prologue(e, k_contacts, N, &pl);
   if (rc != MJPL_OK) return rc;
-  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
-  const size_t lds = lds_bytes(e, 1);
-  rc = allow_lds(k_contacts, lds);
-  if (rc != MJPL_OK) return rc;
-  for (int64_t i0 = 0; i0 < N; i0 += rows) {
-    const int64_t n = std::min<int64_t>(rows, N - i0);
+  for (int64_t i0 = 0; i0 < N; i0 += pl.rows) {
+    const int64_t n = std::min<int64_t>(pl.rows, N - i0);
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_contacts, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
-                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, P, W, dQ, N, i0, n, layout, gx, gm, ng, dbits);
+    hipLaunchKernelGGL(k_contacts, dim3(grid), dim3(kBlock), pl.lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
+                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, P, W, dQ, N, i0, n, layout, pl.gx, pl.gm, e->m.ngeom,
+                       dbits);
     HIP_TRY(hipGetLastError());
   }
   return MJPL_OK;
 }
 
 // The distance table beside the candidate table (mjpl_distance.h: DT_*): rb1 + rb2 and the allowed flag per
-// pair.  Depends on the model only, so it is made once, on first use.
+// pair.  Depends on the model only: called once, at mjpl_create.
 int build_distance_table(mjpl_engine *e) {
   const int P = (int)e->ct_g1.size();
-  if (e->d_dt || P == 0) return MJPL_OK;
+  if (P == 0) return MJPL_OK;
   std::vector<double> dt((size_t)P * DT_LEN);
   for (int p = 0; p < P; p++) {
     const int g1 = e->ct_g1[p], g2 = e->ct_g2[p];
@@ -2048,38 +2068,7 @@ int build_distance_table(mjpl_engine *e) {
   return MJPL_OK;
 }
 
-// One k_distance launch per kContactRows configurations: D [N][P] (dclear == nullptr), or (C, pair) [N].
-int launch_distance(mjpl_engine *e, const double *dQ, int64_t N, int layout, double distmax, double *ddist,
-                    double *dclear, int32_t *dpair) {
-  const bool clear = dclear != nullptr;
-  const int P = (int)e->ct_g1.size();
-  if (N == 0 || (!clear && P == 0)) return MJPL_OK;
-  if (e->ct_unsupported >= 0) {
-    const int p = e->ct_unsupported;
-    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no distance routine here measures it",
-                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
-  }
-  int rc = build_distance_table(e);
-  if (rc != MJPL_OK) return rc;
-  const int ng = e->m.ngeom;
-  const int64_t rows = std::min<int64_t>(N, kContactRows);
-  if ((rc = contact_scratch(e, rows)) != MJPL_OK) return rc;
-  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
-  const size_t lds = lds_bytes(e, 1);
-  auto kernel = clear ? k_distance<true> : k_distance<false>;
-  if ((rc = allow_lds(kernel, lds)) != MJPL_OK) return rc;
-  for (int64_t i0 = 0; i0 < N; i0 += rows) {
-    const int64_t n = std::min<int64_t>(rows, N - i0);
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
-                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, gx, gm, ng,
-                       ddist, dclear, dpair);
-    HIP_TRY(hipGetLastError());
-  }
-  return MJPL_OK;
-}
-
-// The tables of k_clearance_grad (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
+// The tables of k_distance<DM_GRAD> (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
 // the number of later joints on that body and the body's subtree as DFS times; per model joint its type, axis,
 // position and where its dq comes from (as the FK program computes it); per geom the DFS entry time of its body.
 // Depends on the model and the planning selection: made at mjpl_create and by mjpl_set_planning.
@@ -2149,60 +2138,44 @@ int build_grad_table(mjpl_engine *e) {
   return MJPL_OK;
 }
 
-// One k_clearance_grad launch per kContactRows configurations (the scratch holds that many rows of geom and
-// body poses).  dfromto / dnormal may be null.
-int launch_clearance_grad(mjpl_engine *e, const double *dQ, int64_t N, int layout, double distmax, double *dclear,
-                          int32_t *dpair, double *dgrad, double *dfromto, double *dnormal, int32_t *dstatus) {
+// One k_distance<mode> launch per kContactRows configurations: D [N][P] (DM_DIST), (C, pair) [N] (DM_CLEAR), or
+// (C, pair), grad [N][nplan], fromto [N][6], normal [N][3] and status [N] (DM_GRAD; fromto / normal may be null).
+int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int layout, double distmax, double *ddist,
+                    double *dclear, int32_t *dpair, double *dgrad = nullptr, double *dfromto = nullptr,
+                    double *dnormal = nullptr, int32_t *dstatus = nullptr) {
   const int P = (int)e->ct_g1.size();
-  if (N == 0) return MJPL_OK;
-  if (e->ct_unsupported >= 0) {
-    const int p = e->ct_unsupported;
-    return fail(MJPL_E_PAIRTYPE, "candidate pair (%d, %d) has geom types (%d, %d): no distance routine here measures it",
-                e->ct_g1[p], e->ct_g2[p], e->m.geom_type[e->ct_g1[p]], e->m.geom_type[e->ct_g2[p]]);
-  }
-  int rc = build_distance_table(e);
+  if (N == 0 || (mode == DM_DIST && P == 0)) return MJPL_OK;
+  const auto kernel = mode == DM_DIST    ? k_distance<DM_DIST>
+                      : mode == DM_CLEAR ? k_distance<DM_CLEAR>
+                                         : k_distance<DM_GRAD>;
+  PairLaunch pl;
+  int rc = pair_query_prologue(e, kernel, N, &pl);
   if (rc != MJPL_OK) return rc;
-  const int ng = e->m.ngeom, nb = e->m.nbody, nplan = (int)e->qidx.size();
-  const int64_t rows = std::min<int64_t>(N, kContactRows);
-  if ((rc = contact_scratch(e, rows)) != MJPL_OK) return rc;
-  const size_t need = (size_t)rows * (size_t)nb * 7 * sizeof(double);
-  if (need > e->gr_scratch_bytes) {
-    if (e->d_gr_scratch) HIP_TRY(hipFree(e->d_gr_scratch));
-    e->d_gr_scratch = nullptr;
-    e->gr_scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&e->d_gr_scratch, need));
-    e->gr_scratch_bytes = need;
-  }
-  double *gx = e->d_ct_scratch, *gm = e->d_ct_scratch + (size_t)rows * ng * 3;
   GradOut go = {};
-  go.xpos = e->d_gr_scratch;
-  go.xquat = e->d_gr_scratch + (size_t)rows * nb * 3;
-  go.nbody = nb;
-  go.gcol = e->d_gr;
-  go.gjnt = e->d_gr + (size_t)nplan * GC_LEN;
-  go.gtin = go.gjnt + (size_t)e->m.njnt * JR_LEN;
-  go.status = dstatus;
-  const size_t lds = lds_bytes(e, 1);
-  if ((rc = allow_lds(k_clearance_grad, lds)) != MJPL_OK) return rc;
-  for (int64_t i0 = 0; i0 < N; i0 += rows) {
-    const int64_t n = std::min<int64_t>(rows, N - i0);
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    // (the epilogue indexes its outputs by the batch row i: whole arrays, as clear / pair)
+  if (mode == DM_GRAD) {
+    const int nb = e->m.nbody, nplan = (int)e->qidx.size();
+    rc = grow_device(e->d_gr_scratch, e->gr_scratch_bytes, (size_t)pl.rows * nb * 7 * sizeof(double));
+    if (rc != MJPL_OK) return rc;
+    go.xpos = e->d_gr_scratch;
+    go.xquat = e->d_gr_scratch + (size_t)pl.rows * nb * 3;
+    go.nbody = nb;
+    go.gcol = e->d_gr;
+    go.gjnt = e->d_gr + (size_t)nplan * GC_LEN;
+    go.gtin = go.gjnt + (size_t)e->m.njnt * JR_LEN;
     go.grad = dgrad;
     go.fromto = dfromto;
     go.normal = dnormal;
-    hipLaunchKernelGGL(k_clearance_grad, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
-                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, gx, gm, ng,
-                       dclear, dpair, go);
+    go.status = dstatus;
+  }
+  for (int64_t i0 = 0; i0 < N; i0 += pl.rows) {
+    const int64_t n = std::min<int64_t>(pl.rows, N - i0);
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    // (all outputs are indexed by the batch row i: whole arrays)
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), pl.lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
+                       (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, pl.gx,
+                       pl.gm, e->m.ngeom, ddist, dclear, dpair, go);
     HIP_TRY(hipGetLastError());
   }
-  return MJPL_OK;
-}
-
-// argument checks shared by the four distance entry points (after check_common)
-int check_distance_args(double distmax, int64_t N, const void *out1, const void *out2) {
-  if (!(distmax > 0)) return fail(MJPL_E_ARG, "distmax must be > 0 (NaN is refused), got %g", distmax);
-  if (N > 0 && (!out1 || !out2)) return fail(MJPL_E_ARG, "NULL output pointer");
   return MJPL_OK;
 }
 
@@ -2211,6 +2184,54 @@ int check_common(const mjpl_engine *e, const void *a, int64_t n, int layout) {
   if (n < 0) return fail(MJPL_E_ARG, "negative batch size");
   if (n > 0 && !a) return fail(MJPL_E_ARG, "NULL batch pointer");
   if (layout != MJPL_SOA && layout != MJPL_AOS) return fail(MJPL_E_ARG, "layout must be MJPL_SOA or MJPL_AOS");
+  return MJPL_OK;
+}
+
+// Argument checks of the pair queries: check_common, distmax > 0 (NaN refused; the contacts have none and pass +inf)
+// and, when N > 0, every listed output non-null.
+int check_query_args(const mjpl_engine *e, const void *Q, int64_t N, int layout, double distmax,
+                     std::initializer_list<const void *> outs) {
+  int rc = check_common(e, Q, N, layout);
+  if (rc != MJPL_OK) return rc;
+  if (!(distmax > 0)) return fail(MJPL_E_ARG, "distmax must be > 0 (NaN is refused), got %g", distmax);
+  if (N > 0)
+    for (const void *o : outs)
+      if (!o) return fail(MJPL_E_ARG, "NULL output pointer");
+  return MJPL_OK;
+}
+
+// The host-pointer form of a pair query: Q ([N][nplan] doubles) staged into stage[0], the outputs laid out one after
+// another in stage[1] (a null host pointer gets no span and a null device pointer), launch(dQ, device outputs), then
+// every span copied back and the stream synchronised.  List float64 outputs before int32 ones (alignment).
+struct HostOut {
+  void *host;
+  size_t bytes;
+};
+
+template <class F>
+int staged_query(mjpl_engine *e, const double *Q, int64_t N, std::initializer_list<HostOut> outs, F launch) {
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  size_t ob = 0;
+  for (const HostOut &o : outs)
+    if (o.host) ob += o.bytes;
+  int rc;
+  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
+  if ((rc = stage_reserve(e, 1, ob)) != MJPL_OK) return rc;
+  std::vector<void *> dev;
+  char *at = (char *)e->stage[1];
+  for (const HostOut &o : outs) {
+    dev.push_back(o.host ? at : nullptr);
+    if (o.host) at += o.bytes;
+  }
+  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
+  if ((rc = launch((const double *)e->stage[0], dev.data())) != MJPL_OK) return rc;
+  const void *const *d = dev.data();
+  for (const HostOut &o : outs) {
+    if (o.host && o.bytes) HIP_TRY(hipMemcpyAsync(o.host, *d, o.bytes, hipMemcpyDeviceToHost, e->stream));
+    d++;
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return MJPL_OK;
 }
 
@@ -2314,6 +2335,8 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
   rc = compile_program(e);
   if (rc != MJPL_OK) return bail(rc);
   rc = build_contact_table(e);
+  if (rc != MJPL_OK) return bail(rc);
+  rc = build_distance_table(e);
   if (rc != MJPL_OK) return bail(rc);
   rc = build_grad_table(e);
   if (rc != MJPL_OK) return bail(rc);
@@ -3425,7 +3448,7 @@ int mjpl_contact_pairs(mjpl_engine *e, int32_t *geom1, int32_t *geom2, uint8_t *
 }
 
 int mjpl_contacts_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, uint64_t *dbits) {
-  int rc = check_common(e, dQ, N, layout);
+  int rc = check_query_args(e, dQ, N, layout, INFINITY, {});
   if (rc != MJPL_OK) return rc;
   if (N > 0 && !e->ct_g1.empty() && !dbits) return fail(MJPL_E_ARG, "NULL output pointer");
   HIP_TRY(hipSetDevice(e->device));
@@ -3433,136 +3456,74 @@ int mjpl_contacts_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layou
 }
 
 int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, uint64_t *bits) {
-  int rc = check_common(e, Q, N, layout);
+  int rc = check_query_args(e, Q, N, layout, INFINITY, {});
   if (rc != MJPL_OK) return rc;
   const int64_t W = ((int64_t)e->ct_g1.size() + 63) / 64;
   if (N == 0 || W == 0) return MJPL_OK;
   if (!bits) return fail(MJPL_E_ARG, "NULL output pointer");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  const size_t bb = (size_t)N * (size_t)W * sizeof(uint64_t);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, bb)) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_contacts(e, (const double *)e->stage[0], N, layout, (unsigned long long *)e->stage[1])) != MJPL_OK)
-    return rc;
-  HIP_TRY(hipMemcpyAsync(bits, e->stage[1], bb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  return staged_query(e, Q, N, {{bits, (size_t)N * (size_t)W * sizeof(uint64_t)}}, [&](const double *dQ, void **d) {
+    return launch_contacts(e, dQ, N, layout, (unsigned long long *)d[0]);
+  });
 }
 
 // ---- distances and clearance per configuration (mjpl_distance.h)
 
 int mjpl_distances_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *ddist) {
-  int rc = check_common(e, dQ, N, layout);
+  int rc = check_query_args(e, dQ, N, layout, distmax, {ddist});
   if (rc != MJPL_OK) return rc;
-  if ((rc = check_distance_args(distmax, N, ddist, ddist)) != MJPL_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  return launch_distance(e, dQ, N, layout, distmax, ddist, nullptr, nullptr);
+  return launch_distance(e, DM_DIST, dQ, N, layout, distmax, ddist, nullptr, nullptr);
 }
 
 int mjpl_distances(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *dist) {
-  int rc = check_common(e, Q, N, layout);
+  int rc = check_query_args(e, Q, N, layout, distmax, {dist});
   if (rc != MJPL_OK) return rc;
-  if ((rc = check_distance_args(distmax, N, dist, dist)) != MJPL_OK) return rc;
-  const int64_t P = (int64_t)e->ct_g1.size();
+  const size_t P = e->ct_g1.size();
   if (N == 0 || P == 0) return MJPL_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  const size_t db = (size_t)N * (size_t)P * sizeof(double);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, db)) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_distance(e, (const double *)e->stage[0], N, layout, distmax, (double *)e->stage[1], nullptr,
-                            nullptr)) != MJPL_OK)
-    return rc;
-  HIP_TRY(hipMemcpyAsync(dist, e->stage[1], db, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  return staged_query(e, Q, N, {{dist, (size_t)N * P * sizeof(double)}}, [&](const double *dQ, void **d) {
+    return launch_distance(e, DM_DIST, dQ, N, layout, distmax, (double *)d[0], nullptr, nullptr);
+  });
 }
 
 int mjpl_clearance_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *dclear,
                        int32_t *dpair) {
-  int rc = check_common(e, dQ, N, layout);
-  if (rc != MJPL_OK) return rc;
-  if ((rc = check_distance_args(distmax, N, dclear, dpair)) != MJPL_OK) return rc;
-  if (N == 0) return MJPL_OK;
+  int rc = check_query_args(e, dQ, N, layout, distmax, {dclear, dpair});
+  if (rc != MJPL_OK || N == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  return launch_distance(e, dQ, N, layout, distmax, nullptr, dclear, dpair);
+  return launch_distance(e, DM_CLEAR, dQ, N, layout, distmax, nullptr, dclear, dpair);
 }
 
 int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *clear,
                    int32_t *pair) {
-  int rc = check_common(e, Q, N, layout);
-  if (rc != MJPL_OK) return rc;
-  if ((rc = check_distance_args(distmax, N, clear, pair)) != MJPL_OK) return rc;
-  if (N == 0) return MJPL_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  const size_t cb = (size_t)N * sizeof(double), pb = (size_t)N * sizeof(int32_t);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, cb + pb)) != MJPL_OK) return rc;
-  double *dclear = (double *)e->stage[1];
-  int32_t *dpair = (int32_t *)((char *)e->stage[1] + cb);
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_distance(e, (const double *)e->stage[0], N, layout, distmax, nullptr, dclear, dpair)) != MJPL_OK)
-    return rc;
-  HIP_TRY(hipMemcpyAsync(clear, dclear, cb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(pair, dpair, pb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  int rc = check_query_args(e, Q, N, layout, distmax, {clear, pair});
+  if (rc != MJPL_OK || N == 0) return rc;
+  const std::initializer_list<HostOut> outs = {{clear, (size_t)N * sizeof(double)}, {pair, (size_t)N * sizeof(int32_t)}};
+  return staged_query(e, Q, N, outs, [&](const double *dQ, void **d) {
+    return launch_distance(e, DM_CLEAR, dQ, N, layout, distmax, nullptr, (double *)d[0], (int32_t *)d[1]);
+  });
 }
 
 // ---- clearance gradients and witness points per configuration (mjpl_distance_grad.h)
 
-namespace {
-int check_grad_args(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, const double *clear,
-                    const int32_t *pair, const double *grad, const int32_t *status) {
-  int rc = check_common(e, Q, N, layout);
-  if (rc != MJPL_OK) return rc;
-  if ((rc = check_distance_args(distmax, N, clear, pair)) != MJPL_OK) return rc;
-  if (N > 0 && (!grad || !status)) return fail(MJPL_E_ARG, "NULL output pointer");
-  return MJPL_OK;
-}
-}  // namespace
-
 int mjpl_clearance_grad_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, double *dclear,
                             int32_t *dpair, double *dgrad, double *dfromto, double *dnormal, int32_t *dstatus) {
-  int rc = check_grad_args(e, dQ, N, layout, distmax, dclear, dpair, dgrad, dstatus);
+  int rc = check_query_args(e, dQ, N, layout, distmax, {dclear, dpair, dgrad, dstatus});
   if (rc != MJPL_OK || N == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  return launch_clearance_grad(e, dQ, N, layout, distmax, dclear, dpair, dgrad, dfromto, dnormal, dstatus);
+  return launch_distance(e, DM_GRAD, dQ, N, layout, distmax, nullptr, dclear, dpair, dgrad, dfromto, dnormal, dstatus);
 }
 
 int mjpl_clearance_grad(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, double *clear,
                         int32_t *pair, double *grad, double *fromto, double *normal, int32_t *status) {
-  int rc = check_grad_args(e, Q, N, layout, distmax, clear, pair, grad, status);
+  int rc = check_query_args(e, Q, N, layout, distmax, {clear, pair, grad, status});
   if (rc != MJPL_OK || N == 0) return rc;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t nplan = e->qidx.size();
-  const size_t qb = (size_t)N * nplan * sizeof(double);
-  // one staging block: grad, fromto, normal, clear (float64), then pair, status (int32)
-  const size_t gb = (size_t)N * nplan * sizeof(double), fb = fromto ? (size_t)N * 6 * sizeof(double) : 0,
-               nb = normal ? (size_t)N * 3 * sizeof(double) : 0, cb = (size_t)N * sizeof(double),
-               ib = (size_t)N * sizeof(int32_t);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, gb + fb + nb + cb + 2 * ib)) != MJPL_OK) return rc;
-  char *o = (char *)e->stage[1];
-  double *dgrad = (double *)o, *dfromto = fromto ? (double *)(o + gb) : nullptr,
-         *dnormal = normal ? (double *)(o + gb + fb) : nullptr, *dclear = (double *)(o + gb + fb + nb);
-  int32_t *dpair = (int32_t *)(o + gb + fb + nb + cb), *dstatus = (int32_t *)(o + gb + fb + nb + cb + ib);
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_clearance_grad(e, (const double *)e->stage[0], N, layout, distmax, dclear, dpair, dgrad, dfromto,
-                                  dnormal, dstatus)) != MJPL_OK)
-    return rc;
-  if (gb) HIP_TRY(hipMemcpyAsync(grad, dgrad, gb, hipMemcpyDeviceToHost, e->stream));
-  if (fb) HIP_TRY(hipMemcpyAsync(fromto, dfromto, fb, hipMemcpyDeviceToHost, e->stream));
-  if (nb) HIP_TRY(hipMemcpyAsync(normal, dnormal, nb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(clear, dclear, cb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(pair, dpair, ib, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(status, dstatus, ib, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  const size_t n = N, db = sizeof(double), ib = sizeof(int32_t);
+  const std::initializer_list<HostOut> outs = {{grad, n * e->qidx.size() * db}, {fromto, n * 6 * db},
+                                               {normal, n * 3 * db}, {clear, n * db}, {pair, n * ib}, {status, n * ib}};
+  return staged_query(e, Q, N, outs, [&](const double *dQ, void **d) {
+    return launch_distance(e, DM_GRAD, dQ, N, layout, distmax, nullptr, (double *)d[3], (int32_t *)d[4], (double *)d[0],
+                           (double *)d[1], (double *)d[2], (int32_t *)d[5]);
+  });
 }
 
 // ---- memory / stream helpers

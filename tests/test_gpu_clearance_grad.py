@@ -377,6 +377,15 @@ def test_only_allowed_pairs_is_flat():
     assert np.all(grad == 0) and np.isnan(fromto).all() and np.isnan(normal).all()
 
 
+def test_empty_candidate_table_is_flat():
+    from test_gpu_distance import no_pair_model
+    e = eng_mod.Engine(no_pair_model())
+    for distmax in (INF, 0.05):
+        C, pair, grad, fromto, normal, status = e.clearance_grad(np.linspace(-1, 1, 5)[:, None], distmax)
+        assert np.all(status == eng_mod.GRAD_FLAT) and np.all(pair == -1) and np.all(C == distmax)
+        assert grad.shape == (5, 1) and np.all(grad == 0) and np.isnan(fromto).all() and np.isnan(normal).all()
+
+
 def test_argument_errors():
     import ctypes as C
     m = scenes.franka_p(obstacles=True)

@@ -17,6 +17,7 @@ from test_gpu_models import random_model
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1  # MJPL_E_ARG
+E_PAIRTYPE = -3  # MJPL_E_PAIRTYPE
 TOL = 1e-9
 INF = float("inf")
 ALLOWED = (("link5", "hand"), ("link0", "link6"), ("world", "left_finger"))
@@ -207,6 +208,42 @@ def test_argument_errors():
     assert lib.mjpl_clearance_dev(h, None, 1, 1, INF, None, None) == E_ARG
     assert lib.mjpl_distances(h, q.ctypes.data_as(F64), 0, 1, INF, None) == 0
     assert lib.mjpl_clearance(h, q.ctypes.data_as(F64), 0, 1, INF, None, None) == 0
+
+
+def no_pair_model():
+    """Two spheres whose contype / conaffinity never meet: an empty candidate table (P = 0)."""
+    mb = ModelBuilder()
+    mb.add_body("a")
+    mb.add_joint("a", "ja", range=(-1, 1))
+    mb.add_geom("a", "sphere", (0.1,), contype=1, conaffinity=0)
+    mb.add_geom("world", "sphere", (0.1,), contype=1, conaffinity=0)
+    return mb.compile()
+
+
+def test_empty_candidate_table():
+    e = eng_mod.Engine(no_pair_model())
+    assert e.contact_pairs()[0].shape == (0, 2)
+    Q = np.linspace(-1, 1, 5)[:, None]
+    assert e.distances(Q).shape == (5, 0)
+    for distmax in (INF, 0.05):
+        C, pair = e.clearance(Q, distmax)
+        assert np.all(C == distmax) and np.all(pair == -1)
+
+
+def test_unsupported_pair_type_is_refused_by_every_query():
+    # a cylinder (no routine here) that only meets an allowed body: the engine creates, every pair query refuses
+    mb = ModelBuilder()
+    mb.add_body("m")
+    mb.add_joint("m", "j", type="slide", axis=(1, 0, 0), range=(-2, 2))
+    mb.add_geom("world", type="cylinder", size=(0.1, 0.2))
+    mb.add_geom("m", type="sphere", size=(0.1,), pos=(0.5, 0, 0))
+    e = eng_mod.Engine(mb.compile(), [("world", "m")])
+    assert e.contact_pairs()[0].shape == (1, 2) and e.contact_pairs()[1].all()
+    Q = np.zeros((3, 1))
+    for query in (e.contacts, e.distances, e.clearance, e.clearance_grad):
+        with pytest.raises(eng_mod.MjplError) as ei:
+            query(Q)
+        assert ei.value.code == E_PAIRTYPE, query.__name__
 
 
 # ---- other models
