@@ -394,11 +394,13 @@ struct mjpl_engine {
   // RCCL communicator of the frontier planner's exchange (mjpl_comm_init); none = a world of one
   void *comm = nullptr;
   int comm_rank = 0, comm_world = 1;
-  // grow-only staging buffers for the host-pointer entry points
-  void *stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // ([6]: the parked-row list of a two-launch projection)
-  size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
-  // pinned, grow-only host block of the fused small-batch path of the host-pointer entry points
-  // (one H2D and one D2H per call instead of five copies from / to pageable memory)
+  // grow-only device staging slots: a host-pointer entry point's inputs and outputs (staged()), the program of an IK
+  // solve, the parked-row list of a two-launch projection
+  struct Slot {
+    void *p = nullptr;
+    size_t bytes = 0;
+  } stage_in, stage_out, stage_ik, stage_parked;
+  // pinned, grow-only host block of the small-batch tiers of staged()
   void *h_pin = nullptr;
   size_t h_pin_bytes = 0;
   // candidate pairs of mj_collision for mjpl_contacts* (build_contact_table): made once at create from the model
@@ -424,14 +426,14 @@ namespace {
 
 void load_spec(mjpl_engine *e, bool generic_ok, int nstage);
 
-int stage_reserve(mjpl_engine *e, int k, size_t bytes) {
-  if (bytes <= e->stage_bytes[k]) return MJPL_OK;
-  if (e->stage[k]) HIP_TRY(hipFree(e->stage[k]));
-  e->stage[k] = nullptr;
-  e->stage_bytes[k] = 0;
+int stage_reserve(mjpl_engine::Slot &s, size_t bytes) {
+  if (bytes <= s.bytes) return MJPL_OK;
+  if (s.p) HIP_TRY(hipFree(s.p));
+  s.p = nullptr;
+  s.bytes = 0;
   size_t want = std::max<size_t>(bytes, 1 << 16);
-  HIP_TRY(hipMalloc(&e->stage[k], want));
-  e->stage_bytes[k] = want;
+  HIP_TRY(hipMalloc(&s.p, want));
+  s.bytes = want;
   return MJPL_OK;
 }
 
@@ -556,21 +558,6 @@ void load_spec(mjpl_engine *e, bool generic_ok = false, int nstage = 0) {
     e->spec_generic = true;
   }
 }
-
-int pin_reserve(mjpl_engine *e, size_t bytes) {
-  if (bytes <= e->h_pin_bytes) return MJPL_OK;
-  if (e->h_pin) HIP_TRY(hipHostFree(e->h_pin));
-  e->h_pin = nullptr;
-  e->h_pin_bytes = 0;
-  const size_t want = std::max<size_t>(bytes, 1 << 16);
-  HIP_TRY(hipHostMalloc(&e->h_pin, want));
-  e->h_pin_bytes = want;
-  return MJPL_OK;
-}
-constexpr size_t kFusedHostBytes = (size_t)256 << 10;  // batches up to this size take the fused path
-// ... and up to this size the kernels read the pinned block and write into it themselves, over the bus: no copy
-// operation on the stream at all (a scalar valid_config pays launches and one synchronisation; MJPL_ZERO_COPY_BYTES)
-size_t zero_copy_bytes(const mjpl_engine *e) { return e->zero_copy_bytes; }  // (option "zero_copy_bytes")
 
 // mj_collision pair filters [MJ-recalled: engine_collision_driver.c filterBitmask /
 // filterBodyPair] + the a6 ruleset folded in.  returns true if the pair is tested.
@@ -2200,38 +2187,101 @@ int check_query_args(const mjpl_engine *e, const void *Q, int64_t N, int layout,
   return MJPL_OK;
 }
 
-// The host-pointer form of a pair query: Q ([N][nplan] doubles) staged into stage[0], the outputs laid out one after
-// another in stage[1] (a null host pointer gets no span and a null device pointer), launch(dQ, device outputs), then
-// every span copied back and the stream synchronised.  List float64 outputs before int32 ones (alignment).
+// ---- staging of the host-pointer entry points
+// An array of a call in host memory: an input copied in, or an output copied back.  A null output is one the caller
+// does not want: it gets no space and a null device pointer.  An output with `from` set is not written by the launch:
+// it is copied from that device address after it (the edge pipeline's status word).
+struct HostIn {
+  const void *host;
+  size_t bytes;
+};
 struct HostOut {
   void *host;
   size_t bytes;
+  const void *from = nullptr;
 };
 
-template <class F>
-int staged_query(mjpl_engine *e, const double *Q, int64_t N, std::initializer_list<HostOut> outs, F launch) {
+constexpr size_t kSpanAlign = 256;  // every span starts at a multiple of this in its slot or in the pinned block
+size_t span_bytes(size_t bytes) { return (bytes + kSpanAlign - 1) & ~(kSpanAlign - 1); }
+// Calls whose spans total at most this go through the pinned block in one copy each way (small-batch tier 1)
+constexpr size_t kPinnedCopyBytes = (size_t)256 << 10;
+
+int pin_reserve(mjpl_engine *e, size_t bytes) {
+  if (bytes <= e->h_pin_bytes) return MJPL_OK;
+  if (e->h_pin) HIP_TRY(hipHostFree(e->h_pin));
+  e->h_pin = nullptr;
+  e->h_pin_bytes = 0;
+  const size_t want = std::max<size_t>(bytes, 1 << 16);
+  HIP_TRY(hipHostMalloc(&e->h_pin, want));
+  e->h_pin_bytes = want;
+  return MJPL_OK;
+}
+
+// The host-pointer form of an entry point: the inputs packed into the engine's input slot and the outputs into its
+// output slot, launch(device inputs, device outputs) enqueued between the copies, the stream synchronised.  How the
+// spans move goes by their total, wanted outputs or not (so the outputs a call asks for do not change its tier):
+//   0. up to the option "zero_copy_bytes", if `small_tiers`: the kernels read the pinned block and write into it
+//      themselves, over the bus -- no copy operation on the stream at all (a scalar valid_config pays launches and one
+//      synchronisation);
+//   1. up to kPinnedCopyBytes, if `small_tiers`: through the pinned block, one copy each way;
+//   2. otherwise: one copy per span from and to the caller's pageable memory.
+template <size_t NI, size_t NO, class F>
+int staged(mjpl_engine *e, bool small_tiers, const HostIn (&in)[NI], const HostOut (&out)[NO], F launch) {
   HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  size_t ob = 0;
-  for (const HostOut &o : outs)
-    if (o.host) ob += o.bytes;
+  size_t at_in[NI], at_out[NO], ib = 0, ob = 0, total = 0;
+  for (size_t k = 0; k < NI; k++) {
+    at_in[k] = ib;
+    ib += span_bytes(in[k].bytes);
+  }
+  for (size_t k = 0; k < NO; k++) {
+    at_out[k] = ob;
+    total += span_bytes(out[k].bytes);
+    if (out[k].host) ob += span_bytes(out[k].bytes);
+  }
+  total += ib;
+  const int tier = !small_tiers ? 2 : total <= e->zero_copy_bytes ? 0 : total <= kPinnedCopyBytes ? 1 : 2;
   int rc;
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, ob)) != MJPL_OK) return rc;
-  std::vector<void *> dev;
-  char *at = (char *)e->stage[1];
-  for (const HostOut &o : outs) {
-    dev.push_back(o.host ? at : nullptr);
-    if (o.host) at += o.bytes;
+  char *pin = nullptr, *dev_in, *dev_out;
+  if (tier < 2) {
+    if ((rc = pin_reserve(e, ib + ob)) != MJPL_OK) return rc;
+    pin = (char *)e->h_pin;
+    for (size_t k = 0; k < NI; k++) memcpy(pin + at_in[k], in[k].host, in[k].bytes);
   }
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch((const double *)e->stage[0], dev.data())) != MJPL_OK) return rc;
-  const void *const *d = dev.data();
-  for (const HostOut &o : outs) {
-    if (o.host && o.bytes) HIP_TRY(hipMemcpyAsync(o.host, *d, o.bytes, hipMemcpyDeviceToHost, e->stream));
-    d++;
+  if (tier == 0) {
+    HIP_TRY(hipHostGetDevicePointer((void **)&dev_in, pin, 0));
+    dev_out = dev_in + ib;
+  } else {
+    if ((rc = stage_reserve(e->stage_in, ib)) != MJPL_OK) return rc;
+    if ((rc = stage_reserve(e->stage_out, ob)) != MJPL_OK) return rc;
+    dev_in = (char *)e->stage_in.p;
+    dev_out = (char *)e->stage_out.p;
+    if (tier == 1) HIP_TRY(hipMemcpyAsync(dev_in, pin, ib, hipMemcpyHostToDevice, e->stream));
+    for (size_t k = 0; k < NI && tier == 2; k++)
+      if (in[k].bytes) HIP_TRY(hipMemcpyAsync(dev_in + at_in[k], in[k].host, in[k].bytes, hipMemcpyHostToDevice, e->stream));
   }
+  void *din[NI], *dout[NO];
+  for (size_t k = 0; k < NI; k++) din[k] = dev_in + at_in[k];
+  for (size_t k = 0; k < NO; k++) dout[k] = out[k].host ? dev_out + at_out[k] : nullptr;
+  if ((rc = launch(din, dout)) != MJPL_OK) return rc;
+  for (size_t k = 0; k < NO; k++) {
+    const HostOut &o = out[k];
+    if (!o.host || !o.bytes) continue;
+    if (tier == 0 && o.from) HIP_TRY(hipMemcpyAsync(pin + ib + at_out[k], o.from, o.bytes, hipMemcpyDeviceToHost, e->stream));
+    if (tier == 1 && o.from) HIP_TRY(hipMemcpyAsync(dout[k], o.from, o.bytes, hipMemcpyDeviceToDevice, e->stream));
+    if (tier == 2) HIP_TRY(hipMemcpyAsync(o.host, o.from ? o.from : dout[k], o.bytes, hipMemcpyDeviceToHost, e->stream));
+  }
+  if (tier == 1) HIP_TRY(hipMemcpyAsync(pin + ib, dev_out, ob, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < NO && tier < 2; k++)
+    if (out[k].host) memcpy(out[k].host, pin + ib + at_out[k], out[k].bytes);
+  return MJPL_OK;
+}
+
+// The edge pipeline's status word (kStatus*: mjpl_filter.h, mjpl_fused.h) as a return code, with its message
+int edge_status(int s) {
+  if (s & (kStatusTailTimeout | kStatusFusedTimeout))
+    return fail(MJPL_E_HIP, "a kernel of the edge pipeline gave up waiting (status %d: 2 = the tail kernel for its walking workgroups, 4 = a wave of the fused kernel for its work pool)", s);
+  if (s & kStatusNonFinite) return fail(MJPL_E_NONFINITE, "an edge holds NaN/inf or needs more than %d waypoints", kMaxWaypoints);
   return MJPL_OK;
 }
 
@@ -2360,8 +2410,8 @@ void mjpl_destroy(mjpl_engine *e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->comm) (void)mjpl_comm_destroy(e);
-  for (int k = 0; k < 7; k++)
-    if (e->stage[k]) (void)hipFree(e->stage[k]);
+  for (const mjpl_engine::Slot *s : {&e->stage_in, &e->stage_out, &e->stage_ik, &e->stage_parked})
+    if (s->p) (void)hipFree(s->p);
   if (e->h_pin) (void)hipHostFree(e->h_pin);
   if (e->d_ip) (void)hipFree(e->d_ip);
   if (e->d_dp) (void)hipFree(e->d_dp);
@@ -2617,8 +2667,9 @@ int mjpl_take_status(mjpl_engine *e, int32_t *status) {
   HIP_TRY(hipMemcpyAsync(&s, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  if (s & (kStatusTailTimeout | kStatusFusedTimeout)) return fail(MJPL_E_HIP, "a kernel of the edge pipeline gave up waiting (status %d: 2 = the tail kernel for its walking workgroups, 4 = a wave of the fused kernel for its work pool)", s);
-  *status = (s & kStatusNonFinite) ? MJPL_E_NONFINITE : MJPL_OK;
+  const int rc = edge_status(s);
+  if (rc == MJPL_E_HIP) return rc;
+  *status = rc;
   return MJPL_OK;
 }
 
@@ -3245,37 +3296,10 @@ int mjpl_check_configs(mjpl_engine *e, const double *Q, int64_t N, int32_t layou
   if (rc != MJPL_OK) return rc;
   if (N == 0) return MJPL_OK;
   if (!valid) return fail(MJPL_E_ARG, "NULL output pointer");
-  HIP_TRY(hipSetDevice(e->device));
   const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 2, (size_t)N)) != MJPL_OK) return rc;
-  if (qb + (size_t)N <= zero_copy_bytes(e)) {
-    if ((rc = pin_reserve(e, qb + (size_t)N)) != MJPL_OK) return rc;
-    char *pin = (char *)e->h_pin, *dpin = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&dpin, pin, 0));
-    memcpy(pin, Q, qb);
-    if ((rc = launch_configs(e, (const double *)dpin, N, layout, (uint8_t *)(dpin + qb), nullptr)) != MJPL_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    memcpy(valid, pin + qb, (size_t)N);
-    return MJPL_OK;
-  }
-  if (qb + (size_t)N <= kFusedHostBytes) {
-    // planner-sized batch: through the pinned block, one copy each way
-    if ((rc = pin_reserve(e, qb + (size_t)N)) != MJPL_OK) return rc;
-    char *pin = (char *)e->h_pin;
-    memcpy(pin, Q, qb);
-    HIP_TRY(hipMemcpyAsync(e->stage[0], pin, qb, hipMemcpyHostToDevice, e->stream));
-    if ((rc = launch_configs(e, (const double *)e->stage[0], N, layout, (uint8_t *)e->stage[2], nullptr)) != MJPL_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin + qb, e->stage[2], (size_t)N, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    memcpy(valid, pin + qb, (size_t)N);
-    return MJPL_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_configs(e, (const double *)e->stage[0], N, layout, (uint8_t *)e->stage[2], nullptr)) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(valid, e->stage[2], (size_t)N, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  return staged(e, true, {{Q, qb}}, {{valid, (size_t)N}}, [&](void **in, void **out) {
+    return launch_configs(e, (const double *)in[0], N, layout, (uint8_t *)out[0], nullptr);
+  });
 }
 
 int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t E, double step_dist,
@@ -3285,7 +3309,6 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
   if (!(step_dist > 0.0)) return fail(MJPL_E_ARG, "`step_dist` must be > 0");
   if (E == 0) return MJPL_OK;
   if (!QB || !valid) return fail(MJPL_E_ARG, "NULL pointer");
-  HIP_TRY(hipSetDevice(e->device));
   const size_t qb = (size_t)E * e->qidx.size() * sizeof(double);
   // A handful of LONG edges (path shortcutting, smooth_path: planning/utils.py:9-87) is better served by the two
   // persistent kernels, which keep every 32nd exact waypoint as a checkpoint: the fused kernel rebuilds an undecided
@@ -3305,77 +3328,14 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
     }
     e->fused_skip_once = std::sqrt(longest2) > 64.0 * step_dist;
   }
-  if (2 * qb + 5 * (size_t)E + 16 <= zero_copy_bytes(e)) {
-    const size_t vb = ((size_t)E + 7) & ~(size_t)7, fbb = (size_t)E * sizeof(int32_t);
-    if ((rc = pin_reserve(e, 2 * qb + vb + fbb + 8)) != MJPL_OK) return rc;
-    char *pin = (char *)e->h_pin, *dpin = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&dpin, pin, 0));
-    memcpy(pin, QA, qb);
-    memcpy(pin + qb, QB, qb);
-    HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
-    char *dout = dpin + 2 * qb, *hout = pin + 2 * qb;
-    if ((rc = launch_edges(e, (const double *)dpin, (const double *)(dpin + qb), E, step_dist, layout, flags, (uint8_t *)dout,
-                           first_bad ? (int32_t *)(dout + vb) : nullptr)) != MJPL_OK)
-      return rc;
-    HIP_TRY(hipMemcpyAsync(hout + vb + fbb, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    memcpy(valid, hout, (size_t)E);
-    if (first_bad) memcpy(first_bad, hout + vb, fbb);
-    int status = 0;
-    memcpy(&status, hout + vb + fbb, sizeof(int));
-    if (status & (kStatusTailTimeout | kStatusFusedTimeout)) return fail(MJPL_E_HIP, "a kernel of the edge pipeline gave up waiting (status %d: 2 = the tail kernel for its walking workgroups, 4 = a wave of the fused kernel for its work pool)", status);
-    if (status & kStatusNonFinite)
-      return fail(MJPL_E_NONFINITE, "an edge holds NaN/inf or needs more than %d waypoints", kMaxWaypoints);
-    return MJPL_OK;
-  }
-  if (2 * qb + 5 * (size_t)E + 16 <= kFusedHostBytes) {
-    // planner-sized batch: QA | QB go up in one copy from the pinned block, valid | first_bad |
-    // status come back in one
-    const size_t vb = ((size_t)E + 7) & ~(size_t)7, fbb = (size_t)E * sizeof(int32_t);
-    if ((rc = stage_reserve(e, 0, 2 * qb)) != MJPL_OK) return rc;
-    if ((rc = stage_reserve(e, 2, vb + fbb + 8)) != MJPL_OK) return rc;
-    if ((rc = pin_reserve(e, 2 * qb + vb + fbb + 8)) != MJPL_OK) return rc;
-    char *pin = (char *)e->h_pin;
-    memcpy(pin, QA, qb);
-    memcpy(pin + qb, QB, qb);
-    char *dq = (char *)e->stage[0], *dout = (char *)e->stage[2];
-    HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
-    HIP_TRY(hipMemcpyAsync(dq, pin, 2 * qb, hipMemcpyHostToDevice, e->stream));
-    if ((rc = launch_edges(e, (const double *)dq, (const double *)(dq + qb), E, step_dist, layout, flags, (uint8_t *)dout,
-                           first_bad ? (int32_t *)(dout + vb) : nullptr)) != MJPL_OK)
-      return rc;
-    HIP_TRY(hipMemcpyAsync(dout + vb + fbb, e->d_status, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
-    char *hout = pin + 2 * qb;
-    HIP_TRY(hipMemcpyAsync(hout, dout, vb + fbb + 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    memcpy(valid, hout, (size_t)E);
-    if (first_bad) memcpy(first_bad, hout + vb, fbb);
-    int status = 0;
-    memcpy(&status, hout + vb + fbb, sizeof(int));
-    if (status & (kStatusTailTimeout | kStatusFusedTimeout)) return fail(MJPL_E_HIP, "a kernel of the edge pipeline gave up waiting (status %d: 2 = the tail kernel for its walking workgroups, 4 = a wave of the fused kernel for its work pool)", status);
-    if (status & kStatusNonFinite)
-      return fail(MJPL_E_NONFINITE, "an edge holds NaN/inf or needs more than %d waypoints", kMaxWaypoints);
-    return MJPL_OK;
-  }
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 2, (size_t)E)) != MJPL_OK) return rc;
-  if (first_bad && (rc = stage_reserve(e, 3, (size_t)E * sizeof(int32_t))) != MJPL_OK) return rc;
-  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
-  HIP_TRY(hipMemcpyAsync(e->stage[0], QA, qb, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->stage[1], QB, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = launch_edges(e, (const double *)e->stage[0], (const double *)e->stage[1], E, step_dist, layout, flags,
-                         (uint8_t *)e->stage[2], first_bad ? (int32_t *)e->stage[3] : nullptr)) != MJPL_OK)
-    return rc;
   int status = 0;
-  HIP_TRY(hipMemcpyAsync(valid, e->stage[2], (size_t)E, hipMemcpyDeviceToHost, e->stream));
-  if (first_bad) HIP_TRY(hipMemcpyAsync(first_bad, e->stage[3], (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&status, e->d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (status & (kStatusTailTimeout | kStatusFusedTimeout)) return fail(MJPL_E_HIP, "a kernel of the edge pipeline gave up waiting (status %d: 2 = the tail kernel for its walking workgroups, 4 = a wave of the fused kernel for its work pool)", status);
-  if (status & kStatusNonFinite)
-    return fail(MJPL_E_NONFINITE, "an edge holds NaN/inf or needs more than %d waypoints", kMaxWaypoints);
-  return MJPL_OK;
+  const HostOut outs[] = {{valid, (size_t)E}, {first_bad, (size_t)E * sizeof(int32_t)}, {&status, sizeof(int), e->d_status}};
+  rc = staged(e, true, {{QA, qb}, {QB, qb}}, outs, [&](void **in, void **out) {
+    HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
+    return launch_edges(e, (const double *)in[0], (const double *)in[1], E, step_dist, layout, flags, (uint8_t *)out[0],
+                        (int32_t *)out[1]);
+  });
+  return rc != MJPL_OK ? rc : edge_status(status);
 }
 
 int mjpl_fk(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double *xpos, double *xquat,
@@ -3383,34 +3343,27 @@ int mjpl_fk(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double *
   int rc = check_common(e, Q, N, layout);
   if (rc != MJPL_OK) return rc;
   if (N == 0) return MJPL_OK;
-  HIP_TRY(hipSetDevice(e->device));
   const HostModel &m = e->m;
-  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
-  const size_t sz[4] = {(size_t)N * m.nbody * 3 * 8, (size_t)N * m.nbody * 4 * 8, (size_t)N * m.ngeom * 3 * 8,
-                        (size_t)N * m.ngeom * 9 * 8};
-  double *host[4] = {xpos, xquat, geom_xpos, geom_xmat};
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  for (int k = 0; k < 4; k++)
-    if (host[k] && (rc = stage_reserve(e, 2 + k, sz[k])) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  FkOut out;
-  out.xpos = xpos ? (double *)e->stage[2] : nullptr;
-  out.xquat = xquat ? (double *)e->stage[3] : nullptr;
-  out.geom_xpos = geom_xpos ? (double *)e->stage[4] : nullptr;
-  out.geom_xmat = geom_xmat ? (double *)e->stage[5] : nullptr;
-  out.nbody = m.nbody;
-  out.ngeom = m.ngeom;
-  const size_t lds = lds_bytes(e, 1);
-  const unsigned grid = (unsigned)((N + kBlock - 1) / kBlock);
-  rc = allow_lds(k_fk, lds);
-  if (rc == MJPL_OK)
-    hipLaunchKernelGGL(k_fk, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
-                       (int)e->dp.size(), (const double *)e->stage[0], N, layout, out);
+  const size_t n = (size_t)N, qb = n * e->qidx.size() * sizeof(double);
+  const HostOut outs[] = {{xpos, n * m.nbody * 3 * 8}, {xquat, n * m.nbody * 4 * 8}, {geom_xpos, n * m.ngeom * 3 * 8},
+                          {geom_xmat, n * m.ngeom * 9 * 8}};
+  rc = staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
+    FkOut fo;
+    fo.xpos = (double *)out[0];
+    fo.xquat = (double *)out[1];
+    fo.geom_xpos = (double *)out[2];
+    fo.geom_xmat = (double *)out[3];
+    fo.nbody = m.nbody;
+    fo.ngeom = m.ngeom;
+    const size_t lds = lds_bytes(e, 1);
+    const int rc2 = allow_lds(k_fk, lds);
+    if (rc2 != MJPL_OK) return rc2;
+    hipLaunchKernelGGL(k_fk, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), lds, e->stream, e->d_ip,
+                       (int)e->ip.size(), e->d_dp, (int)e->dp.size(), (const double *)in[0], N, layout, fo);
+    HIP_TRY(hipGetLastError());
+    return MJPL_OK;
+  });
   if (rc != MJPL_OK) return rc;
-  HIP_TRY(hipGetLastError());
-  for (int k = 0; k < 4; k++)
-    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], e->stage[2 + k], sz[k], hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
   // bodies/geoms welded to the world do not depend on qpos: poses folded at create
   for (int64_t i = 0; i < N; i++) {
     for (int b = 0; b < m.nbody; b++) {
@@ -3461,8 +3414,9 @@ int mjpl_contacts(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, ui
   const int64_t W = ((int64_t)e->ct_g1.size() + 63) / 64;
   if (N == 0 || W == 0) return MJPL_OK;
   if (!bits) return fail(MJPL_E_ARG, "NULL output pointer");
-  return staged_query(e, Q, N, {{bits, (size_t)N * (size_t)W * sizeof(uint64_t)}}, [&](const double *dQ, void **d) {
-    return launch_contacts(e, dQ, N, layout, (unsigned long long *)d[0]);
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  return staged(e, false, {{Q, qb}}, {{bits, (size_t)N * (size_t)W * sizeof(uint64_t)}}, [&](void **in, void **out) {
+    return launch_contacts(e, (const double *)in[0], N, layout, (unsigned long long *)out[0]);
   });
 }
 
@@ -3480,8 +3434,9 @@ int mjpl_distances(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, d
   if (rc != MJPL_OK) return rc;
   const size_t P = e->ct_g1.size();
   if (N == 0 || P == 0) return MJPL_OK;
-  return staged_query(e, Q, N, {{dist, (size_t)N * P * sizeof(double)}}, [&](const double *dQ, void **d) {
-    return launch_distance(e, DM_DIST, dQ, N, layout, distmax, (double *)d[0], nullptr, nullptr);
+  const size_t qb = (size_t)N * e->qidx.size() * sizeof(double);
+  return staged(e, false, {{Q, qb}}, {{dist, (size_t)N * P * sizeof(double)}}, [&](void **in, void **out) {
+    return launch_distance(e, DM_DIST, (const double *)in[0], N, layout, distmax, (double *)out[0], nullptr, nullptr);
   });
 }
 
@@ -3497,9 +3452,9 @@ int mjpl_clearance(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, d
                    int32_t *pair) {
   int rc = check_query_args(e, Q, N, layout, distmax, {clear, pair});
   if (rc != MJPL_OK || N == 0) return rc;
-  const std::initializer_list<HostOut> outs = {{clear, (size_t)N * sizeof(double)}, {pair, (size_t)N * sizeof(int32_t)}};
-  return staged_query(e, Q, N, outs, [&](const double *dQ, void **d) {
-    return launch_distance(e, DM_CLEAR, dQ, N, layout, distmax, nullptr, (double *)d[0], (int32_t *)d[1]);
+  const size_t n = N, qb = n * e->qidx.size() * sizeof(double);
+  return staged(e, false, {{Q, qb}}, {{clear, n * sizeof(double)}, {pair, n * sizeof(int32_t)}}, [&](void **in, void **out) {
+    return launch_distance(e, DM_CLEAR, (const double *)in[0], N, layout, distmax, nullptr, (double *)out[0], (int32_t *)out[1]);
   });
 }
 
@@ -3517,12 +3472,11 @@ int mjpl_clearance_grad(mjpl_engine *e, const double *Q, int64_t N, int32_t layo
                         int32_t *pair, double *grad, double *fromto, double *normal, int32_t *status) {
   int rc = check_query_args(e, Q, N, layout, distmax, {clear, pair, grad, status});
   if (rc != MJPL_OK || N == 0) return rc;
-  const size_t n = N, db = sizeof(double), ib = sizeof(int32_t);
-  const std::initializer_list<HostOut> outs = {{grad, n * e->qidx.size() * db}, {fromto, n * 6 * db},
-                                               {normal, n * 3 * db}, {clear, n * db}, {pair, n * ib}, {status, n * ib}};
-  return staged_query(e, Q, N, outs, [&](const double *dQ, void **d) {
-    return launch_distance(e, DM_GRAD, dQ, N, layout, distmax, nullptr, (double *)d[3], (int32_t *)d[4], (double *)d[0],
-                           (double *)d[1], (double *)d[2], (int32_t *)d[5]);
+  const size_t n = N, db = sizeof(double), ib = sizeof(int32_t), qb = n * e->qidx.size() * db;
+  const HostOut outs[] = {{clear, n * db}, {pair, n * ib}, {grad, qb}, {fromto, n * 6 * db}, {normal, n * 3 * db}, {status, n * ib}};
+  return staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
+    return launch_distance(e, DM_GRAD, (const double *)in[0], N, layout, distmax, nullptr, (double *)out[0], (int32_t *)out[1],
+                           (double *)out[2], (double *)out[3], (double *)out[4], (int32_t *)out[5]);
   });
 }
 
@@ -3859,8 +3813,8 @@ int mjpl_pose_apply_dev(mjpl_pose *p, const double *dQold, const double *dQ, int
     const int phase_steps = e->pose_phase_steps;  // (option "pose_phase_steps")
     if (rs.G == 1 && phase_steps > 0) {
       const size_t need = ((size_t)N * 2 + 16) * sizeof(int32_t);
-      if ((rc = stage_reserve(e, 6, need)) != MJPL_OK) return rc;
-      int32_t *list = (int32_t *)e->stage[6], *itst = list + N;
+      if ((rc = stage_reserve(e->stage_parked, need)) != MJPL_OK) return rc;
+      int32_t *list = (int32_t *)e->stage_parked.p, *itst = list + N;
       int *count = (int *)(itst + N);
       HIP_TRY(hipMemsetAsync(count, 0, sizeof(int), e->stream));
       const PosePhase first = {phase_steps, nullptr, nullptr, list, count, itst};
@@ -3903,46 +3857,24 @@ int mjpl_pose_apply(mjpl_pose *p, const double *Q_old, const double *Q, int64_t 
   if (rc != MJPL_OK) return rc;
   if (N == 0) return MJPL_OK;
   if (!Q_old || !Q_out || !ok) return fail(MJPL_E_ARG, "NULL pointer");
-  mjpl_engine *e = p->e;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * p->nq * sizeof(double);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 4, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 2, (size_t)N)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 3, (size_t)N * sizeof(int32_t))) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q_old, qb, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->stage[1], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = mjpl_pose_apply_dev(p, (const double *)e->stage[0], (const double *)e->stage[1], N,
-                                (double *)e->stage[4], (uint8_t *)e->stage[2], (int32_t *)e->stage[3])) != MJPL_OK)
-    return rc;
-  HIP_TRY(hipMemcpyAsync(Q_out, e->stage[4], qb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(ok, e->stage[2], (size_t)N, hipMemcpyDeviceToHost, e->stream));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, e->stage[3], (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  const size_t n = N, qb = n * p->nq * sizeof(double);
+  return staged(p->e, false, {{Q_old, qb}, {Q, qb}}, {{Q_out, qb}, {ok, n}, {iters, n * sizeof(int32_t)}},
+                [&](void **in, void **out) {
+                  return mjpl_pose_apply_dev(p, (const double *)in[0], (const double *)in[1], N, (double *)out[0],
+                                             (uint8_t *)out[1], (int32_t *)out[2]);
+                });
 }
 
 int mjpl_pose_valid(mjpl_pose *p, const double *Q, int64_t N, uint8_t *valid, double *xpos, double *xmat) {
   int rc = pose_check(p, Q, N);
   if (rc != MJPL_OK) return rc;
   if (N == 0) return MJPL_OK;
-  mjpl_engine *e = p->e;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * p->nq * sizeof(double);
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 2, (size_t)N)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 4, (size_t)N * 3 * sizeof(double))) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 5, (size_t)N * 9 * sizeof(double))) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = mjpl_pose_valid_dev(p, (const double *)e->stage[0], N, (uint8_t *)e->stage[2], (double *)e->stage[4],
-                                (double *)e->stage[5])) != MJPL_OK)
-    return rc;
-  if (valid) HIP_TRY(hipMemcpyAsync(valid, e->stage[2], (size_t)N, hipMemcpyDeviceToHost, e->stream));
-  if (xpos) HIP_TRY(hipMemcpyAsync(xpos, e->stage[4], (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (xmat) HIP_TRY(hipMemcpyAsync(xmat, e->stage[5], (size_t)N * 9 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  const size_t n = N, db = sizeof(double);
+  return staged(p->e, false, {{Q, n * p->nq * db}}, {{valid, n}, {xpos, n * 3 * db}, {xmat, n * 9 * db}},
+                [&](void **in, void **out) {
+                  return mjpl_pose_valid_dev(p, (const double *)in[0], N, (uint8_t *)out[0], (double *)out[1],
+                                             (double *)out[2]);
+                });
 }
 
 // ---- row f3: IK seeds ------------------------------------------------------------------------
@@ -3993,9 +3925,9 @@ int mjpl_ik_solve_dev(mjpl_engine *e, const mjpl_ik_desc *d, const double *dQ, i
   KtScope kt_scope(e, 1);  // (option "kernel_timer")
   // the program is tiny and changes with every target: staged through the engine's scratch
   const size_t ib = pi.size() * sizeof(int), db = pd.size() * sizeof(double);
-  if ((rc = stage_reserve(e, 5, ((ib + 7) & ~(size_t)7) + db)) != MJPL_OK) return rc;
-  int *d_pi = (int *)e->stage[5];
-  double *d_pd = (double *)((char *)e->stage[5] + ((ib + 7) & ~(size_t)7));
+  if ((rc = stage_reserve(e->stage_ik, ((ib + 7) & ~(size_t)7) + db)) != MJPL_OK) return rc;
+  int *d_pi = (int *)e->stage_ik.p;
+  double *d_pd = (double *)((char *)e->stage_ik.p + ((ib + 7) & ~(size_t)7));
   HIP_TRY(hipStreamSynchronize(e->stream));  // pageable host vectors go out of scope on return
   HIP_TRY(hipMemcpy(d_pi, pi.data(), ib, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_pd, pd.data(), db, hipMemcpyHostToDevice));
@@ -4019,24 +3951,12 @@ int mjpl_ik_solve(mjpl_engine *e, const mjpl_ik_desc *d, const double *Q, int64_
   if (N < 0) return fail(MJPL_E_ARG, "negative batch size");
   if (N == 0) return MJPL_OK;
   if (!Q || !Q_out || !ok) return fail(MJPL_E_ARG, "NULL pointer");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t qb = (size_t)N * e->m.nq * sizeof(double);
-  int rc;
-  if ((rc = stage_reserve(e, 0, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 1, qb)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 2, (size_t)N)) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 3, (size_t)N * sizeof(int32_t))) != MJPL_OK) return rc;
-  if ((rc = stage_reserve(e, 4, (size_t)N * 2 * sizeof(double))) != MJPL_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->stage[0], Q, qb, hipMemcpyHostToDevice, e->stream));
-  if ((rc = mjpl_ik_solve_dev(e, d, (const double *)e->stage[0], N, (double *)e->stage[1], (uint8_t *)e->stage[2],
-                              (int32_t *)e->stage[3], (double *)e->stage[4])) != MJPL_OK)
-    return rc;
-  HIP_TRY(hipMemcpyAsync(Q_out, e->stage[1], qb, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(ok, e->stage[2], (size_t)N, hipMemcpyDeviceToHost, e->stream));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, e->stage[3], (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  if (err) HIP_TRY(hipMemcpyAsync(err, e->stage[4], (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MJPL_OK;
+  const size_t n = N, qb = n * e->m.nq * sizeof(double);
+  const HostOut outs[] = {{Q_out, qb}, {ok, n}, {iters, n * sizeof(int32_t)}, {err, n * 2 * sizeof(double)}};
+  return staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
+    return mjpl_ik_solve_dev(e, d, (const double *)in[0], N, (double *)out[0], (uint8_t *)out[1], (int32_t *)out[2],
+                             (double *)out[3]);
+  });
 }
 
 }  // extern "C"

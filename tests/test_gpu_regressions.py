@@ -326,6 +326,81 @@ def test_host_pointer_paths_agree():
     assert outs[0] == outs[1] == outs[2], outs
 
 
+@pytest.mark.parametrize("n", [1, 7, 300, 40000])
+def test_pose_and_ik_host_forms_are_the_device_forms(n):
+    """mjpl_pose_apply, mjpl_pose_valid and mjpl_ik_solve return byte for byte what their _dev twins leave in device
+    memory, with every optional output (iters, err, valid, xpos, xmat) asked for and left NULL."""
+    import ctypes as C
+    import mjpl_amd as mjpl
+    F, U8, I32 = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    m = scenes.franka_p(obstacles=False)
+    q_home = m.keyframe("home").qpos.copy()
+    e = eng_mod.Engine(m)
+    lib = e.lib
+    frame = mjpl.site_pose(m, q_home, "ee_site", engine=e)
+    pc = mjpl.PoseConstraint(m, "ee_site", frame, z_translation=(-0.05, 0.05), roll=(-0.1, 0.1), pitch=(-0.1, 0.1),
+                             q_step=0.5, engine=e)
+    ph = pc._proj.h
+    rng = np.random.default_rng(40 + n)
+    lo, hi = m.jnt_range[:, 0], m.jnt_range[:, 1]
+    Q = np.clip(q_home + rng.normal(scale=0.06, size=(n, m.nq)), lo, hi)
+    Q_old = np.clip(q_home + rng.normal(scale=0.02, size=(n, m.nq)), lo, hi)
+    dQ, dQ_old = e.alloc(Q.nbytes).upload(Q), e.alloc(Q.nbytes).upload(Q_old)
+    dq_out, dok, dit, derr = e.alloc(Q.nbytes), e.alloc(n), e.alloc(4 * n), e.alloc(16 * n)
+    dxpos, dxmat = e.alloc(24 * n), e.alloc(72 * n)
+
+    def ptr(a):
+        return a.ctypes.data_as(F if a.dtype == np.float64 else U8 if a.dtype == np.uint8 else I32) if a is not None else None
+
+    def dptr(b, want):
+        return b.ptr if want else None
+
+    # site validity and pose: valid, xpos, xmat (each asked for in one call, NULL in the other)
+    for wv in (True, False):
+        valid = np.zeros(n, np.uint8) if wv else None
+        xpos, xmat = (None, None) if wv else (np.empty((n, 3)), np.empty((n, 9)))
+        assert lib.mjpl_pose_valid(ph, ptr(Q), n, ptr(valid), ptr(xpos), ptr(xmat)) == 0
+        assert lib.mjpl_pose_valid_dev(ph, dQ.ptr, n, dptr(dok, wv), dptr(dxpos, not wv), dptr(dxmat, not wv)) == 0
+        if wv:
+            assert valid.tobytes() == dok.download(np.uint8, n).tobytes()
+        else:
+            assert xpos.tobytes() == dxpos.download(np.float64, 3 * n).tobytes()
+            assert xmat.tobytes() == dxmat.download(np.float64, 9 * n).tobytes()
+    for want in (True, False):
+        # projection: Q_out, ok, iters
+        q_out, ok = np.empty_like(Q), np.zeros(n, np.uint8)
+        it = np.zeros(n, np.int32) if want else None
+        assert lib.mjpl_pose_apply(ph, ptr(Q_old), ptr(Q), n, ptr(q_out), ptr(ok), ptr(it)) == 0
+        assert lib.mjpl_pose_apply_dev(ph, dQ_old.ptr, dQ.ptr, n, dq_out.ptr, dok.ptr, dptr(dit, want)) == 0
+        assert q_out.tobytes() == dq_out.download(np.float64, n * m.nq).tobytes()
+        assert ok.tobytes() == dok.download(np.uint8, n).tobytes()
+        if want:
+            assert it.tobytes() == dit.download(np.int32, n).tobytes()
+        # IK seeds: Q_out, ok, iters, err
+        d = eng_mod.IKDesc()
+        sid = m.site("ee_site").id
+        d.site_body = int(m.site_bodyid[sid])
+        d.site_pos[:], d.site_quat[:] = list(m.site_pos[sid]), list(m.site_quat[sid])
+        d.target_pos[:], d.target_quat[:] = list(frame.translation() + [0.05, -0.05, 0.02]), list(frame.rotation().wxyz)
+        d.pos_tolerance, d.ori_tolerance, d.iterations = 1e-3, 1e-3, 60
+        d.damping, d.lm_damping, d.max_step, d.restarts, d.restart_seed = 0.0, -1.0, 0.0, 2, 7
+        jr, mv = np.ascontiguousarray(m.jnt_range, np.float64).reshape(-1), np.ones(m.njnt, np.uint8)
+        d.jnt_range, d.movable = ptr(jr), ptr(mv)
+        q_out, ok = np.empty_like(Q), np.zeros(n, np.uint8)
+        it, err = (np.zeros(n, np.int32), np.zeros((n, 2))) if want else (None, None)
+        assert lib.mjpl_ik_solve(e.h, C.byref(d), ptr(Q), n, ptr(q_out), ptr(ok), ptr(it), ptr(err)) == 0
+        assert lib.mjpl_ik_solve_dev(e.h, C.byref(d), dQ.ptr, n, dq_out.ptr, dok.ptr, dptr(dit, want), dptr(derr, want)) == 0
+        assert q_out.tobytes() == dq_out.download(np.float64, n * m.nq).tobytes()
+        assert ok.tobytes() == dok.download(np.uint8, n).tobytes()
+        if want:
+            assert it.tobytes() == dit.download(np.int32, n).tobytes()
+            assert err.tobytes() == derr.download(np.float64, 2 * n).tobytes()
+    for buf in (dQ, dQ_old, dq_out, dok, dit, derr, dxpos, dxmat):
+        buf.free()
+    pc._proj.close()
+    e.close()
+
+
 def test_engines_taking_batches_in_turns_return_a_single_engine_s_verdicts(oracle_mod):
     """EngineRing: three engines (three streams) validate six different batches in turns, all enqueued before the
     first synchronisation; every batch's verdicts and first-bad indices are the oracle's."""
