@@ -63,6 +63,39 @@ int fail(int code, const char *fmt, ...) {
                   __FILE__, __LINE__);                                                  \
   } while (0)
 
+#define MJPL_TRY(expr)                  \
+  do {                                  \
+    int _rc = (expr);                   \
+    if (_rc != MJPL_OK) return _rc;     \
+  } while (0)
+
+// A device allocation that only grows.  reserve(n) frees, empties, then allocates, in that order: a failed hipMalloc
+// leaves the buffer empty and the next launch tries again.  hipFree synchronises the device, so it is called only
+// when a buffer must grow: steady-state launches call none.  The engine's buffers go with it (mjpl_destroy).
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;  // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int release() {
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    return MJPL_OK;
+  }
+  int reserve(size_t n, size_t at_least = 0) {  // (at_least: the smallest allocation worth making)
+    if (n <= cap) return MJPL_OK;
+    MJPL_TRY(release());
+    n = std::max(n, at_least);
+    HIP_TRY(hipMalloc(&p, n * sizeof(T)));
+    cap = n;
+    return MJPL_OK;
+  }
+};
+
 // ------------------------------------------------------------------------------- kernels
 
 // ---- exact path (float64): final verdicts --------------------------------------------------
@@ -290,14 +323,12 @@ struct mjpl_engine {
   float *d_fp_base = nullptr;    // allocation behind d_fp (= d_fp_base + scene.size())
   bool spec_off = false;          // mjpl_set_spec(e, 0): run the interpreting kernels whatever libraries exist
   bool spec_generic_only = false; // mjpl_set_spec(e, 2): pass over the program's own library, take the robot's scene-generic one
-  int *d_ulist = nullptr;   // items (configurations / whole edges) the filter left undecided
+  DevBuf<int> d_ulist;      // items (configurations / whole edges) the filter left undecided
   int *d_ucount_base = nullptr;  // both counter sets; d_ucount = the one the last launch used
   bool counters_stale = false;
   int *d_ucount = nullptr;  // [0] how many of those, [1] undecided waypoints of edges, [2] edges in d_slist
-  int *d_slist = nullptr;   // two-pass edge filter: edges whose endpoint passed
-  size_t slist_cap = 0;
+  DevBuf<int> d_slist;      // two-pass edge filter: edges whose endpoint passed
   bool two_pass = true;
-  size_t ulist_cap = 0;
   // timing runs (mjpl_time_edges_stages_dev): marks[k] is recorded after stage k - 1 of the launch
   // (marks[0] at its start); nullptr in ordinary launches
   hipEvent_t *marks = nullptr;
@@ -306,14 +337,15 @@ struct mjpl_engine {
   // "kernel_timer2_ms" read the sums since the option was set, "kernel_timer[2]_launches" how many
   int kt_mode = 0, kt_used[2] = {0, 0};  // (kt_mode: bit 0 = class 1, bit 1 = class 2)
   std::vector<hipEvent_t> kt_ev[2];
-  double *d_ucq = nullptr;  // undecided waypoints: rows of nplan float64
-  int *d_ucedge = nullptr, *d_ucidx = nullptr, *d_ucga = nullptr, *d_ucgb = nullptr;
+  // undecided waypoints, uc_cap of each (uc_reserve): rows of nplan float64 (allocated as rows of nq), edge, check index, geom pair
+  DevBuf<double> d_ucq;
+  DevBuf<int> d_ucedge, d_ucidx, d_ucga, d_ucgb;
   double *d_geomtab = nullptr;  // GTB_LEN doubles per model geom (k_patch_pairs)
   // lane-per-waypoint interior pass: (edge, idx) items, long-edge list
-  double *d_tstep = nullptr, *d_itemck = nullptr;  // (checkpoint rows: allocated by the first launch with long items)
-  size_t itemck_cap = 0;
-  int *d_itemedge = nullptr, *d_itemidx = nullptr, *d_llist = nullptr, *d_icount = nullptr;
-  int *d_eclaim = nullptr;  // [llist_cap] per-edge claim word: the launch generation that listed the edge in d_ulist
+  DevBuf<double> d_tstep, d_itemck;  // (checkpoint rows: allocated by the first launch with long items)
+  DevBuf<int> d_itemedge, d_itemidx, d_llist;
+  int *d_icount = nullptr;
+  DevBuf<int> d_eclaim;  // [llist_cap] per-edge claim word: the launch generation that listed the edge in d_ulist
   int claim_gen = 0;
   size_t item_cap = 0, llist_cap = 0;
   bool expand = true;
@@ -335,9 +367,8 @@ struct mjpl_engine {
   bool fused_mbox = false;
   bool f64_queued = true;  // MJPL_F64_QUEUED: the float64 pool kernel checks through the candidate queues (A/B switch)
   int fused_single_max = 32768;  // MJPL_FUSED_SINGLE: batches up to this many edges check every configuration of an edge in one round (measured: 0.068 vs 0.087 ms at 1 024 edges, 0.090 vs 0.102 at 32 768, 0.116 vs 0.106 at 65 536)
-  bool fused_skip_once = false;  // mjpl_check_edges: this launch holds a few long edges -> the kernels with checkpoints
   const char *fused_dbg_path = nullptr;  // MJPL_FUSED_DEBUG=<file> (with a -DMJPL_FUSED_DEBUG build of the kernels)
-  unsigned long long *d_fused_dbg = nullptr;
+  DevBuf<unsigned long long> d_fused_dbg;
   size_t item_cap_limit = (size_t)1 << 26;  // MJPL_ITEM_CAP: edges beyond it take the walking kernel
   void *d_nn = nullptr;         // nearest neighbour: per-chunk partial results
   size_t nn_bytes = 0;
@@ -396,10 +427,7 @@ struct mjpl_engine {
   int comm_rank = 0, comm_world = 1;
   // grow-only device staging slots: a host-pointer entry point's inputs and outputs (staged()), the program of an IK
   // solve, the parked-row list of a two-launch projection
-  struct Slot {
-    void *p = nullptr;
-    size_t bytes = 0;
-  } stage_in, stage_out, stage_ik, stage_parked;
+  DevBuf<char> stage_in, stage_out, stage_ik, stage_parked;
   // pinned, grow-only host block of the small-batch tiers of staged()
   void *h_pin = nullptr;
   size_t h_pin_bytes = 0;
@@ -411,31 +439,20 @@ struct mjpl_engine {
   int ct_unsupported = -1;  // index of a candidate pair no narrowphase routine here decides (-1: none)
   int *d_ct_ip = nullptr;
   double *d_ct_dp = nullptr;
-  double *d_ct_scratch = nullptr;  // FK scratch rows of one launch (grow-only)
-  size_t ct_scratch_bytes = 0;
+  DevBuf<double> d_ct_scratch;  // FK scratch rows of one launch
   // distance table of mjpl_distances* / mjpl_clearance* (mjpl_distance.h: DT_*), made at mjpl_create from the model
   double *d_dt = nullptr;
   // column / joint / geom tables of mjpl_clearance_grad* (mjpl_distance_grad.h: GC_*, JR_*), made at mjpl_create and
   // remade by mjpl_set_planning; body pose scratch rows of one launch (grow-only)
   double *d_gr = nullptr;
-  double *d_gr_scratch = nullptr;
-  size_t gr_scratch_bytes = 0;
+  DevBuf<double> d_gr_scratch;
 };
 
 namespace {
 
 void load_spec(mjpl_engine *e, bool generic_ok, int nstage);
 
-int stage_reserve(mjpl_engine::Slot &s, size_t bytes) {
-  if (bytes <= s.bytes) return MJPL_OK;
-  if (s.p) HIP_TRY(hipFree(s.p));
-  s.p = nullptr;
-  s.bytes = 0;
-  size_t want = std::max<size_t>(bytes, 1 << 16);
-  HIP_TRY(hipMalloc(&s.p, want));
-  s.bytes = want;
-  return MJPL_OK;
-}
+constexpr size_t kStageFloor = 1 << 16;  // a staging slot is never smaller (DevBuf::reserve: at_least)
 
 // ---- per-model specialised filter kernels (mjpl_amd/specialise.py builds them) ----
 // A library libmjpl_spec_<hash>.so holds the three float32 filter kernels of mjpl_filter.h instantiated
@@ -1303,21 +1320,25 @@ size_t lds_bytes(const mjpl_engine *e, int ncolsets, size_t scalar = sizeof(doub
   return bytes ? bytes : 8;
 }
 
+// Buffers that share one capacity (uc_cap, llist_cap, item_cap) are all freed before any of them is allocated again.
+template <class... B>
+int release_all(B &...bufs) {
+  int rc = MJPL_OK;
+  ((rc = rc != MJPL_OK ? rc : bufs.release()), ...);
+  return rc;
+}
+
 int uc_reserve(mjpl_engine *e, int64_t n) {
   // MJPL_UC_CAP (create-time, tests): a small hand-over buffer, to exercise its overflow paths
   const size_t want = e->uc_cap_limit ? e->uc_cap_limit : (size_t)std::max<int64_t>(4096, n);
   if (want <= e->uc_cap) return MJPL_OK;
-  if (e->d_ucq) HIP_TRY(hipFree(e->d_ucq));
-  if (e->d_ucedge) HIP_TRY(hipFree(e->d_ucedge));
-  if (e->d_ucidx) HIP_TRY(hipFree(e->d_ucidx));
-  if (e->d_ucga) HIP_TRY(hipFree(e->d_ucga));
-  if (e->d_ucgb) HIP_TRY(hipFree(e->d_ucgb));
-  e->d_ucq = nullptr; e->d_ucedge = e->d_ucidx = e->d_ucga = e->d_ucgb = nullptr; e->uc_cap = 0;
-  HIP_TRY(hipMalloc(&e->d_ucq, want * std::max<size_t>(1, e->m.nq) * sizeof(double)));
-  HIP_TRY(hipMalloc(&e->d_ucedge, want * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_ucidx, want * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_ucga, want * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_ucgb, want * sizeof(int)));
+  MJPL_TRY(release_all(e->d_ucq, e->d_ucedge, e->d_ucidx, e->d_ucga, e->d_ucgb));
+  e->uc_cap = 0;
+  MJPL_TRY(e->d_ucq.reserve(want * std::max<size_t>(1, e->m.nq)));
+  MJPL_TRY(e->d_ucedge.reserve(want));
+  MJPL_TRY(e->d_ucidx.reserve(want));
+  MJPL_TRY(e->d_ucga.reserve(want));
+  MJPL_TRY(e->d_ucgb.reserve(want));
   if (!e->d_geomtab) {
     const HostModel &m = e->m;
     std::vector<double> t((size_t)m.ngeom * GTB_LEN, 0.0);
@@ -1338,6 +1359,16 @@ int uc_reserve(mjpl_engine *e, int64_t n) {
   return MJPL_OK;
 }
 
+// where the filter kernels hand single undecided pairs over (uc_reserve first)
+UndecidedConfigs undecided(const mjpl_engine *e) {
+  UndecidedConfigs uc = {};
+  uc.q = e->d_ucq.p; uc.edge = e->d_ucedge.p; uc.idx = e->d_ucidx.p;
+  uc.ga = e->d_ucga.p; uc.gb = e->d_ucgb.p;
+  uc.count = e->d_ucount + kCtr;
+  uc.cap = (int)std::min<size_t>(e->uc_cap, (size_t)1 << 30);
+  return uc;
+}
+
 int ulist_reserve(mjpl_engine *e, int64_t n) {
   if (!e->d_ucount) {
     // five device counters, each on its own 128-byte line (they are hammered by wave-level atomics
@@ -1351,12 +1382,29 @@ int ulist_reserve(mjpl_engine *e, int64_t n) {
     e->d_ucount = e->d_ucount_base;
     e->d_icount = e->d_ucount + 3 * kCtr;
   }
-  if ((size_t)n > e->ulist_cap) {
-    if (e->d_ulist) HIP_TRY(hipFree(e->d_ulist));
-    e->d_ulist = nullptr;
-    e->ulist_cap = 0;
-    HIP_TRY(hipMalloc(&e->d_ulist, (size_t)n * sizeof(int)));
-    e->ulist_cap = (size_t)n;
+  return e->d_ulist.reserve((size_t)n);
+}
+
+// per-edge scratch of the launches that work from a pool or an item space: walking list, step fractions, claim
+// words of the undecided-edge list (cleared when they are made: no generation has claimed anything yet)
+int llist_reserve(mjpl_engine *e, int64_t E) {
+  if ((size_t)E <= e->llist_cap) return MJPL_OK;
+  MJPL_TRY(release_all(e->d_tstep, e->d_llist, e->d_eclaim));
+  e->llist_cap = 0;
+  MJPL_TRY(e->d_llist.reserve((size_t)E));
+  MJPL_TRY(e->d_tstep.reserve((size_t)E));
+  MJPL_TRY(e->d_eclaim.reserve((size_t)E));
+  HIP_TRY(hipMemsetAsync(e->d_eclaim.p, 0, (size_t)E * sizeof(int), e->stream));
+  e->claim_gen = 0;
+  e->llist_cap = (size_t)E;
+  return MJPL_OK;
+}
+
+// a filter launch's generation of the claim words: generations never repeat between clears
+int next_claim_gen(mjpl_engine *e) {
+  if (++e->claim_gen == std::numeric_limits<int>::max()) {
+    HIP_TRY(hipMemsetAsync(e->d_eclaim.p, 0, e->llist_cap * sizeof(int), e->stream));
+    e->claim_gen = 1;
   }
   return MJPL_OK;
 }
@@ -1378,12 +1426,40 @@ int allow_lds(K kernel, size_t bytes) {
   return MJPL_OK;
 }
 
+// ---- the two ways a kernel is launched: an interpreting kernel of this library on the engine's stream ...
+template <class K, class... A>
+int launch_kernel(const mjpl_engine *e, K kern, unsigned grid, int block, size_t lds, A... args) {
+  MJPL_TRY(allow_lds(kern, lds));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, e->stream, args...);
+  return MJPL_OK;
+}
+
+// (a persistent grid: the workgroups that are resident under that LDS grant, or fewer for `ntile` tiles of 64)
+template <class K, class... A>
+int launch_persistent(const mjpl_engine *e, K kern, size_t lds, long long ntile, A... args) {
+  MJPL_TRY(allow_lds(kern, lds));
+  hipLaunchKernelGGL(kern, dim3(persistent_grid(kern, lds, ntile)), dim3(kBlock), lds, e->stream, args...);
+  return MJPL_OK;
+}
+
+// (a pool kernel of mjpl_fused.h: fused_launch sizes the grid)
+template <class K>
+int launch_pool(const mjpl_engine *e, K kern, int nwaves, size_t lds, const FusedArgs &fa, const char *what) {
+  MJPL_TRY(allow_lds(kern, lds));
+  return fused_launch(kern, nwaves, lds, fa, e->stream) == hipSuccess ? MJPL_OK : fail(MJPL_E_HIP, "the %s kernel failed to launch", what);
+}
+
+// ... or the entry point of a model's library, which answers non-zero when its launch failed
+int spec_rc(int launched, const char *what) {
+  return launched == 0 ? MJPL_OK : fail(MJPL_E_HIP, "specialised %s kernel failed to launch", what);
+}
+
 // Can this engine's edge launches run the fused filter kernel (mjpl_fused.h), and how: waves per workgroup
 // (twelve = one workgroup per CU at three waves per SIMD; four for the one-wave-per-SIMD build of models with
 // moving boxes), entries of a workgroup's pool (what the CU's LDS leaves, at least 64 per wave: one endpoint tile
-// each) and the dynamic LDS of a workgroup.
-bool fused_plan(const mjpl_engine *e, int *nwaves, size_t *lds, int *ring = nullptr, const SpecLib *lib = nullptr) {
-  const SpecLib *spec = lib ? lib : e->spec;  // (lib: the certificate build instead of the engine's default library)
+// each) and the dynamic LDS of a workgroup.  `spec`: the library that would launch it (the engine's own, or its
+// certificate build).
+bool fused_plan(const mjpl_engine *e, const SpecLib *spec, int *nwaves, size_t *lds, int *ring) {
   if (!e->fused || !e->filter || !e->filter_usable || !e->two_pass || !e->expand || e->immediate()) return false;
   const int nplan = (int)e->qidx.size();
   const bool mbox = e->filter_mbox();
@@ -1398,9 +1474,9 @@ bool fused_plan(const mjpl_engine *e, int *nwaves, size_t *lds, int *ring = null
   if (base + (size_t)(64 * nw + 64) * kFusedEntryBytes > budget) return false;
   int r = (int)std::min<size_t>(kFusedMaxPool, (budget - base) / kFusedEntryBytes / 64 * 64);
   if (e->fused_pool_cap > 0) r = std::max(64 * nw + 64, std::min(r, e->fused_pool_cap / 64 * 64));  // (tests: a ring that wraps)
-  if (nwaves) *nwaves = nw;
-  if (lds) *lds = fused_lds_bytes(nw, nplan, e->nsave, e->fp.size(), mbox, r, cert);
-  if (ring) *ring = r;
+  *nwaves = nw;
+  *lds = fused_lds_bytes(nw, nplan, e->nsave, e->fp.size(), mbox, r, cert);
+  *ring = r;
   return true;
 }
 
@@ -1408,6 +1484,85 @@ bool fused_plan(const mjpl_engine *e, int *nwaves, size_t *lds, int *ring = null
 bool fused_f64_ok(const mjpl_engine *e) {
   return e->fused && e->two_pass && e->expand &&
          fused_f64_lds_bytes(kFusedF64Waves, (int)e->qidx.size(), e->nsave, 64 * kFusedF64Waves + 64) <= (size_t)160 * 1024;
+}
+
+// ---- What one edge launch will do, decided before anything is reserved or enqueued (no HIP call in here).
+// mjpl_get_info reports from the same function what a launch WOULD do.
+//   kFused      the binary32 filter as ONE kernel (k_edges_fused): endpoint and waypoint tiles from a pool in LDS
+//   kTwoKernel  endpoint kernel, then (expand) the item kernel over the waypoints it emitted; ordinary or persistent grids
+//   kOnePass    the walking kernel alone (one pass asked for, or only the interior)
+//   kF64Pool    filter off: the float64 checks through the pool (k_edges_fused_f64), then k_check_edges over the walking list
+//   kExact      filter off: k_check_edges is the whole launch
+// The first three are the filter's; behind them comes either k_tail (`tail`: walking role, pair re-check and exact
+// edge role in one launch) or the walking kernel, the pair re-check and k_check_edges over the undecided edges.
+enum class EdgePipe { kFused, kTwoKernel, kOnePass, kF64Pool, kExact };
+
+struct EdgePlan {
+  EdgePipe pipe;
+  bool two_pass;    // endpoints of all edges, then the interior of the edges whose endpoint passed (unless only the interior was asked for)
+  // interior waypoints: one lane per waypoint for ordinary edges (the endpoint kernel emits the waypoints as items),
+  // the walking kernel for long edges and for models with moving boxes
+  bool expand;
+  // endpoint and item kernels as persistent grids (one wave per tile of 64, tiles from a device counter): the default
+  // for the queued interpreter when the interior waypoints become items
+  bool persistent;
+  bool tail;        // everything behind the item pass in one launch (k_tail)
+  int single;       // fused: a batch that leaves most of the chip idle takes one round of checks, not two (the endpoint as an item)
+  // fused: the library that launches it, null for the interpreting kernel (a big batch goes to the model's certificate
+  // build, if the engine found one beside the program's own library: load_spec)
+  const SpecLib *flib;
+  // float64 pool: the check through the candidate queues (narrowphase with full lanes) where the model has the queued
+  // build's shape and eight waves' queues fit beside the rows and a pool, else the immediate interpreter
+  // (MJPL_F64_QUEUED=0); generated: the library's straight-line check (ExactFull) is tried first (MJPL_F64_SPEC=0: never)
+  bool queued, generated;
+  unsigned grid, fgrid;  // exact kernels (kBlock threads), filter kernels (fblock threads)
+  int fblock;
+  size_t lds_exact;
+  size_t lds_walk;       // walking kernel: float64 columns
+  size_t lds_items;      // endpoint and item kernels of the queued interpreter keep binary32 columns
+  size_t lds_endpoints;  // ... the immediate interpreter's endpoint kernel walks the waypoint recurrence in a second column set
+  size_t lds_persistent, lds_tail, lds_pool;
+  int fwaves, pool;      // fused / float64 pool: waves per workgroup, entries of a workgroup's pool (0: neither kernel runs)
+};
+
+EdgePlan plan_edges(const mjpl_engine *e, int64_t E, int flags, bool long_edges) {
+  EdgePlan p = {};
+  const bool imm = e->immediate();
+  const int nplan = (int)e->qidx.size();
+  p.grid = (unsigned)((E + kBlock - 1) / kBlock);
+  p.fblock = imm ? kBlock : kFilterBlock;
+  p.fgrid = (unsigned)((E + p.fblock - 1) / p.fblock);
+  p.lds_exact = lds_bytes(e, 1);
+  p.lds_walk = lds_bytes(e, 1, sizeof(float), p.fblock, !imm);
+  p.lds_items = lds_bytes(e, 1, sizeof(float), p.fblock, !imm, imm ? sizeof(double) : sizeof(float));
+  p.lds_endpoints = imm ? lds_bytes(e, 2, sizeof(float), p.fblock, false) : p.lds_items;
+  p.lds_persistent = persistent_lds_bytes(nplan, e->nsave, e->fp.size(), e->filter_mbox());
+  p.lds_tail = std::max(p.lds_walk, p.lds_exact);
+  p.two_pass = e->two_pass && !(flags & MJPL_EDGE_INTERIOR_ONLY);
+  p.expand = p.two_pass && e->expand;
+  p.persistent = (e->persist < 0 ? e->spec != nullptr : e->persist != 0) && p.expand && !imm;
+  p.tail = p.expand && e->fused_tail && !imm;
+  p.single = (E <= (int64_t)e->fused_single_max) ? 1 : 0;
+  p.flib = (e->spec && !e->spec_generic && e->spec_cert && e->fused_cert && e->fused_cert_min_edges > 0 && E >= e->fused_cert_min_edges &&
+            E > (int64_t)e->fused_single_max) ? e->spec_cert : e->spec;
+  if (e->filter && e->filter_usable && E < (int64_t)1 << 29) {  // item ids travel in 29 bits of the per-lane flag words
+    // (long_edges: the batch holds a few long edges -> the kernels with checkpoints, see mjpl_check_edges)
+    if (p.expand && !long_edges && fused_plan(e, p.flib, &p.fwaves, &p.lds_pool, &p.pool)) p.pipe = EdgePipe::kFused;
+    else p.pipe = p.two_pass ? EdgePipe::kTwoKernel : EdgePipe::kOnePass;
+  } else if (fused_f64_ok(e) && !(flags & MJPL_EDGE_INTERIOR_ONLY) && E < (int64_t)1 << 30) {
+    p.pipe = EdgePipe::kF64Pool;
+    p.fwaves = kFusedF64Waves;
+    p.queued = e->f64_queued && !e->exact_general() &&
+               fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 64 * kFusedF64Waves + 64, true) <= (size_t)160 * 1024;
+    p.generated = p.queued && e->spec && e->spec->fused_f64 && e->f64_spec && e->spec->generic_rows == 0;
+    const size_t base = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 0, p.queued);
+    p.pool = (int)std::min<size_t>(kFusedMaxPool, ((size_t)160 * 1024 - base) / kFusedEntryBytes / 64 * 64);
+    if (e->fused_pool_cap > 0) p.pool = std::max(64 * kFusedF64Waves + 64, std::min(p.pool, e->fused_pool_cap / 64 * 64));
+    p.lds_pool = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, p.pool, p.queued);
+  } else {
+    p.pipe = EdgePipe::kExact;
+  }
+  return p;
 }
 
 // A filter launch takes the cleared counter set and returns the other one, which its first kernel is
@@ -1466,17 +1621,16 @@ struct KtScope {  // ... around everything a scope enqueues on the engine's stre
   ~KtScope() { kt_mark(e, mode, e->stream); }
 };
 
-// exact re-check of the undecided pairs: the model's own straight-line float64 FK if it has a library
-int launch_patch(mjpl_engine *e, unsigned pgrid, size_t ldsc, const UndecidedConfigs &uc, uint8_t *dvalid, int32_t *dfb) {
-  GeomTable gt = {e->d_geomtab, e->moving_base};
+// exact re-check of the undecided pairs: the model's own straight-line float64 FK if it has a library.  The grid is
+// sized for a generous share of the batch; surplus blocks return at once.
+int launch_patch(mjpl_engine *e, const UndecidedConfigs &uc, uint8_t *dvalid, int32_t *dfb) {
+  const unsigned pgrid = (unsigned)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 1024);
+  const size_t ldsc = lds_bytes(e, 1);
+  const GeomTable gt = {e->d_geomtab, e->moving_base};
   if (e->spec)
-    return e->spec->patch(e->stream, pgrid, (unsigned)kBlock, ldsc, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(), gt,
-                          uc, dvalid, dfb) == 0 ? MJPL_OK : fail(MJPL_E_HIP, "specialised pair kernel failed to launch");
-  int rc = allow_lds(k_patch_pairs<void>, ldsc);
-  if (rc != MJPL_OK) return rc;
-  hipLaunchKernelGGL(k_patch_pairs<void>, dim3(pgrid), dim3(kBlock), ldsc, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
-                     (int)e->dp.size(), gt, uc, dvalid, dfb);
-  return MJPL_OK;
+    return spec_rc(e->spec->patch(e->stream, pgrid, (unsigned)kBlock, ldsc, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(), gt, uc, dvalid,
+                                  dfb), "pair");
+  return launch_kernel(e, k_patch_pairs<void>, pgrid, kBlock, ldsc, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(), gt, uc, dvalid, dfb);
 }
 
 struct CounterGuard {  // marks the counter sets for a full clear unless the launch got through
@@ -1488,64 +1642,260 @@ struct CounterGuard {  // marks the counter sets for a full clear unless the lau
 int launch_configs(mjpl_engine *e, const double *dQ, int64_t N, int layout, uint8_t *dvalid,
                    unsigned long long *dbits) {
   if (N == 0) return MJPL_OK;
-  const unsigned grid = (unsigned)((N + kBlock - 1) / kBlock);
+  const int nip = (int)e->ip.size(), nfp = (int)e->fp.size(), ndp = (int)e->dp.size();
   const bool filter = e->filter && e->filter_usable && dvalid && !dbits && N < (int64_t)1 << 29;
   if (filter) {
-    int rc = ulist_reserve(e, N);
-    if (rc != MJPL_OK) return rc;
+    MJPL_TRY(ulist_reserve(e, N));
     int *zero_next = next_counters(e);
     CounterGuard guard{e, true};
-    UndecidedConfigs uc = {};
-    if (rc == MJPL_OK) {  // (both interpreters hand single undecided pairs over)
-      rc = uc_reserve(e, N);
-      uc.q = e->d_ucq; uc.edge = e->d_ucedge; uc.idx = e->d_ucidx;
-      uc.ga = e->d_ucga; uc.gb = e->d_ucgb;
-      uc.count = e->d_ucount + kCtr;
-      uc.cap = (int)std::min<size_t>(e->uc_cap, (size_t)1 << 30);
-    }
-    if (rc != MJPL_OK) return rc;
+    MJPL_TRY(uc_reserve(e, N));  // (both interpreters hand single undecided pairs over)
+    const UndecidedConfigs uc = undecided(e);
     const int fblock = e->immediate() ? kBlock : kFilterBlock;
     const unsigned fgrid = (unsigned)((N + fblock - 1) / fblock);
-    // (queued interpreter: binary32 columns)
-    const size_t ldsf = lds_bytes(e, 1, sizeof(float), fblock, !e->immediate(), e->immediate() ? sizeof(double) : sizeof(float));
+    // (queued interpreter: binary32 columns; the immediate one: float64 columns)
+    const size_t lds_filter = lds_bytes(e, 1, sizeof(float), fblock, !e->immediate(), e->immediate() ? sizeof(double) : sizeof(float));
     kt_mark(e, 1, e->stream);
-    if (e->spec)
-      rc = e->spec->configs(e->stream, fgrid, (unsigned)fblock, ldsf, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(), dQ, N,
-                            layout, e->filter_tol, dvalid, e->d_ulist, e->d_ucount, uc, zero_next) == 0 ? MJPL_OK
-           : fail(MJPL_E_HIP, "specialised configuration kernel failed to launch");
-    else rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-      auto kern = k_filter_configs<void, decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-      int r = allow_lds(kern, ldsf);
-      if (r != MJPL_OK) return r;
-      hipLaunchKernelGGL(kern, dim3(fgrid), dim3(fblock), ldsf, e->stream, e->d_ip, (int)e->ip.size(),
-                         e->d_fp, (int)e->fp.size(), dQ, N, layout, e->filter_tol, dvalid, e->d_ulist,
-                         e->d_ucount, uc, zero_next);
-      return MJPL_OK;
-    });
+    const int rc = e->spec
+        ? spec_rc(e->spec->configs(e->stream, fgrid, (unsigned)fblock, lds_filter, e->d_ip, nip, e->d_fp, nfp, dQ, N, layout, e->filter_tol,
+                                   dvalid, e->d_ulist.p, e->d_ucount, uc, zero_next), "configuration")
+        : dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+            return launch_kernel(e, k_filter_configs<void, S(), W(), M()>, fgrid, fblock, lds_filter, e->d_ip, nip, e->d_fp, nfp, dQ, N, layout,
+                                 e->filter_tol, dvalid, e->d_ulist.p, e->d_ucount, uc, zero_next);
+          });
     kt_mark(e, 1, e->stream);
-    if (rc != MJPL_OK) return rc;
+    MJPL_TRY(rc);
     guard.armed = false;
-    if (uc.count) {  // exact re-check of the undecided pairs; rows here are planning columns, AoS
-      const size_t ldsc = lds_bytes(e, 1);
-      const unsigned pgrid = (unsigned)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 1024);
-      rc = launch_patch(e, pgrid, ldsc, uc, dvalid, nullptr);
-      if (rc != MJPL_OK) return rc;
-    }
+    MJPL_TRY(launch_patch(e, uc, dvalid, nullptr));  // the undecided pairs; rows here are planning columns, AoS
   }
-  const size_t lds = lds_bytes(e, 1);
-  int rc = dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
-    auto kern = k_check_configs<decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-    int r = allow_lds(kern, lds);
-    if (r != MJPL_OK) return r;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(),
-                       e->d_dp, (int)e->dp.size(), dQ, N, layout, dvalid, dbits,
-                       filter ? e->d_ulist : nullptr, filter ? e->d_ucount : nullptr, UndecidedConfigs{},
-                       (int32_t *)nullptr);
-    return MJPL_OK;
-  });
-  if (rc != MJPL_OK) return rc;
+  const unsigned grid = (unsigned)((N + kBlock - 1) / kBlock);
+  MJPL_TRY(dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
+    return launch_kernel(e, k_check_configs<S(), W(), M()>, grid, kBlock, lds_bytes(e, 1), e->d_ip, nip, e->d_dp, ndp, dQ, N, layout, dvalid, dbits,
+                         filter ? (const int *)e->d_ulist.p : nullptr, filter ? (const int *)e->d_ucount : nullptr, UndecidedConfigs{},
+                         (int32_t *)nullptr);
+  }));
   HIP_TRY(hipGetLastError());
   return MJPL_OK;
+}
+
+// ---- one edge launch: the batch as the caller gave it, and a function per stage of the pipelines of plan_edges
+
+struct EdgeBatch {
+  const double *QA, *QB; int64_t E; double step; int layout, flags;
+  uint8_t *valid; int32_t *first_bad;
+};
+
+// What FusedArgs and TailArgs have in common: the batch, the program, the walking list -- and, with `uc`, the filter's
+// side of a launch (binary32 tables, tolerance, both undecided lists), which the float64 pool launch leaves zero.
+template <class A>
+A batch_args(const mjpl_engine *e, const EdgeBatch &b, const UndecidedConfigs *uc) {
+  A a = {};
+  a.ip = e->d_ip; a.nip = (int)e->ip.size();
+  a.QA = b.QA; a.QB = b.QB; a.E = (long long)b.E; a.layout = b.layout; a.step = b.step;
+  a.valid = b.valid; a.first_bad = b.first_bad;
+  a.status = e->d_status;
+  a.llist = e->d_llist.p; a.lcount = e->d_icount + kCtr;
+  if (uc) {
+    a.fp = e->d_fp; a.nfp = (int)e->fp.size();
+    a.tol = e->filter_tol;
+    a.uc = *uc;
+    a.ulist = e->d_ulist.p; a.ucount = e->d_ucount;
+  }
+  return a;
+}
+
+// ... and the two pool kernels: statistics, the counter set to clear, pool and policy
+FusedArgs pool_args(const mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs *uc, int *zero_next) {
+  FusedArgs fa = batch_args<FusedArgs>(e, b, uc);
+  fa.item_count = e->d_ucount + 5 * kCtr;
+  fa.surv_count = e->d_ucount + (5 + kItemRegions) * kCtr;
+  fa.cert_count = e->d_ucount + (size_t)kCtrCertified * kCtr;
+  fa.zero_next = zero_next;
+  fa.pool = p.pool; fa.policy = e->fused_policy;
+  return fa;
+}
+
+// kFused: ONE filter kernel for the launch (mjpl_fused.h), endpoint tiles and waypoint tiles from one work pool
+int stage_fused(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc, int *zero_next) {
+  FusedArgs fa = pool_args(e, p, b, &uc, zero_next);
+  fa.claim = e->d_eclaim.p; fa.gen = e->claim_gen;
+  fa.tstep = e->d_tstep.p;
+  fa.cert = e->fused_cert;
+  fa.kmax = e->fused_kmax;
+  fa.single = p.single;
+  if (e->fused_dbg_path) {  // diagnostic runs: per-wave counters of the most recent launch, written out at mjpl_destroy
+    MJPL_TRY(e->d_fused_dbg.reserve(kFusedDbgWaves * 8));
+    HIP_TRY(hipMemsetAsync(e->d_fused_dbg.p, 0, kFusedDbgWaves * 8 * sizeof(unsigned long long), e->stream));
+    fa.dbg = e->d_fused_dbg.p;
+  }
+  if (p.flib) return spec_rc(p.flib->fused(e->stream, p.fwaves, p.lds_pool, fa), "fused");
+  return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+    if constexpr (S() <= kQueuedMaxSlots) {
+      constexpr int NW = M() ? 4 : kFusedWaves;
+      if (p.fwaves != NW) return fail(MJPL_E_ARG, "fused kernel: %d waves per workgroup asked for, this build has %d", p.fwaves, NW);
+      return launch_pool(e, k_edges_fused<void, S(), W(), M(), NW>, NW, p.lds_pool, fa, "fused");
+    } else {
+      return fail(MJPL_E_ARG, "the fused kernel serves the queued interpreter");
+    }
+  });
+}
+
+// kTwoKernel with expand: the item space of the launch.  Room for 8 waypoints per edge on average, and never less
+// than a quarter of a million items: a handful of long edges (path shortcutting) is best served one waypoint per
+// lane, too
+int items_reserve(mjpl_engine *e, const EdgePlan &p, int64_t E, ItemBuffers *ib) {
+  size_t want = std::min<size_t>(std::max<size_t>((size_t)E * 8, (size_t)1 << 18) + 4096, e->item_cap_limit);
+  want = (want + p.fblock - 1) / p.fblock * p.fblock;  // whole blocks (the item space is split into regions of them)
+  if (want > e->item_cap) {
+    MJPL_TRY(release_all(e->d_itemedge, e->d_itemidx));
+    e->item_cap = 0;
+    MJPL_TRY(e->d_itemedge.reserve(want));
+    MJPL_TRY(e->d_itemidx.reserve(want));
+    e->item_cap = want;
+  }
+  const int kmax = (int)std::min<size_t>(std::max<size_t>(e->item_cap / (size_t)E, kExpandMinWaypoints), 1 << 16);
+  double *ckpt = nullptr;
+  if (kmax >= kCkptEvery) {
+    // checkpoint rows, made by the first launch with long items: one per item slot, sized by nq, the upper bound of
+    // nplan (mjpl_set_planning may widen the planning set)
+    MJPL_TRY(e->d_itemck.reserve(e->item_cap * std::max<size_t>(1, e->m.nq)));
+    ckpt = e->d_itemck.p;
+  }
+  // regions: enough workgroups behind each counter to fill it evenly, few enough waves to not queue up
+  const int regions = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kItemRegions, p.fgrid / 8), e->item_cap / p.fblock));
+  const int regcap = (int)(e->item_cap / regions / p.fblock * p.fblock);
+  *ib = ItemBuffers{e->d_itemedge.p, e->d_itemidx.p, e->d_ucount + 5 * kCtr, regions * regcap, regions, regcap,
+                    e->d_ucount + (5 + kItemRegions) * kCtr, e->d_llist.p,
+                    e->d_icount + kCtr, kmax, e->d_tstep.p, ckpt, e->d_eclaim.p, e->claim_gen};
+  return MJPL_OK;
+}
+
+// kTwoKernel: endpoints of all edges; the survivors go to d_slist, or (expand) their waypoints to the item space
+int stage_endpoints(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc, const ItemBuffers &ib,
+                    int *zero_next) {
+  const int nip = (int)e->ip.size(), nfp = (int)e->fp.size();
+  int *scount = e->d_ucount + 2 * kCtr, *etiles = e->d_ucount + kCtrEndpointTiles * kCtr;
+  if (p.persistent && e->spec)
+    return spec_rc(e->spec->endpoints_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E, b.layout, e->filter_tol, b.valid,
+                                         b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, ib, b.step, zero_next, etiles), "endpoint");
+  if (p.persistent)
+    return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+      if constexpr (S() <= kQueuedMaxSlots) {
+        return launch_persistent(e, k_filter_endpoints_pw<void, S(), W(), M()>, p.lds_persistent, (b.E + 63) / 64, e->d_ip, nip, e->d_fp, nfp, b.QA,
+                                 b.QB, b.E, b.layout, e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, ib, b.step,
+                                 zero_next, etiles);
+      } else {
+        return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
+      }
+    });
+  if (e->spec)
+    return spec_rc(e->spec->endpoints(e->stream, p.fgrid, (unsigned)p.fblock, p.lds_endpoints, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E, b.layout,
+                                      e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib,
+                                      b.step, zero_next), "endpoint");
+  return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+    return launch_kernel(e, k_filter_endpoints<void, S(), W(), M()>, p.fgrid, p.fblock, p.lds_endpoints, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E,
+                         b.layout, e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib, b.step,
+                         zero_next);
+  });
+}
+
+// kTwoKernel with expand: one lane per waypoint item
+int stage_items(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc, const ItemBuffers &ib) {
+  const int nip = (int)e->ip.size(), nfp = (int)e->fp.size();
+  const unsigned igrid = (unsigned)(ib.cap / p.fblock);  // (regions of whole blocks)
+  const EdgeSource src = {b.QA, b.QB, (long long)b.E, b.layout, b.step, ib.ckpt};
+  int *itiles = e->d_ucount + kCtrItemTiles * kCtr;
+  if (p.persistent && e->spec)
+    return spec_rc(e->spec->items_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol, b.valid, b.first_bad,
+                                     e->d_ulist.p, e->d_ucount, uc, itiles), "item");
+  if (p.persistent)
+    return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+      if constexpr (S() <= kQueuedMaxSlots) {
+        return launch_persistent(e, k_filter_items_pw<void, S(), W(), M()>, p.lds_persistent, (long long)ib.cap / 64, e->d_ip, nip, e->d_fp, nfp, ib,
+                                 src, e->filter_tol, b.valid, b.first_bad, e->d_ulist.p, e->d_ucount, uc, itiles);
+      } else {
+        return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
+      }
+    });
+  if (e->spec)
+    return spec_rc(e->spec->items(e->stream, igrid, (unsigned)p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol, b.valid,
+                                  b.first_bad, e->d_ulist.p, e->d_ucount, uc), "item");
+  return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+    return launch_kernel(e, k_filter_items<void, S(), W(), M()>, igrid, p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol,
+                         b.valid, b.first_bad, e->d_ulist.p, e->d_ucount, uc);
+  });
+}
+
+// everything behind the item pass in one launch: walking role over the long-edge list, pair
+// re-check, exact edge role over the undecided-edge list (k_tail)
+int stage_tail(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc) {
+  TailArgs ta = batch_args<TailArgs>(e, b, &uc);
+  ta.dp = e->d_dp; ta.ndp = (int)e->dp.size();
+  ta.gt = GeomTable{e->d_geomtab, e->moving_base};
+  ta.flags = b.flags;
+  ta.done = e->d_ucount + kCtrTailDone * kCtr;
+  ta.nw = ta.nx = (int)std::min<int64_t>((b.E + kBlock - 1) / kBlock, 64);
+  ta.np = (int)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 64);
+  if (e->spec) return spec_rc(e->spec->tail(e->stream, p.lds_tail, ta), "tail");
+  auto go = [&](auto SF, auto SD, auto W, auto M) -> int {
+    return launch_kernel(e, k_tail<void, SF(), SD(), W(), M()>, (unsigned)(ta.nw + ta.np + ta.nx), kBlock, p.lds_tail, ta);
+  };
+  if (e->exact_general())  // (moving boxes: 24-slot queued filter build, general exact build)
+    return go(std::integral_constant<int, kQueuedMaxSlots>{}, std::integral_constant<int, 32>{}, std::true_type{}, std::true_type{});
+  return dispatch_variant(e, [&](auto S, auto W, auto M) -> int { return go(S, S, W, M); });
+}
+
+// the walking kernel (k_filter_edges) over `rlist`: every edge in a one-pass launch (null list), which is then the
+// launch's first kernel and clears the other counter set
+int stage_walk(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc, const int *rlist, const int *rcount,
+               int *zero_next) {
+  return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
+    return launch_kernel(e, k_filter_edges<S(), W(), M()>, p.fgrid, p.fblock, p.lds_walk, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(),
+                         b.QA, b.QB, b.E, b.step, b.layout, p.two_pass ? (b.flags | MJPL_EDGE_INTERIOR_ONLY) : b.flags, e->filter_tol, b.valid,
+                         b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, rlist, rcount, p.two_pass ? (int *)nullptr : zero_next);
+  });
+}
+
+// undecided waypoints: the exact configuration kernel in patch mode for the whole configurations the immediate
+// filter hands over (entries with ga < 0), then the single geom pairs (entries with ga >= 0)
+int stage_patch(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc) {
+  if (e->immediate()) {
+    const unsigned pgrid = (unsigned)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 1024);
+    MJPL_TRY(dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
+      return launch_kernel(e, k_check_configs<S(), W(), M()>, pgrid, kBlock, p.lds_exact, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(),
+                           (const double *)uc.q, (int64_t)0, (int)MJPL_AOS, b.valid, (unsigned long long *)nullptr, (const int *)nullptr,
+                           (const int *)nullptr, uc, b.first_bad);
+    }));
+  }
+  return launch_patch(e, uc, b.valid, b.first_bad);
+}
+
+// kF64Pool: endpoints, then the interior waypoints of the survivors as items; edges of more than kFusedF64Kmax
+// waypoints are left on the walking list
+int stage_pool_f64(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, int *zero_next) {
+  FusedArgs fa = pool_args(e, p, b, nullptr, zero_next);
+  fa.dp = e->d_dp; fa.ndp = (int)e->dp.size();
+  fa.kmax = kFusedF64Kmax;
+  if (p.generated) {
+    const int r = e->spec->fused_f64(e->stream, kFusedF64Waves, p.lds_pool, fa);
+    if (r == 0) return MJPL_OK;
+    if (r != -1) return fail(MJPL_E_HIP, "the generated float64 pool kernel failed to launch");  // (-1: refused, the interpreting kernel runs)
+  }
+  return dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
+    if constexpr (!M() && S() <= 16) {
+      if (p.queued)
+        return launch_pool(e, k_edges_fused_f64<S(), W(), false, kFusedF64Waves, true>, kFusedF64Waves, p.lds_pool, fa, "float64 pool");
+    }
+    return launch_pool(e, k_edges_fused_f64<S(), W(), M(), kFusedF64Waves, false>, kFusedF64Waves, p.lds_pool, fa, "float64 pool");
+  });
+}
+
+// k_check_edges, the exact kernel: over the edges of `list` (the undecided edges of a filter launch; the walking list
+// of the float64 pool, interior waypoints only: the endpoint's verdict stands), or over the whole batch (null)
+int stage_exact(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, int flags, const int *list, const int *count) {
+  return dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
+    return launch_kernel(e, k_check_edges<S(), W(), M()>, p.grid, kBlock, p.lds_exact, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(), b.QA,
+                         b.QB, b.E, b.step, b.layout, flags, b.valid, b.first_bad, e->d_status, list, count);
+  });
 }
 
 // stages of one edge launch, in stream order (include/mjpl_hip.h: MJPL_STAGE_*)
@@ -1554,429 +1904,81 @@ int launch_configs(mjpl_engine *e, const double *dQ, int64_t N, int layout, uint
     if (e->marks) HIP_TRY(hipEventRecord(e->marks[k], e->stream));            \
   } while (0)
 
+// One edge launch.  What runs between the marks, per pipeline (plan_edges):
+//   kFused       0  k_edges_fused                        1  2 |  with the tail:  3  k_tail  4  5
+//   kTwoKernel   0  endpoints  1  items (expand)            2 |  without:        walk  3  patch  4  k_check_edges  5
+//   kOnePass     0             1                            2 |  (never the tail)
+//   kF64Pool     0  k_edges_fused_f64  1  2  3  4  k_check_edges over the walking list  5
+//   kExact       0  1  2  3  4  k_check_edges  5
+// Of the two counter sets a launch works in the cleared one; its first kernel clears the other (zero_next), and from
+// then on the guard stands down: the sets are in step again.
 int launch_edges(mjpl_engine *e, const double *dQA, const double *dQB, int64_t E, double step,
-                 int layout, int flags, uint8_t *dvalid, int32_t *dfb) {
+                 int layout, int flags, uint8_t *dvalid, int32_t *dfb, bool long_edges) {
   if (E == 0) return MJPL_OK;
-  const unsigned grid = (unsigned)((E + kBlock - 1) / kBlock);
-  const bool filter = e->filter && e->filter_usable && E < (int64_t)1 << 29;  // item ids travel in 29 bits of the per-lane flag words
-  UndecidedConfigs uc = {};
-  if (filter) {
-    int rc = ulist_reserve(e, E);
-    if (rc == MJPL_OK) rc = uc_reserve(e, E);
-    if (rc != MJPL_OK) return rc;
-    int *zero_next = next_counters(e);  // (this launch's own set was cleared by the launch before it)
-    CounterGuard guard{e, true};
-    uc.q = e->d_ucq; uc.edge = e->d_ucedge; uc.idx = e->d_ucidx;
-    uc.ga = e->d_ucga; uc.gb = e->d_ucgb;
-    uc.count = e->d_ucount + kCtr;
-    uc.cap = (int)std::min<size_t>(e->uc_cap, (size_t)1 << 30);
-    MJPL_MARK(0);
-    const int fblock = e->immediate() ? kBlock : kFilterBlock;
-    const unsigned fgrid = (unsigned)((E + fblock - 1) / fblock);
-    const size_t ldsf = lds_bytes(e, 1, sizeof(float), fblock, !e->immediate());  // walking kernel: float64 columns
-    // endpoint and item kernels of the queued interpreter keep binary32 columns
-    const size_t ldsq = lds_bytes(e, 1, sizeof(float), fblock, !e->immediate(), e->immediate() ? sizeof(double) : sizeof(float));
-    // the endpoint kernel of the immediate interpreter walks the waypoint recurrence in a second
-    // column set (the queued one reuses the workgroup's columns, saves and queues)
-    const size_t ldse = e->immediate() ? lds_bytes(e, 2, sizeof(float), fblock, false) : ldsq;
-    // two passes unless only the interior was asked for: endpoints of all edges, then the interior
-    // waypoints of the edges whose endpoint passed
-    const bool two_pass = e->two_pass && !(flags & MJPL_EDGE_INTERIOR_ONLY);
-    // interior waypoints: one lane per waypoint for ordinary edges (the endpoint kernel emits the
-    // waypoints as items), the walking kernel for long edges and for models with moving boxes
-    const bool expand = two_pass && e->expand;
-    const int *rlist = nullptr, *rcount = nullptr;  // work list of the walking kernel
-    ItemBuffers ib = {};
-    int fwaves = 0, fring = 0;
-    size_t flds = 0;
-    // (a big batch goes to the model's certificate build, if the engine found one beside the program's own library: load_spec)
-    const SpecLib *flib = (e->spec && !e->spec_generic && e->spec_cert && e->fused_cert && e->fused_cert_min_edges > 0 && E >= e->fused_cert_min_edges &&
-                           E > (int64_t)e->fused_single_max) ? e->spec_cert : e->spec;
-    const bool fused = expand && !e->fused_skip_once && fused_plan(e, &fwaves, &flds, &fring, flib);
-    e->fused_skip_once = false;  // (set by the host-pointer entry point for the launch that follows it)
-    if (expand) {
-      // per-edge scratch: walking list, step fractions, claim words of the undecided-edge list
-      if ((size_t)E > e->llist_cap) {
-        for (void *ptr : {(void *)e->d_tstep, (void *)e->d_llist, (void *)e->d_eclaim})
-          if (ptr) HIP_TRY(hipFree(ptr));
-        e->d_tstep = nullptr;
-        e->d_llist = e->d_eclaim = nullptr;
-        e->llist_cap = 0;
-        HIP_TRY(hipMalloc(&e->d_llist, (size_t)E * sizeof(int)));
-        HIP_TRY(hipMalloc(&e->d_tstep, (size_t)E * sizeof(double)));
-        HIP_TRY(hipMalloc(&e->d_eclaim, (size_t)E * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(e->d_eclaim, 0, (size_t)E * sizeof(int), e->stream));
-        e->claim_gen = 0;
-        e->llist_cap = (size_t)E;
-      }
-      if (++e->claim_gen == std::numeric_limits<int>::max()) {  // generations never repeat between clears
-        HIP_TRY(hipMemsetAsync(e->d_eclaim, 0, e->llist_cap * sizeof(int), e->stream));
-        e->claim_gen = 1;
-      }
-    }
-    if (expand && !fused) {
-      // room for 8 waypoints per edge on average, and never less than a quarter of a million items:
-      // a handful of long edges (path shortcutting) is best served one waypoint per lane, too
-      size_t want = std::min<size_t>(std::max<size_t>((size_t)E * 8, (size_t)1 << 18) + 4096, e->item_cap_limit);
-      want = (want + fblock - 1) / fblock * fblock;  // whole blocks (the item space is split into regions of them)
-      if (want > e->item_cap) {
-        for (void *ptr : {(void *)e->d_itemedge, (void *)e->d_itemidx})
-          if (ptr) HIP_TRY(hipFree(ptr));
-        e->d_itemedge = e->d_itemidx = nullptr;
-        e->item_cap = 0;
-        HIP_TRY(hipMalloc(&e->d_itemedge, want * sizeof(int)));
-        HIP_TRY(hipMalloc(&e->d_itemidx, want * sizeof(int)));
-        e->item_cap = want;
-      }
-      const int kmax = (int)std::min<size_t>(std::max<size_t>(e->item_cap / (size_t)E, kExpandMinWaypoints), 1 << 16);
-      double *ckpt = nullptr;
-      if (kmax >= kCkptEvery) {
-        // rows are sized by nq, the upper bound of nplan (mjpl_set_planning may widen the planning set)
-        if (e->itemck_cap < e->item_cap) {
-          if (e->d_itemck) HIP_TRY(hipFree(e->d_itemck));
-          e->d_itemck = nullptr; e->itemck_cap = 0;
-          HIP_TRY(hipMalloc(&e->d_itemck, e->item_cap * std::max<size_t>(1, e->m.nq) * sizeof(double)));
-          e->itemck_cap = e->item_cap;
-        }
-        ckpt = e->d_itemck;
-      }
-      // regions: enough workgroups behind each counter to fill it evenly, few enough waves to not queue up
-      const int regions = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kItemRegions, fgrid / 8), e->item_cap / fblock));
-      const int regcap = (int)(e->item_cap / regions / fblock * fblock);
-      ib = ItemBuffers{e->d_itemedge, e->d_itemidx, e->d_ucount + 5 * kCtr, regions * regcap, regions, regcap,
-                       e->d_ucount + (5 + kItemRegions) * kCtr, e->d_llist,
-                       e->d_icount + kCtr, kmax, e->d_tstep, ckpt, e->d_eclaim, e->claim_gen};
-    }
-    if (fused) {
-      // ---- ONE filter kernel for the launch (mjpl_fused.h): endpoint tiles and waypoint tiles from one work pool
-      FusedArgs fa = {};
-      fa.ip = e->d_ip; fa.nip = (int)e->ip.size();
-      fa.fp = e->d_fp; fa.nfp = (int)e->fp.size();
-      fa.QA = dQA; fa.QB = dQB; fa.E = (long long)E; fa.layout = layout;
-      fa.tol = e->filter_tol; fa.step = step;
-      fa.valid = dvalid; fa.first_bad = dfb;
-      fa.status = e->d_status; fa.ulist = e->d_ulist; fa.ucount = e->d_ucount;
-      fa.uc = uc;
-      fa.llist = e->d_llist; fa.lcount = e->d_icount + kCtr;
-      fa.claim = e->d_eclaim; fa.gen = e->claim_gen;
-      fa.tstep = e->d_tstep;
-      fa.item_count = e->d_ucount + 5 * kCtr;
-      fa.surv_count = e->d_ucount + (5 + kItemRegions) * kCtr;
-      fa.cert_count = e->d_ucount + (size_t)kCtrCertified * kCtr;
-      fa.cert = e->fused_cert;
-      fa.zero_next = zero_next;
-      fa.kmax = e->fused_kmax; fa.pool = fring; fa.policy = e->fused_policy;
-      // a batch that leaves most of the chip idle: one round of checks instead of two (the endpoint as an item)
-      fa.single = (E <= (int64_t)e->fused_single_max) ? 1 : 0;
-      if (e->fused_dbg_path) {  // diagnostic runs: per-wave counters of the most recent launch, written out at mjpl_destroy
-        if (!e->d_fused_dbg) {
-          HIP_TRY(hipMalloc(&e->d_fused_dbg, kFusedDbgWaves * 8 * sizeof(unsigned long long)));
-        }
-        HIP_TRY(hipMemsetAsync(e->d_fused_dbg, 0, kFusedDbgWaves * 8 * sizeof(unsigned long long), e->stream));
-        fa.dbg = e->d_fused_dbg;
-      }
-      if (flib) {
-        rc = flib->fused(e->stream, fwaves, flds, fa) == 0 ? MJPL_OK : fail(MJPL_E_HIP, "specialised fused kernel failed to launch");
-      } else {
-        rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-          if constexpr (decltype(S)::value <= kQueuedMaxSlots) {
-            constexpr int NW = decltype(M)::value ? 4 : kFusedWaves;
-            auto kern = k_edges_fused<void, decltype(S)::value, decltype(W)::value, decltype(M)::value, NW>;
-            if (fwaves != NW) return fail(MJPL_E_ARG, "fused kernel: %d waves per workgroup asked for, this build has %d", fwaves, NW);
-            int r = allow_lds(kern, flds);
-            if (r != MJPL_OK) return r;
-            if (fused_launch(kern, NW, flds, fa, e->stream) != hipSuccess) return fail(MJPL_E_HIP, "the fused kernel failed to launch");
-            return MJPL_OK;
-          } else {
-            return fail(MJPL_E_ARG, "the fused kernel serves the queued interpreter");
-          }
-        });
-      }
-      if (rc != MJPL_OK) return rc;
-      guard.armed = false;
-      MJPL_MARK(1);
-      rlist = e->d_llist;  // what is left for the walking role
-      rcount = e->d_icount + kCtr;
-    }
-    if (two_pass && !fused) {
-      if ((size_t)E > e->slist_cap) {
-        if (e->d_slist) HIP_TRY(hipFree(e->d_slist));
-        e->d_slist = nullptr; e->slist_cap = 0;
-        HIP_TRY(hipMalloc(&e->d_slist, (size_t)E * sizeof(int)));
-        e->slist_cap = (size_t)E;
-      }
-      rlist = e->d_slist;
-      rcount = e->d_ucount + 2 * kCtr;
-      // persistent grids (one wave per tile of 64, tiles from a device counter): the default for the
-      // queued interpreter when the interior waypoints become items
-      const bool pw = (e->persist < 0 ? e->spec != nullptr : e->persist != 0) && expand && !e->immediate();
-      const size_t ldsp = persistent_lds_bytes((int)e->qidx.size(), e->nsave, e->fp.size(), e->filter_mbox());
-      int *etiles = e->d_ucount + kCtrEndpointTiles * kCtr;
-      if (pw && e->spec)
-        rc = e->spec->endpoints_pw(e->stream, ldsp, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(), dQA, dQB, E, layout,
-                                   e->filter_tol, dvalid, dfb, e->d_status, e->d_ulist, e->d_ucount, uc, ib, step, zero_next,
-                                   etiles) == 0 ? MJPL_OK : fail(MJPL_E_HIP, "specialised endpoint kernel failed to launch");
-      else if (pw)
-        rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-          if constexpr (decltype(S)::value <= kQueuedMaxSlots) {
-            auto kern = k_filter_endpoints_pw<void, decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-            int r = allow_lds(kern, ldsp);
-            if (r != MJPL_OK) return r;
-            hipLaunchKernelGGL(kern, dim3(persistent_grid(kern, ldsp, (E + 63) / 64)), dim3(kBlock), ldsp, e->stream, e->d_ip,
-                               (int)e->ip.size(), e->d_fp, (int)e->fp.size(), dQA, dQB, E, layout, e->filter_tol, dvalid, dfb,
-                               e->d_status, e->d_ulist, e->d_ucount, uc, ib, step, zero_next, etiles);
-            return MJPL_OK;
-          } else {
-            return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
-          }
-        });
-      else if (e->spec)
-        rc = e->spec->endpoints(e->stream, fgrid, (unsigned)fblock, ldse, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(), dQA,
-                                dQB, E, layout, e->filter_tol, dvalid, dfb, e->d_status, e->d_ulist, e->d_ucount, uc, e->d_slist,
-                                e->d_ucount + 2 * kCtr, ib, step, zero_next) == 0 ? MJPL_OK
-             : fail(MJPL_E_HIP, "specialised endpoint kernel failed to launch");
-      else rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-        auto kern = k_filter_endpoints<void, decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-        int r = allow_lds(kern, ldse);
-        if (r != MJPL_OK) return r;
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(fblock), ldse, e->stream, e->d_ip, (int)e->ip.size(),
-                           e->d_fp, (int)e->fp.size(), dQA, dQB, E, layout, e->filter_tol, dvalid, dfb,
-                           e->d_status, e->d_ulist, e->d_ucount, uc, e->d_slist, e->d_ucount + 2 * kCtr, ib, step,
-                           zero_next);
-        return MJPL_OK;
-      });
-      if (rc != MJPL_OK) return rc;
-      guard.armed = false;
-    }
-    if (!fused) MJPL_MARK(1);  // after k_filter_endpoints (nothing ran yet in a one-pass launch)
-    if (expand && !fused) {
-      const unsigned igrid = (unsigned)(ib.cap / fblock);  // (regions of whole blocks)
-      const EdgeSource src = {dQA, dQB, (long long)E, layout, step, ib.ckpt};
-      const bool pw = (e->persist < 0 ? e->spec != nullptr : e->persist != 0) && !e->immediate();
-      const size_t ldsp = persistent_lds_bytes((int)e->qidx.size(), e->nsave, e->fp.size(), e->filter_mbox());
-      int *itiles = e->d_ucount + kCtrItemTiles * kCtr;
-      if (pw && e->spec)
-        rc = e->spec->items_pw(e->stream, ldsp, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(), ib, src, e->filter_tol, dvalid,
-                               dfb, e->d_ulist, e->d_ucount, uc, itiles) == 0 ? MJPL_OK
-             : fail(MJPL_E_HIP, "specialised item kernel failed to launch");
-      else if (pw)
-        rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-          if constexpr (decltype(S)::value <= kQueuedMaxSlots) {
-            auto kern = k_filter_items_pw<void, decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-            int r = allow_lds(kern, ldsp);
-            if (r != MJPL_OK) return r;
-            hipLaunchKernelGGL(kern, dim3(persistent_grid(kern, ldsp, (long long)ib.cap / 64)), dim3(kBlock), ldsp, e->stream, e->d_ip,
-                               (int)e->ip.size(), e->d_fp, (int)e->fp.size(), ib, src, e->filter_tol, dvalid, dfb, e->d_ulist,
-                               e->d_ucount, uc, itiles);
-            return MJPL_OK;
-          } else {
-            return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
-          }
-        });
-      else if (e->spec)
-        rc = e->spec->items(e->stream, igrid, (unsigned)fblock, ldsq, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(), ib,
-                            src, e->filter_tol, dvalid, dfb, e->d_ulist, e->d_ucount, uc) == 0 ? MJPL_OK
-             : fail(MJPL_E_HIP, "specialised item kernel failed to launch");
-      else rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-        auto kern = k_filter_items<void, decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-        int r = allow_lds(kern, ldsq);
-        if (r != MJPL_OK) return r;
-        hipLaunchKernelGGL(kern, dim3(igrid), dim3(fblock), ldsq, e->stream, e->d_ip, (int)e->ip.size(),
-                           e->d_fp, (int)e->fp.size(), ib, src, e->filter_tol, dvalid, dfb, e->d_ulist, e->d_ucount,
-                           uc);
-        return MJPL_OK;
-      });
-      if (rc != MJPL_OK) return rc;
-      rlist = e->d_llist;  // what is left for the walking kernel
-      rcount = e->d_icount + kCtr;
-    }
-    MJPL_MARK(2);  // after k_filter_items
-    if (expand && e->fused_tail && !e->immediate()) {
-      // everything behind the item pass in one launch: walking role over the long-edge list, pair
-      // re-check, exact edge role over the undecided-edge list (k_tail)
-      MJPL_MARK(3);
-      const size_t ldst = std::max(ldsf, lds_bytes(e, 1));
-      TailArgs ta = {};
-      ta.ip = e->d_ip; ta.nip = (int)e->ip.size();
-      ta.fp = e->d_fp; ta.nfp = (int)e->fp.size();
-      ta.dp = e->d_dp; ta.ndp = (int)e->dp.size();
-      ta.gt = GeomTable{e->d_geomtab, e->moving_base};
-      ta.uc = uc;
-      ta.QA = dQA; ta.QB = dQB; ta.E = (long long)E; ta.step = step; ta.layout = layout; ta.flags = flags;
-      ta.tol = e->filter_tol;
-      ta.valid = dvalid; ta.first_bad = dfb;
-      ta.status = e->d_status; ta.ulist = e->d_ulist; ta.ucount = e->d_ucount;
-      ta.llist = e->d_llist; ta.lcount = e->d_icount + kCtr;
-      ta.done = e->d_ucount + kCtrTailDone * kCtr;
-      const int eblocks = (int)std::min<int64_t>((E + kBlock - 1) / kBlock, 64);
-      ta.nw = eblocks;
-      ta.np = (int)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 64);
-      ta.nx = eblocks;
-      if (e->spec) {
-        rc = e->spec->tail(e->stream, ldst, ta) == 0 ? MJPL_OK : fail(MJPL_E_HIP, "specialised tail kernel failed to launch");
-      } else {
-        auto go = [&](auto SF, auto SD, auto W, auto M) -> int {
-          auto kern = k_tail<void, decltype(SF)::value, decltype(SD)::value, decltype(W)::value, decltype(M)::value>;
-          int r = allow_lds(kern, ldst);
-          if (r != MJPL_OK) return r;
-          hipLaunchKernelGGL(kern, dim3((unsigned)(ta.nw + ta.np + ta.nx)), dim3(kBlock), ldst, e->stream, ta);
-          return MJPL_OK;
-        };
-        if (e->exact_general())  // (moving boxes: 24-slot queued filter build, general exact build)
-          rc = go(std::integral_constant<int, kQueuedMaxSlots>{}, std::integral_constant<int, 32>{}, std::true_type{}, std::true_type{});
-        else
-          rc = dispatch_variant(e, [&](auto S, auto W, auto M) -> int { return go(S, S, W, M); });
-      }
-      if (rc != MJPL_OK) return rc;
-      guard.armed = false;
-      MJPL_MARK(4);
-      MJPL_MARK(5);
-      HIP_TRY(hipGetLastError());
-      return MJPL_OK;
-    }
-    rc = dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-      auto kern = k_filter_edges<decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-      int r = allow_lds(kern, ldsf);
-      if (r != MJPL_OK) return r;
-      hipLaunchKernelGGL(kern, dim3(fgrid), dim3(fblock), ldsf, e->stream, e->d_ip, (int)e->ip.size(),
-                         e->d_fp, (int)e->fp.size(), dQA, dQB, E, step, layout,
-                         two_pass ? (flags | MJPL_EDGE_INTERIOR_ONLY) : flags, e->filter_tol, dvalid,
-                         dfb, e->d_status, e->d_ulist, e->d_ucount, uc, rlist, rcount,
-                         two_pass ? (int *)nullptr : zero_next);
-      return MJPL_OK;
-    });
-    if (rc != MJPL_OK) return rc;
-    guard.armed = false;
-    MJPL_MARK(3);  // after k_filter_edges (the walking kernel)
-    // undecided waypoints: exact configuration kernel in patch mode (grid sized for a generous
-    // share of the batch; surplus blocks return at once)
-    const size_t ldsc = lds_bytes(e, 1);
-    const unsigned pgrid = (unsigned)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 1024);
-    if (e->immediate()) {  // immediate filter: also whole configurations (entries with ga < 0)
-      rc = dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
-        auto kern = k_check_configs<decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-        int r = allow_lds(kern, ldsc);
-        if (r != MJPL_OK) return r;
-        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(kBlock), ldsc, e->stream, e->d_ip, (int)e->ip.size(),
-                           e->d_dp, (int)e->dp.size(), (const double *)uc.q, (int64_t)0, (int)MJPL_AOS, dvalid,
-                           (unsigned long long *)nullptr, (const int *)nullptr, (const int *)nullptr, uc, dfb);
-        return MJPL_OK;
-      });
-      if (rc != MJPL_OK) return rc;
-    }
-    {  // single geom pairs (entries with ga >= 0)
-      rc = launch_patch(e, pgrid, ldsc, uc, dvalid, dfb);
-      if (rc != MJPL_OK) return rc;
-    }
-    MJPL_MARK(4);  // after the exact re-check of undecided pairs / configurations
-  } else if (fused_f64_ok(e) && !(flags & MJPL_EDGE_INTERIOR_ONLY) && E < (int64_t)1 << 30) {
-    // ---- filter off, the float64 checks through the pool (mjpl_fused.h: k_edges_fused_f64): endpoints, then the interior
-    // waypoints of the survivors as items; edges of more than kFusedF64Kmax waypoints are left to k_check_edges below
-    int rc = ulist_reserve(e, E);
-    if (rc != MJPL_OK) return rc;
-    if ((size_t)E > e->llist_cap) {
-      for (void *ptr : {(void *)e->d_tstep, (void *)e->d_llist, (void *)e->d_eclaim})
-        if (ptr) HIP_TRY(hipFree(ptr));
-      e->d_tstep = nullptr;
-      e->d_llist = e->d_eclaim = nullptr;
-      e->llist_cap = 0;
-      HIP_TRY(hipMalloc(&e->d_llist, (size_t)E * sizeof(int)));
-      HIP_TRY(hipMalloc(&e->d_tstep, (size_t)E * sizeof(double)));
-      HIP_TRY(hipMalloc(&e->d_eclaim, (size_t)E * sizeof(int)));
-      HIP_TRY(hipMemsetAsync(e->d_eclaim, 0, (size_t)E * sizeof(int), e->stream));
-      e->claim_gen = 0;
-      e->llist_cap = (size_t)E;
-    }
+  const EdgePlan p = plan_edges(e, E, flags, long_edges);
+  const EdgeBatch b = {dQA, dQB, E, step, layout, flags, dvalid, dfb};
+  if (p.pipe == EdgePipe::kExact) {
+    for (int k = 0; k <= 4; k++) MJPL_MARK(k);
+    MJPL_TRY(stage_exact(e, p, b, flags, nullptr, nullptr));
+  } else if (p.pipe == EdgePipe::kF64Pool) {
+    MJPL_TRY(ulist_reserve(e, E));
+    MJPL_TRY(llist_reserve(e, E));
     int *zero_next = next_counters(e);
     CounterGuard guard{e, true};
-    const int nplan = (int)e->qidx.size();
-    // the check through the candidate queues (narrowphase with full lanes) where the model has the queued build's
-    // shape and eight waves' queues fit beside the rows and a pool; else the immediate interpreter (MJPL_F64_QUEUED=0)
-    const bool queued = e->f64_queued && !e->exact_general() &&
-                        fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 64 * kFusedF64Waves + 64, true) <= (size_t)160 * 1024;
-    const size_t base = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 0, queued);
-    int pool = (int)std::min<size_t>(kFusedMaxPool, ((size_t)160 * 1024 - base) / kFusedEntryBytes / 64 * 64);
-    if (e->fused_pool_cap > 0) pool = std::max(64 * kFusedF64Waves + 64, std::min(pool, e->fused_pool_cap / 64 * 64));
-    const size_t flds = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, pool, queued);
-    FusedArgs fa = {};
-    fa.ip = e->d_ip; fa.nip = (int)e->ip.size();
-    fa.dp = e->d_dp; fa.ndp = (int)e->dp.size();
-    fa.QA = dQA; fa.QB = dQB; fa.E = (long long)E; fa.layout = layout;
-    fa.step = step;
-    fa.valid = dvalid; fa.first_bad = dfb;
-    fa.status = e->d_status;
-    fa.llist = e->d_llist; fa.lcount = e->d_icount + kCtr;
-    fa.item_count = e->d_ucount + 5 * kCtr;
-    fa.surv_count = e->d_ucount + (5 + kItemRegions) * kCtr;
-    fa.cert_count = e->d_ucount + (size_t)kCtrCertified * kCtr;
-    fa.cert = 0;
-    fa.zero_next = zero_next;
-    fa.kmax = kFusedF64Kmax; fa.pool = pool; fa.policy = e->fused_policy;
     MJPL_MARK(0);
-    // a model's library may carry the check as straight-line code (ExactFull; MJPL_F64_SPEC=0: the interpreting kernel)
-    bool generated = false;
-    if (queued && e->spec && e->spec->fused_f64 && e->f64_spec && e->spec->generic_rows == 0) {
-      const int r2 = e->spec->fused_f64(e->stream, kFusedF64Waves, flds, fa);
-      if (r2 == 0) generated = true;
-      else if (r2 != -1) return fail(MJPL_E_HIP, "the generated float64 pool kernel failed to launch");
-    }
-    rc = generated ? MJPL_OK : dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
-      auto go = [&](auto kern) -> int {
-        int r = allow_lds(kern, flds);
-        if (r != MJPL_OK) return r;
-        if (fused_launch(kern, kFusedF64Waves, flds, fa, e->stream) != hipSuccess) return fail(MJPL_E_HIP, "the float64 pool kernel failed to launch");
-        return MJPL_OK;
-      };
-      if constexpr (!decltype(M)::value && decltype(S)::value <= 16) {
-        if (queued) return go(k_edges_fused_f64<decltype(S)::value, decltype(W)::value, false, kFusedF64Waves, true>);
-      }
-      return go(k_edges_fused_f64<decltype(S)::value, decltype(W)::value, decltype(M)::value, kFusedF64Waves, false>);
-    });
-    if (rc != MJPL_OK) return rc;
+    MJPL_TRY(stage_pool_f64(e, p, b, zero_next));
     guard.armed = false;
     for (int k = 1; k <= 4; k++) MJPL_MARK(k);
-    // the walking list (long edges): k_check_edges, interior waypoints only (the endpoint's verdict stands)
-    const size_t ldsw = lds_bytes(e, 1);
-    rc = dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
-      auto kern = k_check_edges<decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-      int r = allow_lds(kern, ldsw);
-      if (r != MJPL_OK) return r;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), ldsw, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(),
-                         dQA, dQB, E, step, layout, flags | MJPL_EDGE_INTERIOR_ONLY, dvalid, dfb, e->d_status,
-                         (const int *)e->d_llist, (const int *)(e->d_icount + kCtr));
-      return MJPL_OK;
-    });
-    if (rc != MJPL_OK) return rc;
-    MJPL_MARK(5);
-    HIP_TRY(hipGetLastError());
-    return MJPL_OK;
+    MJPL_TRY(stage_exact(e, p, b, flags | MJPL_EDGE_INTERIOR_ONLY, e->d_llist.p, e->d_icount + kCtr));
   } else {
-    for (int k = 0; k <= 4; k++) MJPL_MARK(k);  // filter off: the exact kernel is the whole launch
+    MJPL_TRY(ulist_reserve(e, E));
+    MJPL_TRY(uc_reserve(e, E));
+    int *zero_next = next_counters(e);  // (this launch's own set was cleared by the launch before it)
+    CounterGuard guard{e, true};
+    const UndecidedConfigs uc = undecided(e);
+    MJPL_MARK(0);
+    if (p.expand) {
+      MJPL_TRY(llist_reserve(e, E));
+      MJPL_TRY(next_claim_gen(e));
+    }
+    const int *rlist = nullptr, *rcount = nullptr;  // work list of the walking kernel: all edges, ...
+    ItemBuffers ib = {};
+    if (p.pipe == EdgePipe::kFused) {
+      MJPL_TRY(stage_fused(e, p, b, uc, zero_next));
+      guard.armed = false;
+    } else {
+      if (p.expand) MJPL_TRY(items_reserve(e, p, E, &ib));
+      if (p.two_pass) {
+        MJPL_TRY(e->d_slist.reserve((size_t)E));
+        MJPL_TRY(stage_endpoints(e, p, b, uc, ib, zero_next));
+        guard.armed = false;
+        rlist = e->d_slist.p;  // ... those whose endpoint passed, ...
+        rcount = e->d_ucount + 2 * kCtr;
+      }
+    }
+    MJPL_MARK(1);
+    if (p.expand) {
+      if (p.pipe != EdgePipe::kFused) MJPL_TRY(stage_items(e, p, b, uc, ib));
+      rlist = e->d_llist.p;  // ... or what the pool or the item space left to it
+      rcount = e->d_icount + kCtr;
+    }
+    MJPL_MARK(2);
+    if (p.tail) {
+      MJPL_MARK(3);
+      MJPL_TRY(stage_tail(e, p, b, uc));
+      guard.armed = false;
+      MJPL_MARK(4);
+    } else {
+      MJPL_TRY(stage_walk(e, p, b, uc, rlist, rcount, zero_next));
+      guard.armed = false;
+      MJPL_MARK(3);
+      MJPL_TRY(stage_patch(e, p, b, uc));
+      MJPL_MARK(4);
+      MJPL_TRY(stage_exact(e, p, b, flags, e->d_ulist.p, e->d_ucount));
+    }
   }
-  const size_t lds = lds_bytes(e, 1);
-  int rc = dispatch_variant(e, [&](auto S, auto W, auto M) -> int {
-    auto kern = k_check_edges<decltype(S)::value, decltype(W)::value, decltype(M)::value>;
-    int r = allow_lds(kern, lds);
-    if (r != MJPL_OK) return r;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, e->stream, e->d_ip, (int)e->ip.size(),
-                       e->d_dp, (int)e->dp.size(), dQA, dQB, E, step, layout, flags, dvalid, dfb, e->d_status,
-                       filter ? (const int *)e->d_ulist : nullptr, filter ? (const int *)e->d_ucount : nullptr);
-    return MJPL_OK;
-  });
-  if (rc != MJPL_OK) return rc;
-  MJPL_MARK(5);  // after k_check_edges
+  MJPL_MARK(5);
   HIP_TRY(hipGetLastError());
-  return MJPL_OK;
-}
-
-// A grow-only device buffer of at least `need` bytes
-int grow_device(double *&buf, size_t &have, size_t need) {
-  if (need <= have) return MJPL_OK;
-  if (buf) HIP_TRY(hipFree(buf));
-  buf = nullptr;
-  have = 0;
-  HIP_TRY(hipMalloc(&buf, need));
-  have = need;
   return MJPL_OK;
 }
 
@@ -2003,10 +2005,10 @@ int pair_query_prologue(mjpl_engine *e, K kernel, int64_t N, PairLaunch *pl) {
   if (rc != MJPL_OK) return rc;
   const size_t ng = e->m.ngeom;
   pl->rows = std::min<int64_t>(N, kContactRows);
-  rc = grow_device(e->d_ct_scratch, e->ct_scratch_bytes, (size_t)pl->rows * ng * 12 * sizeof(double));
+  rc = e->d_ct_scratch.reserve((size_t)pl->rows * ng * 12);
   if (rc != MJPL_OK) return rc;
-  pl->gx = e->d_ct_scratch;
-  pl->gm = e->d_ct_scratch + (size_t)pl->rows * ng * 3;
+  pl->gx = e->d_ct_scratch.p;
+  pl->gm = e->d_ct_scratch.p + (size_t)pl->rows * ng * 3;
   pl->lds = lds_bytes(e, 1);
   return allow_lds(kernel, pl->lds);
 }
@@ -2141,10 +2143,10 @@ int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int l
   GradOut go = {};
   if (mode == DM_GRAD) {
     const int nb = e->m.nbody, nplan = (int)e->qidx.size();
-    rc = grow_device(e->d_gr_scratch, e->gr_scratch_bytes, (size_t)pl.rows * nb * 7 * sizeof(double));
+    rc = e->d_gr_scratch.reserve((size_t)pl.rows * nb * 7);
     if (rc != MJPL_OK) return rc;
-    go.xpos = e->d_gr_scratch;
-    go.xquat = e->d_gr_scratch + (size_t)pl.rows * nb * 3;
+    go.xpos = e->d_gr_scratch.p;
+    go.xquat = e->d_gr_scratch.p + (size_t)pl.rows * nb * 3;
     go.nbody = nb;
     go.gcol = e->d_gr;
     go.gjnt = e->d_gr + (size_t)nplan * GC_LEN;
@@ -2251,10 +2253,10 @@ int staged(mjpl_engine *e, bool small_tiers, const HostIn (&in)[NI], const HostO
     HIP_TRY(hipHostGetDevicePointer((void **)&dev_in, pin, 0));
     dev_out = dev_in + ib;
   } else {
-    if ((rc = stage_reserve(e->stage_in, ib)) != MJPL_OK) return rc;
-    if ((rc = stage_reserve(e->stage_out, ob)) != MJPL_OK) return rc;
-    dev_in = (char *)e->stage_in.p;
-    dev_out = (char *)e->stage_out.p;
+    if ((rc = e->stage_in.reserve(ib, kStageFloor)) != MJPL_OK) return rc;
+    if ((rc = e->stage_out.reserve(ob, kStageFloor)) != MJPL_OK) return rc;
+    dev_in = e->stage_in.p;
+    dev_out = e->stage_out.p;
     if (tier == 1) HIP_TRY(hipMemcpyAsync(dev_in, pin, ib, hipMemcpyHostToDevice, e->stream));
     for (size_t k = 0; k < NI && tier == 2; k++)
       if (in[k].bytes) HIP_TRY(hipMemcpyAsync(dev_in + at_in[k], in[k].host, in[k].bytes, hipMemcpyHostToDevice, e->stream));
@@ -2395,54 +2397,37 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
 }
 
 void mjpl_destroy(mjpl_engine *e) {
-  if (e && e->d_fused_dbg && e->fused_dbg_path) {
+  if (e && e->d_fused_dbg.p && e->fused_dbg_path) {
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
     std::vector<unsigned long long> h(kFusedDbgWaves * 8);
-    if (hipMemcpy(h.data(), e->d_fused_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess)
+    if (hipMemcpy(h.data(), e->d_fused_dbg.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess)
       if (FILE *f = fopen(e->fused_dbg_path, "wb")) {
         fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
         fclose(f);
       }
-    (void)hipFree(e->d_fused_dbg);
   }
   if (!e) return;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->comm) (void)mjpl_comm_destroy(e);
-  for (const mjpl_engine::Slot *s : {&e->stage_in, &e->stage_out, &e->stage_ik, &e->stage_parked})
-    if (s->p) (void)hipFree(s->p);
   if (e->h_pin) (void)hipHostFree(e->h_pin);
   if (e->d_ip) (void)hipFree(e->d_ip);
   if (e->d_dp) (void)hipFree(e->d_dp);
   if (e->d_fp_base) (void)hipFree(e->d_fp_base);
-  if (e->d_ulist) (void)hipFree(e->d_ulist);
   if (e->d_ucount_base) (void)hipFree(e->d_ucount_base);
-  if (e->d_slist) (void)hipFree(e->d_slist);
-  if (e->d_ucga) (void)hipFree(e->d_ucga);
-  if (e->d_ucgb) (void)hipFree(e->d_ucgb);
   if (e->d_geomtab) (void)hipFree(e->d_geomtab);
   if (e->d_nn) (void)hipFree(e->d_nn);
   if (e->d_nn16) (void)hipFree(e->d_nn16);
   if (e->d_nn_tmp) (void)hipFree(e->d_nn_tmp);
-  if (e->d_tstep) (void)hipFree(e->d_tstep);
-  if (e->d_itemck) (void)hipFree(e->d_itemck);
-  if (e->d_itemedge) (void)hipFree(e->d_itemedge);
-  if (e->d_itemidx) (void)hipFree(e->d_itemidx);
-  if (e->d_llist) (void)hipFree(e->d_llist);
-  if (e->d_eclaim) (void)hipFree(e->d_eclaim);
-  if (e->d_ucq) (void)hipFree(e->d_ucq);
-  if (e->d_ucedge) (void)hipFree(e->d_ucedge);
-  if (e->d_ucidx) (void)hipFree(e->d_ucidx);
   if (e->d_status) (void)hipFree(e->d_status);
   if (e->d_ct_ip) (void)hipFree(e->d_ct_ip);
   if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
-  if (e->d_ct_scratch) (void)hipFree(e->d_ct_scratch);
   if (e->d_dt) (void)hipFree(e->d_dt);
   if (e->d_gr) (void)hipFree(e->d_gr);
-  if (e->d_gr_scratch) (void)hipFree(e->d_gr_scratch);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  const hipStream_t stream = e->stream;
+  delete e;  // (frees its DevBufs: with the device set, and before the stream goes)
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 int mjpl_program_dump(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t nallowed, const int32_t *qidx,
@@ -2545,14 +2530,14 @@ int64_t mjpl_filter_last_undecided(mjpl_engine *e) {
 // kernel -- which pairs the float32 filter could not decide.  Returns how many there were (the arrays receive up to
 // `cap` of them), or -1.
 int64_t mjpl_filter_undecided_pairs(mjpl_engine *e, int32_t *edge, int32_t *idx, int32_t *ga, int32_t *gb, int64_t cap) {
-  if (!e || !e->filter || !e->filter_usable || !e->d_ucount || !e->d_ucedge) return 0;
+  if (!e || !e->filter || !e->filter_usable || !e->d_ucount || !e->d_ucedge.p) return 0;
   if (hipSetDevice(e->device) != hipSuccess) return -1;
   if (hipStreamSynchronize(e->stream) != hipSuccess) return -1;
   int n = 0;
   if (hipMemcpy(&n, e->d_ucount + kCtr, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   const size_t m = (size_t)std::max<int64_t>(0, std::min<int64_t>(std::min<int64_t>(n, cap), (int64_t)e->uc_cap));
   int32_t *dst[4] = {edge, idx, ga, gb};
-  const int *src[4] = {e->d_ucedge, e->d_ucidx, e->d_ucga, e->d_ucgb};
+  const int *src[4] = {e->d_ucedge.p, e->d_ucidx.p, e->d_ucga.p, e->d_ucgb.p};
   for (int k = 0; k < 4; k++)
     if (dst[k] && m && hipMemcpy(dst[k], src[k], m * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
@@ -2616,16 +2601,13 @@ int mjpl_get_info(const mjpl_engine *e, mjpl_info *out) {
   out->filter_block_threads = e->immediate() ? kBlock : kFilterBlock;
   out->lds_bytes_filter = (int)lds_bytes(e, 1, sizeof(float), out->filter_block_threads, !e->immediate(),
                                          e->immediate() ? sizeof(double) : sizeof(float));
-  out->persistent_kernels = ((e->persist < 0 ? e->spec != nullptr : e->persist != 0) && e->two_pass && e->expand && !e->immediate()) ? 1 : 0;
-  out->fused_tail = (e->fused_tail && e->two_pass && e->expand && !e->immediate()) ? 1 : 0;
-  if (e->filter && e->filter_usable) {
-    int nw = 0;
-    out->fused_edges = fused_plan(e, &nw, nullptr) ? 1 : 0;
-    out->fused_waves = out->fused_edges ? nw : 0;
-  } else {  // (filter off: the float64 checks through the pool)
-    out->fused_edges = fused_f64_ok(e) ? 1 : 0;
-    out->fused_waves = out->fused_edges ? kFusedF64Waves : 0;
-  }
+  // what an ordinary edge launch would do (an empty batch: below every threshold of the batch size, so the library
+  // is the program's own)
+  const EdgePlan p = plan_edges(e, 0, 0, false);
+  out->persistent_kernels = p.persistent ? 1 : 0;
+  out->fused_tail = p.tail ? 1 : 0;
+  out->fused_edges = (p.pipe == EdgePipe::kFused || p.pipe == EdgePipe::kF64Pool) ? 1 : 0;  // (filter off: the float64 checks through the pool)
+  out->fused_waves = p.fwaves;
   out->block_threads = kBlock;
   out->compute_units = e->prop.multiProcessorCount;
   strncpy(out->arch, e->prop.gcnArchName, sizeof(out->arch) - 1);
@@ -2657,7 +2639,7 @@ int mjpl_check_edges_dev(mjpl_engine *e, const double *dQA, const double *dQB, i
   if (E > 0 && (!dQB || !dvalid)) return fail(MJPL_E_ARG, "NULL pointer");
   if (!(step_dist > 0.0)) return fail(MJPL_E_ARG, "`step_dist` must be > 0");
   HIP_TRY(hipSetDevice(e->device));
-  return launch_edges(e, dQA, dQB, E, step_dist, layout, flags, dvalid, dfirst_bad);
+  return launch_edges(e, dQA, dQB, E, step_dist, layout, flags, dvalid, dfirst_bad, false);
 }
 
 int mjpl_take_status(mjpl_engine *e, int32_t *status) {
@@ -3314,7 +3296,7 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
   // persistent kernels, which keep every 32nd exact waypoint as a checkpoint: the fused kernel rebuilds an undecided
   // waypoint by the recurrence from the start of its edge (measured: 64 edges of 2 400 waypoints 3.9 vs 7.6 ms).  The
   // rows are in host memory here, so a small batch can simply be looked at.
-  e->fused_skip_once = false;
+  bool long_edges = false;
   if (E <= 4096) {
     const int64_t np = (int64_t)e->qidx.size();
     double longest2 = 0;
@@ -3326,14 +3308,14 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
       }
       if (s > longest2) longest2 = s;  // (a NaN never compares greater: such an edge is reported by the kernels)
     }
-    e->fused_skip_once = std::sqrt(longest2) > 64.0 * step_dist;
+    long_edges = std::sqrt(longest2) > 64.0 * step_dist;
   }
   int status = 0;
   const HostOut outs[] = {{valid, (size_t)E}, {first_bad, (size_t)E * sizeof(int32_t)}, {&status, sizeof(int), e->d_status}};
   rc = staged(e, true, {{QA, qb}, {QB, qb}}, outs, [&](void **in, void **out) {
     HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), e->stream));
     return launch_edges(e, (const double *)in[0], (const double *)in[1], E, step_dist, layout, flags, (uint8_t *)out[0],
-                        (int32_t *)out[1]);
+                        (int32_t *)out[1], long_edges);
   });
   return rc != MJPL_OK ? rc : edge_status(status);
 }
@@ -3813,7 +3795,7 @@ int mjpl_pose_apply_dev(mjpl_pose *p, const double *dQold, const double *dQ, int
     const int phase_steps = e->pose_phase_steps;  // (option "pose_phase_steps")
     if (rs.G == 1 && phase_steps > 0) {
       const size_t need = ((size_t)N * 2 + 16) * sizeof(int32_t);
-      if ((rc = stage_reserve(e->stage_parked, need)) != MJPL_OK) return rc;
+      if ((rc = e->stage_parked.reserve(need, kStageFloor)) != MJPL_OK) return rc;
       int32_t *list = (int32_t *)e->stage_parked.p, *itst = list + N;
       int *count = (int *)(itst + N);
       HIP_TRY(hipMemsetAsync(count, 0, sizeof(int), e->stream));
@@ -3925,9 +3907,9 @@ int mjpl_ik_solve_dev(mjpl_engine *e, const mjpl_ik_desc *d, const double *dQ, i
   KtScope kt_scope(e, 1);  // (option "kernel_timer")
   // the program is tiny and changes with every target: staged through the engine's scratch
   const size_t ib = pi.size() * sizeof(int), db = pd.size() * sizeof(double);
-  if ((rc = stage_reserve(e->stage_ik, ((ib + 7) & ~(size_t)7) + db)) != MJPL_OK) return rc;
+  if ((rc = e->stage_ik.reserve(((ib + 7) & ~(size_t)7) + db, kStageFloor)) != MJPL_OK) return rc;
   int *d_pi = (int *)e->stage_ik.p;
-  double *d_pd = (double *)((char *)e->stage_ik.p + ((ib + 7) & ~(size_t)7));
+  double *d_pd = (double *)(e->stage_ik.p + ((ib + 7) & ~(size_t)7));
   HIP_TRY(hipStreamSynchronize(e->stream));  // pageable host vectors go out of scope on return
   HIP_TRY(hipMemcpy(d_pi, pi.data(), ib, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_pd, pd.data(), db, hipMemcpyHostToDevice));

@@ -968,7 +968,7 @@ int rrt_extend(mjpl_rrt *r, int t, const double *Tgt, int second, int *nnew) {
     // the buffer, and only RC_ACTIVE says whether any lane emitted)
     const int E = projecting ? (int)std::min<int64_t>((int64_t)S * active_bound, r->cd.cap) : std::min(r->h_ctr[RC_EDGES], r->cd.cap);
     if (r->istep > 0)
-      rc = launch_edges(e, r->cd.A, r->cd.B, E, r->istep, MJPL_AOS, 0, r->cd.valid, nullptr);
+      rc = launch_edges(e, r->cd.A, r->cd.B, E, r->istep, MJPL_AOS, 0, r->cd.valid, nullptr, false);
     else
       rc = launch_configs(e, r->cd.B, E, MJPL_AOS, r->cd.valid, nullptr);
     if (rc != MJPL_OK) return rc;

@@ -178,24 +178,44 @@ class Driver:
         dbits.free()
         return out
 
-    def _meta(self, e, kind):
+    def _meta(self, e, kind, counters=False):
         meta = {"spec_kind": e.spec_kind(), "spec_cert_loaded": e.get_option("spec_cert_loaded")}
         if kind == "edges":
             meta["certified"] = e.last_certified() > 0
+        if counters:
+            meta.update(last_items=e.last_items(), last_interior_edges=e.last_interior_edges(), info=e.info())
         return meta
 
-    def launch(self, kind, n, layout=eng_mod.AOS, interior_only=False, dev=False, expect=None):
+    def long_edges(self, n):
+        """A host-pointer launch of n edges, the first of them longer than 64 steps, against a fresh engine."""
+        qa, qb = (x.copy() for x in self._edges(n))
+        lo, hi = self.m.jnt_range[self.qidx, 0], self.m.jnt_range[self.qidx, 1]
+        qa[0], qb[0] = lo + 0.1 * (hi - lo), lo + 0.9 * (hi - lo)
+        assert np.linalg.norm(qb[0] - qa[0]) > 64 * STEP
+        msg = f"{self.label}: long_edges({n}) after " + " -> ".join(self.history)
+        got = self.e.check_edges(qa, qb, STEP, first_bad=True)
+        ref = self._fresh()
+        try:
+            want = ref.check_edges(qa, qb, STEP, first_bad=True)
+        finally:
+            ref.close()
+        for x, y in zip(got, want):
+            np.testing.assert_array_equal(x, y, err_msg=msg)
+        self.history.append(f"long_edges({n})")
+
+    def launch(self, kind, n, layout=eng_mod.AOS, interior_only=False, dev=False, expect=None, counters=False):
         """One launch on the live engine, then the same launch on a fresh engine, the other entry point (host or
-        device pointers) on the live engine, and the oracle on a sample.  `expect`: getters asserted outright."""
+        device pointers) on the live engine, and the oracle on a sample.  `expect`: getters asserted outright;
+        `counters`: the item and interior-edge counters and mjpl_get_info are compared with the fresh engine's, too."""
         what = f"{kind}({n}, layout={layout}, interior_only={interior_only}, dev={dev})"
         msg = f"{self.label}: {what} after " + " -> ".join(self.history)
         got = self._launch(self.e, kind, n, layout, interior_only, dev)
-        meta = self._meta(self.e, kind)
+        meta = self._meta(self.e, kind, counters)
         self._assert_options(self.e, "live")
         ref = self._fresh()
         try:
             want = self._launch(ref, kind, n, layout, interior_only, dev)
-            ref_meta = self._meta(ref, kind)
+            ref_meta = self._meta(ref, kind, counters)
         finally:
             ref.close()
         for x, y in zip(got, want):
@@ -369,4 +389,20 @@ def test_scene_generic_robot_short_sequence(oracle_mod):
            ("planning", qidx, base), ("launch", "edges", n, eng_mod.AOS, False, False, {"spec_kind": 2}),
            ("launch", "contacts", 4096),
            ("set_spec", 2), ("launch", "configs", n)])
+    d.close()
+
+
+def test_long_edges_with_the_filter_off_leave_nothing_behind(oracle_mod):
+    """(g) What a host-pointer launch learns about ITS batch -- here: it holds an edge of more than 64 steps, made with
+    the filter off -- must not shape a later launch: with the filter on again, an ordinary batch of more than
+    fused_single_max edges through device pointers gives a fresh engine's verdicts, first-bad indices, item and
+    interior-edge counters and mjpl_get_info."""
+    m, qidx, base = _franka()
+    d = Driver(oracle_mod, m, qidx, base, label="long edges with the filter off")
+    n = 40000
+    assert n > d.e.get_option("fused_single")
+    d.run([("set_filter", False),
+           ("long_edges", 64),
+           ("set_filter", True, 1e-4),
+           ("launch", "edges", n, eng_mod.AOS, False, True, None, True)])
     d.close()
