@@ -22,7 +22,7 @@
 
 namespace mjpl {
 
-// candidate table, one record per pair (built at mjpl_create, mjpl_hip.hip: build_contact_table).
+// candidate table, one record per pair (built at mjpl_create, mjpl_compile.h: build_contact_table).
 // `cur` is the moving geom the check places LATER (its partner `par` is a static geom or an earlier
 // moving one), exactly as run_config pairs them.
 enum : int { CI_CUR = 0,  // model geom id of cur (moving)

@@ -27,7 +27,7 @@
 
 namespace mjpl {
 
-// per-pair record of the distance table (mjpl_hip.hip: build_distance_table), beside the candidate table of
+// per-pair record of the distance table (mjpl_compile.h: build_distance_table), beside the candidate table of
 // mjpl_contacts.h: rb1 + rb2 (geom_rbound; a plane's is 0) and whether the ruleset allows the pair
 enum : int { DT_RBSUM = 0, DT_ALLOWED, DT_LEN = 2 };
 

@@ -9,7 +9,7 @@
 //      w_par - w_cur = D n.  The pair types differ per lane, so this step diverges once per lane.
 //   3. grad_j = n . (v_j(w2) - v_j(w1)) over the planning columns, v_j(x) = axis_j x (x - anchor_j) (hinge) or
 //      axis_j (slide), 0 unless column j's body is the point's body or an ancestor.  Axis and anchor come from
-//      the body pose FK wrote to scratch and the per-engine column table (mjpl_hip.hip: build_grad_table).
+//      the body pose FK wrote to scratch and the per-engine column table (mjpl_compile.h: build_grad_table).
 //
 // Witnesses.  Disjoint cores: the closest points of the minimising feature pair (end point, segment interior,
 // box vertex, box edge), pushed out by the radii along n.  Overlapping cores: the separating axis u of least
@@ -25,7 +25,7 @@ enum : int { GS_OK = 0, GS_FLAT = 1, GS_DEGENERATE = 2, GS_NONFINITE = 3 };
 // a core gap below this (metres) has no direction: MJPL_GRAD_DEGENERATE
 constexpr double kGradDegenerate = 1e-10;
 
-// column table (per planning column) and joint table (per model joint), mjpl_hip.hip: build_grad_table.
+// column table (per planning column) and joint table (per model joint), mjpl_compile.h: build_grad_table.
 // A column's joint j sits on body GC_BODY; the body's joints after j (GC_NLATER of them, model joints
 // j + 1 ...) are undone from the body's final pose to get the frame j moved.  GC_TIN / GC_TOUT: the body's
 // subtree as an interval of DFS entry times (geom g is moved by the column iff tin(body(g)) lies in it).

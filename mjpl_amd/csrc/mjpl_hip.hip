@@ -233,6 +233,38 @@ struct HostModel {
   std::vector<double> geom_size, geom_pos, geom_quat, geom_rbound, geom_margin;
 };
 
+// What the compiler derives once from the model, the allowed body pairs and the planning selection, and every later
+// stage and table builder reads (mjpl_compile.h: layout_model).
+struct ModelLayout {
+  // world-welded bodies and geoms, their folded poses (FK output reads them)
+  std::vector<char> body_static, geom_static;
+  std::vector<double> st_xpos, st_xquat, st_xmat, st_gxpos, st_gxmat;
+  std::vector<int> world_row;  // static geom -> its row of the world tables (-1: a moving geom)
+  std::vector<int> winfo;      // world row -> geom type | geom id << 8
+  // moving bodies in id order; parent_src[k] of order[k]: PARENT_STATIC, PARENT_CUR or LDS save slot + 1; save_slot per body
+  std::vector<int> order, parent_src, save_slot;
+  // moving geoms in processing order (stage_of: geom -> index in mgeoms, -1: static); per stage the last stage that
+  // reads it, its register slots, its static partners (geom ids) and stored ones (earlier stages)
+  std::vector<int> mgeoms, stage_of, last_user, slot_of;
+  std::vector<std::vector<int>> world_partners, stored_partners;
+  std::vector<int> col_of;  // qpos address -> planning column (-1: constant)
+  int nslots = 0, nsave = 0, maxs = 4;
+  bool wbox = false, mbox = false;
+  int npairs = 0, npairs_world = 0, nmoving = 0, nplanes = 0;  // (nmoving: moving geoms; nplanes: static planes)
+  int nworld() const { return (int)winfo.size(); }  // static geoms: every one has a row
+  int moving_base() const { return mgeoms.empty() ? 0 : mgeoms[0]; }  // model id of the first moving geom
+};
+
+// The filter's binary32 error bound and what follows from it (mjpl_compile.h: filter_error_bound)
+struct FilterBound {
+  double ferr_a = 0, ferr_b = 0;  // |pose error| <= ferr_a + ferr_b * max coordinate
+  double fmax_coord = 0;
+  float tol = 1e-4f;              // tolerance band in force (>= what was asked for)
+  bool usable = true;             // false: this model's binary32 error floor is too high, exact path only
+  int npoisoned = 0;              // static geoms too large / far for binary32: their pairs are always undecided
+  std::vector<int> poison_rows;   // ... their world rows: NaN in the float image
+};
+
 template <class T>
 std::vector<T> copy_n(const T *p, size_t n) {
   return std::vector<T>(p, p + n);
@@ -303,13 +335,9 @@ struct mjpl_engine {
   int *d_status = nullptr;
   // float32 filter + exact re-run of what it cannot decide
   bool filter = true;
-  float filter_tol = 1e-4f;       // tolerance band in force (>= filter_tol_req)
   float filter_tol_req = 1e-4f;   // what the caller (or the default) asked for
   bool filter_tol_user = false;   // asked for through mjpl_set_filter / MJPL_FILTER_TOL
-  bool filter_usable = true;      // false: this model's binary32 error floor is too high, exact path only
-  double ferr_a = 0, ferr_b = 0;  // |pose error| <= ferr_a + ferr_b * max coordinate (DESIGN.md 5.1b)
-  double fmax_coord = 0;
-  int npoisoned = 0;              // static geoms too large / far for binary32: their pairs are always undecided
+  FilterBound fb;                 // the band in force, and whether the filter serves this model at all
   uint64_t program_hash = 0;      // FNV-1a of the compiled tables (ip, fp, dp), the kernel variant and the header digest
   const SpecLib *spec = nullptr;  // this model's own filter kernels, if a library for program_hash was found
   // ... or, failing that, a scene-generic library of the ROBOT (robot_hash: moving bodies, their geoms and
@@ -318,7 +346,6 @@ struct mjpl_engine {
   // obstacles may change without a compiler
   bool spec_generic = false;
   uint64_t robot_hash = 0;
-  int moving_base = 0;           // model id of the first moving geom
   std::vector<float> scene;      // [scene header | per moving geom: kSceneRows rows of 8] (compile_program)
   float *d_fp_base = nullptr;    // allocation behind d_fp (= d_fp_base + scene.size())
   bool spec_off = false;          // mjpl_set_spec(e, 0): run the interpreting kernels whatever libraries exist
@@ -406,22 +433,17 @@ struct mjpl_engine {
   const int32_t *nn_last_count = nullptr; int nn_last_waves = 0, nn_last_nsub = 0;  // the last cell-ordered scan's candidate counts
   int nn_last = 0;              // what the last mjpl_nearest_dev launched: 0 float64 scan, 1 binary32 screen, 2 matrix-core screen (or 1: see its flag)
   size_t uc_cap = 0, uc_cap_limit = 0;
-  int nslots = 0, nsave = 0, maxs = 4;
-  bool wbox = false, mbox = false;
+  ModelLayout lay;  // static poses for FK output, slot and save counts, kernel shape
   // the immediate (non-queued) interpreter serves models with moving boxes and models that keep
   // more than 16 geoms in the slot file (one general <32, true, true> build)
   // Which builds a model runs.  Exact kernels: <4|8|16, wbox, false>, or the general <32, true, true>
   // for moving boxes / more than 16 stored geoms.  Filter kernels: the same small builds, then
   // <24, true, true> -- still the queued interpreter, moving boxes through its box queue -- and
   // only beyond 24 stored geoms the immediate interpreter <32, true, true>.
-  bool exact_general() const { return mbox || maxs > 16; }
+  bool exact_general() const { return lay.mbox || lay.maxs > 16; }
   bool force_immediate = false;  // MJPL_FORCE_IMMEDIATE (create-time, tests)
-  bool immediate() const { return nslots > kQueuedMaxSlots || (force_immediate && exact_general()); }
+  bool immediate() const { return lay.nslots > kQueuedMaxSlots || (force_immediate && exact_general()); }
   bool filter_mbox() const { return exact_general() && !immediate(); }
-  int npairs = 0, npairs_world = 0, nmoving = 0, nstatic = 0;
-  // static poses for FK output
-  std::vector<double> st_xpos, st_xquat, st_gxpos, st_gxmat;
-  std::vector<char> body_static, geom_static;
   // RCCL communicator of the frontier planner's exchange (mjpl_comm_init); none = a world of one
   void *comm = nullptr;
   int comm_rank = 0, comm_world = 1;
@@ -449,8 +471,6 @@ struct mjpl_engine {
 };
 
 namespace {
-
-void load_spec(mjpl_engine *e, bool generic_ok, int nstage);
 
 constexpr size_t kStageFloor = 1 << 16;  // a staging slot is never smaller (DevBuf::reserve: at_least)
 
@@ -560,7 +580,7 @@ void load_spec(mjpl_engine *e, bool generic_ok = false, int nstage = 0) {
   e->spec = nullptr;
   e->spec_generic = false;
   e->spec_cert = nullptr;  // (before the early return: a certificate build never outlives the default library it was found beside)
-  if (e->spec_off || e->immediate() || (e->exact_general() && !e->filter_mbox()) || !e->filter_usable) return;  // (the generator covers the queued builds)
+  if (e->spec_off || e->immediate() || (e->exact_general() && !e->filter_mbox()) || !e->fb.usable) return;  // (the generator covers the queued builds)
   if (!e->spec_generic_only) e->spec = find_spec(e->program_hash, false);
   // (round 6: the certificate pays from about a million edges per launch on -- +7 ... 11 % -- and costs 4 % at 262 144,
   //  profiles/README.md round 5: both builds are loaded, launch_edges picks by the batch's size)
@@ -576,740 +596,68 @@ void load_spec(mjpl_engine *e, bool generic_ok = false, int nstage = 0) {
   }
 }
 
-// mj_collision pair filters [MJ-recalled: engine_collision_driver.c filterBitmask /
-// filterBodyPair] + the a6 ruleset folded in.  returns true if the pair is tested.
-bool pair_enabled(const mjpl_engine *e, int g1, int g2) {
-  const HostModel &m = e->m;
-  const int ct1 = m.geom_contype[g1], ca1 = m.geom_conaffinity[g1];
-  const int ct2 = m.geom_contype[g2], ca2 = m.geom_conaffinity[g2];
-  if (!(ct1 & ca2) && !(ct2 & ca1)) return false;
-  const int b1 = m.geom_bodyid[g1], b2 = m.geom_bodyid[g2];
-  const int w1 = m.body_weldid[b1], w2 = m.body_weldid[b2];
-  if (w1 == w2) return false;
-  const int wp1 = m.body_weldid[m.body_parentid[w1]];
-  const int wp2 = m.body_weldid[m.body_parentid[w2]];
-  if (w1 != 0 && w2 != 0 && (w1 == wp2 || w2 == wp1)) return false;
-  const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
-  if (t1 == GT_PLANE && t2 == GT_PLANE) return false;  // no collision function
-  // CollisionRuleset: a contact between an allowed body pair never invalidates
-  if (e->allowed.count({std::min(b1, b2), std::max(b1, b2)})) return false;
-  return true;
-}
+}  // namespace
 
-bool type_supported(int t) { return t == GT_PLANE || t == GT_SPHERE || t == GT_CAPSULE || t == GT_BOX; }
+#include "mjpl_compile.h"
 
-// Compile the model into the ip/dp program the kernels interpret.
-int compile_program(mjpl_engine *e) {
-  const HostModel &m = e->m;
-  const int nb = m.nbody, ng = m.ngeom;
+namespace {
 
-  for (int j = 0; j < m.njnt; j++)
-    if (m.jnt_type[j] != JT_SLIDE && m.jnt_type[j] != JT_HINGE)
-      return fail(MJPL_E_JOINT, "joint %d has type %d; only slide(2)/hinge(3) are supported", j,
-                  m.jnt_type[j]);
-
-  // ---- static (world-welded) bodies: poses folded here with the kernels' own arithmetic
-  e->body_static.assign(nb, 0);
-  e->st_xpos.assign(3 * nb, 0.0);
-  e->st_xquat.assign(4 * nb, 0.0);
-  std::vector<double> st_xmat(9 * nb, 0.0);
-  e->st_xquat[0] = 1.0;
-  st_xmat[0] = st_xmat[4] = st_xmat[8] = 1.0;
-  e->body_static[0] = 1;
-  for (int b = 1; b < nb; b++) {
-    if (m.body_weldid[b] != 0) continue;
-    if (m.body_jntnum[b] != 0) return fail(MJPL_E_ARG, "body %d is welded to the world but has joints", b);
-    const int p = m.body_parentid[b];
-    if (!e->body_static[p]) return fail(MJPL_E_ARG, "body %d: weld id 0 below a moving parent", b);
-    e->body_static[b] = 1;
-    double np[3], nq[4];
-    mul_mat_vec3(np, &st_xmat[9 * p], &m.body_pos[3 * b]);
-    for (int k = 0; k < 3; k++) np[k] += e->st_xpos[3 * p + k];
-    mul_quat(nq, &e->st_xquat[4 * p], &m.body_quat[4 * b]);
-    normalize4(nq);
-    for (int k = 0; k < 3; k++) e->st_xpos[3 * b + k] = np[k];
-    for (int k = 0; k < 4; k++) e->st_xquat[4 * b + k] = nq[k];
-    quat2mat(&st_xmat[9 * b], nq);
+// Replace a create-time device table by a host vector: the old block is freed first, and a failed allocation or copy
+// leaves the slot null (an empty vector, too: nothing is allocated for it).
+template <class T>
+int upload_table(T **slot, const std::vector<T> &host) {
+  T *old = *slot;
+  *slot = nullptr;
+  if (old) HIP_TRY(hipFree(old));
+  if (host.empty()) return MJPL_OK;
+  T *d = nullptr;
+  HIP_TRY(hipMalloc(&d, host.size() * sizeof(T)));
+  const hipError_t err = hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    HIP_TRY(err);
   }
-
-  // ---- geoms
-  e->geom_static.assign(ng, 0);
-  e->st_gxpos.assign(3 * ng, 0.0);
-  e->st_gxmat.assign(9 * ng, 0.0);
-  std::vector<int> world_row(ng, -1);
-  std::vector<double> wcull_tab, wnarrow_tab;
-  std::vector<int> winfo;
-  std::vector<std::pair<size_t, int>> info_at;  // dp index -> int stored there (first 4 bytes)
-  std::vector<size_t> sq_bound_at, plane_bound_at;  // dp indices of cull bounds
-  std::vector<int> poison_rows;                     // world rows whose binary32 narrowphase data is NaN
-  e->nstatic = e->nmoving = 0;
-  for (int g = 0; g < ng; g++) {
-    const int b = m.geom_bodyid[g];
-    if (!type_supported(m.geom_type[g])) {
-      // a geom that can never collide is harmless; otherwise refuse
-      bool used = false;
-      for (int h = 0; h < ng && !used; h++)
-        if (h != g) used = pair_enabled(e, std::min(g, h), std::max(g, h));
-      if (used) return fail(MJPL_E_PAIRTYPE, "geom %d has unsupported type %d", g, m.geom_type[g]);
-    }
-    if (!e->body_static[b]) { e->nmoving++; continue; }
-    e->geom_static[g] = 1;
-    e->nstatic++;
-    double gp[3], gq[4];
-    mul_mat_vec3(gp, &st_xmat[9 * b], &m.geom_pos[3 * g]);
-    for (int k = 0; k < 3; k++) e->st_gxpos[3 * g + k] = gp[k] + e->st_xpos[3 * b + k];
-    mul_quat(gq, &e->st_xquat[4 * b], &m.geom_quat[4 * g]);
-    quat2mat(&e->st_gxmat[9 * g], gq);
-    world_row[g] = (int)winfo.size();
-    {
-      const double *gmx = &e->st_gxmat[9 * g];
-      double rc[WC_LEN] = {0}, rn[WN_LEN] = {0};
-      for (int k = 0; k < 3; k++) {
-        rc[WC_POS + k] = e->st_gxpos[3 * g + k];
-        rn[WN_XAXIS + k] = gmx[3 * k + 0];
-        rn[WN_YAXIS + k] = gmx[3 * k + 1];
-        rn[WN_ZAXIS + k] = gmx[3 * k + 2];
-        rn[WN_SIZE + k] = m.geom_size[3 * g + k];
-      }
-      const int32_t info[2] = {m.geom_type[g] | (g << 8), 0};
-      memcpy(&rc[WC_INFO], info, sizeof(double));
-      const int w = (int)winfo.size();
-      winfo.push_back(info[0]);
-      // four rows side by side per chunk (wc_at); one spare chunk: the kernels may prefetch ahead
-      wcull_tab.resize((size_t)((w >> 2) + 2) * 16, 0.0);
-      for (int f = 0; f < WC_LEN; f++) wcull_tab[wc_at(w, f)] = rc[f];
-      wnarrow_tab.insert(wnarrow_tab.end(), rn, rn + WN_LEN);
-    }
-  }
-  const int nworld = (int)winfo.size();
-  const int nwpad = (nworld + 3) / 4 * 4;
-  wcull_tab.resize((size_t)(nwpad + 4) * WC_LEN, 0.0);
-  if (nworld > 64) return fail(MJPL_E_CAPACITY, "%d static geoms; this build enables at most 64 per moving geom", nworld);
-  if (ng >= (1 << 23)) return fail(MJPL_E_CAPACITY, "too many geoms");
-
-  // ---- moving bodies in id order (parents precede children)
-  std::vector<int> order;
-  for (int b = 1; b < nb; b++)
-    if (!e->body_static[b]) order.push_back(b);
-  std::vector<int> save_slot(nb, -1);
-  int nsave = 0;
-  for (size_t k = 0; k < order.size(); k++) {
-    const int p = m.body_parentid[order[k]];
-    if (e->body_static[p]) continue;
-    if (k > 0 && order[k - 1] == p) continue;
-    if (save_slot[p] < 0) save_slot[p] = nsave++;
-  }
-
-  // moving geoms in processing order, their partners, and register-slot allocation
-  std::vector<int> mgeoms;
-  for (int b : order)
-    for (int g = 0; g < ng; g++)
-      if (m.geom_bodyid[g] == b) mgeoms.push_back(g);
-  const int nm = (int)mgeoms.size();
-  std::vector<std::vector<int>> stored_partners(nm), world_partners(nm);
-  std::vector<int> last_user(nm, -1);
-  e->npairs = e->npairs_world = 0;
-  e->wbox = e->mbox = false;
-  auto note_pair = [&](int ga, int gb) {  // ga is the moving geom being placed
-    if (m.geom_type[ga] == GT_BOX) e->mbox = true;
-    if (m.geom_type[gb] == GT_BOX) (e->geom_static[gb] ? e->wbox : e->mbox) = true;
-  };
-  for (int k = 0; k < nm; k++) {
-    const int g = mgeoms[k];
-    for (int s = 0; s < ng; s++)
-      if (e->geom_static[s] && pair_enabled(e, std::min(g, s), std::max(g, s))) {
-        world_partners[k].push_back(s);
-        note_pair(g, s);
-        e->npairs++; e->npairs_world++;
-      }
-    for (int k2 = 0; k2 < k; k2++) {
-      const int h = mgeoms[k2];
-      if (!pair_enabled(e, std::min(g, h), std::max(g, h))) continue;
-      stored_partners[k].push_back(k2);
-      note_pair(g, h);
-      last_user[k2] = k;
-      e->npairs++;
-    }
-    if (m.geom_type[g] == GT_PLANE) return fail(MJPL_E_PAIRTYPE, "plane geom %d on a moving body", g);
-  }
-  // register slots: one per kept sphere/capsule, two per kept box; a slot is reusable once the
-  // last geom that needs its occupant has been processed (a geom is stored after its own tests)
-  std::vector<int> slot_of(nm, -1);
-  {
-    std::vector<int> free_at;  // slot -> index of the last geom that reads it
-    auto take = [&](int k) {
-      for (size_t t = 0; t < free_at.size(); t++)
-        if (free_at[t] <= k) { free_at[t] = last_user[k]; return (int)t; }
-      free_at.push_back(last_user[k]);
-      return (int)free_at.size() - 1;
-    };
-    for (int k = 0; k < nm; k++) {
-      if (last_user[k] < 0) continue;
-      const int s1 = take(k);
-      const int s2 = (m.geom_type[mgeoms[k]] == GT_BOX) ? take(k) : (int)SLOT_NONE;
-      slot_of[k] = s1 | (s2 << 6);
-    }
-    e->nslots = (int)free_at.size();
-  }
-  if (e->nslots > MAX_SLOTS)
-    return fail(MJPL_E_CAPACITY, "%d moving geoms must be held at once; this build has %d register slots",
-                e->nslots, (int)MAX_SLOTS);
-  e->maxs = e->nslots <= 4 ? 4 : (e->nslots <= 8 ? 8 : (e->nslots <= 16 ? 16 : 32));  // vector widths with indirect addressing
-  e->nsave = nsave;
-
-  // ---- emit
-  std::vector<int> &ip = e->ip;
-  std::vector<double> &dp = e->dp;
-  ip.assign(H_SIZE, 0);
-  dp.clear();
-  const int nplan = (int)e->qidx.size();
-  std::vector<int> col_of(m.nq, -1);
-  for (int c = 0; c < nplan; c++) col_of[e->qidx[c]] = c;
-
-  ip[H_NPLAN] = nplan;
-  ip[H_NSAVE] = nsave;
-  ip[H_NSLOTS] = e->nslots;
-  ip[H_NBODYOPS] = (int)order.size();
-  ip[H_OFF_WCULL] = 0;
-  ip[H_NWORLD] = nworld;
-  ip[H_NWPAD] = nwpad;
-  dp = wcull_tab;
-  for (int w = 0; w < nworld; w++) info_at.push_back({(size_t)wc_at(w, WC_INFO), winfo[w]});
-  ip[H_OFF_WNARROW] = (int)dp.size();
-  dp.insert(dp.end(), wnarrow_tab.begin(), wnarrow_tab.end());
-
-  // column permutation: ascending qpos address (the order np.linalg.norm sums the full vector)
-  ip[H_OFF_PERM] = (int)ip.size();
-  {
-    std::vector<int> perm(nplan);
-    for (int c = 0; c < nplan; c++) perm[c] = c;
-    std::sort(perm.begin(), perm.end(), [&](int a, int b) { return e->qidx[a] < e->qidx[b]; });
-    for (int c : perm) ip.push_back(c);
-  }
-
-  ip[H_OFF_BODYOPS] = (int)ip.size();
-  int gk = 0;  // index into mgeoms
-  for (size_t k = 0; k < order.size(); k++) {
-    const int b = order[k], p = m.body_parentid[b];
-    int parent_src;
-    if (e->body_static[p]) parent_src = PARENT_STATIC;
-    else if (k > 0 && order[k - 1] == p) parent_src = PARENT_CUR;
-    else parent_src = save_slot[p] + 1;
-    const size_t base = ip.size();
-    ip.resize(base + B_SIZE);
-    ip[base + B_PARENT] = parent_src;
-    ip[base + B_DOFF] = (int)dp.size();
-    ip[base + B_BODYID] = b;
-    ip[base + B_NJNT] = m.body_jntnum[b];
-    ip[base + B_SAVE] = save_slot[b];
-    for (int k3 = 0; k3 < 3; k3++) dp.push_back(m.body_pos[3 * b + k3]);
-    for (int k4 = 0; k4 < 4; k4++) dp.push_back(m.body_quat[4 * b + k4]);
-    if (parent_src == PARENT_STATIC) {
-      for (int k3 = 0; k3 < 3; k3++) dp.push_back(e->st_xpos[3 * p + k3]);
-      for (int k4 = 0; k4 < 4; k4++) dp.push_back(e->st_xquat[4 * p + k4]);
-      for (int k9 = 0; k9 < 9; k9++) dp.push_back(st_xmat[9 * p + k9]);
-    }
-    for (int j = 0; j < m.body_jntnum[b]; j++) {
-      const int jid = m.body_jntadr[b] + j;
-      const int qadr = m.jnt_qposadr[jid];
-      const double *jp = &m.jnt_pos[3 * jid];
-      ip.push_back(m.jnt_type[jid]);
-      ip.push_back(col_of[qadr]);
-      ip.push_back((jp[0] != 0 || jp[1] != 0 || jp[2] != 0) ? JF_POS_NONZERO : 0);
-      ip.push_back((int)dp.size());
-      for (int k3 = 0; k3 < 3; k3++) dp.push_back(m.jnt_axis[3 * jid + k3]);
-      for (int k3 = 0; k3 < 3; k3++) dp.push_back(jp[k3]);
-      dp.push_back(m.qpos0[qadr]);
-      dp.push_back(e->qbase[qadr]);
-    }
-    int ngeom_here = 0;
-    for (; gk < nm && m.geom_bodyid[mgeoms[gk]] == b; gk++, ngeom_here++) {
-      const int g = mgeoms[gk];
-      const double *gp = &m.geom_pos[3 * g], *gq = &m.geom_quat[4 * g];
-      int flags = 0;
-      if (gp[0] == 0 && gp[1] == 0 && gp[2] == 0) flags |= GF_SAMEPOS;
-      if (gq[0] == 1 && gq[1] == 0 && gq[2] == 0 && gq[3] == 0) flags |= GF_SAMEROT;
-      unsigned long long wmask = 0, pmask = 0;
-      for (int sgeom : world_partners[gk])
-        (m.geom_type[sgeom] == GT_PLANE ? pmask : wmask) |= 1ull << world_row[sgeom];
-      unsigned smask = 0;
-      for (int k2 : stored_partners[gk]) smask |= 1u << (slot_of[k2] & 63);
-      ip.push_back(m.geom_type[g]);
-      ip.push_back(flags);
-      ip.push_back((int)dp.size());
-      ip.push_back(slot_of[gk]);
-      ip.push_back(g);
-      ip.push_back((int)smask);
-      ip.push_back((int)(uint32_t)(wmask & 0xffffffffull));
-      ip.push_back((int)(uint32_t)(wmask >> 32));
-      ip.push_back((int)(uint32_t)(pmask & 0xffffffffull));
-      ip.push_back((int)(uint32_t)(pmask >> 32));
-      const size_t swords_at = ip.size();
-      ip.insert(ip.end(), MAX_SLOTS, 0);
-      for (int k3 = 0; k3 < 3; k3++) dp.push_back(gp[k3]);
-      for (int k4 = 0; k4 < 4; k4++) dp.push_back(gq[k4]);
-      for (int k3 = 0; k3 < 3; k3++) dp.push_back(m.geom_size[3 * g + k3]);
-      dp.push_back((double)g);  // GD_GEOMID
-      dp.push_back(0.0);
-
-      // cull bound and margin of the pair (g, h) in mj_collision's (g1 < g2) order
-      auto pair_bound = [&](int h, double *bound, double *margin) {
-        const int g1 = std::min(g, h), g2 = std::max(g, h);
-        *margin = std::fmax(m.geom_margin[g1], m.geom_margin[g2]);
-        const double r1 = m.geom_rbound[g1], r2 = m.geom_rbound[g2];
-        *bound = std::numeric_limits<double>::infinity();
-        if (r1 > 0 && r2 > 0) {
-          const double bsum = r1 + r2 + *margin;
-          *bound = bsum * bsum;
-        } else if (m.geom_type[h] == GT_PLANE && m.geom_rbound[g] > 0) {
-          *bound = *margin + m.geom_rbound[g];
-        }
-      };
-      const double inf = std::numeric_limits<double>::infinity();
-      {
-        // rows that are no partner of this geom: -inf, so the queued culls need no enable mask
-        std::vector<double> wb(nwpad, -inf), wm(nwpad, 0.0);
-        for (int sgeom : world_partners[gk]) {
-          pair_bound(sgeom, &wb[world_row[sgeom]], &wm[world_row[sgeom]]);
-          (m.geom_type[sgeom] == GT_PLANE ? plane_bound_at : sq_bound_at).push_back(dp.size() + world_row[sgeom]);
-        }
-        dp.insert(dp.end(), wb.begin(), wb.end());
-        dp.insert(dp.end(), wm.begin(), wm.end());
-      }
-      {
-        std::vector<double> sb(MAX_SLOTS, inf), sm(MAX_SLOTS, 0.0), ss(3 * MAX_SLOTS, 0.0), sg(MAX_SLOTS, -1.0);
-        for (int k2 : stored_partners[gk]) {
-          const int h = mgeoms[k2];
-          const int s1 = slot_of[k2] & 63, s2 = (slot_of[k2] >> 6) & 63;
-          const int g1 = std::min(g, h), g2 = std::max(g, h);
-          const int first = (m.geom_type[g1] > m.geom_type[g2]) ? g2 : g1;
-          ip[swords_at + s1] = s2 | (m.geom_type[h] << 12) | (first == h ? P_FIRST : 0);
-          pair_bound(h, &sb[s1], &sm[s1]);
-          sq_bound_at.push_back(dp.size() + s1);
-          for (int k3 = 0; k3 < 3; k3++) ss[3 * s1 + k3] = m.geom_size[3 * h + k3];
-          sg[s1] = (double)h;
-        }
-        dp.insert(dp.end(), sb.begin(), sb.end());
-        dp.insert(dp.end(), sm.begin(), sm.end());
-        dp.insert(dp.end(), ss.begin(), ss.end());
-        dp.insert(dp.end(), sg.begin(), sg.end());  // GS_GEOMID
-      }
-    }
-    ip[base + B_NGEOM] = ngeom_here;
-  }
-
-  // the kernels prefetch one entry past the one they test: keep that read inside the tables
-  ip.insert(ip.end(), 32, 0);
-  dp.insert(dp.end(), 24, 0.0);
-
-  // ---- binary32 error bound of the filter.  eps = 2^-24.  For every
-  // moving body b, by induction along the chain (every operation of run_config_queued counted with
-  // its worst-case rounding; fused multiply-adds only lower these):
-  //   rot(b) <= rot(parent) + (20 + 42 * hinges(b)) eps          orientation error, radians
-  //   pos(b) <= posA(b) + posB(b) * C                            position error, metres, where C
-  //             bounds every moving coordinate magnitude (enforced per lane: FC_MAXCOORD), and
-  //   posA(b) = posA(parent) + L_b (rot(parent) + 8 eps) + 3 eps L_b + sum_hinges 2 |jnt_pos| (rot(b) + 8 eps)
-  //   posB(b) = posB(parent) + sqrt(3) eps (1 + slides(b) + 2 offcentre_hinges(b))
-  // A geom adds |lpos| (rot + 8 eps) + extent (rot + 24 eps) + 2 eps |size| and sqrt(3) eps C; a static
-  // geom is off by the rounding of its constants; evaluating a narrowphase formula on binary32
-  // poses adds 16 eps (pair scale) + 4 eps C.  Signed distances are 1-Lipschitz in every point of
-  // either geom, so |distance32 - distance64| <= E = A + B C over all enabled pairs.
-  {
-    const double eps = std::ldexp(1.0, -24);
-    const double r3 = std::sqrt(3.0);
-    auto norm3 = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
-    std::vector<double> rot(nb, 0.0), posA(nb, 0.0), posB(nb, 0.0);
-    for (int b = 0; b < nb; b++)
-      if (e->body_static[b]) { rot[b] = 2 * eps; posA[b] = r3 * eps * norm3(&e->st_xpos[3 * b]); }
-    for (int b : order) {
-      const int p = m.body_parentid[b];
-      int hinges = 0, slides = 0, off = 0;
-      double jp = 0;
-      for (int j = 0; j < m.body_jntnum[b]; j++) {
-        const int jid = m.body_jntadr[b] + j;
-        if (m.jnt_type[jid] == JT_HINGE) {
-          hinges++;
-          const double l = norm3(&m.jnt_pos[3 * jid]);
-          if (l > 0) { off++; jp += l; }
-        } else {
-          slides++;
-        }
-      }
-      const double L = norm3(&m.body_pos[3 * b]);
-      rot[b] = rot[p] + (20.0 + 42.0 * hinges) * eps;
-      posA[b] = posA[p] + L * (rot[p] + 8 * eps) + 3 * eps * L + 2 * jp * (rot[b] + 8 * eps);
-      posB[b] = posB[p] + r3 * eps * (1 + slides + 2 * off);
-    }
-    auto extent = [&](int g) {  // farthest point of the geom from its frame origin along rotating directions
-      const double *sz = &m.geom_size[3 * g];
-      if (m.geom_type[g] == GT_CAPSULE) return sz[1];
-      if (m.geom_type[g] == GT_BOX) return norm3(sz);
-      return 0.0;
-    };
-    std::vector<double> gA(ng, 0.0), gB(ng, 0.0);
-    e->npoisoned = 0;
-    std::vector<char> poisoned(ng, 0);
-    const double tolh_req = 0.5 * e->filter_tol_req;
-    for (int g = 0; g < ng; g++) {
-      const int b = m.geom_bodyid[g];
-      const double lp = norm3(&m.geom_pos[3 * g]), sz = norm3(&m.geom_size[3 * g]);
-      if (e->geom_static[g]) {
-        gA[g] = r3 * eps * (norm3(&e->st_gxpos[3 * g]) + extent(g)) + 2 * eps * sz;
-        // a static geom whose own constants do not fit binary32 within an eighth of the band: its
-        // narrowphase rows are NaN in the float tables, so every pair that passes its (widened)
-        // cull comes out undecided and is settled by the float64 pair kernel
-        if (gA[g] > 0.25 * tolh_req) { poisoned[g] = 1; e->npoisoned++; }
-      } else {
-        gA[g] = posA[b] + lp * (rot[b] + 8 * eps) + extent(g) * (rot[b] + 24 * eps) + 2 * eps * sz;
-        gB[g] = posB[b] + r3 * eps;
-      }
-    }
-    double A = 0, B = 0;
-    for (int k = 0; k < nm; k++) {
-      const int g = mgeoms[k];
-      auto pair = [&](int h) {
-        if (poisoned[h]) return;
-        const double scale = m.geom_rbound[g] + m.geom_rbound[h] + std::fmax(m.geom_margin[g], m.geom_margin[h]) +
-                             (m.geom_type[h] == GT_PLANE ? norm3(&e->st_gxpos[3 * h]) : 0.0);
-        A = std::fmax(A, gA[g] + gA[h] + 16 * eps * scale);
-        B = std::fmax(B, gB[g] + gB[h] + 4 * eps);
-      };
-      for (int sgeom : world_partners[k]) pair(sgeom);
-      for (int k2 : stored_partners[k]) pair(mgeoms[k2]);
-    }
-    e->ferr_a = A;
-    e->ferr_b = B;
-    // half the band is the error budget: E(C) = A + B C <= tol / 2.  A default tolerance grows with
-    // the model's floor; one the caller asked for is kept, and if the floor does not fit under it
-    // the filter steps aside for this model (exact path only).
-    double tol = e->filter_tol_req;
-    e->filter_usable = true;
-    if (A > 0.4 * tol) {
-      if (e->filter_tol_user) e->filter_usable = false;
-      else tol = A / 0.4;
-      if (!(tol < 1e-2)) e->filter_usable = false;  // a band of centimetres decides nothing useful
-    }
-    e->filter_tol = (float)tol;
-    // (a candidate record of the filter's queues carries its geom's table offset in 16 bits -- the other half of the word
-    //  is the candidate's certificate margin, mjpl_device.h: queue_drain --: a table of 64 K entries or more, far beyond
-    //  any model the slot file holds, takes the exact path)
-    if (dp.size() + 64 >= 65536) e->filter_usable = false;
-    double maxc = (B > 0) ? (0.5 * tol - A) / B : 1e6;
-    maxc = std::fmin(std::fmax(maxc, 0.0), 1e6);
-    e->fmax_coord = e->filter_usable ? maxc : 0.0;
-    ip[H_OFF_FCONST] = (int)dp.size();
-    double fc[FC_SIZE] = {0};
-    fc[FC_MAXCOORD] = e->fmax_coord;
-    fc[FC_MAXANGLE] = kFilterMaxAngle;
-    dp.insert(dp.end(), fc, fc + FC_SIZE);
-    // NaN rows: written into the float image below
-    for (int g = 0; g < ng; g++)
-      if (poisoned[g]) poison_rows.push_back(world_row[g]);
-  }
-
-  // ---- the filter's float32 image: same offsets; cull bounds widened by the tolerance so that
-  // a pair culled in float32 is certainly culled (or contact-free) in float64
-  std::vector<float> &fp = e->fp;
-  fp.resize(dp.size());
-  for (size_t k = 0; k < dp.size(); k++) fp[k] = (float)dp[k];
-  // (a poisoned static geom's own rounding may exceed the band: its bounds are widened by that, too)
-  const double tol = e->filter_tol;
-  double poison_slack = 0;
-  for (int w : poison_rows) {
-    const double *wt = &dp[(size_t)ip[H_OFF_WCULL]];
-    const double rc[3] = {wt[wc_at(w, 0)], wt[wc_at(w, 1)], wt[wc_at(w, 2)]};
-    const double *rn = &dp[(size_t)ip[H_OFF_WNARROW] + (size_t)w * WN_LEN];
-    const double mag = std::fabs(rc[0]) + std::fabs(rc[1]) + std::fabs(rc[2]) + std::fabs(rn[WN_SIZE]) +
-                       std::fabs(rn[WN_SIZE + 1]) + std::fabs(rn[WN_SIZE + 2]);
-    poison_slack = std::fmax(poison_slack, 4 * std::ldexp(1.0, -24) * mag);
-  }
-  for (size_t k : sq_bound_at)
-    if (std::isfinite(dp[k])) {
-      const double r = std::sqrt(dp[k]) + tol + poison_slack;
-      fp[k] = (float)(r * r * (1.0 + 1e-6));
-    }
-  for (size_t k : plane_bound_at)
-    if (std::isfinite(dp[k])) fp[k] = (float)(dp[k] + tol + poison_slack + 1e-6 * std::fabs(dp[k]));
-  for (auto &kv : info_at) memcpy(&fp[kv.first], &kv.second, sizeof(float));
-  // the whole narrowphase row (axes and sizes; the position belongs to the cull table): every
-  // routine then computes NaN and classifies the pair as undecided
-  for (int w : poison_rows)
-    for (int k = 0; k < WN_LEN; k++) fp[(size_t)ip[H_OFF_WNARROW] + (size_t)w * WN_LEN + k] = std::numeric_limits<float>::quiet_NaN();
-
-  // ---- identity of the compiled program: what a per-model specialised library is keyed by
-  {
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](const void *ptr, size_t n) {
-      const unsigned char *b = (const unsigned char *)ptr;
-      for (size_t k = 0; k < n; k++) { h ^= b[k]; h *= 0x100000001b3ull; }
-    };
-    mix(ip.data(), ip.size() * sizeof(int));
-    mix(fp.data(), fp.size() * sizeof(float));
-    // the float64 table as well: the generated exact pair re-check (ExactSpec::fk_pair) carries ITS values
-    // as literals, and two programs may share a binary32 image while their float64 constants differ
-    mix(dp.data(), dp.size() * sizeof(double));
-    const int shape[4] = {e->maxs, e->wbox ? 1 : 0, e->mbox ? 1 : 0, MJPL_SPEC_ABI};
-    mix(shape, sizeof(shape));
-    const unsigned long long stamp = MJPL_SRC_STAMP;
-    mix(&stamp, sizeof(stamp));
-    e->program_hash = h;
-  }
-  // ---- identity of the ROBOT alone, and the cull table a scene-generic library reads.
-  // Everything the generated code of such a library carries as literals goes into robot_hash: the moving
-  // bodies with their constants, joints (planning column or constant), geoms, register slots and self
-  // pairs with their bounds, tolerance, kernel shape.  Nothing of the static geoms: those reach the code
-  // through `scene` -- a header, then for every moving geom kSceneRows cull rows [a0 a1 a2 thr] followed by
-  // kSceneRows descriptor words: a plane partner (rows 0, 1) passes its cull when a . c <= thr (a =
-  // normal), any other (rows 2 ..) when |c|^2 + a . c <= thr (a = -2 X: the expanded form, threshold
-  // raised by the form's rounding bound for a centre within the geom's reach); the descriptor says what a
-  // candidate of that pair is queued as.  Rows that are no pair of the geom never pass (thr = -inf).
-  const int nstage = nm;
-  e->moving_base = nm > 0 ? mgeoms[0] : 0;
-  int nplanes = 0;
-  for (int w = 0; w < nworld; w++) nplanes += (winfo[w] & 255) == GT_PLANE ? 1 : 0;
-  // (a robot with moving boxes, or 17 .. 24 stored geoms: the 24-slot queued build has generated code, too)
-  bool generic_ok = !e->immediate() && e->filter_usable && nplanes <= kScenePlaneRows && nworld - nplanes <= kSceneRows - kScenePlaneRows &&
-                    nstage <= kSceneMaxStages && nstage > 0;
-  for (int k = 1; k < nm && generic_ok; k++) generic_ok = mgeoms[k] == mgeoms[0] + k;  // (the pair re-check counts geoms from the first moving one)
-  {
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](const void *ptr, size_t n) {
-      const unsigned char *b = (const unsigned char *)ptr;
-      for (size_t k = 0; k < n; k++) { h ^= b[k]; h *= 0x100000001b3ull; }
-    };
-    auto mixi = [&](int v) { mix(&v, sizeof(v)); };
-    auto mixd = [&](const double *v, int n) { mix(v, sizeof(double) * (size_t)n); };
-    mixi(nplan); mixi(e->maxs); mixi(e->nslots); mixi(nsave); mixi(MJPL_SPEC_ABI); mixi(kSceneRows);
-    const unsigned long long stamp = MJPL_SRC_STAMP;
-    mix(&stamp, sizeof(stamp));
-    const float tolf = e->filter_tol;
-    mix(&tolf, sizeof(tolf));
-    int gk2 = 0;
-    for (size_t k = 0; k < order.size(); k++) {
-      const int b = order[k], p = m.body_parentid[b];
-      const int psrc = e->body_static[p] ? (int)PARENT_STATIC : ((k > 0 && order[k - 1] == p) ? (int)PARENT_CUR : save_slot[p] + 1);
-      mixi(psrc);
-      mixd(&m.body_pos[3 * b], 3); mixd(&m.body_quat[4 * b], 4);
-      if (psrc == PARENT_STATIC) { mixd(&e->st_xpos[3 * p], 3); mixd(&e->st_xquat[4 * p], 4); mixd(&st_xmat[9 * p], 9); }
-      mixi(m.body_jntnum[b]); mixi(save_slot[b]);
-      for (int j = 0; j < m.body_jntnum[b]; j++) {
-        const int jid = m.body_jntadr[b] + j, qadr = m.jnt_qposadr[jid];
-        mixi(m.jnt_type[jid]); mixi(col_of[qadr]);
-        mixd(&m.jnt_axis[3 * jid], 3); mixd(&m.jnt_pos[3 * jid], 3); mixd(&m.qpos0[qadr], 1);
-        const double qc = col_of[qadr] < 0 ? e->qbase[qadr] : 0.0;
-        mixd(&qc, 1);
-      }
-      for (; gk2 < nm && m.geom_bodyid[mgeoms[gk2]] == b; gk2++) {
-        const int g = mgeoms[gk2];
-        mixi(m.geom_type[g]); mixi(slot_of[gk2]);
-        mixd(&m.geom_pos[3 * g], 3); mixd(&m.geom_quat[4 * g], 4); mixd(&m.geom_size[3 * g], 3);
-        mixd(&m.geom_rbound[g], 1); mixd(&m.geom_margin[g], 1);
-        for (int k2 : stored_partners[gk2]) { mixi(k2); mixi(slot_of[k2]); }
-        mixi(-1);
-      }
-      mixi(-2);
-    }
-    e->robot_hash = h;
-  }
-  e->scene.clear();
-  if (generic_ok) {
-    const size_t S = scene_floats(nstage);
-    e->scene.assign(S, 0.0f);
-    auto seti = [&](size_t at, int v) { memcpy(&e->scene[at], &v, sizeof(float)); };
-    const double u24 = std::ldexp(1.0, -24);
-    auto round_up = [](double v) {
-      float f = (float)v;
-      if ((double)f < v) f = std::nextafterf(f, std::numeric_limits<float>::infinity());
-      return f;
-    };
-    // how far from the origin a moving geom's centre can be while its lane is alive (specialise.py: the same)
-    const double box_reach = std::sqrt(3.0) * (double)(float)e->fmax_coord;
-    std::vector<double> breach(nb, 0.0);
-    auto n3 = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
-    for (int b : order) {
-      const int p = m.body_parentid[b];
-      double r = (e->body_static[p] ? n3(&e->st_xpos[3 * p]) : breach[p]) + n3(&m.body_pos[3 * b]);
-      for (int j = 0; j < m.body_jntnum[b]; j++) {
-        const int jid = m.body_jntadr[b] + j;
-        if (m.jnt_type[jid] == JT_SLIDE) r = std::numeric_limits<double>::infinity();
-        else r += 2.0 * n3(&m.jnt_pos[3 * jid]);
-      }
-      breach[b] = std::fmin(r, box_reach);
-    }
-    // [0] planes (0 .. 2: the last rows), [1] first pair of rows in use, [2] nwpad, [3] offset of the narrowphase table
-    // The rows of a geom are filled from the END: the planes last, the bounded geoms below them; the code is one
-    // straight line over all kSceneRows rows, entered at the first pair of rows that holds anything ([1]).
-    const int nbounded = nworld - nplanes;
-    const int first_row = std::min(kSceneRows - 2, (kSceneRows - nplanes - nbounded) & ~1);
-    seti(0, nplanes); seti(1, first_row);
-    seti(2, nwpad); seti(3, ip[H_OFF_WNARROW]);
-    e->scene[4] = (float)e->fmax_coord;
-    e->scene[5] = kFilterMaxAngle;
-    int gk3 = 0, pc = ip[H_OFF_BODYOPS];
-    for (size_t k = 0; k < order.size(); k++) {
-      const int b = order[k];
-      const int njnt = ip[pc + B_NJNT], ngeom_here = ip[pc + B_NGEOM];
-      pc += B_SIZE + njnt * J_SIZE;
-      for (int gi = 0; gi < ngeom_here; gi++, gk3++) {
-        const int g = mgeoms[gk3], gtype = m.geom_type[g], gdoff = ip[pc + G_DOFF];
-        pc += G_SIZE + MAX_SLOTS;
-        seti(8 + gk3, gdoff);
-        const double reach = breach[b] + n3(&m.geom_pos[3 * g]);
-        std::set<int> partners(world_partners[gk3].begin(), world_partners[gk3].end());
-        float *rows = &e->scene[(size_t)kSceneHeader + (size_t)gk3 * kSceneStageFloats];
-        float *descs = rows + (size_t)kSceneRows * 4;
-        for (int r0 = 0; r0 < kSceneRows; r0++) rows[(size_t)r0 * 4 + 3] = -std::numeric_limits<float>::infinity();
-        for (int pass = 0; pass < 2; pass++) {  // the planes in the last rows, the others below them
-          int r = pass == 0 ? kSceneRows - nplanes : kSceneRows - nplanes - nbounded;
-          for (int sgeom = 0; sgeom < ng; sgeom++) {
-            if (!e->geom_static[sgeom] || world_row[sgeom] < 0) continue;
-            const int w = world_row[sgeom], ptype = winfo[w] & 255;
-            if ((ptype == GT_PLANE) != (pass == 0)) continue;
-            float *row = rows + (size_t)r * 4;
-            float *dword = descs + r;
-            r++;
-            if (!partners.count(sgeom)) continue;  // (not a pair of this geom: a row that never passes)
-            const double X[3] = {(double)fp[wc_at(w, 0)], (double)fp[wc_at(w, 1)], (double)fp[wc_at(w, 2)]};
-            const double bound = (double)fp[(size_t)gdoff + GD_WBOUND + w];
-            int desc;
-            if (ptype == GT_PLANE) {
-              const float *rw = &fp[(size_t)ip[H_OFF_WNARROW] + (size_t)w * WN_LEN];
-              const double n[3] = {(double)rw[WN_ZAXIS], (double)rw[WN_ZAXIS + 1], (double)rw[WN_ZAXIS + 2]};
-              const double off = n[0] * X[0] + n[1] * X[1] + n[2] * X[2];
-              for (int c = 0; c < 3; c++) row[c] = (float)n[c];
-              // three fused multiply-adds on a centre within `reach`: each rounds by at most u (reach + |n . p0| + |bound|)
-              row[3] = std::isfinite(reach) ? round_up(bound + off + 4.0 * u24 * (1.01 * reach + std::fabs(off) + std::fabs(bound)))
-                                            : std::numeric_limits<float>::infinity();
-              // (bit 15: the candidate goes to the box queue -- a static box, or ANY partner of a moving box, whose
-              //  records carry whole frames)
-              desc = EK_PLANE | (w << 2) | (GT_PLANE << 10) | (1 << 14) | ((gtype == GT_BOX && e->filter_mbox() ? 1 : 0) << 15);
-            } else {
-              const double nx = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-              for (int c = 0; c < 3; c++) row[c] = (float)(-2.0 * X[c]);
-              // (the allowance of specialise.py: expanded_threshold)
-              const double allow = 8.0 * u24 * (1.01 * reach + nx) * (1.01 * reach + nx);
-              row[3] = std::isfinite(reach) ? round_up(bound - (X[0] * X[0] + X[1] * X[1] + X[2] * X[2]) + allow)
-                                            : std::numeric_limits<float>::infinity();
-              if (!std::isfinite(bound)) row[3] = (float)bound;
-              const int pgid = winfo[w] >> 8;
-              const int pfirst = (ptype < gtype || (ptype == gtype && pgid < g)) ? 1 : 0;
-              desc = EK_STATIC | (w << 2) | (ptype << 10) | (pfirst << 14) |
-                     (((ptype == GT_BOX || (gtype == GT_BOX && e->filter_mbox())) ? 1 : 0) << 15);
-            }
-            memcpy(dword, &desc, sizeof(float));
-          }
-        }
-      }
-    }
-  }
-  if (e->device < 0) return MJPL_OK;  // mjpl_program_dump: host tables only
-  load_spec(e, generic_ok, nstage);
-  if (!e->spec_generic) e->scene.clear();
-
-  // ---- upload
-  if (e->d_ip) (void)hipFree(e->d_ip);
-  if (e->d_dp) (void)hipFree(e->d_dp);
-  if (e->d_fp_base) (void)hipFree(e->d_fp_base);
-  e->d_ip = nullptr;
-  e->d_dp = nullptr;
-  e->d_fp = e->d_fp_base = nullptr;
-  HIP_TRY(hipMalloc(&e->d_ip, ip.size() * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_dp, dp.size() * sizeof(double)));
-  HIP_TRY(hipMalloc(&e->d_fp_base, (e->scene.size() + fp.size()) * sizeof(float)));
-  e->d_fp = e->d_fp_base + e->scene.size();  // (the kernels' table pointer: a scene-generic library reads backwards from it)
-  HIP_TRY(hipMemcpy(e->d_ip, ip.data(), ip.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_dp, dp.data(), dp.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!e->scene.empty()) HIP_TRY(hipMemcpy(e->d_fp_base, e->scene.data(), e->scene.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_fp, fp.data(), fp.size() * sizeof(float), hipMemcpyHostToDevice));
+  *slot = d;
   return MJPL_OK;
 }
 
-// The candidate pairs of mj_collision (oracle/mjpl_oracle.c: orc_collision's enumeration): every pair g1 < g2 that
-// passes the contype/conaffinity, same-weld-body and weld parent-child filters and has a collision function (all but
-// plane-plane and plane-hfield), allowed body pairs INCLUDED.  The kernel's record of each pair restates what
-// run_config tests for it: cur = the moving geom it places later, its partner, pfirst, margin and cull bound
-// (compile_program: pair_bound).  Depends on the model only: called once, at mjpl_create.
-int build_contact_table(mjpl_engine *e) {
-  const HostModel &m = e->m;
-  const int ng = m.ngeom;
-  constexpr int kGeomHfield = 1;
-  std::vector<int> world_row(ng, -1);
-  for (int g = 0, w = 0; g < ng; g++)
-    if (e->geom_static[g]) world_row[g] = w++;
-  // processing order of the moving geoms: bodies in id order, a body's geoms in id order
-  auto later = [&](int a, int b) {
-    const int ba = m.geom_bodyid[a], bb = m.geom_bodyid[b];
-    return ba != bb ? ba > bb : a > b;
-  };
+// Compile the model into the ip/dp program the kernels interpret (mjpl_compile.h: stages 1 to 6 on the host), find
+// its library and put the tables on the device.
+int compile_program(mjpl_engine *e) {
+  MJPL_TRY(compile_host(e));
+  load_spec(e, !e->scene.empty(), (int)e->lay.mgeoms.size());
+  if (!e->spec_generic) e->scene.clear();
+  e->d_fp = nullptr;
+  MJPL_TRY(upload_table(&e->d_ip, e->ip));
+  MJPL_TRY(upload_table(&e->d_dp, e->dp));
+  std::vector<float> image(e->scene);  // (the scene table in front: a scene-generic library reads backwards from the kernels' table pointer)
+  image.insert(image.end(), e->fp.begin(), e->fp.end());
+  MJPL_TRY(upload_table(&e->d_fp_base, image));
+  e->d_fp = e->d_fp_base + e->scene.size();
+  return MJPL_OK;
+}
+
+// candidate and distance tables of the pair queries: from the model alone, once, at mjpl_create
+int make_pair_tables(mjpl_engine *e) {
   std::vector<int> ip;
   std::vector<double> dp;
-  e->ct_g1.clear(); e->ct_g2.clear(); e->ct_allowed.clear();
-  e->ct_unsupported = -1;
-  const double inf = std::numeric_limits<double>::infinity();
-  for (int g1 = 0; g1 < ng; g1++)
-    for (int g2 = g1 + 1; g2 < ng; g2++) {
-      const int ct1 = m.geom_contype[g1], ca1 = m.geom_conaffinity[g1];
-      const int ct2 = m.geom_contype[g2], ca2 = m.geom_conaffinity[g2];
-      if (!(ct1 & ca2) && !(ct2 & ca1)) continue;
-      const int b1 = m.geom_bodyid[g1], b2 = m.geom_bodyid[g2];
-      const int w1 = m.body_weldid[b1], w2 = m.body_weldid[b2];
-      if (w1 == w2) continue;
-      const int wp1 = m.body_weldid[m.body_parentid[w1]], wp2 = m.body_weldid[m.body_parentid[w2]];
-      if (w1 != 0 && w2 != 0 && (w1 == wp2 || w2 == wp1)) continue;
-      const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
-      const int tlo = std::min(t1, t2), thi = std::max(t1, t2);
-      if (tlo == GT_PLANE && (thi == GT_PLANE || thi == kGeomHfield)) continue;  // no collision function
-      const int p = (int)e->ct_g1.size();
-      e->ct_g1.push_back(t1 > t2 ? g2 : g1);
-      e->ct_g2.push_back(t1 > t2 ? g1 : g2);
-      e->ct_allowed.push_back(e->allowed.count({std::min(b1, b2), std::max(b1, b2)}) ? 1 : 0);
-      // (one geom is moving: both static means both welded to the world, filtered above)
-      const bool s1 = e->geom_static[g1], s2 = e->geom_static[g2];
-      int cur, par;
-      if (s1 || s2) { cur = s1 ? g2 : g1; par = s1 ? g1 : g2; }
-      else { cur = later(g1, g2) ? g1 : g2; par = cur == g1 ? g2 : g1; }
-      const int tcur = m.geom_type[cur], tpar = m.geom_type[par];
-      if (!type_supported(tcur) || !type_supported(tpar) || tcur == GT_PLANE) {
-        if (e->ct_unsupported < 0) e->ct_unsupported = p;
-      }
-      const bool pstatic = e->geom_static[par] != 0;
-      const bool pfirst = (tpar < tcur) || (tpar == tcur && par < cur);
-      int rec[CI_LEN] = {0};
-      rec[CI_CUR] = cur;
-      rec[CI_PAR] = pstatic ? world_row[par] : par;
-      rec[CI_TCUR] = tcur;
-      rec[CI_TPAR] = tpar;
-      rec[CI_FLAGS] = (pfirst ? CF_PFIRST : 0) | (pstatic ? CF_STATIC : 0);
-      rec[CI_PARID] = par;
-      ip.insert(ip.end(), rec, rec + CI_LEN);
-      double d[CD_LEN] = {0};
-      d[CD_MARGIN] = std::fmax(m.geom_margin[g1], m.geom_margin[g2]);
-      const double r1 = m.geom_rbound[g1], r2 = m.geom_rbound[g2];
-      d[CD_BOUND] = inf;
-      if (r1 > 0 && r2 > 0) {
-        const double bsum = r1 + r2 + d[CD_MARGIN];
-        d[CD_BOUND] = bsum * bsum;
-      } else if (tpar == GT_PLANE && m.geom_rbound[cur] > 0) {
-        d[CD_BOUND] = d[CD_MARGIN] + m.geom_rbound[cur];
-      }
-      for (int k = 0; k < 3; k++) {
-        d[CD_SCUR + k] = m.geom_size[3 * cur + k];
-        d[CD_SPAR + k] = m.geom_size[3 * par + k];
-      }
-      dp.insert(dp.end(), d, d + CD_LEN);
-    }
-  if (ip.empty()) return MJPL_OK;
-  HIP_TRY(hipMalloc(&e->d_ct_ip, ip.size() * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_ct_dp, dp.size() * sizeof(double)));
-  HIP_TRY(hipMemcpy(e->d_ct_ip, ip.data(), ip.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_ct_dp, dp.data(), dp.size() * sizeof(double), hipMemcpyHostToDevice));
-  return MJPL_OK;
+  build_contact_table(e, ip, dp);
+  MJPL_TRY(upload_table(&e->d_ct_ip, ip));
+  MJPL_TRY(upload_table(&e->d_ct_dp, dp));
+  return upload_table(&e->d_dt, build_distance_table(e));
+}
+
+// ... and the gradient tables, which follow the planning selection: mjpl_create and mjpl_set_planning
+int make_grad_table(mjpl_engine *e) {
+  std::vector<double> t;
+  MJPL_TRY(build_grad_table(e, t));
+  return upload_table(&e->d_gr, t);
 }
 
 size_t lds_bytes(const mjpl_engine *e, int ncolsets, size_t scalar = sizeof(double), int block = kBlock,
                  bool queued = false, size_t colscalar = sizeof(double)) {
   const size_t nplan = e->qidx.size();
-  size_t bytes = (((size_t)ncolsets * nplan * block * colscalar + 7) & ~(size_t)7) + (size_t)e->nsave * 7 * block * scalar;
+  size_t bytes = (((size_t)ncolsets * nplan * block * colscalar + 7) & ~(size_t)7) + (size_t)e->lay.nsave * 7 * block * scalar;
   bytes = (bytes + 7) & ~(size_t)7;
   if (queued)
     bytes += (size_t)(block / 64) * (e->filter_mbox() ? WaveQueue<float, true>::bytes() : WaveQueue<float, false>::bytes()) +
@@ -1348,12 +696,11 @@ int uc_reserve(mjpl_engine *e, int64_t n) {
       for (int k = 0; k < 3; k++) r[GTB_SIZE + k] = m.geom_size[3 * g + k];
       r[GTB_RBOUND] = m.geom_rbound[g];
       r[GTB_MARGIN] = m.geom_margin[g];
-      r[GTB_STATIC] = e->geom_static[g] ? 1.0 : 0.0;
-      for (int k = 0; k < 3; k++) r[GTB_XPOS + k] = e->st_gxpos[3 * g + k];
-      for (int k = 0; k < 9; k++) r[GTB_XMAT + k] = e->st_gxmat[9 * g + k];
+      r[GTB_STATIC] = e->lay.geom_static[g] ? 1.0 : 0.0;
+      for (int k = 0; k < 3; k++) r[GTB_XPOS + k] = e->lay.st_gxpos[3 * g + k];
+      for (int k = 0; k < 9; k++) r[GTB_XMAT + k] = e->lay.st_gxmat[9 * g + k];
     }
-    HIP_TRY(hipMalloc(&e->d_geomtab, t.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_geomtab, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    MJPL_TRY(upload_table(&e->d_geomtab, t));
   }
   e->uc_cap = want;
   return MJPL_OK;
@@ -1460,22 +807,22 @@ int spec_rc(int launched, const char *what) {
 // each) and the dynamic LDS of a workgroup.  `spec`: the library that would launch it (the engine's own, or its
 // certificate build).
 bool fused_plan(const mjpl_engine *e, const SpecLib *spec, int *nwaves, size_t *lds, int *ring) {
-  if (!e->fused || !e->filter || !e->filter_usable || !e->two_pass || !e->expand || e->immediate()) return false;
+  if (!e->fused || !e->filter || !e->fb.usable || !e->two_pass || !e->expand || e->immediate()) return false;
   const int nplan = (int)e->qidx.size();
   const bool mbox = e->filter_mbox();
   // (models with moving boxes run one wave per SIMD: four waves per workgroup, and measured 5 % SLOWER fused than as the
   // two kernels -- 1.63 vs 1.55 ms on Franka-P with the ten pad boxes; MJPL_FUSED_MBOX=1 runs them fused all the same)
   if (mbox && !e->fused_mbox && !spec) return false;
-  if (!fused_fits(nplan, e->nsave, mbox)) return false;
+  if (!fused_fits(nplan, e->lay.nsave, mbox)) return false;
   const int nw = spec ? spec->fused_waves : (mbox ? 4 : kFusedWaves);
   const size_t budget = (size_t)160 * 1024;
   const bool cert = spec && spec->fused_cert;
-  const size_t base = fused_lds_bytes(nw, nplan, e->nsave, e->fp.size(), mbox, 0, cert);
+  const size_t base = fused_lds_bytes(nw, nplan, e->lay.nsave, e->fp.size(), mbox, 0, cert);
   if (base + (size_t)(64 * nw + 64) * kFusedEntryBytes > budget) return false;
   int r = (int)std::min<size_t>(kFusedMaxPool, (budget - base) / kFusedEntryBytes / 64 * 64);
   if (e->fused_pool_cap > 0) r = std::max(64 * nw + 64, std::min(r, e->fused_pool_cap / 64 * 64));  // (tests: a ring that wraps)
   *nwaves = nw;
-  *lds = fused_lds_bytes(nw, nplan, e->nsave, e->fp.size(), mbox, r, cert);
+  *lds = fused_lds_bytes(nw, nplan, e->lay.nsave, e->fp.size(), mbox, r, cert);
   *ring = r;
   return true;
 }
@@ -1483,7 +830,7 @@ bool fused_plan(const mjpl_engine *e, const SpecLib *spec, int *nwaves, size_t *
 // ... and with the filter off: the float64 checks through the same pool (k_edges_fused_f64)
 bool fused_f64_ok(const mjpl_engine *e) {
   return e->fused && e->two_pass && e->expand &&
-         fused_f64_lds_bytes(kFusedF64Waves, (int)e->qidx.size(), e->nsave, 64 * kFusedF64Waves + 64) <= (size_t)160 * 1024;
+         fused_f64_lds_bytes(kFusedF64Waves, (int)e->qidx.size(), e->lay.nsave, 64 * kFusedF64Waves + 64) <= (size_t)160 * 1024;
 }
 
 // ---- What one edge launch will do, decided before anything is reserved or enqueued (no HIP call in here).
@@ -1536,7 +883,7 @@ EdgePlan plan_edges(const mjpl_engine *e, int64_t E, int flags, bool long_edges)
   p.lds_walk = lds_bytes(e, 1, sizeof(float), p.fblock, !imm);
   p.lds_items = lds_bytes(e, 1, sizeof(float), p.fblock, !imm, imm ? sizeof(double) : sizeof(float));
   p.lds_endpoints = imm ? lds_bytes(e, 2, sizeof(float), p.fblock, false) : p.lds_items;
-  p.lds_persistent = persistent_lds_bytes(nplan, e->nsave, e->fp.size(), e->filter_mbox());
+  p.lds_persistent = persistent_lds_bytes(nplan, e->lay.nsave, e->fp.size(), e->filter_mbox());
   p.lds_tail = std::max(p.lds_walk, p.lds_exact);
   p.two_pass = e->two_pass && !(flags & MJPL_EDGE_INTERIOR_ONLY);
   p.expand = p.two_pass && e->expand;
@@ -1545,7 +892,7 @@ EdgePlan plan_edges(const mjpl_engine *e, int64_t E, int flags, bool long_edges)
   p.single = (E <= (int64_t)e->fused_single_max) ? 1 : 0;
   p.flib = (e->spec && !e->spec_generic && e->spec_cert && e->fused_cert && e->fused_cert_min_edges > 0 && E >= e->fused_cert_min_edges &&
             E > (int64_t)e->fused_single_max) ? e->spec_cert : e->spec;
-  if (e->filter && e->filter_usable && E < (int64_t)1 << 29) {  // item ids travel in 29 bits of the per-lane flag words
+  if (e->filter && e->fb.usable && E < (int64_t)1 << 29) {  // item ids travel in 29 bits of the per-lane flag words
     // (long_edges: the batch holds a few long edges -> the kernels with checkpoints, see mjpl_check_edges)
     if (p.expand && !long_edges && fused_plan(e, p.flib, &p.fwaves, &p.lds_pool, &p.pool)) p.pipe = EdgePipe::kFused;
     else p.pipe = p.two_pass ? EdgePipe::kTwoKernel : EdgePipe::kOnePass;
@@ -1553,12 +900,12 @@ EdgePlan plan_edges(const mjpl_engine *e, int64_t E, int flags, bool long_edges)
     p.pipe = EdgePipe::kF64Pool;
     p.fwaves = kFusedF64Waves;
     p.queued = e->f64_queued && !e->exact_general() &&
-               fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 64 * kFusedF64Waves + 64, true) <= (size_t)160 * 1024;
+               fused_f64_lds_bytes(kFusedF64Waves, nplan, e->lay.nsave, 64 * kFusedF64Waves + 64, true) <= (size_t)160 * 1024;
     p.generated = p.queued && e->spec && e->spec->fused_f64 && e->f64_spec && e->spec->generic_rows == 0;
-    const size_t base = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, 0, p.queued);
+    const size_t base = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->lay.nsave, 0, p.queued);
     p.pool = (int)std::min<size_t>(kFusedMaxPool, ((size_t)160 * 1024 - base) / kFusedEntryBytes / 64 * 64);
     if (e->fused_pool_cap > 0) p.pool = std::max(64 * kFusedF64Waves + 64, std::min(p.pool, e->fused_pool_cap / 64 * 64));
-    p.lds_pool = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->nsave, p.pool, p.queued);
+    p.lds_pool = fused_f64_lds_bytes(kFusedF64Waves, nplan, e->lay.nsave, p.pool, p.queued);
   } else {
     p.pipe = EdgePipe::kExact;
   }
@@ -1583,10 +930,10 @@ template <class F>
 int dispatch_variant(const mjpl_engine *e, F &&f) {
   if (e->exact_general()) return f(std::integral_constant<int, 32>{}, std::true_type{}, std::true_type{});
   auto with_box = [&](auto S) -> int {
-    if (e->wbox) return f(S, std::true_type{}, std::false_type{});
+    if (e->lay.wbox) return f(S, std::true_type{}, std::false_type{});
     return f(S, std::false_type{}, std::false_type{});
   };
-  switch (e->maxs) {
+  switch (e->lay.maxs) {
     case 4: return with_box(std::integral_constant<int, 4>{});
     case 8: return with_box(std::integral_constant<int, 8>{});
     case 16: return with_box(std::integral_constant<int, 16>{});
@@ -1626,7 +973,7 @@ struct KtScope {  // ... around everything a scope enqueues on the engine's stre
 int launch_patch(mjpl_engine *e, const UndecidedConfigs &uc, uint8_t *dvalid, int32_t *dfb) {
   const unsigned pgrid = (unsigned)std::min<size_t>((uc.cap + kBlock - 1) / kBlock, 1024);
   const size_t ldsc = lds_bytes(e, 1);
-  const GeomTable gt = {e->d_geomtab, e->moving_base};
+  const GeomTable gt = {e->d_geomtab, e->lay.moving_base()};
   if (e->spec)
     return spec_rc(e->spec->patch(e->stream, pgrid, (unsigned)kBlock, ldsc, e->d_ip, (int)e->ip.size(), e->d_dp, (int)e->dp.size(), gt, uc, dvalid,
                                   dfb), "pair");
@@ -1643,7 +990,7 @@ int launch_configs(mjpl_engine *e, const double *dQ, int64_t N, int layout, uint
                    unsigned long long *dbits) {
   if (N == 0) return MJPL_OK;
   const int nip = (int)e->ip.size(), nfp = (int)e->fp.size(), ndp = (int)e->dp.size();
-  const bool filter = e->filter && e->filter_usable && dvalid && !dbits && N < (int64_t)1 << 29;
+  const bool filter = e->filter && e->fb.usable && dvalid && !dbits && N < (int64_t)1 << 29;
   if (filter) {
     MJPL_TRY(ulist_reserve(e, N));
     int *zero_next = next_counters(e);
@@ -1656,11 +1003,11 @@ int launch_configs(mjpl_engine *e, const double *dQ, int64_t N, int layout, uint
     const size_t lds_filter = lds_bytes(e, 1, sizeof(float), fblock, !e->immediate(), e->immediate() ? sizeof(double) : sizeof(float));
     kt_mark(e, 1, e->stream);
     const int rc = e->spec
-        ? spec_rc(e->spec->configs(e->stream, fgrid, (unsigned)fblock, lds_filter, e->d_ip, nip, e->d_fp, nfp, dQ, N, layout, e->filter_tol,
+        ? spec_rc(e->spec->configs(e->stream, fgrid, (unsigned)fblock, lds_filter, e->d_ip, nip, e->d_fp, nfp, dQ, N, layout, e->fb.tol,
                                    dvalid, e->d_ulist.p, e->d_ucount, uc, zero_next), "configuration")
         : dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
             return launch_kernel(e, k_filter_configs<void, S(), W(), M()>, fgrid, fblock, lds_filter, e->d_ip, nip, e->d_fp, nfp, dQ, N, layout,
-                                 e->filter_tol, dvalid, e->d_ulist.p, e->d_ucount, uc, zero_next);
+                                 e->fb.tol, dvalid, e->d_ulist.p, e->d_ucount, uc, zero_next);
           });
     kt_mark(e, 1, e->stream);
     MJPL_TRY(rc);
@@ -1696,7 +1043,7 @@ A batch_args(const mjpl_engine *e, const EdgeBatch &b, const UndecidedConfigs *u
   a.llist = e->d_llist.p; a.lcount = e->d_icount + kCtr;
   if (uc) {
     a.fp = e->d_fp; a.nfp = (int)e->fp.size();
-    a.tol = e->filter_tol;
+    a.tol = e->fb.tol;
     a.uc = *uc;
     a.ulist = e->d_ulist.p; a.ucount = e->d_ucount;
   }
@@ -1775,13 +1122,13 @@ int stage_endpoints(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const
   const int nip = (int)e->ip.size(), nfp = (int)e->fp.size();
   int *scount = e->d_ucount + 2 * kCtr, *etiles = e->d_ucount + kCtrEndpointTiles * kCtr;
   if (p.persistent && e->spec)
-    return spec_rc(e->spec->endpoints_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E, b.layout, e->filter_tol, b.valid,
+    return spec_rc(e->spec->endpoints_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E, b.layout, e->fb.tol, b.valid,
                                          b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, ib, b.step, zero_next, etiles), "endpoint");
   if (p.persistent)
     return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
       if constexpr (S() <= kQueuedMaxSlots) {
         return launch_persistent(e, k_filter_endpoints_pw<void, S(), W(), M()>, p.lds_persistent, (b.E + 63) / 64, e->d_ip, nip, e->d_fp, nfp, b.QA,
-                                 b.QB, b.E, b.layout, e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, ib, b.step,
+                                 b.QB, b.E, b.layout, e->fb.tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, ib, b.step,
                                  zero_next, etiles);
       } else {
         return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
@@ -1789,11 +1136,11 @@ int stage_endpoints(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const
     });
   if (e->spec)
     return spec_rc(e->spec->endpoints(e->stream, p.fgrid, (unsigned)p.fblock, p.lds_endpoints, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E, b.layout,
-                                      e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib,
+                                      e->fb.tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib,
                                       b.step, zero_next), "endpoint");
   return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
     return launch_kernel(e, k_filter_endpoints<void, S(), W(), M()>, p.fgrid, p.fblock, p.lds_endpoints, e->d_ip, nip, e->d_fp, nfp, b.QA, b.QB, b.E,
-                         b.layout, e->filter_tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib, b.step,
+                         b.layout, e->fb.tol, b.valid, b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, e->d_slist.p, scount, ib, b.step,
                          zero_next);
   });
 }
@@ -1805,22 +1152,22 @@ int stage_items(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const Und
   const EdgeSource src = {b.QA, b.QB, (long long)b.E, b.layout, b.step, ib.ckpt};
   int *itiles = e->d_ucount + kCtrItemTiles * kCtr;
   if (p.persistent && e->spec)
-    return spec_rc(e->spec->items_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol, b.valid, b.first_bad,
+    return spec_rc(e->spec->items_pw(e->stream, p.lds_persistent, e->d_ip, nip, e->d_fp, nfp, ib, src, e->fb.tol, b.valid, b.first_bad,
                                      e->d_ulist.p, e->d_ucount, uc, itiles), "item");
   if (p.persistent)
     return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
       if constexpr (S() <= kQueuedMaxSlots) {
         return launch_persistent(e, k_filter_items_pw<void, S(), W(), M()>, p.lds_persistent, (long long)ib.cap / 64, e->d_ip, nip, e->d_fp, nfp, ib,
-                                 src, e->filter_tol, b.valid, b.first_bad, e->d_ulist.p, e->d_ucount, uc, itiles);
+                                 src, e->fb.tol, b.valid, b.first_bad, e->d_ulist.p, e->d_ucount, uc, itiles);
       } else {
         return fail(MJPL_E_ARG, "persistent kernels serve the queued interpreter");
       }
     });
   if (e->spec)
-    return spec_rc(e->spec->items(e->stream, igrid, (unsigned)p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol, b.valid,
+    return spec_rc(e->spec->items(e->stream, igrid, (unsigned)p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->fb.tol, b.valid,
                                   b.first_bad, e->d_ulist.p, e->d_ucount, uc), "item");
   return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
-    return launch_kernel(e, k_filter_items<void, S(), W(), M()>, igrid, p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->filter_tol,
+    return launch_kernel(e, k_filter_items<void, S(), W(), M()>, igrid, p.fblock, p.lds_items, e->d_ip, nip, e->d_fp, nfp, ib, src, e->fb.tol,
                          b.valid, b.first_bad, e->d_ulist.p, e->d_ucount, uc);
   });
 }
@@ -1830,7 +1177,7 @@ int stage_items(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const Und
 int stage_tail(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const UndecidedConfigs &uc) {
   TailArgs ta = batch_args<TailArgs>(e, b, &uc);
   ta.dp = e->d_dp; ta.ndp = (int)e->dp.size();
-  ta.gt = GeomTable{e->d_geomtab, e->moving_base};
+  ta.gt = GeomTable{e->d_geomtab, e->lay.moving_base()};
   ta.flags = b.flags;
   ta.done = e->d_ucount + kCtrTailDone * kCtr;
   ta.nw = ta.nx = (int)std::min<int64_t>((b.E + kBlock - 1) / kBlock, 64);
@@ -1850,7 +1197,7 @@ int stage_walk(mjpl_engine *e, const EdgePlan &p, const EdgeBatch &b, const Unde
                int *zero_next) {
   return dispatch_filter(e, [&](auto S, auto W, auto M) -> int {
     return launch_kernel(e, k_filter_edges<S(), W(), M()>, p.fgrid, p.fblock, p.lds_walk, e->d_ip, (int)e->ip.size(), e->d_fp, (int)e->fp.size(),
-                         b.QA, b.QB, b.E, b.step, b.layout, p.two_pass ? (b.flags | MJPL_EDGE_INTERIOR_ONLY) : b.flags, e->filter_tol, b.valid,
+                         b.QA, b.QB, b.E, b.step, b.layout, p.two_pass ? (b.flags | MJPL_EDGE_INTERIOR_ONLY) : b.flags, e->fb.tol, b.valid,
                          b.first_bad, e->d_status, e->d_ulist.p, e->d_ucount, uc, rlist, rcount, p.two_pass ? (int *)nullptr : zero_next);
   });
 }
@@ -2029,101 +1376,6 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
                        dbits);
     HIP_TRY(hipGetLastError());
   }
-  return MJPL_OK;
-}
-
-// The distance table beside the candidate table (mjpl_distance.h: DT_*): rb1 + rb2 and the allowed flag per
-// pair.  Depends on the model only: called once, at mjpl_create.
-int build_distance_table(mjpl_engine *e) {
-  const int P = (int)e->ct_g1.size();
-  if (P == 0) return MJPL_OK;
-  std::vector<double> dt((size_t)P * DT_LEN);
-  for (int p = 0; p < P; p++) {
-    const int g1 = e->ct_g1[p], g2 = e->ct_g2[p];
-    // (a plane partner's bound is the half-space itself: only the other geom's radius counts)
-    const double rb1 = e->m.geom_type[g1] == GT_PLANE ? 0.0 : e->m.geom_rbound[g1];
-    const double rb2 = e->m.geom_type[g2] == GT_PLANE ? 0.0 : e->m.geom_rbound[g2];
-    dt[(size_t)p * DT_LEN + DT_RBSUM] = rb1 + rb2;
-    dt[(size_t)p * DT_LEN + DT_ALLOWED] = e->ct_allowed[p] ? 1.0 : 0.0;
-  }
-  double *d = nullptr;
-  HIP_TRY(hipMalloc(&d, dt.size() * sizeof(double)));
-  const hipError_t err = hipMemcpy(d, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(d);
-    HIP_TRY(err);
-  }
-  e->d_dt = d;
-  return MJPL_OK;
-}
-
-// The tables of k_distance<DM_GRAD> (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
-// the number of later joints on that body and the body's subtree as DFS times; per model joint its type, axis,
-// position and where its dq comes from (as the FK program computes it); per geom the DFS entry time of its body.
-// Depends on the model and the planning selection: made at mjpl_create and by mjpl_set_planning.
-int build_grad_table(mjpl_engine *e) {
-  const HostModel &m = e->m;
-  const int nplan = (int)e->qidx.size(), nj = m.njnt, ng = m.ngeom, nb = m.nbody;
-  // DFS entry / exit times of the body tree (children in id order)
-  std::vector<std::vector<int>> kids(nb);
-  for (int b = 1; b < nb; b++) kids[m.body_parentid[b]].push_back(b);
-  std::vector<int> tin(nb, 0), tout(nb, 0), stack = {0};
-  std::vector<size_t> next(nb, 0);
-  int clock = 0;
-  tin[0] = clock++;
-  while (!stack.empty()) {
-    const int b = stack.back();
-    if (next[b] < kids[b].size()) {
-      const int k = kids[b][next[b]++];
-      tin[k] = clock++;
-      stack.push_back(k);
-    } else {
-      tout[b] = clock;
-      stack.pop_back();
-    }
-  }
-  std::vector<int> col_of(m.nq, -1);
-  for (int c = 0; c < nplan; c++) col_of[e->qidx[c]] = c;
-  std::vector<int> jnt_body(nj, 0);
-  for (int b = 0; b < nb; b++)
-    for (int j = 0; j < m.body_jntnum[b]; j++) jnt_body[m.body_jntadr[b] + j] = b;
-  std::vector<double> t((size_t)nplan * GC_LEN + (size_t)nj * JR_LEN + ng, 0.0);
-  double *gc = t.data(), *jr = gc + (size_t)nplan * GC_LEN, *gt = jr + (size_t)nj * JR_LEN;
-  for (int j = 0; j < nj; j++) {
-    const int qadr = m.jnt_qposadr[j];
-    double *r = jr + (size_t)j * JR_LEN;
-    r[JR_TYPE] = m.jnt_type[j];
-    for (int k = 0; k < 3; k++) {
-      r[JR_AXIS + k] = m.jnt_axis[3 * j + k];
-      r[JR_POS + k] = m.jnt_pos[3 * j + k];
-    }
-    r[JR_COL] = col_of[qadr];
-    r[JR_Q0] = col_of[qadr] >= 0 ? m.qpos0[qadr] : e->qbase[qadr] - m.qpos0[qadr];  // (the FK's qv - jd[6])
-  }
-  for (int c = 0; c < nplan; c++) {
-    int j = -1;
-    for (int k = 0; k < nj; k++)
-      if (m.jnt_qposadr[k] == e->qidx[c]) j = k;
-    if (j < 0) return fail(MJPL_E_JOINT, "planning column %d names qpos %d, which no joint owns", c, e->qidx[c]);
-    const int b = jnt_body[j];
-    double *r = gc + (size_t)c * GC_LEN;
-    r[GC_BODY] = b;
-    r[GC_JNT] = j;
-    r[GC_NLATER] = m.body_jntadr[b] + m.body_jntnum[b] - 1 - j;
-    r[GC_TIN] = tin[b];
-    r[GC_TOUT] = tout[b];
-  }
-  for (int g = 0; g < ng; g++) gt[g] = tin[m.geom_bodyid[g]];
-  if (e->d_gr) HIP_TRY(hipFree(e->d_gr));
-  e->d_gr = nullptr;
-  double *d = nullptr;
-  HIP_TRY(hipMalloc(&d, std::max<size_t>(t.size(), 1) * sizeof(double)));
-  const hipError_t err = hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(d);
-    HIP_TRY(err);
-  }
-  e->d_gr = d;
   return MJPL_OK;
 }
 
@@ -2384,14 +1636,8 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
   int rc = engine_from_desc(e, d, allowed_bodies, nallowed);
   if (rc != MJPL_OK) return bail(rc);
   apply_debug_environment(e);
-  rc = compile_program(e);
-  if (rc != MJPL_OK) return bail(rc);
-  rc = build_contact_table(e);
-  if (rc != MJPL_OK) return bail(rc);
-  rc = build_distance_table(e);
-  if (rc != MJPL_OK) return bail(rc);
-  rc = build_grad_table(e);
-  if (rc != MJPL_OK) return bail(rc);
+  if ((rc = compile_program(e)) != MJPL_OK || (rc = make_pair_tables(e)) != MJPL_OK || (rc = make_grad_table(e)) != MJPL_OK)
+    return bail(rc);
   *out = e;
   return MJPL_OK;
 }
@@ -2437,7 +1683,6 @@ int mjpl_program_dump(const mjpl_model_desc *d, const int32_t *allowed_bodies, i
   if (d->nq < 0 || d->njnt < 0 || d->nbody < 1 || d->ngeom < 0 || nallowed < 0) return fail(MJPL_E_ARG, "negative size");
   if (d->nq != d->njnt) return fail(MJPL_E_JOINT, "nq != njnt: only 1-DoF joints are supported");
   std::unique_ptr<mjpl_engine> e(new mjpl_engine());
-  e->device = -1;  // host tables only: nothing is allocated or uploaded
   int rc = engine_from_desc(e.get(), d, allowed_bodies, nallowed);
   if (rc != MJPL_OK) return rc;
   if (qidx) {
@@ -2447,14 +1692,14 @@ int mjpl_program_dump(const mjpl_model_desc *d, const int32_t *allowed_bodies, i
   }
   if (qpos_base) e->qbase.assign(qpos_base, qpos_base + d->nq);
   if (filter_tol > 0.0) { e->filter_tol_req = (float)filter_tol; e->filter_tol_user = true; }
-  if ((rc = compile_program(e.get())) != MJPL_OK) return rc;
+  if ((rc = compile_host(e.get())) != MJPL_OK) return rc;  // (host tables only: nothing is allocated or uploaded)
   memset(info, 0, sizeof(*info));
   info->hash = e->program_hash;
   // (maxs: the slot-file width of the FILTER kernels a library is built around -- 24 for the queued build of models with
   // moving boxes; immediate: only the immediate interpreter serves this program, nothing to specialise)
-  info->maxs = e->filter_mbox() ? kQueuedMaxSlots : e->maxs; info->wbox = e->wbox; info->mbox = e->mbox || e->filter_mbox();
+  info->maxs = e->filter_mbox() ? kQueuedMaxSlots : e->lay.maxs; info->wbox = e->lay.wbox; info->mbox = e->lay.mbox || e->filter_mbox();
   info->immediate = e->immediate() || (e->exact_general() && !e->filter_mbox());
-  info->filter_usable = e->filter_usable; info->filter_tol = e->filter_tol; info->nslots = e->nslots; info->nsave = e->nsave;
+  info->filter_usable = e->fb.usable; info->filter_tol = e->fb.tol; info->nslots = e->lay.nslots; info->nsave = e->lay.nsave;
   info->spec_abi = MJPL_SPEC_ABI;
   info->robot_hash = e->robot_hash;
   info->scene_rows = kSceneRows;
@@ -2500,7 +1745,7 @@ int mjpl_set_planning(mjpl_engine *e, const int32_t *qidx, int32_t nplan, const 
   if (qpos_base) e->qbase.assign(qpos_base, qpos_base + e->m.nq);
   const int rc = compile_program(e);
   if (rc != MJPL_OK) return rc;
-  return build_grad_table(e);
+  return make_grad_table(e);
 }
 
 int mjpl_set_filter(mjpl_engine *e, int32_t enable, double tol) {
@@ -2518,7 +1763,7 @@ int mjpl_set_filter(mjpl_engine *e, int32_t enable, double tol) {
 }
 
 int64_t mjpl_filter_last_undecided(mjpl_engine *e) {
-  if (!e || !e->filter || !e->filter_usable || !e->d_ucount) return 0;
+  if (!e || !e->filter || !e->fb.usable || !e->d_ucount) return 0;
   int n[5 * kCtr];
   if (hipSetDevice(e->device) != hipSuccess) return -1;
   if (hipStreamSynchronize(e->stream) != hipSuccess) return -1;
@@ -2530,7 +1775,7 @@ int64_t mjpl_filter_last_undecided(mjpl_engine *e) {
 // kernel -- which pairs the float32 filter could not decide.  Returns how many there were (the arrays receive up to
 // `cap` of them), or -1.
 int64_t mjpl_filter_undecided_pairs(mjpl_engine *e, int32_t *edge, int32_t *idx, int32_t *ga, int32_t *gb, int64_t cap) {
-  if (!e || !e->filter || !e->filter_usable || !e->d_ucount || !e->d_ucedge.p) return 0;
+  if (!e || !e->filter || !e->fb.usable || !e->d_ucount || !e->d_ucedge.p) return 0;
   if (hipSetDevice(e->device) != hipSuccess) return -1;
   if (hipStreamSynchronize(e->stream) != hipSuccess) return -1;
   int n = 0;
@@ -2583,20 +1828,20 @@ int mjpl_get_info(const mjpl_engine *e, mjpl_info *out) {
   memset(out, 0, sizeof(*out));
   out->device = e->device;
   out->nplan = (int)e->qidx.size();
-  out->nmoving_geoms = e->nmoving;
-  out->nstatic_geoms = e->nstatic;
-  out->npairs = e->npairs;
-  out->npairs_world = e->npairs_world;
-  out->nslots = e->nslots;
-  out->nsaves = e->nsave;
+  out->nmoving_geoms = e->lay.nmoving;
+  out->nstatic_geoms = e->lay.nworld();
+  out->npairs = e->lay.npairs;
+  out->npairs_world = e->lay.npairs_world;
+  out->nslots = e->lay.nslots;
+  out->nsaves = e->lay.nsave;
   out->lds_bytes_configs = (int)lds_bytes(e, 1);
   out->lds_bytes_edges = (int)lds_bytes(e, 1);
-  out->filter_enabled = (e->filter && e->filter_usable) ? 1 : 0;
-  out->filter_tol = e->filter_tol;
-  out->filter_max_coord = (float)e->fmax_coord;
-  out->filter_err_a = (float)e->ferr_a;
-  out->filter_err_b = (float)e->ferr_b;
-  out->filter_poisoned_geoms = e->npoisoned;
+  out->filter_enabled = (e->filter && e->fb.usable) ? 1 : 0;
+  out->filter_tol = e->fb.tol;
+  out->filter_max_coord = (float)e->fb.fmax_coord;
+  out->filter_err_a = (float)e->fb.ferr_a;
+  out->filter_err_b = (float)e->fb.ferr_b;
+  out->filter_poisoned_geoms = e->fb.npoisoned;
   out->filter_interpreter = e->immediate() ? 2 : (e->filter_mbox() ? 1 : 0);
   out->filter_block_threads = e->immediate() ? kBlock : kFilterBlock;
   out->lds_bytes_filter = (int)lds_bytes(e, 1, sizeof(float), out->filter_block_threads, !e->immediate(),
@@ -3349,14 +2594,14 @@ int mjpl_fk(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double *
   // bodies/geoms welded to the world do not depend on qpos: poses folded at create
   for (int64_t i = 0; i < N; i++) {
     for (int b = 0; b < m.nbody; b++) {
-      if (!e->body_static[b]) continue;
-      if (xpos) memcpy(xpos + (i * m.nbody + b) * 3, &e->st_xpos[3 * b], 3 * sizeof(double));
-      if (xquat) memcpy(xquat + (i * m.nbody + b) * 4, &e->st_xquat[4 * b], 4 * sizeof(double));
+      if (!e->lay.body_static[b]) continue;
+      if (xpos) memcpy(xpos + (i * m.nbody + b) * 3, &e->lay.st_xpos[3 * b], 3 * sizeof(double));
+      if (xquat) memcpy(xquat + (i * m.nbody + b) * 4, &e->lay.st_xquat[4 * b], 4 * sizeof(double));
     }
     for (int g = 0; g < m.ngeom; g++) {
-      if (!e->geom_static[g]) continue;
-      if (geom_xpos) memcpy(geom_xpos + (i * m.ngeom + g) * 3, &e->st_gxpos[3 * g], 3 * sizeof(double));
-      if (geom_xmat) memcpy(geom_xmat + (i * m.ngeom + g) * 9, &e->st_gxmat[9 * g], 9 * sizeof(double));
+      if (!e->lay.geom_static[g]) continue;
+      if (geom_xpos) memcpy(geom_xpos + (i * m.ngeom + g) * 3, &e->lay.st_gxpos[3 * g], 3 * sizeof(double));
+      if (geom_xmat) memcpy(geom_xmat + (i * m.ngeom + g) * 9, &e->lay.st_gxmat[9 * g], 9 * sizeof(double));
     }
   }
   return MJPL_OK;
@@ -3557,7 +2802,7 @@ int mjpl_time_edges_dev(mjpl_engine *e, const double *dQA, const double *dQB, in
   const int rc = mjpl_time_edges_stages_dev(e, dQA, dQB, E, step_dist, layout, dvalid, iters, 1, &mean,
                                             ms_first ? stage : nullptr, nullptr);
   if (rc != MJPL_OK) return rc;
-  const int main_stage = (e->filter && e->filter_usable) ? MJPL_STAGE_ITEMS : MJPL_STAGE_EXACT;
+  const int main_stage = (e->filter && e->fb.usable) ? MJPL_STAGE_ITEMS : MJPL_STAGE_EXACT;
   for (int k = 0; k < iters; k++) {
     ms[k] = mean;
     if (ms_first) ms_first[k] = stage[main_stage];
@@ -3605,59 +2850,6 @@ int pose_check(const mjpl_pose *p, const void *a, int64_t n) {
   if (n > 0 && !a) return fail(MJPL_E_ARG, "NULL batch pointer");
   return MJPL_OK;
 }
-}  // namespace
-
-namespace {
-// chain program shared by the pose and IK handles: per body {njnt}, per joint {type, qadr, jid}
-int build_chain(const HostModel &m, int site_body, std::vector<int> &pi, std::vector<double> &pd, int *nj) {
-  std::vector<int> chain;
-  for (int b = site_body; b > 0; b = m.body_parentid[b]) chain.push_back(b);
-  std::reverse(chain.begin(), chain.end());
-  pi.assign(PH_SIZE, 0);
-  *nj = 0;
-  for (int b : chain) {
-    pi.push_back(m.body_jntnum[b]);
-    for (int k = 0; k < 3; k++) pd.push_back(m.body_pos[3 * b + k]);
-    for (int k = 0; k < 4; k++) pd.push_back(m.body_quat[4 * b + k]);
-    for (int j = 0; j < m.body_jntnum[b]; j++) {
-      const int jid = m.body_jntadr[b] + j;
-      if (m.jnt_type[jid] != JT_SLIDE && m.jnt_type[jid] != JT_HINGE)
-        return fail(MJPL_E_JOINT, "joint %d: only slide and hinge joints are supported", jid);
-      pi.push_back(m.jnt_type[jid]);
-      pi.push_back(m.jnt_qposadr[jid]);
-      pi.push_back(jid);
-      for (int k = 0; k < 3; k++) pd.push_back(m.jnt_axis[3 * jid + k]);
-      for (int k = 0; k < 3; k++) pd.push_back(m.jnt_pos[3 * jid + k]);
-      pd.push_back(m.qpos0[m.jnt_qposadr[jid]]);
-      (*nj)++;
-    }
-  }
-  pi[PH_NBODY] = (int)chain.size();
-  pi[PH_NJOINT] = *nj;
-  pi[PH_NQ] = m.nq;
-  return MJPL_OK;
-}
-}  // namespace
-
-namespace {
-// what a generated projection carries as literals: the chain program without its run-time tail (site offset,
-// constraint, tolerances, iteration bound), the library ABI and the digest of the shared headers
-uint64_t chain_hash_of(const std::vector<int> &pi, const std::vector<double> &pd, size_t chain_doubles) {
-  uint64_t h = 0xcbf29ce484222325ull;
-  auto mix = [&](const void *ptr, size_t n) {
-    const unsigned char *b = (const unsigned char *)ptr;
-    for (size_t k = 0; k < n; k++) { h ^= b[k]; h *= 0x100000001b3ull; }
-  };
-  const int head[3] = {pi[PH_NBODY], pi[PH_NJOINT], pi[PH_NQ]};
-  mix(head, sizeof(head));
-  mix(pi.data() + PH_SIZE, (pi.size() - PH_SIZE) * sizeof(int));
-  mix(pd.data(), chain_doubles * sizeof(double));
-  const int abi = MJPL_SPEC_ABI;
-  mix(&abi, sizeof(abi));
-  const unsigned long long stamp = MJPL_SRC_STAMP;
-  mix(&stamp, sizeof(stamp));
-  return h;
-}
 
 // How a batch of N rows (projections, IK seeds, active planner lanes) goes to the row kernels of mjpl_rows.h.  The
 // kernels hold one wave per SIMD (their registers), 1 024 waves on the chip.  While ALL rows can be resident at once
@@ -3696,7 +2888,6 @@ int mjpl_pose_chain_dump(const mjpl_model_desc *d, int32_t site_body, int32_t *p
   if (!d || !npi || !npd || !hash) return fail(MJPL_E_ARG, "mjpl_pose_chain_dump: NULL argument");
   if (d->nq != d->njnt) return fail(MJPL_E_JOINT, "nq != njnt: only 1-DoF joints are supported");
   std::unique_ptr<mjpl_engine> e(new mjpl_engine());
-  e->device = -1;
   int rc = engine_from_desc(e.get(), d, nullptr, 0);
   if (rc != MJPL_OK) return rc;
   if (site_body < 0 || site_body >= e->m.nbody) return fail(MJPL_E_ARG, "site body %d out of range", site_body);
@@ -3747,10 +2938,8 @@ int mjpl_pose_create(mjpl_engine *e, const mjpl_pose_desc *d, mjpl_pose **out) {
   if (pose_lds(p.get()) > 64 * 1024)
     return fail(MJPL_E_CAPACITY, "pose projection: %d qpos + %d chain joints exceed the LDS budget", p->nq, p->nj);
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMalloc(&p->d_pi, p->pi.size() * sizeof(int)));
-  HIP_TRY(hipMalloc(&p->d_pd, p->pd.size() * sizeof(double)));
-  HIP_TRY(hipMemcpy(p->d_pi, p->pi.data(), p->pi.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p->d_pd, p->pd.data(), p->pd.size() * sizeof(double), hipMemcpyHostToDevice));
+  MJPL_TRY(upload_table(&p->d_pi, p->pi));
+  MJPL_TRY(upload_table(&p->d_pd, p->pd));
   *out = p.release();
   return MJPL_OK;
 }
