@@ -63,9 +63,9 @@ int fail(int code, const char *fmt, ...) {
                   __FILE__, __LINE__);                                                  \
   } while (0)
 
-#define MJPL_TRY(expr)                  \
+#define MJPL_TRY(...)                   \
   do {                                  \
-    int _rc = (expr);                   \
+    int _rc = (__VA_ARGS__);            \
     if (_rc != MJPL_OK) return _rc;     \
   } while (0)
 
@@ -94,6 +94,22 @@ struct DevBuf {
     cap = n;
     return MJPL_OK;
   }
+};
+
+// What a nearest-neighbour look-up keeps between calls: its scratch, and what the last look-up ON THIS SCRATCH did.  The
+// engine has one; the planner a second for the look-ups on its second stream (mjpl_rrt.h), which go with the planner.
+struct NnScratch {
+  DevBuf<char> parts;    // per-chunk partial results and the seed row
+  DevBuf<char> arena;    // the screens' operands (binary16 rows), partial results, the cell-ordered scan's lists and sorted rows
+  DevBuf<double> spare;  // distances of a ranged look-up whose caller wants none
+  // (reset at the top of every look-up.  An offset into the arena, not a pointer: a reader that finds the arena smaller
+  //  than the offset -- released, or never grown -- answers "unknown")
+  struct Last {
+    int path = 0;         // 0 float64 scan, 1 binary32 screen, 2 matrix-core screen (or 1: see its flag, mjpl_nearest_last_screen)
+    bool cells = false;   // ... as the cell-ordered scan
+    size_t count_at = 0;  // its candidate counts: byte offset in the arena, `waves` of them, of `nsub` sub-chunks
+    int waves = 0, nsub = 0;
+  } last;
 };
 
 // ------------------------------------------------------------------------------- kernels
@@ -397,12 +413,8 @@ struct mjpl_engine {
   const char *fused_dbg_path = nullptr;  // MJPL_FUSED_DEBUG=<file> (with a -DMJPL_FUSED_DEBUG build of the kernels)
   DevBuf<unsigned long long> d_fused_dbg;
   size_t item_cap_limit = (size_t)1 << 26;  // MJPL_ITEM_CAP: edges beyond it take the walking kernel
-  void *d_nn = nullptr;         // nearest neighbour: per-chunk partial results
-  size_t nn_bytes = 0;
-  void *d_nn16 = nullptr;       // ... the matrix-core screen's operands (binary16 rows) and partial results
-  size_t nn16_bytes = 0;
+  NnScratch nn;                 // nearest neighbour: the scratch of the look-ups on the engine's stream
   int nn_mfma = 1;              // MJPL_NN_MFMA=0: binary32 screen only
-  void *d_nn_tmp = nullptr; size_t nn_tmp_bytes = 0;  // distances of a ranged look-up whose caller wants none
   int64_t nn_reserve_nodes = 0; // packed-node rows the screened look-up's scratch is sized for at least (mjpl_rrt_create: the planner's capacity, 2^23 at most)
   int64_t nn_sample = 65536;    // MJPL_NN_SAMPLE: nodes of the strided sample the matrix cores take every query's bound from
   // switches that used to be read from the environment wherever they were used (round 6: options, include/mjpl_hip.h)
@@ -428,10 +440,7 @@ struct mjpl_engine {
   // round against 19.5 without (it evaluates every parked pair twice where the first evaluation decides most), the home pass
   // 19.6 (what it saves the scan it costs itself).  Kept for trees and batches of other shapes.
   int nn_home = 0, nn_second_screen = 0;
-  int nn_last_cells = 0;        // the last look-up took it
   int nn_probe = 0;             // option "nn_probe" (2: count the exact evaluations)
-  const int32_t *nn_last_count = nullptr; int nn_last_waves = 0, nn_last_nsub = 0;  // the last cell-ordered scan's candidate counts
-  int nn_last = 0;              // what the last mjpl_nearest_dev launched: 0 float64 scan, 1 binary32 screen, 2 matrix-core screen (or 1: see its flag)
   size_t uc_cap = 0, uc_cap_limit = 0;
   ModelLayout lay;  // static poses for FK output, slot and save counts, kernel shape
   // the immediate (non-queued) interpreter serves models with moving boxes and models that keep
@@ -773,12 +782,18 @@ int allow_lds(K kernel, size_t bytes) {
   return MJPL_OK;
 }
 
-// ---- the two ways a kernel is launched: an interpreting kernel of this library on the engine's stream ...
+// ---- the two ways a kernel is launched: a kernel of this library on a stream (the engine's, unless the caller names one:
+// the look-up's kernels also go to the planner's second) ...
+template <class K, class... A>
+int launch_kernel(hipStream_t st, K kern, dim3 grid, int block, size_t lds, A... args) {
+  MJPL_TRY(allow_lds(kern, lds));
+  hipLaunchKernelGGL(kern, grid, dim3(block), lds, st, args...);
+  return MJPL_OK;
+}
+
 template <class K, class... A>
 int launch_kernel(const mjpl_engine *e, K kern, unsigned grid, int block, size_t lds, A... args) {
-  MJPL_TRY(allow_lds(kern, lds));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, e->stream, args...);
-  return MJPL_OK;
+  return launch_kernel(e->stream, kern, dim3(grid), block, lds, args...);
 }
 
 // (a persistent grid: the workgroups that are resident under that LDS grant, or fewer for `ntile` tiles of 64)
@@ -1663,9 +1678,6 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->d_fp_base) (void)hipFree(e->d_fp_base);
   if (e->d_ucount_base) (void)hipFree(e->d_ucount_base);
   if (e->d_geomtab) (void)hipFree(e->d_geomtab);
-  if (e->d_nn) (void)hipFree(e->d_nn);
-  if (e->d_nn16) (void)hipFree(e->d_nn16);
-  if (e->d_nn_tmp) (void)hipFree(e->d_nn_tmp);
   if (e->d_status) (void)hipFree(e->d_status);
   if (e->d_ct_ip) (void)hipFree(e->d_ct_ip);
   if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
@@ -1912,6 +1924,11 @@ double kt_sum(mjpl_engine *e, int c) {
   }
   return sum;
 }
+// (what the last look-up on the engine's scratch left at byte `at` of its arena; false: no such bytes, or the copy failed)
+bool nn_arena_read(mjpl_engine *e, size_t at, void *dst, size_t bytes) {
+  if (at + bytes > e->nn.arena.cap) return false;
+  return hipStreamSynchronize(e->stream) == hipSuccess && hipMemcpy(dst, e->nn.arena.p + at, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+}
 struct EngineOption {
   const char *name;
   double (*get)(mjpl_engine *);
@@ -1979,7 +1996,9 @@ const EngineOption kEngineOptions[] = {
      [](mjpl_engine *e, double v) { if (!(v >= 32 && v < 9e15)) return false; e->nn_cells_sample = std::max<int64_t>(1024, (int64_t)v) / 32 * 32; return true; }},
     {"nn_sample", [](mjpl_engine *e) { return (double)e->nn_sample; },
      [](mjpl_engine *e, double v) { if (!(v >= 32 && v < 9e15)) return false; e->nn_sample = std::max<int64_t>(1024, (int64_t)v) / 32 * 32; return true; }},
-    {"nn_last_cells", [](mjpl_engine *e) { return (double)e->nn_last_cells; }, nullptr},  // (read-only: the last look-up took the cell-ordered scan)
+    // (read-only, like the two below and mjpl_nearest_last_screen: the last look-up on the engine's own scratch -- none of the
+    //  planner's on its second stream -- took the cell-ordered scan)
+    {"nn_last_cells", [](mjpl_engine *e) { return e->nn.last.cells ? 1.0 : 0.0; }, nullptr},
     {"kernel_timer", [](mjpl_engine *e) { return (double)e->kt_mode; },
      [](mjpl_engine *e, double v) {
        if (!(v >= 0 && v <= 3)) return false;
@@ -2002,25 +2021,23 @@ const EngineOption kEngineOptions[] = {
     //  A switch that dropped them unevaluated, for timing, gave wrong answers by design and is not in the product: see round 5.)
     {"nn_probe", [](mjpl_engine *e) { return (double)e->nn_probe; },
      [](mjpl_engine *e, double v) { if (v != 0.0 && v != 2.0) return false; e->nn_probe = (int)v; return true; }},
-    {"nn_last_exact_pairs",  // (read-only; synchronises; counted only with "nn_probe" = 2)
+    {"nn_last_exact_pairs",  // (read-only; synchronises; counted only with "nn_probe" = 2, by a cell-ordered scan: else -1)
      [](mjpl_engine *e) {
        unsigned x[4] = {0, 0, 0, 0};
-       if (!e->d_nn16 || hipStreamSynchronize(e->stream) != hipSuccess || hipMemcpy(x, e->d_nn16, sizeof(x), hipMemcpyDeviceToHost) != hipSuccess)
-         return -1.0;
+       if (!e->nn.last.cells || !nn_arena_read(e, 0, x, sizeof(x))) return -1.0;
        return (double)x[3];
      },
      nullptr},
     // (read-only; synchronises: the share of the tree's sub-chunks a wave of the last cell-ordered scan had on its list, averaged)
     {"nn_last_candidate_fraction",
      [](mjpl_engine *e) {
-       if (!e->nn_last_cells || !e->nn_last_count || e->nn_last_waves < 1 || e->nn_last_nsub < 1) return -1.0;
-       std::vector<int32_t> c((size_t)e->nn_last_waves);
-       if (hipStreamSynchronize(e->stream) != hipSuccess ||
-           hipMemcpy(c.data(), e->nn_last_count, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-         return -1.0;
+       const NnScratch::Last &last = e->nn.last;
+       if (!last.cells || last.waves < 1 || last.nsub < 1) return -1.0;
+       std::vector<int32_t> c((size_t)last.waves);
+       if (!nn_arena_read(e, last.count_at, c.data(), c.size() * sizeof(int32_t))) return -1.0;
        double sum = 0;
        for (int32_t v : c) sum += v;
-       return sum / ((double)c.size() * e->nn_last_nsub);
+       return sum / ((double)c.size() * last.nsub);
      },
      nullptr},
 };
@@ -2076,43 +2093,486 @@ int mjpl_get_option(mjpl_engine *e, const char *name, double *value) {
 
 int32_t mjpl_nearest_last_screen(mjpl_engine *e) {
   if (!e) return -1;
-  if (e->nn_last != 2) return e->nn_last;
+  if (e->nn.last.path != 2) return e->nn.last.path;
   unsigned x[2] = {0, 0};
-  if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
-      hipMemcpy(x, e->d_nn16, sizeof(x), hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
+  if (hipSetDevice(e->device) != hipSuccess || !nn_arena_read(e, 0, x, sizeof(x))) return -1;
   return x[1] ? 1 : 2;  // (coordinates too large for binary16: the binary32 screen ran)
 }
 
 }  // extern "C"
 
-// the look-up over nodes [0, n) of the slab at `dnodes` (column stride `cap`); outer_d2 (or NULL): a distance every query
-// already has an answer at -- nothing farther is of interest
-static int nearest_core(mjpl_engine *e, const double *dnodes, int64_t n, int64_t cap, const double *dqueries, int64_t M,
-                        int32_t *dout_idx, double *dout_dist2, const double *outer_d2);
+// ---- nearest neighbour (mjpl_nearest.h, mjpl_nearest_cells.h): a plan, a scratch (NnScratch), a function per stage
 
-// mjpl_nearest_dev over the node range [n0, n) behind an answer (outer_idx, outer_d2: NULL = none) for the nodes below n0
-int nearest_range(mjpl_engine *e, const double *dnodes, int64_t n0, int64_t n, int64_t cap, const double *dqueries, int64_t M,
-                  int32_t *dout_idx, double *dout_dist2, const int32_t *outer_idx, const double *outer_d2) {
-  if (n0 == 0 && !outer_idx) return nearest_core(e, dnodes, n, cap, dqueries, M, dout_idx, dout_dist2, nullptr);
+// ---- What one look-up will do, decided before anything is reserved or enqueued (no HIP call in here).
+//   kLds       more planning columns than the chunked kernels take (or no nodes): k_nearest, a tile of nodes in LDS
+//   kPlain     the float64 scan: 512 queries per block x node chunks, then a reduction over the chunks
+//   kScreen32  large trees and query sets.  First a strided sample of the nodes, exactly: every query gets a bound close to
+//              its answer.  Then the binary32-screened scan of all nodes, eight queries per lane, which evaluates exactly
+//              only what lies within that bound
+//   kMfma      ... the screened scan on the matrix cores (nplan <= 7), unless some coordinate is too large for binary16 --
+//              which the device finds out while it packs the operands: then those kernels return at once and the float64
+//              sample scan and the binary32 screen run (which in turn return at once when the matrix cores serve the call)
+//   kCells     ... the cell-ordered scan (mjpl_nearest_cells.h): nodes sorted along a space-filling curve, queries by where
+//              on it their bound was found, a wave scans the sub-chunks some query of it can have its answer in
+enum class NnPath { kLds, kPlain, kScreen32, kMfma, kCells };
+
+struct NnPlan {
+  NnPath path;
+  int nplan;
+  unsigned rgridM;  // one thread per query, kBlock of them
+  // float64 scan: blocks of queries, node chunks of `chunk`, partial rows the scratch holds
+  int64_t qtiles, nchunks, chunk;
+  size_t maxchunks;
+  // the float64 scan of the sample: every stride-th node, nsamp64 of them in chunks of ch0 (nc0 planned, nch0 launched)
+  int64_t stride, nc0, ch0, nsamp64, nch0;
+  // the binary32 screen
+  int64_t qt32, nc32, ch32;
+  // the matrix cores: padded counts, blocks of 512 queries, node chunks of chm (kMfma) or rows of mask words (kCells) per
+  // workgroup row, partial rows; their sample of msample nodes, every mstride-th, in ssplit chunks of schunk
+  int64_t npad, Mpad, qblocks, nsplit, chm, msample, mstride, ssplit, schunk;
+  int mparts, sshift;  // (sshift: a bound's low 16 bits carry the sample position, scaled by it)
+  int64_t nres;        // node rows the arena is sized for when it must grow
+  // the cell-ordered scan: sub-chunks, mask words over them, sub-chunks padded to whole words
+  int nsub, nwords, nsubp;
+};
+
+constexpr int64_t kSampleNodes = 16384;
+
+NnPlan plan_nearest(const mjpl_engine *e, int64_t n, int64_t cap, int64_t M, bool have_bound) {
+  NnPlan p = {};
+  const int nplan = p.nplan = (int)e->qidx.size();
+  p.rgridM = (unsigned)((M + kBlock - 1) / kBlock);
+  p.path = NnPath::kLds;
+  if (nplan > kNNMaxPlan || n <= 0) return p;
+  // 2-D decomposition: 512 queries per block x node chunks, then a reduction over the chunks;
+  // chunks sized for about eight two-wave blocks per SIMD quartet (the scan is one dependent
+  // chain per query: waves, not instructions, hide its latencies)
+  const int qblock = kNNQueries * kNNThreads;
+  p.qtiles = (M + qblock - 1) / qblock;
+  p.nchunks = std::max<int64_t>(1, (8192 + p.qtiles - 1) / p.qtiles);
+  p.nchunks = std::min<int64_t>(p.nchunks, (n + kNNThreads - 1) / kNNThreads);
+  p.nchunks = std::max<int64_t>(p.nchunks, 1);
+  p.chunk = (n + p.nchunks - 1) / p.nchunks;
+  p.chunk = (p.chunk + kNNThreads - 1) / kNNThreads * kNNThreads;
+  p.nchunks = (n + p.chunk - 1) / p.chunk;
+  // partial results: room for twice the chunks of the float64 scan (the screened scan below
+  // cuts the nodes up to twice as fine), and one seed row
+  p.maxchunks = 2 * (size_t)p.nchunks + 1;
+  p.path = NnPath::kPlain;
+  // (4 096 queries: the planner's look-up of its tail lanes.  A ranged look-up brings a bound for every query with it -- the
+  //  distance already found below the range: screened from 8 192 nodes on.  It still takes the sample of its range: the
+  //  nodes a round adds reach into places the tree was far from, and a query there would otherwise park every one of them)
+  if (!(M >= 4096 && (n >= 16 * kSampleNodes || (have_bound && n >= 8192)) && nplan >= 2 && nplan <= 9)) return p;
+  p.stride = std::max<int64_t>(1, n / kSampleNodes);
+  // (chunks of the float64 sample scan: whole multiples of the scan's tile, and never more of them than partial rows --
+  //  16 384 / nc0 rounded DOWN gave one chunk too many for some node counts, whose row was the seed row: ADVICE r05)
+  p.nc0 = std::min<int64_t>(p.maxchunks, kSampleNodes / kNNThreads);
+  p.ch0 = ((kSampleNodes + p.nc0 - 1) / p.nc0 + kNNThreads - 1) / kNNThreads * kNNThreads;
+  p.nsamp64 = std::min<int64_t>(kSampleNodes, n / kNNThreads * kNNThreads);  // (a short range: all of it)
+  p.nch0 = (p.nsamp64 + p.ch0 - 1) / p.ch0;
+  const int qb32 = kNN32Queries * kNNThreads;
+  p.qt32 = (M + qb32 - 1) / qb32;
+  p.nc32 = std::max<int64_t>(1, (8192 + p.qt32 - 1) / p.qt32);
+  p.nc32 = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(p.nc32, (int64_t)p.maxchunks), n / (8 * kNNThreads)));
+  p.ch32 = (n + p.nc32 - 1) / p.nc32;
+  p.ch32 = (p.ch32 + kNNThreads - 1) / kNNThreads * kNNThreads;
+  p.nc32 = (n + p.ch32 - 1) / p.ch32;
+  p.path = NnPath::kScreen32;
+  // (the matrix-core kernel reads its node tiles through a buffer descriptor with 32-bit offsets: 2^26 nodes at most)
+  if (!(e->nn_mfma && nplan <= kNNMMaxPlan && n < ((int64_t)1 << 26))) return p;
+  p.Mpad = (M + kNNMQueries - 1) / kNNMQueries * kNNMQueries;
+  p.qblocks = p.Mpad / kNNMQueries;
+  int64_t sample, row;  // nodes of the strided sample asked for; the arena's node rows are whole multiples of `row`
+  if (e->nn_cells && n >= e->nn_cells_min && n >= 64 * kNNCellSub && n < ((int64_t)1 << 25)) {
+    p.path = NnPath::kCells;
+    sample = e->nn_cells_sample;
+    row = kNNCellSub;
+    p.npad = (n + row - 1) / row * row;
+    p.nsub = (int)(p.npad / kNNCellSub);
+    p.nwords = (p.nsub + 63) / 64;
+    p.nsubp = p.nwords * 64;
+    // (sub-chunks per workgroup row: whole mask words, ~2 048 workgroups in all, no more rows than words)
+    p.nsplit = std::max<int64_t>(1, std::min<int64_t>((4096 + p.qblocks - 1) / p.qblocks, p.nwords));
+  } else {
+    p.path = NnPath::kMfma;
+    sample = e->nn_sample;
+    row = 32;
+    p.npad = (n + row - 1) / row * row;
+    p.nsplit = std::max<int64_t>(1, std::min<int64_t>((2048 + p.qblocks - 1) / p.qblocks, n / 4096));
+    p.chm = ((n + p.nsplit - 1) / p.nsplit + 31) / 32 * 32;
+    p.nsplit = (n + p.chm - 1) / p.chm;
+  }
+  p.mparts = (int)(2 * p.nsplit);
+  // (trees grow call by call, and a reallocation stalls the stream: room for four times the nodes, within the slab)
+  // (a planner says how far its trees may grow: nn_reserve_nodes -- no reallocation in the middle of a search)
+  p.nres = std::min<int64_t>((cap + row - 1) / row * row, std::max<int64_t>(4 * p.npad, e->nn_reserve_nodes));
+  if (p.path == NnPath::kCells) p.nres = std::max<int64_t>(p.npad, p.nres);
+  // every query's bound: the sample node the screen likes best, its distance exactly
+  p.msample = std::max<int64_t>(32, std::min<int64_t>(sample, n / 16 / 32 * 32));
+  p.mstride = std::max<int64_t>(1, n / p.msample);
+  // (the sample in as many chunks as give the chip ~1 024 workgroups: a look-up of few queries -- the planner's tail lanes --
+  //  would otherwise scan it with eight)
+  p.ssplit = std::max<int64_t>(1, std::min<int64_t>((1024 + p.qblocks - 1) / p.qblocks, p.msample / 256));
+  p.schunk = ((p.msample + p.ssplit - 1) / p.ssplit + 31) / 32 * 32;
+  for (p.sshift = 0; (p.msample >> p.sshift) > 65536; p.sshift++) {}
+  return p;
+}
+
+// the look-up as the caller gave it: nodes [0, n) of the slab at `nodes` (column stride `cap`); outer_d2 (or NULL): a distance
+// every query already has an answer at -- nothing farther is of interest; st: the stream it is enqueued on
+struct NnBatch {
+  const double *nodes;
+  int64_t n, cap;
+  const double *queries;
+  int64_t M;
+  int32_t *out_idx;
+  double *out_d2;
+  const double *outer_d2;
+  hipStream_t st;
+};
+
+// pick the <NP> instantiation of a look-up's kernel for the planning dimension, LO..HI
+template <int LO, int HI, class F>
+int dispatch_nplan(int nplan, F &&f) {
+  if constexpr (LO > HI) return fail(MJPL_E_ARG, "nearest: no kernel for %d planning columns", nplan);
+  else return nplan == LO ? f(std::integral_constant<int, LO>{}) : dispatch_nplan<LO + 1, HI>(nplan, f);
+}
+
+// An arena's spans, listed once: run without a base the listing gives the byte count, with it the pointers.
+struct Carver {
+  char *base;
+  size_t at = 0;
+  template <class T>
+  T *take(size_t count, size_t align = 256) {  // (the span's bytes rounded up to `align`)
+    T *span = base ? (T *)(base + at) : nullptr;
+    at += (count * sizeof(T) + align - 1) / align * align;
+    return span;
+  }
+};
+
+// the partial rows: maxchunks of them and the seed row, distances then indices
+struct NnParts {
+  double *pd2, *seed_d2;
+  int32_t *pidx, *seed_idx;
+};
+
+int reserve_parts(NnScratch &s, const NnPlan &p, int64_t M, NnParts *r) {
+  MJPL_TRY(s.parts.reserve((p.maxchunks + 1) * (size_t)M * (sizeof(double) + sizeof(int32_t))));
+  r->pd2 = (double *)s.parts.p;
+  r->seed_d2 = r->pd2 + p.maxchunks * (size_t)M;
+  r->pidx = (int32_t *)(r->seed_d2 + (size_t)M);
+  r->seed_idx = r->pidx + p.maxchunks * (size_t)M;
+  return MJPL_OK;
+}
+
+// what the screened scans work on.  Either arena starts with xbits: [0] largest coordinate, [1] wild, [2] largest node
+// norm, [3] option "nn_probe" = 2 counts the exact evaluations here (mjpl_nearest_last_screen and "nn_last_exact_pairs"
+// read them at offset 0)
+struct NnArena {
+  unsigned *xbits;
+  uint4 *q16, *nodes16;  // the operands: queries (in scan order, kCells) and nodes
+  float *qn;
+  double *mp_d2;         // the matrix cores' partial rows
+  int32_t *mp_idx;
+  // kCells
+  unsigned *mm;
+  NncPlan *plan;
+  uint4 *q16u;           // the queries in the callers' order, for the sample
+  float *qnu;
+  double *queries_s, *bound2_s, *nodes_s;
+  float *qf, *q32c, *nbox, *nodes32;
+  unsigned *kq_in, *kq_out, *kn_in, *kn_out;
+  int32_t *pq_in, *perm_q, *pn_in, *perm_n, *ccount, *clist;
+  unsigned long long *masks;
+  void *tmpq, *tmpn;
+  size_t sort_tmp_q, sort_tmp_n;  // (rocprim's, set before the arena is carved)
+};
+
+// kMfma, `nodes` node rows (the node rows last: they are what grows).  (The byte count is the spans' own: a few dozen bytes
+// below what was reserved before this listing existed, which added 32 spare bytes to the unrounded sum.)
+void carve_mfma(Carver &c, const NnPlan &p, int64_t M, int64_t nodes, NnArena *a) {
+  a->xbits = c.take<unsigned>(64);
+  a->q16 = c.take<uint4>((size_t)p.Mpad * 4);
+  a->mp_d2 = c.take<double>((size_t)p.mparts * M, 8);
+  a->qn = c.take<float>((size_t)p.Mpad);
+  a->mp_idx = c.take<int32_t>((size_t)p.mparts * M, 32);
+  a->nodes16 = c.take<uint4>((size_t)nodes * 2, 32);
+}
+
+// kCells, `nodes` node rows (whole sub-chunks): what grows with the tree last -- masks, lists, boxes, keys + permutation
+// (in / out), sort space, sorted rows, packed rows
+void carve_cells(Carver &c, const NnPlan &p, int64_t M, int64_t nodes, NnArena *a) {
+  const size_t waves = (size_t)(p.Mpad / 128), np = (size_t)nodes, words = (size_t)((nodes / kNNCellSub + 63) / 64);
+  a->xbits = c.take<unsigned>(64);
+  a->mm = c.take<unsigned>(64);
+  a->plan = c.take<NncPlan>(1, 512);
+  a->q16u = c.take<uint4>((size_t)p.Mpad * 4);
+  a->q16 = c.take<uint4>((size_t)p.Mpad * 4);
+  a->qnu = c.take<float>((size_t)p.Mpad);
+  a->qn = c.take<float>((size_t)p.Mpad);
+  a->queries_s = c.take<double>((size_t)8 * M);
+  a->bound2_s = c.take<double>((size_t)M);
+  a->qf = c.take<float>((size_t)p.Mpad * 8);
+  a->q32c = c.take<float>((size_t)p.Mpad * 8);
+  a->kq_in = c.take<unsigned>((size_t)M);
+  a->kq_out = c.take<unsigned>((size_t)M);
+  a->pq_in = c.take<int32_t>((size_t)M);
+  a->perm_q = c.take<int32_t>((size_t)M);
+  a->mp_d2 = c.take<double>((size_t)p.mparts * M);
+  a->mp_idx = c.take<int32_t>((size_t)p.mparts * M);
+  a->tmpq = c.take<char>(a->sort_tmp_q);
+  a->ccount = c.take<int32_t>(waves);
+  a->masks = c.take<unsigned long long>(waves * words);
+  a->clist = c.take<int32_t>(waves * words * 64);
+  a->nbox = c.take<float>(16 * words * 64);
+  a->kn_in = c.take<unsigned>(np);
+  a->kn_out = c.take<unsigned>(np);
+  a->pn_in = c.take<int32_t>(np);
+  a->perm_n = c.take<int32_t>(np);
+  a->tmpn = c.take<char>(a->sort_tmp_n);
+  a->nodes_s = c.take<double>(8 * np);
+  a->nodes16 = c.take<uint4>(np * 2);
+  a->nodes32 = c.take<float>(np * 8);
+}
+
+// The arena of a screened look-up.  When it must grow it is sized for p.nres node rows: a search that has declared its
+// capacity never reallocates in the middle.
+int reserve_arena(NnScratch &s, const NnPlan &p, const NnBatch &b, NnArena *a) {
+  const bool cells = p.path == NnPath::kCells;
+  if (cells) {
+    // (rocprim picks its algorithm by the item count: the node sort's space for the count it is sized for AND the one it sorts.
+    //  Were its size not monotonic in the count, a later n could ask for more than the arena reserved at nres holds and grow it
+    //  in the middle of a search: slower once, never wrong -- the arena is carved anew by every call)
+    size_t at_n = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, a->sort_tmp_n, (const unsigned *)nullptr, (unsigned *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)p.nres, 0, kNNCKeyBits, b.st);
+    (void)rocprim::radix_sort_pairs(nullptr, at_n, (const unsigned *)nullptr, (unsigned *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)b.n, 0, kNNCKeyBits, b.st);
+    a->sort_tmp_n = std::max(a->sort_tmp_n, at_n);
+    (void)rocprim::radix_sort_pairs(nullptr, a->sort_tmp_q, (const unsigned *)nullptr, (unsigned *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)b.M, 0, 16, b.st);
+  }
+  auto carve = [&](char *base, int64_t nodes) {
+    Carver c{base};
+    if (cells) carve_cells(c, p, b.M, nodes, a);
+    else carve_mfma(c, p, b.M, nodes, a);
+    return c.at;
+  };
+  if (carve(nullptr, p.npad) > s.arena.cap) MJPL_TRY(s.arena.reserve(carve(nullptr, p.nres)));
+  (void)carve(s.arena.p, p.npad);
+  return MJPL_OK;
+}
+
+// ---- the stages.  Each takes the plan, the scratch it works in (partial rows, arena) and the batch.
+
+// the float64 scan of nodes [0, nn) in chunks of `ch` (stride > 1: a sample; only_if_wild: an arena's xbits, or NULL)
+int stage_scan64(const NnPlan &p, const NnParts &r, const NnBatch &b, int64_t nn, int64_t ch, int64_t nch, int64_t stride,
+                 const unsigned *only_if_wild) {
+  const dim3 grid((unsigned)p.qtiles, (unsigned)nch);
+  auto go = [&](auto NP) -> int {
+    return launch_kernel(b.st, k_nearest_part<NP()>, grid, kNNThreads, 0, b.nodes, nn, b.cap, b.queries, b.M, p.nplan, ch, r.pidx, r.pd2, stride,
+                         only_if_wild);
+  };
+  if (p.nplan < 2 || p.nplan > 9) return go(std::integral_constant<int, 0>{});  // (any number of columns up to 16)
+  return dispatch_nplan<2, 9>(p.nplan, go);
+}
+
+// the operands of the matrix cores: node and query rows in binary16 (kCells: the sorted rows of eight, about the centre)
+int stage_pack(const NnBatch &b, const double *src, int64_t count, int64_t col_stride, int64_t padded, int nplan, int is_query,
+               uint4 *out16, float *nrm, unsigned *xbits, int64_t row_stride, const float *centre) {
+  return launch_kernel(b.st, k_nn_pack, dim3((unsigned)((padded + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), 256, 0, src, count, col_stride,
+                       padded, nplan, is_query, out16, nrm, xbits, row_stride, centre);
+}
+
+// every query's bound (the seed row) from a strided sample of the nodes.  With an arena `a` (kMfma, kCells) the matrix
+// cores take it from the sample node the screen likes best -- sample_nodes with column stride sample_pitch, queries
+// q16 / qn --; wild coordinates: the float64 scan of the callers' sample; either pair of kernels leaves at once when
+// the other serves the call.  Without (kScreen32) the float64 scan is all.  Then never above the callers' own bound.
+int stage_bound(const NnPlan &p, const NnParts &r, const NnBatch &b, const NnArena *a, const double *sample_nodes, int64_t sample_pitch,
+                const uint4 *q16, const float *qn) {
+  const unsigned *xbits = a ? a->xbits : nullptr;
+  const bool cells = p.path == NnPath::kCells;
+  if (a) {
+    NnCells sc{};
+    if (cells) {
+      sc.pack_idx = 1;
+      sc.node_rows = 1;  // (the sorted nodes: rows of eight; the queries still the callers' columns)
+      sc.idx_shift = p.sshift;
+    }
+    const dim3 gs((unsigned)p.qblocks, (unsigned)((p.msample + p.schunk - 1) / p.schunk));
+    MJPL_TRY(launch_kernel(b.st, k_nn_fill_inf, dim3(p.rgridM), kBlock, 0, r.seed_d2, b.M, xbits));
+    MJPL_TRY(dispatch_nplan<2, kNNMMaxPlan>(p.nplan, [&](auto NP) -> int {
+      return launch_kernel(b.st, k_nearest_mfma<NP(), true>, gs, kNNMWaves * 64, 0, sample_nodes, p.msample, sample_pitch, b.queries, b.M,
+                           (const uint4 *)a->nodes16, q16, qn, xbits, p.schunk, p.mstride, r.seed_d2, (int32_t *)nullptr, (double *)nullptr, sc);
+    }));
+  }
+  MJPL_TRY(stage_scan64(p, r, b, p.nsamp64, p.ch0, p.nch0, p.stride, xbits));
+  MJPL_TRY(launch_kernel(b.st, k_nearest_reduce, dim3(p.rgridM), kBlock, 0, (const int32_t *)r.pidx, (const double *)r.pd2, b.M, (int)p.nch0,
+                         r.seed_idx, r.seed_d2, (const int32_t *)nullptr, (const double *)nullptr, xbits));
+  if (!b.outer_d2) return MJPL_OK;
+  if (cells) return launch_kernel(b.st, k_nnc_bound_min, dim3(p.rgridM), kBlock, 0, r.seed_d2, b.outer_d2, b.M, xbits);
+  return launch_kernel(b.st, k_nearest_bound_min, dim3(p.rgridM), kBlock, 0, r.seed_d2, b.outer_d2, b.M);
+}
+
+// the binary32 screen over the callers' rows, within the bounds of the seed row (with an arena: wild coordinates only)
+int stage_screen32(const NnPlan &p, const NnParts &r, const NnBatch &b, const unsigned *only_if_wild) {
+  const dim3 grid((unsigned)p.qt32, (unsigned)p.nc32);
+  return dispatch_nplan<2, 9>(p.nplan, [&](auto NP) -> int {
+    return launch_kernel(b.st, k_nearest_part32<NP()>, grid, kNNThreads, 0, b.nodes, b.n, b.cap, b.queries, b.M, p.ch32, (const double *)r.seed_d2,
+                         r.pidx, r.pd2, only_if_wild);
+  });
+}
+
+// kCells 1: the nodes along the curve, their boxes, and the operands (the queries' in the callers' order, for the sample)
+int stage_cells_order(const NnPlan &p, const NnArena &a, const NnBatch &b) {
+  const int64_t n = b.n;
+  HIP_TRY(hipMemsetAsync(a.xbits, 0, 16, b.st));
+  HIP_TRY(hipMemsetAsync(a.mm, 0xff, 32, b.st));
+  HIP_TRY(hipMemsetAsync(a.mm + 8, 0, 32, b.st));
+  MJPL_TRY(launch_kernel(b.st, k_nnc_minmax, dim3((unsigned)((n + 256 * kNNCMinmaxRows - 1) / (256 * kNNCMinmaxRows))), 256, 0, b.nodes, n, b.cap,
+                         p.nplan, a.mm));
+  MJPL_TRY(launch_kernel(b.st, k_nnc_plan, dim3(1), 64, 0, (const unsigned *)a.mm, p.nplan, a.plan));
+  MJPL_TRY(launch_kernel(b.st, k_nnc_keys, dim3((unsigned)((n + 255) / 256)), 256, 0, b.nodes, n, b.cap, p.nplan, (const NncPlan *)a.plan, a.kn_in,
+                         a.pn_in));
+  size_t tn = a.sort_tmp_n;
+  if (rocprim::radix_sort_pairs(a.tmpn, tn, (const unsigned *)a.kn_in, a.kn_out, (const int32_t *)a.pn_in, a.perm_n, (size_t)n, 0, kNNCKeyBits,
+                                b.st) != hipSuccess)
+    return fail(MJPL_E_HIP, "nearest: sorting the nodes failed");
+  MJPL_TRY(launch_kernel(b.st, k_nnc_gather, dim3((unsigned)((p.npad + 255) / 256)), 256, 0, b.nodes, b.cap, (const int32_t *)a.perm_n, n, p.npad,
+                         p.nplan, a.nodes_s, a.nodes32, (const NncPlan *)a.plan));
+  MJPL_TRY(launch_kernel(b.st, k_nnc_boxes, dim3((unsigned)((p.nsub + 3) / 4)), 256, 0, (const double *)a.nodes_s, n, p.nplan, p.nsub, p.nsubp,
+                         a.nbox));
+  MJPL_TRY(stage_pack(b, a.nodes_s, n, 1, p.npad, p.nplan, 0, a.nodes16, nullptr, a.xbits, 8, a.plan->ctr));
+  return stage_pack(b, b.queries, b.M, b.M, p.Mpad, p.nplan, 1, a.q16u, a.qnu, a.xbits, 1, a.plan->ctr);
+}
+
+// kCells 3, 4: the queries in scan order (by where on the curve the bound was found), every wave's candidate sub-chunks,
+// the scan of those
+int stage_cells_scan(mjpl_engine *e, const NnPlan &p, const NnParts &r, const NnArena &a, const NnBatch &b) {
+  const int64_t M = b.M;
+  MJPL_TRY(launch_kernel(b.st, k_nnc_query_keys, dim3(p.rgridM), kBlock, 0, (const double *)r.seed_d2, M, a.kq_in, a.pq_in));
+  size_t tq = a.sort_tmp_q;
+  if (rocprim::radix_sort_pairs(a.tmpq, tq, (const unsigned *)a.kq_in, a.kq_out, (const int32_t *)a.pq_in, a.perm_q, (size_t)M, 0, 16, b.st) !=
+      hipSuccess)
+    return fail(MJPL_E_HIP, "nearest: sorting the queries failed");
+  MJPL_TRY(launch_kernel(b.st, k_nnc_gather_queries, dim3((unsigned)((p.Mpad + kBlock - 1) / kBlock)), kBlock, 0, b.queries, (const double *)r.seed_d2,
+                         (const int32_t *)a.perm_q, M, p.Mpad, p.nplan, a.queries_s, a.bound2_s, a.qf, a.q32c, (const NncPlan *)a.plan));
+  MJPL_TRY(stage_pack(b, a.queries_s, M, 1, p.Mpad, p.nplan, 1, a.q16, a.qn, a.xbits, 8, a.plan->ctr));
+  if (e->nn_home)
+    MJPL_TRY(launch_kernel(b.st, k_nnc_home, dim3((unsigned)((M + 255) / 256)), 256, 0, (const double *)a.nodes_s, b.n, (const double *)a.queries_s, M,
+                           p.nplan, p.mstride, p.sshift, p.nsub, a.bound2_s, a.qf, (const unsigned *)a.xbits));
+  const unsigned waves = (unsigned)(p.Mpad / 128);
+  MJPL_TRY(launch_kernel(b.st, k_nn_candidates, dim3(waves, (unsigned)((p.nwords + 3) / 4)), 256, 0, (const float *)a.qf, M, (const float *)a.nbox,
+                         p.nsub, p.nsubp, p.nwords, a.masks, (const unsigned *)a.xbits));
+  MJPL_TRY(launch_kernel(b.st, k_nn_compact, dim3((waves + 3) / 4), 256, 0, (const unsigned long long *)a.masks, p.nwords, (int)waves, a.clist,
+                         (int64_t)p.nsubp, a.ccount, (const unsigned *)a.xbits));
+  NnCells cs{};
+  cs.list = a.clist; cs.count = a.ccount; cs.perm_n = a.perm_n; cs.list_pitch = p.nsubp; cs.probe = e->nn_probe; cs.counter = a.xbits + 3;
+  cs.node_rows = 1; cs.query_rows = 1; cs.nodes32 = a.nodes32; cs.queries32 = a.q32c; cs.second = e->nn_second_screen;
+  const dim3 gm(waves, (unsigned)p.nsplit);  // (one wave of 128 queries per workgroup)
+  kt_mark(e, 2, b.st);
+  MJPL_TRY(dispatch_nplan<2, kNNMMaxPlan>(p.nplan, [&](auto NP) -> int {
+    return launch_kernel(b.st, k_nearest_mfma<NP(), false, true>, gm, 64, 0, (const double *)a.nodes_s, b.n, p.npad, (const double *)a.queries_s, M,
+                         (const uint4 *)a.nodes16, (const uint4 *)a.q16, (const float *)a.qn, (const unsigned *)a.xbits, (int64_t)0, (int64_t)1,
+                         a.bound2_s, a.mp_idx, a.mp_d2, cs);
+  }));
+  kt_mark(e, 2, b.st);
+  return MJPL_OK;
+}
+
+// kMfma: the operands, then (behind the bounds) the scan of all nodes in chunks of chm
+int stage_mfma_pack(const NnPlan &p, const NnArena &a, const NnBatch &b) {
+  HIP_TRY(hipMemsetAsync(a.xbits, 0, 12, b.st));
+  MJPL_TRY(stage_pack(b, b.nodes, b.n, b.cap, p.npad, p.nplan, 0, a.nodes16, nullptr, a.xbits, 1, nullptr));
+  return stage_pack(b, b.queries, b.M, b.M, p.Mpad, p.nplan, 1, a.q16, a.qn, a.xbits, 1, nullptr);
+}
+
+int stage_mfma_scan(const NnPlan &p, const NnParts &r, const NnArena &a, const NnBatch &b) {
+  const dim3 gm((unsigned)p.qblocks, (unsigned)p.nsplit);
+  return dispatch_nplan<2, kNNMMaxPlan>(p.nplan, [&](auto NP) -> int {
+    return launch_kernel(b.st, k_nearest_mfma<NP(), false>, gm, kNNMWaves * 64, 0, b.nodes, b.n, b.cap, b.queries, b.M, (const uint4 *)a.nodes16,
+                         (const uint4 *)a.q16, (const float *)a.qn, (const unsigned *)a.xbits, p.chm, (int64_t)1, r.seed_d2, a.mp_idx, a.mp_d2,
+                         NnCells{});
+  });
+}
+
+// One look-up on scratch `s`, enqueued on b.st.  The launches per path (plan_nearest), in order; (w): returns at once
+// unless some coordinate was wild, (m): unless none was:
+//   kLds       k_nearest
+//   kPlain     part                                                                                       reduce
+//   kScreen32  bound [part of the sample, reduce, bound_min]                                      part32  reduce
+//   kMfma      pack x2  bound [fill_inf, mfma<sample> (m), part (w), reduce (w), bound_min]  mfma (m)  part32 (w)  reduce_ties
+//   kCells     minmax, plan, keys, sort, gather, boxes, pack x2  bound [as kMfma, nnc_bound_min]  query_keys, sort,
+//              gather_queries, pack, (home), candidates, compact, | mfma<cells> (m) |  part32 (w)  nnc_reduce
+// (|: the kernel_timer's class 2 brackets the cell-ordered scan.)  What s.last says is set before anything is enqueued.
+int nearest_core(mjpl_engine *e, NnScratch &s, const NnBatch &b) {
+  HIP_TRY(hipSetDevice(e->device));
+  s.last = {};
+  const NnPlan p = plan_nearest(e, b.n, b.cap, b.M, b.outer_d2 != nullptr);
+  if (p.path == NnPath::kLds) {
+    MJPL_TRY(launch_kernel(b.st, k_nearest, dim3(p.rgridM), kBlock, 2 * (size_t)p.nplan * kBlock * sizeof(double), b.nodes, b.n, b.cap, b.queries, b.M,
+                           p.nplan, b.out_idx, b.out_d2));
+    HIP_TRY(hipGetLastError());
+    return MJPL_OK;
+  }
+  NnParts r;
+  MJPL_TRY(reserve_parts(s, p, b.M, &r));
+  const int32_t *parts_idx = r.pidx;
+  const double *parts_d2 = r.pd2;
+  if (p.path == NnPath::kPlain) {
+    MJPL_TRY(stage_scan64(p, r, b, b.n, p.chunk, p.nchunks, 1, nullptr));
+    MJPL_TRY(launch_kernel(b.st, k_nearest_reduce, dim3(p.rgridM), kBlock, 0, parts_idx, parts_d2, b.M, (int)p.nchunks, b.out_idx, b.out_d2,
+                           (const int32_t *)nullptr, (const double *)nullptr, (const unsigned *)nullptr));
+  } else if (p.path == NnPath::kScreen32) {
+    s.last.path = 1;
+    MJPL_TRY(stage_bound(p, r, b, nullptr, nullptr, 0, nullptr, nullptr));
+    MJPL_TRY(stage_screen32(p, r, b, nullptr));
+    MJPL_TRY(launch_kernel(b.st, k_nearest_reduce, dim3(p.rgridM), kBlock, 0, parts_idx, parts_d2, b.M, (int)p.nc32, b.out_idx, b.out_d2,
+                           (const int32_t *)nullptr, (const double *)nullptr, (const unsigned *)nullptr));
+  } else {
+    s.last.path = 2;
+    s.last.cells = p.path == NnPath::kCells;
+    NnArena a = {};
+    MJPL_TRY(reserve_arena(s, p, b, &a));
+    if (s.last.cells) {
+      s.last.count_at = (size_t)((char *)a.ccount - s.arena.p);
+      s.last.waves = (int)((b.M + 127) / 128);
+      s.last.nsub = p.nsub;
+      MJPL_TRY(stage_cells_order(p, a, b));
+      MJPL_TRY(stage_bound(p, r, b, &a, a.nodes_s, p.npad, a.q16u, a.qnu));
+      MJPL_TRY(stage_cells_scan(e, p, r, a, b));
+      MJPL_TRY(stage_screen32(p, r, b, a.xbits));
+      // the answers in the callers' order
+      MJPL_TRY(launch_kernel(b.st, k_nnc_reduce, dim3(p.rgridM), kBlock, 0, (const int32_t *)a.mp_idx, (const double *)a.mp_d2, b.M, p.mparts,
+                             (const int32_t *)a.perm_q, b.out_idx, b.out_d2, (const unsigned *)a.xbits, parts_idx, parts_d2, (int)p.nc32));
+    } else {
+      MJPL_TRY(stage_mfma_pack(p, a, b));
+      MJPL_TRY(stage_bound(p, r, b, &a, b.nodes, b.cap, a.q16, a.qn));
+      MJPL_TRY(stage_mfma_scan(p, r, a, b));
+      MJPL_TRY(stage_screen32(p, r, b, a.xbits));
+      MJPL_TRY(launch_kernel(b.st, k_nearest_reduce_ties, dim3(p.rgridM), kBlock, 0, (const int32_t *)a.mp_idx, (const double *)a.mp_d2, b.M, p.mparts,
+                             b.out_idx, b.out_d2, (const unsigned *)a.xbits, parts_idx, parts_d2, (int)p.nc32));
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+// the look-up over the node range [n0, n) behind an answer (outer_idx, outer_d2: NULL = none) for the nodes below n0
+int nearest_range(mjpl_engine *e, NnScratch &s, hipStream_t st, const double *dnodes, int64_t n0, int64_t n, int64_t cap, const double *dqueries,
+                  int64_t M, int32_t *dout_idx, double *dout_dist2, const int32_t *outer_idx, const double *outer_d2) {
+  if (n0 == 0 && !outer_idx) return nearest_core(e, s, {dnodes, n, cap, dqueries, M, dout_idx, dout_dist2, nullptr, st});
   if (n0 < 0 || n0 > n || (outer_idx && !outer_d2)) return fail(MJPL_E_ARG, "nearest_range: bad range");
   HIP_TRY(hipSetDevice(e->device));
+  s.last = {};
   double *d2 = dout_dist2;
   if (!d2) {
-    if ((size_t)M * sizeof(double) > e->nn_tmp_bytes) {
-      if (e->d_nn_tmp) HIP_TRY(hipFree(e->d_nn_tmp));
-      e->d_nn_tmp = nullptr; e->nn_tmp_bytes = 0;
-      HIP_TRY(hipMalloc(&e->d_nn_tmp, (size_t)M * sizeof(double)));
-      e->nn_tmp_bytes = (size_t)M * sizeof(double);
-    }
-    d2 = (double *)e->d_nn_tmp;
+    MJPL_TRY(s.spare.reserve((size_t)M));
+    d2 = s.spare.p;
   }
-  if (n > n0) {
-    const int rc = nearest_core(e, dnodes + n0, n - n0, cap, dqueries, M, dout_idx, d2, outer_idx ? outer_d2 : nullptr);
-    if (rc != MJPL_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_nearest_rebase, dim3((unsigned)((M + kBlock - 1) / kBlock)), dim3(kBlock), 0, e->stream, M, n0, n > n0 ? 1 : 0, dout_idx,
-                     d2, dout_dist2, outer_idx, outer_d2);
+  if (n > n0) MJPL_TRY(nearest_core(e, s, {dnodes + n0, n - n0, cap, dqueries, M, dout_idx, d2, outer_idx ? outer_d2 : nullptr, st}));
+  MJPL_TRY(launch_kernel(st, k_nearest_rebase, dim3((unsigned)((M + kBlock - 1) / kBlock)), kBlock, 0, M, n0, n > n0 ? 1 : 0, dout_idx, d2, dout_dist2,
+                         outer_idx, outer_d2));
   HIP_TRY(hipGetLastError());
   return MJPL_OK;
 }
@@ -2124,7 +2584,7 @@ int mjpl_nearest_dev(mjpl_engine *e, const double *dnodes, int64_t n, int64_t ca
   if (!e || n < 0 || M < 0 || cap < n) return fail(MJPL_E_ARG, "mjpl_nearest_dev: bad sizes");
   if (M == 0) return MJPL_OK;
   if (!dnodes || !dqueries || !dout_idx) return fail(MJPL_E_ARG, "mjpl_nearest_dev: NULL pointer");
-  return nearest_core(e, dnodes, n, cap, dqueries, M, dout_idx, dout_dist2, nullptr);
+  return nearest_core(e, e->nn, {dnodes, n, cap, dqueries, M, dout_idx, dout_dist2, nullptr, e->stream});
 }
 
 int mjpl_nearest_range_dev(mjpl_engine *e, const double *dnodes, int64_t n0, int64_t n, int64_t cap, const double *dqueries,
@@ -2133,388 +2593,8 @@ int mjpl_nearest_range_dev(mjpl_engine *e, const double *dnodes, int64_t n0, int
   if (M == 0) return MJPL_OK;
   if (!dnodes || !dqueries || !dout_idx || ((dprev_idx == nullptr) != (dprev_dist2 == nullptr)))
     return fail(MJPL_E_ARG, "mjpl_nearest_range_dev: NULL pointer");
-  return nearest_range(e, dnodes, n0, n, cap, dqueries, M, dout_idx, dout_dist2, dprev_idx, dprev_dist2);
+  return nearest_range(e, e->nn, e->stream, dnodes, n0, n, cap, dqueries, M, dout_idx, dout_dist2, dprev_idx, dprev_dist2);
 }
-
-}  // extern "C"
-
-static int nearest_core(mjpl_engine *e, const double *dnodes, int64_t n, int64_t cap, const double *dqueries, int64_t M,
-                        int32_t *dout_idx, double *dout_dist2, const double *outer_d2) {
-  HIP_TRY(hipSetDevice(e->device));
-  const int nplan = (int)e->qidx.size();
-  if (nplan <= kNNMaxPlan && n > 0) {
-    // 2-D decomposition: 512 queries per block x node chunks, then a reduction over the chunks;
-    // chunks sized for about eight two-wave blocks per SIMD quartet (the scan is one dependent
-    // chain per query: waves, not instructions, hide its latencies)
-    const int qblock = kNNQueries * kNNThreads;
-    const int64_t qtiles = (M + qblock - 1) / qblock;
-    int64_t nchunks = std::max<int64_t>(1, (8192 + qtiles - 1) / qtiles);
-    nchunks = std::min<int64_t>(nchunks, (n + kNNThreads - 1) / kNNThreads);
-    nchunks = std::max<int64_t>(nchunks, 1);
-    int64_t chunk = (n + nchunks - 1) / nchunks;
-    chunk = (chunk + kNNThreads - 1) / kNNThreads * kNNThreads;
-    nchunks = (n + chunk - 1) / chunk;
-    // partial results: room for twice the chunks of the float64 scan (the screened scan below
-    // cuts the nodes up to twice as fine), and one seed row
-    const size_t maxchunks = 2 * (size_t)nchunks + 1;
-    const size_t need = (maxchunks + 1) * (size_t)M * (sizeof(double) + sizeof(int32_t));
-    if (need > e->nn_bytes) {
-      if (e->d_nn) HIP_TRY(hipFree(e->d_nn));
-      e->d_nn = nullptr; e->nn_bytes = 0;
-      HIP_TRY(hipMalloc(&e->d_nn, need));
-      e->nn_bytes = need;
-    }
-    double *pd2 = (double *)e->d_nn;
-    double *seed_d2 = pd2 + maxchunks * (size_t)M;
-    int32_t *pidx = (int32_t *)(seed_d2 + (size_t)M);
-    int32_t *seed_idx = pidx + maxchunks * (size_t)M;
-    // the float64 scan of nodes [0, nn) in chunks of `ch`
-    auto scan64 = [&](int64_t nn, int64_t ch, int64_t nch, int64_t stride = 1) {
-      const dim3 grid((unsigned)qtiles, (unsigned)nch);
-#define MJPL_NN_CASE(NPV)                                                                                    \
-      case NPV:                                                                                              \
-        hipLaunchKernelGGL(k_nearest_part<NPV>, grid, dim3(kNNThreads), 0, e->stream, dnodes, nn, cap, dqueries, \
-                           M, nplan, ch, pidx, pd2, stride);                                                 \
-        break;
-      switch (nplan) {
-        MJPL_NN_CASE(2) MJPL_NN_CASE(3) MJPL_NN_CASE(4) MJPL_NN_CASE(5) MJPL_NN_CASE(6) MJPL_NN_CASE(7)
-        MJPL_NN_CASE(8) MJPL_NN_CASE(9)
-        default:
-          hipLaunchKernelGGL(k_nearest_part<0>, grid, dim3(kNNThreads), 0, e->stream, dnodes, nn, cap, dqueries, M,
-                             nplan, ch, pidx, pd2, stride);
-      }
-#undef MJPL_NN_CASE
-    };
-    const unsigned rgridM = (unsigned)((M + kBlock - 1) / kBlock);
-    constexpr int64_t kSampleNodes = 16384;
-    // (4 096 queries: the planner's look-up of its tail lanes.  A ranged look-up brings a bound for every query with it -- the
-    //  distance already found below the range: screened from 8 192 nodes on.  It still takes the sample of its range: the
-    //  nodes a round adds reach into places the tree was far from, and a query there would otherwise park every one of them)
-    const bool have_bound = outer_d2 != nullptr;
-    if (M >= 4096 && (n >= 16 * kSampleNodes || (have_bound && n >= 8192)) && nplan >= 2 && nplan <= 9) {
-      // Large trees and query sets.  First a strided sample of the nodes, exactly: every query gets a
-      // bound close to its answer.  Then the binary32-screened scan of all nodes, eight queries per
-      // lane, which evaluates exactly only what lies within that bound.
-      const int64_t stride = std::max<int64_t>(1, n / kSampleNodes);
-      // (chunks of the float64 sample scan: whole multiples of the scan's tile, and never more of them than partial rows --
-      //  16 384 / nc0 rounded DOWN gave one chunk too many for some node counts, whose row was the seed row: ADVICE r05)
-      const int64_t nc0 = std::min<int64_t>(maxchunks, kSampleNodes / kNNThreads);
-      const int64_t ch0 = ((kSampleNodes + nc0 - 1) / nc0 + kNNThreads - 1) / kNNThreads * kNNThreads;
-      // the screened scan on the matrix cores (nplan <= 7), unless some coordinate is too large for binary16 -- which the
-      // device finds out while it packs the operands: then those kernels return at once and the float64 sample scan and
-      // the binary32 screen run (which in turn return at once when the matrix cores serve the call)
-      // (the matrix-core kernel reads its node tiles through a buffer descriptor with 32-bit offsets: 2^26 nodes at most)
-      const bool mfma = e->nn_mfma && nplan <= kNNMMaxPlan && n < ((int64_t)1 << 26);
-      e->nn_last = mfma ? 2 : 1;
-      unsigned *xbits = nullptr;
-      int32_t *mp_idx = nullptr;
-      double *mp_d2 = nullptr;
-      int mparts = 0;
-      const int64_t nsamp64 = std::min<int64_t>(kSampleNodes, n / kNNThreads * kNNThreads);  // (a short range: all of it)
-      e->nn_last_cells = 0;
-      if (mfma && e->nn_cells && n >= e->nn_cells_min && n >= 64 * kNNCellSub && n < ((int64_t)1 << 25)) {
-        // ---- the cell-ordered scan (mjpl_nearest_cells.h): nodes sorted along a space-filling curve, queries by where on it
-        // their bound was found, a wave scans the sub-chunks some query of it can have its answer in
-        e->nn_last_cells = 1;
-        const int64_t npad = (n + kNNCellSub - 1) / kNNCellSub * kNNCellSub, Mpad = (M + kNNMQueries - 1) / kNNMQueries * kNNMQueries;
-        const int64_t qblocks = Mpad / kNNMQueries;
-        const int nsub = (int)(npad / kNNCellSub), nwords = (nsub + 63) / 64, nsubp = nwords * 64;
-        // (sub-chunks per workgroup row: whole mask words, ~2 048 workgroups in all, no more rows than words)
-        const int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>((4096 + qblocks - 1) / qblocks, nwords));
-        mparts = 2 * nsplit;
-        // the arena: what grows with the tree last
-        auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-        size_t sort_tmp_n = 0, sort_tmp_q = 0;
-        const int64_t nres = std::max<int64_t>(npad, std::min<int64_t>((cap + kNNCellSub - 1) / kNNCellSub * kNNCellSub,
-                                                                       std::max<int64_t>(4 * npad, e->nn_reserve_nodes)));
-        (void)rocprim::radix_sort_pairs(nullptr, sort_tmp_n, (const unsigned *)nullptr, (unsigned *)nullptr, (const int32_t *)nullptr,
-                                        (int32_t *)nullptr, (size_t)nres, 0, kNNCKeyBits, e->stream);
-        (void)rocprim::radix_sort_pairs(nullptr, sort_tmp_q, (const unsigned *)nullptr, (unsigned *)nullptr, (const int32_t *)nullptr,
-                                        (int32_t *)nullptr, (size_t)M, 0, 16, e->stream);
-        const size_t b_q16 = al((size_t)Mpad * 64), b_qn = al((size_t)Mpad * 4), b_qs = al((size_t)8 * M * 8), b_b2 = al((size_t)M * 8);
-        const size_t b_qf = al((size_t)Mpad * 32), b_k = al((size_t)M * 4), b_pd = al((size_t)mparts * M * 8), b_pi = al((size_t)mparts * M * 4);
-        const size_t b_masks = al((size_t)(Mpad / 128) * nwords * 8), b_tmpq = al(sort_tmp_q);
-        const size_t b_cnt = al((size_t)(Mpad / 128) * 4);
-        const size_t fixed = 1024 + 2 * b_q16 + 2 * b_qn + b_qs + b_b2 + 2 * b_qf + 4 * b_k + b_pd + b_pi + b_tmpq + b_cnt;
-        auto grows = [&](int64_t np) {  // masks, lists, boxes, keys + permutation (in / out), sort space, sorted rows, packed rows
-          const size_t words = (size_t)((np / kNNCellSub + 63) / 64);
-          return al((size_t)(Mpad / 128) * words * 8) + al((size_t)(Mpad / 128) * words * 64 * 4) + al(16 * words * 64 * 4) +
-                 4 * al((size_t)np * 4) + al(sort_tmp_n) + al((size_t)8 * np * 8) + 2 * al((size_t)np * 32);
-        };
-        if (fixed + grows(npad) > e->nn16_bytes) {
-          const size_t room = fixed + grows(nres);
-          if (e->d_nn16) HIP_TRY(hipFree(e->d_nn16));
-          e->d_nn16 = nullptr; e->nn16_bytes = 0;
-          HIP_TRY(hipMalloc(&e->d_nn16, room));
-          e->nn16_bytes = room;
-        }
-        char *at = (char *)e->d_nn16;
-        auto take = [&](size_t b) { char *p = at; at += b; return p; };
-        xbits = (unsigned *)take(256);
-        unsigned *mm = (unsigned *)take(256);
-        NncPlan *plan = (NncPlan *)take(512);
-        uint4 *q16u = (uint4 *)take(b_q16), *q16 = (uint4 *)take(b_q16);
-        float *qnu = (float *)take(b_qn), *qn = (float *)take(b_qn);
-        double *queries_s = (double *)take(b_qs), *bound2_s = (double *)take(b_b2);
-        float *qf = (float *)take(b_qf), *q32c = (float *)take(b_qf);
-        unsigned *kq_in = (unsigned *)take(b_k), *kq_out = (unsigned *)take(b_k);
-        int32_t *pq_in = (int32_t *)take(b_k), *perm_q = (int32_t *)take(b_k);
-        mp_d2 = (double *)take(b_pd);
-        mp_idx = (int32_t *)take(b_pi);
-        void *tmpq = take(b_tmpq);
-        int32_t *ccount = (int32_t *)take(b_cnt);
-        unsigned long long *masks = (unsigned long long *)take(b_masks);
-        int32_t *clist = (int32_t *)take(al((size_t)(Mpad / 128) * nsubp * 4));
-        float *nbox = (float *)take(al((size_t)16 * nsubp * 4));
-        unsigned *kn_in = (unsigned *)take(al((size_t)npad * 4)), *kn_out = (unsigned *)take(al((size_t)npad * 4));
-        int32_t *pn_in = (int32_t *)take(al((size_t)npad * 4)), *perm_n = (int32_t *)take(al((size_t)npad * 4));
-        void *tmpn = take(al(sort_tmp_n));
-        double *nodes_s = (double *)take(al((size_t)8 * npad * 8));
-        uint4 *nodes16 = (uint4 *)take(al((size_t)npad * 32));
-        float *nodes32 = (float *)take(al((size_t)npad * 32));
-        // 1. the nodes along the curve
-        HIP_TRY(hipMemsetAsync(xbits, 0, 16, e->stream));  // ([3]: option "nn_probe" = 2 counts the exact evaluations here)
-        HIP_TRY(hipMemsetAsync(mm, 0xff, 32, e->stream));
-        HIP_TRY(hipMemsetAsync(mm + 8, 0, 32, e->stream));
-        hipLaunchKernelGGL(k_nnc_minmax, dim3((unsigned)((n + 256 * kNNCMinmaxRows - 1) / (256 * kNNCMinmaxRows))), dim3(256), 0, e->stream, dnodes, n, cap, nplan, mm);
-        hipLaunchKernelGGL(k_nnc_plan, dim3(1), dim3(64), 0, e->stream, (const unsigned *)mm, nplan, plan);
-        hipLaunchKernelGGL(k_nnc_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, dnodes, n, cap, nplan, (const NncPlan *)plan,
-                           kn_in, pn_in);
-        size_t tn = sort_tmp_n;
-        if (rocprim::radix_sort_pairs(tmpn, tn, (const unsigned *)kn_in, kn_out, (const int32_t *)pn_in, perm_n, (size_t)n, 0, kNNCKeyBits,
-                                      e->stream) != hipSuccess)
-          return fail(MJPL_E_HIP, "nearest: sorting the nodes failed");
-        hipLaunchKernelGGL(k_nnc_gather, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, e->stream, dnodes, cap, (const int32_t *)perm_n, n,
-                           npad, nplan, nodes_s, nodes32, (const NncPlan *)plan);
-        hipLaunchKernelGGL(k_nnc_boxes, dim3((unsigned)((nsub + 3) / 4)), dim3(256), 0, e->stream, (const double *)nodes_s, n, nplan, nsub,
-                           nsubp, nbox);
-        hipLaunchKernelGGL(k_nn_pack, dim3((unsigned)((npad + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), dim3(256), 0, e->stream, (const double *)nodes_s, n, (int64_t)1, npad, nplan,
-                           0, nodes16, (float *)nullptr, xbits, (int64_t)8, (const float *)plan->ctr);
-        hipLaunchKernelGGL(k_nn_pack, dim3((unsigned)((Mpad + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), dim3(256), 0, e->stream, dqueries, M, M, Mpad, nplan, 1, q16u, qnu,
-                           xbits, (int64_t)1, (const float *)plan->ctr);
-        // 2. every query's bound, and where on the curve it was found (wild coordinates: the float64 scan of a sample of the
-        //    callers' rows, as in the plain path; either pair of kernels leaves at once when the other serves the call)
-        const int64_t msample = std::max<int64_t>(32, std::min<int64_t>(e->nn_cells_sample, n / 16 / 32 * 32));
-        const int64_t mstride = std::max<int64_t>(1, n / msample);
-        const int64_t ssplit = std::max<int64_t>(1, std::min<int64_t>((1024 + qblocks - 1) / qblocks, msample / 256));
-        const int64_t schunk = ((msample + ssplit - 1) / ssplit + 31) / 32 * 32;
-        const dim3 gs((unsigned)qblocks, (unsigned)((msample + schunk - 1) / schunk));
-        NnCells sc{};
-        sc.pack_idx = 1;
-        sc.node_rows = 1;  // (the sorted nodes: rows of eight; the queries still the callers' columns)
-        for (sc.idx_shift = 0; (msample >> sc.idx_shift) > 65536; sc.idx_shift++) {}
-        hipLaunchKernelGGL(k_nn_fill_inf, dim3(rgridM), dim3(kBlock), 0, e->stream, seed_d2, M, (const unsigned *)xbits);
-#define MJPL_NNM_CASE(NPV)                                                                                                           \
-        case NPV:                                                                                                                    \
-          hipLaunchKernelGGL((k_nearest_mfma<NPV, true>), gs, dim3(kNNMWaves * 64), 0, e->stream, (const double *)nodes_s, msample, npad,  \
-                             dqueries, M, (const uint4 *)nodes16, (const uint4 *)q16u, (const float *)qnu, (const unsigned *)xbits,  \
-                             schunk, mstride, seed_d2, (int32_t *)nullptr, (double *)nullptr, sc);                                   \
-          break;
-        switch (nplan) {
-          MJPL_NNM_CASE(2) MJPL_NNM_CASE(3) MJPL_NNM_CASE(4) MJPL_NNM_CASE(5) MJPL_NNM_CASE(6) MJPL_NNM_CASE(7)
-        }
-#undef MJPL_NNM_CASE
-        {
-          const dim3 grid((unsigned)qtiles, (unsigned)((nsamp64 + ch0 - 1) / ch0));
-#define MJPL_NN_CASE(NPV)                                                                                    \
-          case NPV:                                                                                          \
-            hipLaunchKernelGGL(k_nearest_part<NPV>, grid, dim3(kNNThreads), 0, e->stream, dnodes, nsamp64, cap, dqueries, \
-                               M, nplan, ch0, pidx, pd2, stride, (const unsigned *)xbits);                   \
-            break;
-          switch (nplan) {
-            MJPL_NN_CASE(2) MJPL_NN_CASE(3) MJPL_NN_CASE(4) MJPL_NN_CASE(5) MJPL_NN_CASE(6) MJPL_NN_CASE(7)
-          }
-#undef MJPL_NN_CASE
-        }
-        hipLaunchKernelGGL(k_nearest_reduce, dim3(rgridM), dim3(kBlock), 0, e->stream, pidx, pd2, M, (int)((nsamp64 + ch0 - 1) / ch0), seed_idx,
-                           seed_d2, (const int32_t *)nullptr, (const double *)nullptr, (const unsigned *)xbits);
-        if (have_bound) hipLaunchKernelGGL(k_nnc_bound_min, dim3(rgridM), dim3(kBlock), 0, e->stream, seed_d2, outer_d2, M, (const unsigned *)xbits);
-        const unsigned rgridM_home = (unsigned)((M + 255) / 256);
-        // 3. the queries in scan order
-        hipLaunchKernelGGL(k_nnc_query_keys, dim3(rgridM), dim3(kBlock), 0, e->stream, (const double *)seed_d2, M, kq_in, pq_in);
-        size_t tq = sort_tmp_q;
-        if (rocprim::radix_sort_pairs(tmpq, tq, (const unsigned *)kq_in, kq_out, (const int32_t *)pq_in, perm_q, (size_t)M, 0, 16, e->stream) !=
-            hipSuccess)
-          return fail(MJPL_E_HIP, "nearest: sorting the queries failed");
-        hipLaunchKernelGGL(k_nnc_gather_queries, dim3((unsigned)((Mpad + kBlock - 1) / kBlock)), dim3(kBlock), 0, e->stream, dqueries,
-                           (const double *)seed_d2, (const int32_t *)perm_q, M, Mpad, nplan, queries_s, bound2_s, qf, q32c, (const NncPlan *)plan);
-        hipLaunchKernelGGL(k_nn_pack, dim3((unsigned)((Mpad + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), dim3(256), 0, e->stream, (const double *)queries_s, M, (int64_t)1, Mpad, nplan,
-                           1, q16, qn, xbits, (int64_t)8, (const float *)plan->ctr);
-        if (e->nn_home)
-          hipLaunchKernelGGL(k_nnc_home, dim3(rgridM_home), dim3(256), 0, e->stream, (const double *)nodes_s, n, (const double *)queries_s, M, nplan,
-                           mstride, sc.idx_shift, nsub, bound2_s, qf, (const unsigned *)xbits);
-        // 4. candidates, scan
-        hipLaunchKernelGGL(k_nn_candidates, dim3((unsigned)(Mpad / 128), (unsigned)((nwords + 3) / 4)), dim3(256), 0, e->stream, (const float *)qf,
-                           M, (const float *)nbox, nsub, nsubp, nwords, masks, (const unsigned *)xbits);
-        hipLaunchKernelGGL(k_nn_compact, dim3((unsigned)((Mpad / 128 + 3) / 4)), dim3(256), 0, e->stream, (const unsigned long long *)masks, nwords,
-                           (int)(Mpad / 128), clist, (int64_t)nsubp, ccount, (const unsigned *)xbits);
-        NnCells cs{};
-        cs.list = clist; cs.count = ccount; cs.perm_n = perm_n; cs.list_pitch = nsubp; cs.probe = e->nn_probe; cs.counter = xbits + 3; cs.node_rows = 1; cs.query_rows = 1; cs.nodes32 = nodes32; cs.queries32 = q32c; cs.second = e->nn_second_screen;
-        e->nn_last_count = ccount; e->nn_last_waves = (int)((M + 127) / 128); e->nn_last_nsub = nsub;
-        const dim3 gm((unsigned)(Mpad / 128), (unsigned)nsplit);  // (one wave of 128 queries per workgroup)
-        kt_mark(e, 2, e->stream);
-#define MJPL_NNM_CASE(NPV)                                                                                                           \
-        case NPV:                                                                                                                    \
-          hipLaunchKernelGGL((k_nearest_mfma<NPV, false, true>), gm, dim3(64), 0, e->stream, (const double *)nodes_s, n, npad, \
-                             (const double *)queries_s, M, (const uint4 *)nodes16, (const uint4 *)q16, (const float *)qn,            \
-                             (const unsigned *)xbits, (int64_t)0, (int64_t)1, bound2_s, mp_idx, mp_d2, cs);                          \
-          break;
-        switch (nplan) {
-          MJPL_NNM_CASE(2) MJPL_NNM_CASE(3) MJPL_NNM_CASE(4) MJPL_NNM_CASE(5) MJPL_NNM_CASE(6) MJPL_NNM_CASE(7)
-        }
-#undef MJPL_NNM_CASE
-        kt_mark(e, 2, e->stream);
-        // 5. wild coordinates: the binary32 screen over the callers' rows; then the answers in the callers' order
-        const int qb32c = kNN32Queries * kNNThreads;
-        const int64_t qt32c = (M + qb32c - 1) / qb32c;
-        int64_t nc32c = std::max<int64_t>(1, (8192 + qt32c - 1) / qt32c);
-        nc32c = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nc32c, (int64_t)maxchunks), n / (8 * kNNThreads)));
-        int64_t ch32c = (n + nc32c - 1) / nc32c;
-        ch32c = (ch32c + kNNThreads - 1) / kNNThreads * kNNThreads;
-        nc32c = (n + ch32c - 1) / ch32c;
-        const dim3 g32c((unsigned)qt32c, (unsigned)nc32c);
-#define MJPL_NN32_CASE(NPV)                                                                                   \
-        case NPV:                                                                                             \
-          hipLaunchKernelGGL(k_nearest_part32<NPV>, g32c, dim3(kNNThreads), 0, e->stream, dnodes, n, cap, dqueries, \
-                             M, ch32c, (const double *)seed_d2, pidx, pd2, (const unsigned *)xbits);          \
-          break;
-        switch (nplan) {
-          MJPL_NN32_CASE(2) MJPL_NN32_CASE(3) MJPL_NN32_CASE(4) MJPL_NN32_CASE(5) MJPL_NN32_CASE(6) MJPL_NN32_CASE(7)
-        }
-#undef MJPL_NN32_CASE
-        hipLaunchKernelGGL(k_nnc_reduce, dim3(rgridM), dim3(kBlock), 0, e->stream, (const int32_t *)mp_idx, (const double *)mp_d2, M, mparts,
-                           (const int32_t *)perm_q, dout_idx, dout_dist2, (const unsigned *)xbits, (const int32_t *)pidx, (const double *)pd2,
-                           (int)nc32c);
-        HIP_TRY(hipGetLastError());
-        return MJPL_OK;
-      }
-      if (!mfma) {
-        scan64(nsamp64, ch0, (nsamp64 + ch0 - 1) / ch0, stride);
-        hipLaunchKernelGGL(k_nearest_reduce, dim3(rgridM), dim3(kBlock), 0, e->stream, pidx, pd2, M, (int)((nsamp64 + ch0 - 1) / ch0), seed_idx,
-                           seed_d2, (const int32_t *)nullptr, (const double *)nullptr, (const unsigned *)nullptr);
-        if (have_bound) hipLaunchKernelGGL(k_nearest_bound_min, dim3(rgridM), dim3(kBlock), 0, e->stream, seed_d2, outer_d2, M);
-      } else {
-        const int64_t npad = (n + 31) / 32 * 32, Mpad = (M + kNNMQueries - 1) / kNNMQueries * kNNMQueries;
-        const int64_t qblocks = Mpad / kNNMQueries;
-        int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>((2048 + qblocks - 1) / qblocks, n / 4096));
-        int64_t chm = ((n + nsplit - 1) / nsplit + 31) / 32 * 32;
-        nsplit = (n + chm - 1) / chm;
-        mparts = (int)(2 * nsplit);
-        const size_t b_nodes = (size_t)npad * 32, b_q = (size_t)Mpad * 64, b_qn = (size_t)Mpad * sizeof(float);
-        const size_t b_pd = (size_t)mparts * (size_t)M * sizeof(double), b_pi = (size_t)mparts * (size_t)M * sizeof(int32_t);
-        const size_t need16 = 256 + b_nodes + b_q + b_qn + b_pd + b_pi + 32;
-        if (need16 > e->nn16_bytes) {
-          // (trees grow call by call, and a reallocation stalls the stream: room for four times the nodes, within the slab)
-          // (a planner says how far its trees may grow: nn_reserve_nodes -- no reallocation in the middle of a search)
-          const size_t room = need16 - b_nodes + (size_t)std::min<int64_t>((cap + 31) / 32 * 32, std::max<int64_t>(4 * npad, e->nn_reserve_nodes)) * 32;
-          if (e->d_nn16) HIP_TRY(hipFree(e->d_nn16));
-          e->d_nn16 = nullptr; e->nn16_bytes = 0;
-          HIP_TRY(hipMalloc(&e->d_nn16, room));
-          e->nn16_bytes = room;
-        }
-        char *at = (char *)e->d_nn16;  // (the node rows last: they are what grows)
-        xbits = (unsigned *)at; at += 256;
-        uint4 *q16 = (uint4 *)at; at += b_q;
-        mp_d2 = (double *)at; at += b_pd;
-        float *qn = (float *)at; at += b_qn;
-        mp_idx = (int32_t *)at; at += (b_pi + 31) / 32 * 32;
-        uint4 *nodes16 = (uint4 *)at;
-        HIP_TRY(hipMemsetAsync(xbits, 0, 12, e->stream));  // [0] largest coordinate, [1] wild, [2] largest node norm
-        hipLaunchKernelGGL(k_nn_pack, dim3((unsigned)((npad + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), dim3(256), 0, e->stream, dnodes, n, cap, npad, nplan, 0,
-                           nodes16, (float *)nullptr, xbits);
-        hipLaunchKernelGGL(k_nn_pack, dim3((unsigned)((Mpad + 256 * kNNPackRows - 1) / (256 * kNNPackRows))), dim3(256), 0, e->stream, dqueries, M, M, Mpad, nplan, 1, q16,
-                           qn, xbits);
-        // every query's bound: the sample node the screen likes best, its distance exactly (wild coordinates: the
-        // float64 scan of the sample as before; either pair of kernels leaves at once when the other serves the call)
-        const int64_t msample = std::max<int64_t>(32, std::min<int64_t>(e->nn_sample, n / 16 / 32 * 32));
-        const int64_t mstride = std::max<int64_t>(1, n / msample);
-        // (the sample in as many chunks as give the chip ~1 024 workgroups: a look-up of few queries -- the planner's tail lanes --
-        //  would otherwise scan it with eight)
-        const int64_t ssplit = std::max<int64_t>(1, std::min<int64_t>((1024 + qblocks - 1) / qblocks, msample / 256));
-        const int64_t schunk = ((msample + ssplit - 1) / ssplit + 31) / 32 * 32;
-        const dim3 gm((unsigned)qblocks, (unsigned)nsplit), gs((unsigned)qblocks, (unsigned)((msample + schunk - 1) / schunk));
-        hipLaunchKernelGGL(k_nn_fill_inf, dim3(rgridM), dim3(kBlock), 0, e->stream, seed_d2, M, (const unsigned *)xbits);
-#define MJPL_NNM_CASE(NPV)                                                                                                       \
-        case NPV:                                                                                                                \
-          hipLaunchKernelGGL((k_nearest_mfma<NPV, true>), gs, dim3(kNNMWaves * 64), 0, e->stream, dnodes, msample, cap, dqueries, M, \
-                             (const uint4 *)nodes16, (const uint4 *)q16, (const float *)qn, (const unsigned *)xbits, schunk,     \
-                             mstride, seed_d2, (int32_t *)nullptr, (double *)nullptr);                                           \
-          break;
-        switch (nplan) {
-          MJPL_NNM_CASE(2) MJPL_NNM_CASE(3) MJPL_NNM_CASE(4) MJPL_NNM_CASE(5) MJPL_NNM_CASE(6) MJPL_NNM_CASE(7)
-        }
-#undef MJPL_NNM_CASE
-        {
-          const dim3 grid((unsigned)qtiles, (unsigned)((nsamp64 + ch0 - 1) / ch0));
-#define MJPL_NN_CASE(NPV)                                                                                    \
-          case NPV:                                                                                          \
-            hipLaunchKernelGGL(k_nearest_part<NPV>, grid, dim3(kNNThreads), 0, e->stream, dnodes, nsamp64, cap, dqueries, \
-                               M, nplan, ch0, pidx, pd2, stride, (const unsigned *)xbits);                   \
-            break;
-          switch (nplan) {
-            MJPL_NN_CASE(2) MJPL_NN_CASE(3) MJPL_NN_CASE(4) MJPL_NN_CASE(5) MJPL_NN_CASE(6) MJPL_NN_CASE(7)
-          }
-#undef MJPL_NN_CASE
-        }
-        hipLaunchKernelGGL(k_nearest_reduce, dim3(rgridM), dim3(kBlock), 0, e->stream, pidx, pd2, M, (int)((nsamp64 + ch0 - 1) / ch0), seed_idx,
-                           seed_d2, (const int32_t *)nullptr, (const double *)nullptr, (const unsigned *)xbits);
-        if (have_bound) hipLaunchKernelGGL(k_nearest_bound_min, dim3(rgridM), dim3(kBlock), 0, e->stream, seed_d2, outer_d2, M);
-#define MJPL_NNM_CASE(NPV)                                                                                                \
-        case NPV:                                                                                                         \
-          hipLaunchKernelGGL((k_nearest_mfma<NPV, false>), gm, dim3(kNNMWaves * 64), 0, e->stream, dnodes, n, cap, dqueries, M,    \
-                             (const uint4 *)nodes16, (const uint4 *)q16, (const float *)qn, (const unsigned *)xbits, chm, \
-                             (int64_t)1, seed_d2, mp_idx, mp_d2);                                                         \
-          break;
-        switch (nplan) {
-          MJPL_NNM_CASE(2) MJPL_NNM_CASE(3) MJPL_NNM_CASE(4) MJPL_NNM_CASE(5) MJPL_NNM_CASE(6) MJPL_NNM_CASE(7)
-        }
-#undef MJPL_NNM_CASE
-      }
-      const int qb32 = kNN32Queries * kNNThreads;
-      const int64_t qt32 = (M + qb32 - 1) / qb32;
-      int64_t nc32 = std::max<int64_t>(1, (8192 + qt32 - 1) / qt32);
-      nc32 = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nc32, (int64_t)maxchunks), n / (8 * kNNThreads)));
-      int64_t ch32 = (n + nc32 - 1) / nc32;
-      ch32 = (ch32 + kNNThreads - 1) / kNNThreads * kNNThreads;
-      nc32 = (n + ch32 - 1) / ch32;
-      const dim3 g32((unsigned)qt32, (unsigned)nc32);
-#define MJPL_NN32_CASE(NPV)                                                                                   \
-      case NPV:                                                                                               \
-        hipLaunchKernelGGL(k_nearest_part32<NPV>, g32, dim3(kNNThreads), 0, e->stream, dnodes, n, cap, dqueries, \
-                           M, ch32, (const double *)seed_d2, pidx, pd2, (const unsigned *)xbits);             \
-        break;
-      switch (nplan) {
-        MJPL_NN32_CASE(2) MJPL_NN32_CASE(3) MJPL_NN32_CASE(4) MJPL_NN32_CASE(5) MJPL_NN32_CASE(6) MJPL_NN32_CASE(7)
-        MJPL_NN32_CASE(8) MJPL_NN32_CASE(9)
-      }
-#undef MJPL_NN32_CASE
-      if (mfma)
-        hipLaunchKernelGGL(k_nearest_reduce_ties, dim3(rgridM), dim3(kBlock), 0, e->stream, (const int32_t *)mp_idx, (const double *)mp_d2, M,
-                           mparts, dout_idx, dout_dist2, (const unsigned *)xbits, (const int32_t *)pidx, (const double *)pd2, (int)nc32);
-      else
-        hipLaunchKernelGGL(k_nearest_reduce, dim3(rgridM), dim3(kBlock), 0, e->stream, pidx, pd2, M, (int)nc32, dout_idx,
-                           dout_dist2, (const int32_t *)nullptr, (const double *)nullptr);
-      HIP_TRY(hipGetLastError());
-      return MJPL_OK;
-    }
-    e->nn_last = 0;
-    scan64(n, chunk, nchunks);
-    hipLaunchKernelGGL(k_nearest_reduce, dim3((unsigned)((M + kBlock - 1) / kBlock)), dim3(kBlock), 0, e->stream,
-                       pidx, pd2, M, (int)nchunks, dout_idx, dout_dist2);
-    HIP_TRY(hipGetLastError());
-    return MJPL_OK;
-  }
-  const size_t lds = 2 * (size_t)nplan * kBlock * sizeof(double);
-  int rc = allow_lds(k_nearest, lds);
-  if (rc != MJPL_OK) return rc;
-  const unsigned grid = (unsigned)((M + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_nearest, dim3(grid), dim3(kBlock), lds, e->stream, dnodes, n, cap, dqueries, M, nplan,
-                     dout_idx, dout_dist2);
-  HIP_TRY(hipGetLastError());
-  return MJPL_OK;
-}
-
-extern "C" {
 
 // ---- host-buffer
 

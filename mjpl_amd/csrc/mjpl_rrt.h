@@ -661,7 +661,7 @@ struct mjpl_rrt {
   double *d_pre_d2 = nullptr;
   hipEvent_t ev_pre = nullptr;
   // the look-ups on the second stream use their own scratch (the engine's may be in use by a look-up on the first)
-  struct NnScratch { void *nn = nullptr; size_t nn_bytes = 0; void *nn16 = nullptr; size_t nn16_bytes = 0; void *tmp = nullptr; size_t tmp_bytes = 0; } side_nn;
+  NnScratch side_nn;
   int *d_ctr = nullptr, *h_ctr = nullptr;
   // projecting extensions read their chunk counters two chunks late (rrt_extend): a ring of pinned copies
   int *h_ring = nullptr;      // 4 slots of kRingStride ints: RC_SIZE counters, then the sequence word
@@ -735,26 +735,13 @@ int rrt_read_ctr(mjpl_rrt *r) {
 
 int rrt_rank(const mjpl_rrt *r);
 
-// a look-up enqueued on the planner's second stream, with its scratch.  (The engine's stream and scratch pointers are swapped
-// for the duration of the CALL -- host code, one thread per engine by the ABI's contract, nothing is enqueued in between --
-// not for the duration of the kernels: those run on `side` with the side scratch while the main stream goes on with its own.
-// The side scratch is allocated by its first look-up of a search, sized like the engine's: nn_reserve_nodes.)
+// a look-up enqueued on the planner's second stream, with its scratch: its kernels run on `side` with the side scratch while
+// the main stream goes on with the engine's.  (The side scratch is allocated by its first look-up of a search, sized like
+// the engine's: nn_reserve_nodes.  mjpl_nearest_last_screen and the "nn_last_*" options speak of the engine's own scratch.)
+// (Past mjpl_nearest_dev's argument checks, its return for M == 0 among them: both callers pass the planner's lanes,
+//  L >= 1, and a tree of at least one node.)
 int rrt_side_nearest(mjpl_rrt *r, const double *nodes, int64_t n, const double *queries, int64_t M, int32_t *idx, double *d2) {
-  mjpl_engine *e = r->e;
-  auto swap_scratch = [&]() {
-    std::swap(e->d_nn, r->side_nn.nn); std::swap(e->nn_bytes, r->side_nn.nn_bytes);
-    std::swap(e->d_nn16, r->side_nn.nn16); std::swap(e->nn16_bytes, r->side_nn.nn16_bytes);
-    std::swap(e->d_nn_tmp, r->side_nn.tmp); std::swap(e->nn_tmp_bytes, r->side_nn.tmp_bytes);
-  };
-  hipStream_t keep = e->stream;
-  const int last = e->nn_last;
-  swap_scratch();
-  e->stream = r->side;  // (the look-up's launches go where the engine's stream points)
-  const int rc = mjpl_nearest_dev(e, nodes, n, r->cap, queries, M, idx, d2);
-  e->stream = keep;
-  swap_scratch();
-  e->nn_last = last;    // (mjpl_nearest_last_screen speaks of the engine's own scratch)
-  return rc;
+  return nearest_core(r->e, r->side_nn, {nodes, n, r->cap, queries, M, idx, d2, nullptr, r->side});
 }
 
 // one extension of tree `t` towards the targets Tgt ([nplan][L]); `second`: the connect phase
@@ -786,7 +773,7 @@ int rrt_extend(mjpl_rrt *r, int t, const double *Tgt, int second, int *nnew) {
     // this round's targets were looked up in the tree's first pre_n0 nodes while the round before ran its tail
     r->pre_round = 0;
     HIP_TRY(hipStreamWaitEvent(st, r->ev_pre, 0));
-    rc = nearest_range(e, r->d_Q[t], r->pre_n0, r->n[t], r->cap, Tgt, L, r->ln.near, nullptr, r->d_pre_idx, r->d_pre_d2);
+    rc = nearest_range(e, e->nn, st, r->d_Q[t], r->pre_n0, r->n[t], r->cap, Tgt, L, r->ln.near, nullptr, r->d_pre_idx, r->d_pre_d2);
     if (rc != MJPL_OK) return rc;
     tr.mark(st, "nearest neighbour (the nodes of the last round; the others were scanned early)", r->n[t] - r->pre_n0);
   } else {
@@ -1079,9 +1066,6 @@ void mjpl_rrt_destroy(mjpl_rrt *r) {
   if (r->ev_tail) (void)hipEventDestroy(r->ev_tail);
   if (r->ev_near) (void)hipEventDestroy(r->ev_near);
   if (r->ev_pre) (void)hipEventDestroy(r->ev_pre);
-  if (r->side_nn.nn) (void)hipFree(r->side_nn.nn);
-  if (r->side_nn.nn16) (void)hipFree(r->side_nn.nn16);
-  if (r->side_nn.tmp) (void)hipFree(r->side_nn.tmp);
   for (void *p : r->owned) (void)hipFree(p);
   if (r->h_ctr) (void)hipHostFree(r->h_ctr);
   if (r->h_ring) (void)hipHostFree(r->h_ring);

@@ -406,3 +406,166 @@ def test_long_edges_with_the_filter_off_leave_nothing_behind(oracle_mod):
            ("set_filter", True, 1e-4),
            ("launch", "edges", n, eng_mod.AOS, False, True, None, True)])
     d.close()
+
+
+# ---- the nearest-neighbour look-up: one scratch per engine, whatever path the look-up before took
+
+NN_N0 = 1000                 # nodes every ranged look-up below already has an answer for
+NN_MFMA = 8192 + 5           # a range of that many nodes behind a bound, 4 096 queries or more: the matrix-core screen
+NN_CELLS = 16384 + 13        # ... with option nn_cells_min_nodes = 16 384: the cell-ordered scan (64 sub-chunks of 256)
+
+
+def _nn_chain(njnt):
+    """A chain of `njnt` hinges, a sphere on every link: planning sets beyond Franka-P's nine joints."""
+    from mjpl_amd.model import ModelBuilder
+    mb = ModelBuilder()
+    parent = "world"
+    for k in range(njnt):
+        parent = mb.add_body(f"link{k}", parent, pos=(0, 0, 0.2))
+        mb.add_joint(parent, f"hinge{k}", axis=((1, 0, 0), (0, 1, 0), (0, 0, 1))[k % 3], range=(-2.9, 2.9))
+        mb.add_geom(parent, "sphere", (0.03,), pos=(0, 0, 0.1))
+    mb.add_keyframe("home", np.zeros(njnt))
+    return mb.compile()
+
+
+def _nn_engine(nplan=7, model=None, **options):
+    m = scenes.franka_p() if model is None else model
+    adr = np.sort(np.asarray(m.jnt_qposadr, dtype=np.int32))
+    if nplan > len(adr):
+        return None
+    e = eng_mod.Engine(m)
+    e.set_planning(adr[:nplan], m.keyframe("home").qpos)  # (Franka-P: the seven arm joints first, then the fingers)
+    e.set_option("nn_cells_min_nodes", 16384)
+    for k, v in options.items():
+        e.set_option(k, v)
+    return e
+
+
+def _nn_reference(nodes, qs, counts):
+    """NumPy's float64 answer for every query over nodes [0, c), c in counts: the sum over the coordinates in the kernel's
+    order, the lowest index wins -- in slices of 256 queries."""
+    M = qs.shape[1]
+    out = {c: (np.empty(M, np.int32), np.empty(M)) for c in counts}
+    for j in range(0, M, 256):
+        s = np.zeros((min(256, M - j), max(counts)))
+        for c in range(nodes.shape[0]):
+            d = nodes[c][None, :max(counts)] - qs[c][j:j + 256][:, None]
+            s = s + d * d
+        for c in counts:
+            out[c][0][j:j + 256] = s[:, :c].argmin(1)
+            out[c][1][j:j + 256] = s[:, :c].min(1)
+    return out
+
+
+def _nn_data(nplan, n, M, seed):
+    """A tree of n nodes (column stride n + 77) and M queries; among the nodes above NN_N0 an exact duplicate of an old
+    node, with a query beside it, and a node ON a query; an old node on a query as well."""
+    rng = np.random.default_rng(seed)
+    nodes = np.zeros((nplan, n + 77))
+    nodes[:, :n] = rng.uniform(-2.9, 2.9, size=(nplan, n))
+    qs = rng.uniform(-2.9, 2.9, size=(nplan, M))
+    if n > NN_N0 + 8:
+        nodes[:, NN_N0 + 7] = nodes[:, 17]
+        qs[:, 3] = nodes[:, 17] + 1e-9
+        nodes[:, NN_N0 + 1] = qs[:, 4]
+        qs[:, 5] = nodes[:, 40]
+    return nodes, qs
+
+
+def _nn_lookup(e, nodes, qs, n0, n, prev=None):
+    """One look-up over nodes [n0, n) behind the answer `prev` for the nodes below n0 -> indices, squared distances."""
+    nodes, qs = np.ascontiguousarray(nodes), np.ascontiguousarray(qs)
+    cap, M = nodes.shape[1], qs.shape[1]
+    dn, dq, di, dd = e.alloc(nodes.nbytes).upload(nodes), e.alloc(qs.nbytes).upload(qs), e.alloc(4 * M), e.alloc(8 * M)
+    if prev is None:
+        e.nearest_dev(dn.ptr, n, cap, dq.ptr, M, di.ptr, dd.ptr)
+    else:
+        pi, pd = e.alloc(4 * M).upload(np.ascontiguousarray(prev[0])), e.alloc(8 * M).upload(np.ascontiguousarray(prev[1]))
+        e.nearest_range_dev(dn.ptr, n0, n, cap, dq.ptr, M, di.ptr, dd.ptr, pi.ptr, pd.ptr)
+    return di.download(np.int32, M), dd.download(np.float64, M)
+
+
+def test_what_the_last_lookup_did_follows_the_last_lookup():
+    """(h) mjpl_nearest_last_screen and the read-only options nn_last_cells / nn_last_candidate_fraction speak of the LAST
+    look-up on the engine's scratch: after a cell-ordered scan, a small look-up (plain float64 scan) must leave none of
+    the cell-ordered scan's record behind."""
+    e = _nn_engine()
+    n, M = NN_N0 + NN_CELLS, 4101
+    nodes, qs = _nn_data(7, n, M, seed=1)
+    prev = _nn_lookup(e, nodes, qs, 0, NN_N0)
+    _nn_lookup(e, nodes, qs, NN_N0, n, prev)
+    assert e.get_option("nn_last_cells") == 1
+    assert e.nearest_last_screen() == 2
+    assert 0 < e.get_option("nn_last_candidate_fraction") <= 1
+    _nn_lookup(e, nodes[:, :500 + 77], qs[:, :10], 0, 500)
+    assert e.get_option("nn_last_cells") == 0
+    assert e.nearest_last_screen() == 0
+    assert e.get_option("nn_last_candidate_fraction") == -1
+    e.close()
+
+
+def test_a_reused_nearest_neighbour_scratch_answers_like_a_fresh_one():
+    """(i) One engine takes the look-up's paths in turn -- plain scan, matrix-core screen, cell-ordered scan, matrix-core
+    screen with more queries (a larger query side in the same arena), binary32 screen --: every call's indices and squared
+    distances are those of a fresh engine that makes only that call, byte for byte, and NumPy's float64 argmin's for every
+    query (n and M ragged against 32, 128 and 512; ties and zero distances in the data)."""
+    n_mfma, n_cells = NN_N0 + NN_MFMA, NN_N0 + NN_CELLS
+    nodes, qs = _nn_data(7, n_cells, 4613, seed=2)
+    ref = _nn_reference(nodes, qs, (NN_N0, 3000, n_mfma, n_cells))
+    # (options, first node, nodes, queries, what nearest_last_screen and nn_last_cells say afterwards)
+    calls = [({}, 0, 3000, 700, 0, 0),
+             ({}, NN_N0, n_mfma, 4101, 2, 0),
+             ({}, NN_N0, n_cells, 4101, 2, 1),
+             ({}, NN_N0, n_mfma, 4613, 2, 0),
+             ({"nn_mfma": 0}, NN_N0, n_mfma, 4613, 1, 0)]
+    live = _nn_engine()
+    for options, n0, n, M, screen, cells in calls:
+        prev = (ref[NN_N0][0][:M], ref[NN_N0][1][:M]) if n0 else None
+        fresh = _nn_engine(**options)
+        for k, v in options.items():
+            live.set_option(k, v)
+        got = _nn_lookup(live, nodes, qs[:, :M], n0, n, prev)
+        want = _nn_lookup(fresh, nodes, qs[:, :M], n0, n, prev)
+        msg = f"nodes [{n0}, {n}), {M} queries, {options}"
+        for eng in (live, fresh):
+            assert (eng.nearest_last_screen(), eng.get_option("nn_last_cells")) == (screen, cells), msg
+        fresh.close()
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes(), msg
+        np.testing.assert_array_equal(got[0], ref[n][0][:M], err_msg=msg)
+        np.testing.assert_array_equal(got[1], ref[n][1][:M], err_msg=msg)
+        if n0:
+            assert got[0][3] == 17 and got[0][4] == NN_N0 + 1 and got[1][4] == 0.0 and got[0][5] == 40, msg
+    live.close()
+
+
+@pytest.mark.parametrize("nplan", [2, 7, 8, 9])
+def test_nearest_neighbour_planning_dimensions(nplan):
+    """(j) The look-up's kernels are instantiated per planning dimension: the matrix-core screen for 2..7 columns (its
+    ends here), the binary32 screen for 8 and 9 (the arm and the fingers).  A ranged look-up of the screened shape
+    answers like NumPy's float64 argmin for every query."""
+    e = _nn_engine(nplan)
+    if e is None:
+        pytest.skip(f"Franka-P has fewer than {nplan} joints to plan over")
+    n, M = NN_N0 + NN_MFMA, 4101
+    nodes, qs = _nn_data(nplan, n, M, seed=10 + nplan)
+    ref = _nn_reference(nodes, qs, (NN_N0, n))
+    got = _nn_lookup(e, nodes, qs, NN_N0, n, ref[NN_N0])
+    assert e.nearest_last_screen() == (2 if nplan <= 7 else 1)
+    np.testing.assert_array_equal(got[0], ref[n][0])
+    np.testing.assert_array_equal(got[1], ref[n][1])
+    e.close()
+
+
+@pytest.mark.parametrize("nplan", [1, 12, 16])
+def test_nearest_neighbour_generic_planning_dimension(nplan):
+    """(k) Planning sets without an instantiation of their own -- one column, ten to sixteen -- take the plain scan's
+    generic kernel: a small look-up answers like NumPy's.  (Franka-P has nine joints: the sets above nine are those of
+    a chain of hinges.)"""
+    e = _nn_engine(nplan, model=_nn_chain(nplan) if nplan > 9 else None)
+    nodes, qs = _nn_data(nplan, 300, 40, seed=20 + nplan)
+    ref = _nn_reference(nodes, qs, (300,))
+    got = _nn_lookup(e, nodes, qs, 0, 300)
+    assert e.nearest_last_screen() == 0
+    np.testing.assert_array_equal(got[0], ref[300][0])
+    np.testing.assert_array_equal(got[1], ref[300][1])
+    e.close()
