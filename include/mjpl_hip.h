@@ -297,6 +297,42 @@ int mjpl_clearance_grad_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t
                             double *dclear, int32_t *dpair, double *dgrad, double *dfromto, double *dnormal,
                             int32_t *dstatus);
 
+/* ---- near pairs: every pair within distmax, with distance, witnesses and gradient ----------
+ * Candidate pair p of the contacts table (same P, same order) is NEAR at q_i if it is not allowed and
+ * d_p(q_i) < distmax: d_p is mjpl_distances' exact signed distance (margins not subtracted), and the
+ * comparison is the one that decides whether mjpl_distances writes d_p or distmax.  Allowed pairs take
+ * no part, as in mjpl_clearance.  K (>= 1) is the number of slots per configuration.
+ *   count[i] = the number of near pairs of q_i, NOT clipped to K; -1 for a row with a non-finite
+ *     planning column.
+ *   Slots k < min(count[i], K) of row i hold the first near pairs in ascending p:
+ *     pair[i*K + k] = p;  dist[i*K + k] = d_p, bit-identical to mjpl_distances.
+ *   In every remaining slot of the row pair = -1 and NOTHING ELSE IS WRITTEN: dist, grad, fromto,
+ *     normal and status keep the caller's bytes there.  Mask by pair (>= 0) or by count.
+ * Per listed slot s = i*K + k, with (g1, g2) row p of mjpl_contact_pairs and D = dist[s]:
+ *   fromto[s*6 + 0..5], normal[s*3 + 0..2] and grad[s*nplan + j] = d d_p / d q_j have the meaning,
+ *     orientation and formula of the mjpl_clearance_grad block above for that pair (w1 on g1, w2 on g2,
+ *     the plane and overlap cases, n from g1 towards g2, w2 - w1 = D n up to rounding, grad over the
+ *     planning columns of mjpl_set_planning).  Where mjpl_clearance_grad picks pair p, its grad, fromto,
+ *     normal and status are these, bit for bit.
+ *   status[s] = MJPL_GRAD_OK or MJPL_GRAD_DEGENERATE, by the same rule and with the same outputs
+ *     (DEGENERATE: grad and normal NaN, fromto = the two core points).  MJPL_GRAD_FLAT and
+ *     MJPL_GRAD_NONFINITE do not occur per slot: a pair at or beyond distmax is not listed, and a
+ *     non-finite row lists nothing.
+ * Unlike the clearance's gradient, which follows one pair and flips where the winner switches, every
+ * pair's own distance is listed with its own gradient: two walls at the same distance are two slots.
+ * fromto and normal may be NULL; every other output is required when N > 0.  distmax > 0, +inf allowed.
+ * MJPL_E_ARG: K < 1, distmax NaN or <= 0, an unknown layout, a NULL required output with N > 0.
+ * MJPL_E_PAIRTYPE as for mjpl_contacts.  N = 0 launches nothing.  Without a non-allowed pair every
+ * count is 0 (-1 for a non-finite row) and every pair -1.  The results depend on no option and no
+ * MJPL_* variable.  The host form synchronises; the device form is asynchronous on the engine's
+ * stream. */
+int mjpl_near_pairs(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, int32_t K,
+                    int32_t *count, int32_t *pair, double *dist, double *grad, double *fromto, double *normal,
+                    int32_t *status);
+int mjpl_near_pairs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, int32_t K,
+                        int32_t *dcount, int32_t *dpair, double *ddist, double *dgrad, double *dfromto,
+                        double *dnormal, int32_t *dstatus);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

@@ -50,6 +50,16 @@ class ClearanceGradient(NamedTuple):
     status: int                        # engine.GRAD_OK / GRAD_FLAT / GRAD_DEGENERATE / GRAD_NONFINITE
 
 
+class NearPair(NamedTuple):
+    """One geom pair closer than distmax at a configuration (``CollisionConstraint.near_pairs``)."""
+    pair: tuple[int, int]              # the geom pair (smaller geom type first)
+    distance: float                    # its signed distance (margins not subtracted)
+    gradient: np.ndarray               # d distance / dq, float64 [nq]
+    fromto: np.ndarray                 # witness points w1 (on pair[0]), w2 (on pair[1]), world frame, float64 [6]
+    normal: np.ndarray                 # unit vector from pair[0] towards pair[1], float64 [3]
+    status: int                        # engine.GRAD_OK / GRAD_DEGENERATE
+
+
 class CollisionRuleset:
     """Which body pairs may touch (reference collision_constraint.py:36-95).
 
@@ -237,6 +247,33 @@ class CollisionConstraint(Constraint):
         grad is [N, nplan], dC/dq over those columns; C and pair equal what a full-nq batch gives there."""
         self._ensure_planning()
         return self.engine.clearance_grad(Qp, distmax, layout)
+
+    # ---- near pairs: every pair within distmax, each with its own distance, witnesses and gradient ----------
+    def near_pairs(self, q: np.ndarray, distmax: float) -> "list[NearPair]":
+        """Every non-allowed candidate pair whose signed distance at the full-nq ``q`` is below ``distmax``, in
+        candidate-table order -> a list of :class:`NearPair`.  ``distance`` is ``pair_distances(q)``'s entry bit for
+        bit; ``gradient`` is that pair's own d distance / dq (where ``clearance_gradient`` follows one pair and flips
+        where the closest pair switches, this lists each pair with its own).  Nothing is cut: the slots are sized to
+        the number of non-allowed pairs.  A non-finite ``q`` raises ValueError (the batch forms report count -1)."""
+        pairs, allowed = self.engine.contact_pairs()
+        K = max(int((~allowed).sum()), 1)
+        count, pair, dist, grad, fromto, normal, status = self.near_pairs_batch(self._full_q(q), distmax, K)
+        if count[0] < 0:
+            raise ValueError("q holds a non-finite value")
+        return [NearPair((int(pairs[p][0]), int(pairs[p][1])), float(dist[0, k]), grad[0, k], fromto[0, k], normal[0, k],
+                         int(status[0, k])) for k, p in enumerate(pair[0, :count[0]])]
+
+    def near_pairs_batch(self, Q: np.ndarray, distmax: float, max_pairs: int = 32):
+        """``near_pairs`` for every row of full-nq configurations [N, nq], one launch, K = max_pairs slots per row ->
+        (count [N], candidate-pair index [N, K], dist [N, K], grad [N, K, nq], fromto [N, K, 6], normal [N, K, 3],
+        status [N, K]).  count is not clipped to K (-1: non-finite row); slots past min(count, K) read -1 / NaN."""
+        return self.engine.near_pairs(self._full_batch(Q), distmax, max_pairs, _engine.AOS)
+
+    def near_pairs_planning(self, Qp: np.ndarray, distmax: float, max_pairs: int = 32, layout: int = _engine.AOS):
+        """``near_pairs_batch`` over the columns of ``set_planning`` (every other joint at its base value): grad is
+        [N, K, nplan], over those columns."""
+        self._ensure_planning()
+        return self.engine.near_pairs(Qp, distmax, max_pairs, layout)
 
     def valid_interval(self, start: np.ndarray, end: np.ndarray, step_dist: float) -> bool:
         """``_valid_collision_interval(start, end, step_dist, self)`` in one launch

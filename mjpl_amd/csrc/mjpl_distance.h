@@ -14,8 +14,9 @@
 //   3. k_distance<DM_DIST> (distances) stores D[i][p] = min(d_p, distmax); k_distance<DM_CLEAR> (clearance) keeps
 //      (min over non-allowed pairs of D - margin, its pair index) in registers and stores 12 bytes per
 //      configuration; k_distance<DM_GRAD> (clearance gradients) does the same, then runs the epilogue of
-//      mjpl_distance_grad.h once per lane.
-// The walks of all three modes and of k_contacts load a pair's geoms with contact_load_pair (mjpl_contacts.h).
+//      mjpl_distance_grad.h once per lane; k_distance<DM_NEAR> (near pairs) lists every non-allowed pair below
+//      distmax with its distance, witnesses and gradient (mjpl_distance_grad.h: near_step), up to K per lane.
+// The walks of all four modes and of k_contacts load a pair's geoms with contact_load_pair (mjpl_contacts.h).
 //
 // The routines reduce every non-plane pair to core distance minus radii (sphere = point, capsule = segment,
 // box = box).  Disjoint cores: the minimum over the feature pairs that can hold the closest points (end
@@ -317,35 +318,52 @@ __device__ __forceinline__ double pair_distance(int tcur, const GeomT<double> &c
   return core_core_distance(cur, scur, tcur == GT_CAPSULE, par, spar, tpar == GT_CAPSULE);
 }
 
-// The kernel's three modes: distances, clearance, and clearance with the gradient epilogue.
-enum : int { DM_DIST = 0, DM_CLEAR, DM_GRAD };
+// The kernel's four modes: distances, clearance, clearance with the gradient epilogue, and the list of near pairs.
+enum : int { DM_DIST = 0, DM_CLEAR, DM_GRAD, DM_NEAR };
 
-// DM_GRAD's scratch, tables and outputs (mjpl_distance_grad.h)
+// DM_GRAD's and DM_NEAR's scratch, tables and outputs (mjpl_distance_grad.h)
 struct GradOut {
   double *xpos, *xquat;  // body pose scratch rows (nbody per row), written by the FK
   int nbody;
   const double *gcol, *gjnt, *gtin;  // column table [nplan][GC_LEN], joint table [njnt][JR_LEN], tin per geom
-  double *grad, *fromto, *normal;    // [N][nplan], [N][6] (may be null), [N][3] (may be null)
+  // DM_GRAD: [N][nplan], [N][6] (may be null), [N][3] (may be null), [N]; DM_NEAR: the same per slot, N * K of each
+  double *grad, *fromto, *normal;
   int *status;
+};
+
+// DM_NEAR's own scratch and outputs, beside GradOut's (mjpl_distance_grad.h: near_step)
+struct NearOut {
+  double *frames;  // column frames scratch [rows][nplan][6]: world axis, anchor of every planning column's joint
+  int K;           // slots per configuration
+  int *count;      // [N]
+  int *pair;       // [N][K]
+  double *dist;    // [N][K]
 };
 
 // DM_GRAD's epilogue (mjpl_distance_grad.h)
 __device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<double> &c, IP ct, DP cd, DP wcull,
                                               DP wnarrow, const double *rx, const double *rm, int64_t i, int64_t row,
                                               int nplan, bool live, int bestp, bool bestcap);
+// DM_NEAR's column frames, once per lane before the walk, and its per-pair step (mjpl_distance_grad.h)
+__device__ __forceinline__ void near_park_frames(const GradOut &go, const NearOut &no, const Carve<double> &c,
+                                                 int64_t row, int nplan, bool active);
+__device__ __forceinline__ void near_step(const GradOut &go, const NearOut &no, const PairGeoms &g, int p, double D,
+                                          int64_t slot, int64_t row, int nplan, bool put);
 
 // Configurations [i0, i0 + n) of the batch Q (N rows, `layout`), FK scratch rows as k_contacts uses them.
 // DM_DIST: dist[i * P + p] = min(d_p, distmax).  DM_CLEAR: clear[i] = min over non-allowed p of
 // (min(d_p, distmax) - margin_p), pair[i] = its lowest index (distmax, -1 without such a pair).  DM_GRAD: clear and
 // pair as DM_CLEAR, the body poses also written to go's scratch rows, then go's outputs at row i.  A row with a
-// non-finite planning column gives NaN (and pair -1).
+// non-finite planning column gives NaN (and pair -1).  DM_NEAR: the non-allowed pairs with d_p < distmax in
+// ascending p: no.count[i] of them (-1 for a non-finite row), the first no.K in slots i * K + k of no.pair, no.dist and
+// go's outputs, no.pair = -1 in the row's remaining slots (nothing else of those is written).
 template <int MODE>
 __global__ void __launch_bounds__(kBlock)
 k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp, int ndp,
            const int *__restrict__ gct, const double *__restrict__ gcd, const double *__restrict__ gdt, int P,
            const double *__restrict__ Q, int64_t N, int64_t i0, int64_t n, int layout, double distmax,
            double *__restrict__ gx, double *__restrict__ gm, int ngeom, double *__restrict__ dist,
-           double *__restrict__ clear, int *__restrict__ pair, GradOut go) {
+           double *__restrict__ clear, int *__restrict__ pair, GradOut go, NearOut no) {
   extern __shared__ double smem[];
   const int B = blockDim.x;
   const int nplan = gip[H_NPLAN];
@@ -359,12 +377,12 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
   for (int k = 0; k < nplan; k++) finite = finite && __builtin_isfinite(c.col0[k * B + threadIdx.x]);
   const bool live = active && finite;
 
-  // 1. forward kinematics into the scratch row (DM_GRAD: the body poses too, for the epilogue)
+  // 1. forward kinematics into the scratch row (DM_GRAD, DM_NEAR: the body poses too, for the column frames)
   FkOut out = {};
   out.geom_xpos = gx;
   out.geom_xmat = gm;
   out.ngeom = ngeom;
-  if (MODE == DM_GRAD) {
+  if (MODE == DM_GRAD || MODE == DM_NEAR) {
     out.xpos = go.xpos;
     out.xquat = go.xquat;
     out.nbody = go.nbody;
@@ -373,6 +391,8 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
                                           out, active ? r : 0);
   const double *rx = gx + (active ? r : 0) * ngeom * 3;
   const double *rm = gm + (active ? r : 0) * ngeom * 9;
+  // DM_NEAR: every planning column's frame, parked in scratch for the pairs that pass
+  if constexpr (MODE == DM_NEAR) near_park_frames(go, no, c, active ? r : 0, nplan, active);
 
   // 2. every candidate pair, in table order
   IP ct = (IP)gct;
@@ -383,6 +403,7 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
   double best = distmax;  // DM_CLEAR / DM_GRAD: least D - margin so far, at pair index bestp
   int bestp = -1;
   bool bestcap = true;  // DM_GRAD: the winner's D is distmax (a cap: no geometry to differentiate)
+  int cnt = 0;          // DM_NEAR: near pairs so far
   for (int p = 0; p < P; p++) {
     // (uniform: allowed pairs take no part in the clearance)
     if (MODE != DM_DIST && uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;
@@ -403,7 +424,7 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
     const bool far = lb >= distmax + kDistCullSlack;  // D = distmax, no routine
     bool need = live && !far;
     // a pair whose D - margin must exceed the least so far cannot change (C, pair)
-    if (MODE != DM_DIST) need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
+    if (MODE == DM_CLEAR || MODE == DM_GRAD) need = need && !(bestp >= 0 && lb >= best + margin + kDistCullSlack);
     double D = distmax;
     if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
       const double x = pair_distance(g.tcur, g.cur, g.scur, g.tpar, g.par, g.spar);
@@ -411,6 +432,13 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
     }
     if constexpr (MODE == DM_DIST) {
       if (active) dist[i * P + p] = live ? D : NAN;
+    } else if constexpr (MODE == DM_NEAR) {
+      // near: the comparison that made D the distance and not the cap.  Every near lane counts; the lanes with a
+      // slot left take the witness step together (the pair's types are wave-uniform, only the lane mask differs).
+      const bool near = need && D < distmax;
+      const bool put = near && cnt < no.K;
+      if (__builtin_amdgcn_ballot_w64(put) != 0ull) near_step(go, no, g, p, D, i * no.K + cnt, active ? r : 0, nplan, put);
+      if (near) cnt++;
     } else {
       const double v = D - margin;
       if (live && (need || far) && (bestp < 0 || v < best)) {
@@ -420,7 +448,11 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
       }
     }
   }
-  if constexpr (MODE != DM_DIST) {
+  if constexpr (MODE == DM_NEAR) {
+    if (!active) return;
+    for (int k = cnt; k < no.K; k++) no.pair[i * no.K + k] = -1;
+    no.count[i] = live ? cnt : -1;
+  } else if constexpr (MODE != DM_DIST) {
     if (!active) return;
     clear[i] = live ? best : NAN;
     pair[i] = live ? bestp : -1;

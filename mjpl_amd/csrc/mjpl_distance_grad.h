@@ -1,4 +1,5 @@
-// mjpl_distance_grad.h -- clearance gradients and witness points per configuration (mjpl_clearance_grad*).
+// mjpl_distance_grad.h -- clearance gradients and witness points per configuration (mjpl_clearance_grad*), and the
+// same for every pair within distmax (mjpl_near_pairs*, at the end of the file).
 //
 // The clearance gradients are k_distance<DM_GRAD> (mjpl_distance.h): the clearance kernel's walk itself, with the
 // body poses also written to scratch and this file's epilogue after it.
@@ -500,6 +501,93 @@ __device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<dou
       gj = (m2 ? dot3(n, v2) : 0.0) - (m1 ? dot3(n, v1) : 0.0);
     }
     grad[j] = st != GS_OK ? NAN : gj;
+  }
+}
+
+// ---- near pairs (mjpl_near_pairs*): k_distance<DM_NEAR>
+// The distances' walk (DM_DIST's cull, allowed pairs skipped), and for every pair below distmax what the epilogue above
+// gives for the winner alone.  The pair index is wave-uniform in the walk, so pair_witness runs here with uniform types:
+// one routine per pair for the whole wave, under the mask of the lanes that list the pair -- not the per-lane type
+// divergence of the epilogue.  What differs per lane is the configuration, so the column frames are made once per lane
+// before the walk and parked in global scratch (54 doubles per lane at nplan = 9: too much for LDS beside the carve,
+// and a runtime-indexed private array would live in scratch memory anyway).
+
+// Before the walk: axis and anchor of every planning column's joint for this lane's configuration, to its scratch row
+__device__ __forceinline__ void near_park_frames(const GradOut &go, const NearOut &no, const Carve<double> &c,
+                                                 int64_t row, int nplan, bool active) {
+  const double *q = c.col0 + threadIdx.x;
+  double *fr = no.frames + row * nplan * 6;
+  for (int j = 0; j < nplan; j++) {
+    double axis[3], anchor[3];
+    int jt;
+    column_frame(go, (DP)go.gcol + j * GC_LEN, q, blockDim.x, row, axis, anchor, &jt);
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        fr[j * 6 + k] = axis[k];
+        fr[j * 6 + 3 + k] = anchor[k];
+      }
+    }
+  }
+}
+
+// One near pair of the walk (g: the pair as the walk loaded it, p and its types wave-uniform; D: its distance), run by
+// the whole wave when any lane lists it: witnesses, then the epilogue's orientation and gradient statements with the
+// parked frames.  Lanes with `put` store slot `slot` (= i * K + the lane's count, below K); the others store nothing.
+__device__ __forceinline__ void near_step(const GradOut &go, const NearOut &no, const PairGeoms &g, int p, double D,
+                                          int64_t slot, int64_t row, int nplan, bool put) {
+  // (copies of their own, as in the epilogue: pair_witness hands the two geoms to its routines in either order, and
+  //  what that keeps out of registers should be these, made for a near pair only, not the walk's g)
+  const GeomT<double> cur = g.cur, par = g.par;
+  const double scur[3] = {g.scur[0], g.scur[1], g.scur[2]}, spar[3] = {g.spar[0], g.spar[1], g.spar[2]};
+  double wc[3], wp[3], n[3];
+  const int st = pair_witness(g.tcur, cur, scur, g.tpar, par, spar, wc, wp, n);
+  // the candidate table's orientation: g1 = par when CF_PFIRST
+  const bool pfirst = (g.flags & CF_PFIRST) != 0;
+  double w1[3], w2[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    w1[k] = pfirst ? wp[k] : wc[k];
+    w2[k] = pfirst ? wc[k] : wp[k];
+    n[k] = st != GS_OK ? NAN : (pfirst ? -n[k] : n[k]);
+  }
+  if (put) {
+    no.pair[slot] = p;
+    no.dist[slot] = D;
+    go.status[slot] = st;
+    if (go.fromto)
+      for (int k = 0; k < 3; k++) {
+        go.fromto[slot * 6 + k] = w1[k];
+        go.fromto[slot * 6 + 3 + k] = w2[k];
+      }
+    if (go.normal)
+      for (int k = 0; k < 3; k++) go.normal[slot * 3 + k] = n[k];
+  }
+  // d d_p/dq_j = n . (v_j(w2) [g2 moved by j] - v_j(w1) [g1 moved by j]); which columns move the pair is wave-uniform
+  const double tin1 = go.gtin[pfirst ? g.gparid : g.gcur], tin2 = go.gtin[pfirst ? g.gcur : g.gparid];
+  const double *fr = no.frames + row * nplan * 6;
+  for (int j = 0; j < nplan; j++) {
+    DP col = (DP)go.gcol + j * GC_LEN;
+    const double lo = col[GC_TIN], hi = col[GC_TOUT];
+    const bool m1 = tin1 >= lo && tin1 < hi, m2 = tin2 >= lo && tin2 < hi;
+    double gj = 0.0;
+    if (m1 || m2) {
+      const int jt = uni((int)((DP)go.gjnt + uni((int)col[GC_JNT]) * JR_LEN)[JR_TYPE]);
+      const double axis[3] = {fr[j * 6], fr[j * 6 + 1], fr[j * 6 + 2]};
+      const double anchor[3] = {fr[j * 6 + 3], fr[j * 6 + 4], fr[j * 6 + 5]};
+      double v1[3], v2[3];
+      if (jt == JT_SLIDE) {
+        set3(v1, axis);
+        set3(v2, axis);
+      } else {
+        const double r1[3] = {w1[0] - anchor[0], w1[1] - anchor[1], w1[2] - anchor[2]};
+        const double r2[3] = {w2[0] - anchor[0], w2[1] - anchor[1], w2[2] - anchor[2]};
+        cross3(v1, axis, r1);
+        cross3(v2, axis, r2);
+      }
+      gj = (m2 ? dot3(n, v2) : 0.0) - (m1 ? dot3(n, v1) : 0.0);
+    }
+    if (put) go.grad[slot * nplan + j] = st != GS_OK ? NAN : gj;
   }
 }
 

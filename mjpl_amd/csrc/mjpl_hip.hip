@@ -477,6 +477,8 @@ struct mjpl_engine {
   // remade by mjpl_set_planning; body pose scratch rows of one launch (grow-only)
   double *d_gr = nullptr;
   DevBuf<double> d_gr_scratch;
+  // column frames scratch rows of one mjpl_near_pairs* launch (mjpl_distance.h: NearOut::frames; grow-only)
+  DevBuf<double> d_nr_frames;
 };
 
 namespace {
@@ -1394,21 +1396,34 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
   return MJPL_OK;
 }
 
-// One k_distance<mode> launch per kContactRows configurations: D [N][P] (DM_DIST), (C, pair) [N] (DM_CLEAR), or
-// (C, pair), grad [N][nplan], fromto [N][6], normal [N][3] and status [N] (DM_GRAD; fromto / normal may be null).
+// One k_distance<mode> launch per kContactRows configurations: D [N][P] (DM_DIST), (C, pair) [N] (DM_CLEAR),
+// (C, pair), grad [N][nplan], fromto [N][6], normal [N][3] and status [N] (DM_GRAD; fromto / normal may be null), or
+// count [N] and K slots per configuration of pair, D (ddist), grad, fromto, normal and status (DM_NEAR: K = near_k,
+// dcount; fromto / normal may be null).
 int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int layout, double distmax, double *ddist,
                     double *dclear, int32_t *dpair, double *dgrad = nullptr, double *dfromto = nullptr,
-                    double *dnormal = nullptr, int32_t *dstatus = nullptr) {
+                    double *dnormal = nullptr, int32_t *dstatus = nullptr, int near_k = 0, int32_t *dcount = nullptr) {
   const int P = (int)e->ct_g1.size();
   if (N == 0 || (mode == DM_DIST && P == 0)) return MJPL_OK;
   const auto kernel = mode == DM_DIST    ? k_distance<DM_DIST>
                       : mode == DM_CLEAR ? k_distance<DM_CLEAR>
-                                         : k_distance<DM_GRAD>;
+                      : mode == DM_GRAD  ? k_distance<DM_GRAD>
+                                         : k_distance<DM_NEAR>;
   PairLaunch pl;
   int rc = pair_query_prologue(e, kernel, N, &pl);
   if (rc != MJPL_OK) return rc;
   GradOut go = {};
-  if (mode == DM_GRAD) {
+  NearOut no = {};
+  if (mode == DM_NEAR) {
+    rc = e->d_nr_frames.reserve((size_t)pl.rows * e->qidx.size() * 6);
+    if (rc != MJPL_OK) return rc;
+    no.frames = e->d_nr_frames.p;
+    no.K = near_k;
+    no.count = dcount;
+    no.pair = dpair;
+    no.dist = ddist;
+  }
+  if (mode == DM_GRAD || mode == DM_NEAR) {
     const int nb = e->m.nbody, nplan = (int)e->qidx.size();
     rc = e->d_gr_scratch.reserve((size_t)pl.rows * nb * 7);
     if (rc != MJPL_OK) return rc;
@@ -1429,7 +1444,7 @@ int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int l
     // (all outputs are indexed by the batch row i: whole arrays)
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), pl.lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
                        (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, pl.gx,
-                       pl.gm, e->m.ngeom, ddist, dclear, dpair, go);
+                       pl.gm, e->m.ngeom, ddist, dclear, dpair, go, no);
     HIP_TRY(hipGetLastError());
   }
   return MJPL_OK;
@@ -1459,7 +1474,8 @@ int check_query_args(const mjpl_engine *e, const void *Q, int64_t N, int layout,
 // ---- staging of the host-pointer entry points
 // An array of a call in host memory: an input copied in, or an output copied back.  A null output is one the caller
 // does not want: it gets no space and a null device pointer.  An output with `from` set is not written by the launch:
-// it is copied from that device address after it (the edge pipeline's status word).
+// it is copied from that device address after it (the edge pipeline's status word).  An output with `keep` set is one
+// the launch writes only in part: the caller's bytes are copied in before it, so what it leaves alone comes back as it was.
 struct HostIn {
   const void *host;
   size_t bytes;
@@ -1468,6 +1484,7 @@ struct HostOut {
   void *host;
   size_t bytes;
   const void *from = nullptr;
+  bool keep = false;
 };
 
 constexpr size_t kSpanAlign = 256;  // every span starts at a multiple of this in its slot or in the pinned block
@@ -1515,6 +1532,8 @@ int staged(mjpl_engine *e, bool small_tiers, const HostIn (&in)[NI], const HostO
     if ((rc = pin_reserve(e, ib + ob)) != MJPL_OK) return rc;
     pin = (char *)e->h_pin;
     for (size_t k = 0; k < NI; k++) memcpy(pin + at_in[k], in[k].host, in[k].bytes);
+    for (size_t k = 0; k < NO; k++)
+      if (out[k].host && out[k].keep) memcpy(pin + ib + at_out[k], out[k].host, out[k].bytes);
   }
   if (tier == 0) {
     HIP_TRY(hipHostGetDevicePointer((void **)&dev_in, pin, 0));
@@ -1527,6 +1546,12 @@ int staged(mjpl_engine *e, bool small_tiers, const HostIn (&in)[NI], const HostO
     if (tier == 1) HIP_TRY(hipMemcpyAsync(dev_in, pin, ib, hipMemcpyHostToDevice, e->stream));
     for (size_t k = 0; k < NI && tier == 2; k++)
       if (in[k].bytes) HIP_TRY(hipMemcpyAsync(dev_in + at_in[k], in[k].host, in[k].bytes, hipMemcpyHostToDevice, e->stream));
+    for (size_t k = 0; k < NO; k++) {
+      const HostOut &o = out[k];
+      if (!o.host || !o.keep || !o.bytes) continue;
+      HIP_TRY(hipMemcpyAsync(dev_out + at_out[k], tier == 1 ? pin + ib + at_out[k] : (const char *)o.host, o.bytes,
+                             hipMemcpyHostToDevice, e->stream));
+    }
   }
   void *din[NI], *dout[NO];
   for (size_t k = 0; k < NI; k++) din[k] = dev_in + at_in[k];
@@ -2784,6 +2809,36 @@ int mjpl_clearance_grad(mjpl_engine *e, const double *Q, int64_t N, int32_t layo
   return staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
     return launch_distance(e, DM_GRAD, (const double *)in[0], N, layout, distmax, nullptr, (double *)out[0], (int32_t *)out[1],
                            (double *)out[2], (double *)out[3], (double *)out[4], (int32_t *)out[5]);
+  });
+}
+
+// ---- every pair within distmax: distance, witnesses and gradient (mjpl_distance_grad.h: near_step)
+
+int mjpl_near_pairs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout, double distmax, int32_t K,
+                        int32_t *dcount, int32_t *dpair, double *ddist, double *dgrad, double *dfromto, double *dnormal,
+                        int32_t *dstatus) {
+  int rc = check_query_args(e, dQ, N, layout, distmax, {dcount, dpair, ddist, dgrad, dstatus});
+  if (rc == MJPL_OK && K < 1) rc = fail(MJPL_E_ARG, "K must be >= 1, got %d", K);
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_distance(e, DM_NEAR, dQ, N, layout, distmax, ddist, nullptr, dpair, dgrad, dfromto, dnormal, dstatus, K,
+                         dcount);
+}
+
+int mjpl_near_pairs(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, double distmax, int32_t K, int32_t *count,
+                    int32_t *pair, double *dist, double *grad, double *fromto, double *normal, int32_t *status) {
+  int rc = check_query_args(e, Q, N, layout, distmax, {count, pair, dist, grad, status});
+  if (rc == MJPL_OK && K < 1) rc = fail(MJPL_E_ARG, "K must be >= 1, got %d", K);
+  if (rc != MJPL_OK || N == 0) return rc;
+  const size_t n = N, nk = n * (size_t)K, db = sizeof(double), ib = sizeof(int32_t), np = e->qidx.size();
+  // (all but count and pair are written in the listed slots only: the caller's other bytes are kept)
+  const HostOut outs[] = {{count, n * ib},           {pair, nk * ib},           {dist, nk * db, nullptr, true},
+                          {grad, nk * np * db, nullptr, true}, {fromto, nk * 6 * db, nullptr, true},
+                          {normal, nk * 3 * db, nullptr, true}, {status, nk * ib, nullptr, true}};
+  return staged(e, false, {{Q, n * np * db}}, outs, [&](void **in, void **out) {
+    return launch_distance(e, DM_NEAR, (const double *)in[0], N, layout, distmax, (double *)out[2], nullptr,
+                           (int32_t *)out[1], (double *)out[3], (double *)out[4], (double *)out[5], (int32_t *)out[6], K,
+                           (int32_t *)out[0]);
   });
 }
 

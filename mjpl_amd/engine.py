@@ -132,6 +132,10 @@ ABI = {
     "mjpl_clearance_grad": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P, _I32P, _F64P, _F64P, _F64P,
                                       _I32P]),
     "mjpl_clearance_grad_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_near_pairs": (C.c_int, [_VP, _F64P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _I32P, _I32P, _F64P, _F64P, _F64P,
+                                  _F64P, _I32P]),
+    "mjpl_near_pairs_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                      _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -564,6 +568,36 @@ class Engine:
         int32, dfromto n * 6 and dnormal n * 3 float64 (either may be None).  Asynchronous on the engine's stream."""
         self._ok(self.lib.mjpl_clearance_grad_dev(self.h, dQ, n, layout, float(distmax), dclear, dpair, dgrad, dfromto,
                                                   dnormal, dstatus))
+
+    # -- near pairs: every non-allowed pair below distmax (include/mjpl_hip.h, mjpl_near_pairs*)
+    def near_pairs(self, Q, distmax, max_pairs=32, layout=AOS):
+        """(count int32 [N], pair int32 [N, K], dist float64 [N, K], grad float64 [N, K, nplan], fromto float64
+        [N, K, 6], normal float64 [N, K, 3], status int32 [N, K]), K = max_pairs.  count = the number of non-allowed
+        candidate pairs with distance below distmax (not clipped to K; -1 for non-finite input); the first K of them, in
+        ascending candidate index, fill the row's slots: pair = the index, dist = distances()'s value bit for bit, and
+        grad / fromto / normal / status as clearance_grad() gives them for that pair (status GRAD_OK or
+        GRAD_DEGENERATE).  The remaining slots read pair -1, status -1 and NaN."""
+        Q, n = self._batch(Q, layout)
+        K = int(max_pairs)
+        count, pair = np.zeros(n, np.int32), np.full((n, K), -1, np.int32)
+        dist, grad = np.full((n, K), np.nan), np.full((n, K, self.nplan), np.nan)
+        fromto, normal = np.full((n, K, 6), np.nan), np.full((n, K, 3), np.nan)
+        status = np.full((n, K), -1, np.int32)
+        self._ok(self.lib.mjpl_near_pairs(self.h, Q.ctypes.data_as(_F64P), n, layout, float(distmax), K,
+                                          count.ctypes.data_as(_I32P), pair.ctypes.data_as(_I32P),
+                                          dist.ctypes.data_as(_F64P), grad.ctypes.data_as(_F64P),
+                                          fromto.ctypes.data_as(_F64P), normal.ctypes.data_as(_F64P),
+                                          status.ctypes.data_as(_I32P)))
+        return count, pair, dist, grad, fromto, normal, status
+
+    def near_pairs_dev(self, dQ, n, layout, distmax, max_pairs, dcount, dpair, ddist, dgrad, dstatus, dfromto=None,
+                       dnormal=None):
+        """near_pairs() on device pointers, K = max_pairs: dcount n int32, dpair n * K int32, ddist n * K float64, dgrad
+        n * K * nplan float64, dstatus n * K int32, dfromto n * K * 6 and dnormal n * K * 3 float64 (either may be
+        None).  Slots past a row's count get pair -1 and are otherwise left as they were.  Asynchronous on the engine's
+        stream."""
+        self._ok(self.lib.mjpl_near_pairs_dev(self.h, dQ, n, layout, float(distmax), int(max_pairs), dcount, dpair, ddist,
+                                              dgrad, dfromto, dnormal, dstatus))
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,
