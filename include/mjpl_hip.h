@@ -333,6 +333,62 @@ int mjpl_near_pairs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t lay
                         int32_t *dcount, int32_t *dpair, double *ddist, double *dgrad, double *dfromto,
                         double *dnormal, int32_t *dstatus);
 
+/* ---- push out: move configurations to at least d_min from everything ----------------------
+ * Q_out[i] is q_i moved until its clearance (mjpl_clearance: min over non-allowed pairs of
+ * d_p - margin_p) is at least d_min, by damped least-squares steps on the near pairs' own gradients.
+ * Parameters (mjpl_push_desc): d_min > 0; overshoot >= 0 (1e-3 is a good default); damping > 0
+ * (1e-4); step_max > 0 (0.2); max_iter >= 1 (16); max_pairs K >= 1 (16); lo, hi: HOST arrays of
+ * nplan bounds over the planning columns of mjpl_set_planning, either may be NULL (no bound), in
+ * both forms of the call.
+ *
+ * M = the largest margin_p over the non-allowed candidate pairs (0 without one); D* = d_min + M is the
+ * distmax of every measurement, taken once at the call.  Per row, from q = q_i:
+ *   1. mjpl_near_pairs at q with distmax D* and K slots (no witnesses).
+ *   2. Slot p is violated if dist_p - margin_p < d_min.
+ *   3. A violated slot with status MJPL_GRAD_DEGENERATE ends the row as DEGENERATE; q is not moved.
+ *   4. No violated slot: the row ends.
+ *   5. Over the violated slots in ascending slot order: r_p = d_min + overshoot - (dist_p - margin_p),
+ *      A = damping I + sum g_p g_p^T, b = sum r_p g_p, delta = A^-1 b by a Cholesky factorisation (A is
+ *      positive definite because damping > 0).
+ *   6. If s = max_j |delta_j| > step_max: delta <- delta * (step_max / s).
+ *   7. q <- q + delta, then clamped to [lo, hi] where given.
+ *   8. After max_iter steps without ending, the row ends as it stands.
+ * Near but satisfied pairs take no part in a step; if a step pushes one into violation the next
+ * iteration sees it.  Then ONE mjpl_clearance launch measures Q_out with distmax D* and fills clear
+ * and pair: they are bit-identical to mjpl_clearance(Q_out, D*).  status[i] follows from that number
+ * and nothing else:
+ *   MJPL_PUSH_OK          clear[i] >= d_min.
+ *   MJPL_PUSH_DEGENERATE  otherwise, if the row ended at step 3.
+ *   MJPL_PUSH_STUCK       otherwise: also a d_min no configuration reaches, and a row whose violated
+ *                         pairs lie beyond slot K.  Q_out is the last iterate.
+ *   MJPL_PUSH_NONFINITE   a planning column is non-finite: Q_out = the caller's row, clear NaN, pair -1,
+ *                         iters 0.
+ * iters[i] = the number of steps taken.  A row that needs no push comes back byte for byte with
+ * iters 0.  Q_out has the layout of Q.
+ * A limit worth knowing: two geoms whose distance no planning column can open bound the clearance
+ * from above.  In the Franka-P + 16 obstacles scene two non-allowed pairs of neighbouring links are
+ * such: link0 - link1 stays at 0.033 m whatever the configuration and link1 - link3 never exceeds
+ * 0.031 m, so no larger d_min is reached there and every row ends STUCK.
+ * MJPL_E_ARG: a parameter outside its range, NaN in any parameter or bound, lo > hi in a column, a
+ * NULL descriptor, a NULL output with N > 0, an unknown layout.  MJPL_E_PAIRTYPE as for
+ * mjpl_near_pairs.  MJPL_E_CAPACITY: more than 16 planning columns, or none.  N = 0 launches nothing.
+ * The results depend on no option and no MJPL_* variable.  The host form synchronises.  The device
+ * form enqueues on the engine's stream but is NOT asynchronous: between iterations it synchronises
+ * that stream to read how many rows are still active (4 bytes). */
+#define MJPL_PUSH_OK          0
+#define MJPL_PUSH_STUCK       1
+#define MJPL_PUSH_DEGENERATE  2
+#define MJPL_PUSH_NONFINITE   3
+typedef struct {
+  double d_min, overshoot, damping, step_max;
+  int32_t max_iter, max_pairs;
+  const double *lo, *hi; /* host, [nplan], may be NULL, both forms */
+} mjpl_push_desc;
+int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *desc, const double *Q, int64_t N, int32_t layout,
+                  double *Q_out, double *clear, int32_t *pair, int32_t *iters, int32_t *status);
+int mjpl_push_out_dev(mjpl_engine *e, const mjpl_push_desc *desc, const double *dQ, int64_t N, int32_t layout,
+                      double *dQ_out, double *dclear, int32_t *dpair, int32_t *diters, int32_t *dstatus);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

@@ -1,6 +1,7 @@
-"""Constraint plug-in surface of the MI355X build: the ABC, the three concrete constraints and
+"""Constraint plug-in surface of the MI355X build: the ABC, the four concrete constraints and
 the two composition helpers (obeys / apply).  Collision and pose validation run in
-``libmjpl_hip.so``; joint limits are a NumPy box test."""
+``libmjpl_hip.so``, as does the push of the clearance constraint; joint limits are a NumPy box test."""
+from . import clearance_constraint as _cl
 from . import collision_constraint as _cc
 from . import constraint_interface as _ci
 from . import joint_limit_constraint as _jl
@@ -9,9 +10,10 @@ from . import utils as _u
 
 Constraint = _ci.Constraint
 CollisionConstraint, CollisionRuleset = _cc.CollisionConstraint, _cc.CollisionRuleset
+ClearanceConstraint = _cl.ClearanceConstraint
 JointLimitConstraint = _jl.JointLimitConstraint
 PoseConstraint = _pc.PoseConstraint
 obeys_constraints, apply_constraints = _u.obeys_constraints, _u.apply_constraints
 
-__all__ = ["Constraint", "CollisionConstraint", "CollisionRuleset", "JointLimitConstraint", "PoseConstraint",
+__all__ = ["Constraint", "ClearanceConstraint", "CollisionConstraint", "CollisionRuleset", "JointLimitConstraint", "PoseConstraint",
            "obeys_constraints", "apply_constraints"]

@@ -34,6 +34,7 @@
 #include "mjpl_contacts.h"
 #include "mjpl_distance.h"
 #include "mjpl_distance_grad.h"
+#include "mjpl_push.h"
 
 namespace {
 
@@ -479,6 +480,13 @@ struct mjpl_engine {
   DevBuf<double> d_gr_scratch;
   // column frames scratch rows of one mjpl_near_pairs* launch (mjpl_distance.h: NearOut::frames; grow-only)
   DevBuf<double> d_nr_frames;
+  // mjpl_push_out* (mjpl_push.h): the largest margin of a non-allowed candidate pair (0 without one), made with the
+  // candidate table; per chunk the two work buffers of rows with their ids and fill counters, and the near-pair outputs
+  // of the active rows (grow-only); the pinned word the host reads a counter into
+  double ct_margin_max = 0.0;
+  DevBuf<double> d_push_f64;
+  DevBuf<int> d_push_i32;
+  int *h_push_n = nullptr;
 };
 
 namespace {
@@ -653,6 +661,9 @@ int make_pair_tables(mjpl_engine *e) {
   std::vector<int> ip;
   std::vector<double> dp;
   build_contact_table(e, ip, dp);
+  e->ct_margin_max = 0.0;
+  for (size_t p = 0; p < e->ct_allowed.size(); p++)
+    if (!e->ct_allowed[p]) e->ct_margin_max = std::max(e->ct_margin_max, dp[p * CD_LEN + CD_MARGIN]);
   MJPL_TRY(upload_table(&e->d_ct_ip, ip));
   MJPL_TRY(upload_table(&e->d_ct_dp, dp));
   return upload_table(&e->d_dt, build_distance_table(e));
@@ -1698,6 +1709,7 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->comm) (void)mjpl_comm_destroy(e);
   if (e->h_pin) (void)hipHostFree(e->h_pin);
+  if (e->h_push_n) (void)hipHostFree(e->h_push_n);
   if (e->d_ip) (void)hipFree(e->d_ip);
   if (e->d_dp) (void)hipFree(e->d_dp);
   if (e->d_fp_base) (void)hipFree(e->d_fp_base);
@@ -2602,6 +2614,101 @@ int nearest_range(mjpl_engine *e, NnScratch &s, hipStream_t st, const double *dn
   return MJPL_OK;
 }
 
+// ---- push configurations out to a minimum clearance (mjpl_push.h)
+namespace {
+
+// Argument checks of mjpl_push_out*: check_common, the ranges of the descriptor (NaN refused everywhere), lo <= hi per
+// planning column, every output non-null when N > 0.
+int check_push_args(const mjpl_engine *e, const mjpl_push_desc *d, const void *Q, int64_t N, int layout,
+                    std::initializer_list<const void *> outs) {
+  MJPL_TRY(check_common(e, Q, N, layout));
+  if (!d) return fail(MJPL_E_ARG, "mjpl_push_out: NULL descriptor");
+  if (!(d->d_min > 0)) return fail(MJPL_E_ARG, "d_min must be > 0 (NaN is refused), got %g", d->d_min);
+  if (!(d->overshoot >= 0)) return fail(MJPL_E_ARG, "overshoot must be >= 0 (NaN is refused), got %g", d->overshoot);
+  if (!(d->damping > 0)) return fail(MJPL_E_ARG, "damping must be > 0 (NaN is refused), got %g", d->damping);
+  if (!(d->step_max > 0)) return fail(MJPL_E_ARG, "step_max must be > 0 (NaN is refused), got %g", d->step_max);
+  if (d->max_iter < 1) return fail(MJPL_E_ARG, "max_iter must be >= 1, got %d", d->max_iter);
+  if (d->max_pairs < 1) return fail(MJPL_E_ARG, "max_pairs must be >= 1, got %d", d->max_pairs);
+  for (size_t k = 0; k < e->qidx.size(); k++) {
+    const double lo = d->lo ? d->lo[k] : -INFINITY, hi = d->hi ? d->hi[k] : INFINITY;
+    if (!(lo <= hi)) return fail(MJPL_E_ARG, "bounds of planning column %d: lo %g, hi %g (NaN and lo > hi are refused)", (int)k, lo, hi);
+  }
+  if (N > 0)
+    for (const void *o : outs)
+      if (!o) return fail(MJPL_E_ARG, "NULL output pointer");
+  return MJPL_OK;
+}
+
+// The loop of mjpl_push_out* on device pointers (include/mjpl_hip.h states the iteration).  Per chunk of at most
+// kContactRows rows: gather into work buffer 0, then per iteration one k_distance<DM_NEAR> launch over the active
+// rows, one k_push_step launch, and one 4-byte read of the other buffer's fill counter, which sizes the next
+// iteration (0: the chunk is done).  Then one k_distance<DM_CLEAR> launch over Q_out and the status rule.
+int launch_push(mjpl_engine *e, const mjpl_push_desc &d, const double *dQ, int64_t N, int layout, double *dQ_out,
+                double *dclear, int32_t *dpair, int32_t *diters, int32_t *dstatus) {
+  MJPL_TRY(check_pair_types(e));
+  const int nplan = (int)e->qidx.size(), K = d.max_pairs;
+  if (nplan < 1 || nplan > kPushMaxPlan)
+    return fail(MJPL_E_CAPACITY, "mjpl_push_out: %d planning columns (1..%d supported)", nplan, kPushMaxPlan);
+  const double dstar = d.d_min + e->ct_margin_max;
+  const hipStream_t st = e->stream;
+  if (!e->h_push_n) HIP_TRY(hipHostMalloc((void **)&e->h_push_n, sizeof(int)));
+  // scratch of a chunk: doubles = 2 work buffers [rows][nplan], dist [rows][K], grad [rows][K][nplan];
+  // ints = 2 id lists [rows], count [rows], pair and status [rows][K], then the two counters
+  const size_t rows = (size_t)std::min<int64_t>(N, kContactRows), rk = rows * (size_t)K, rn = rows * (size_t)nplan;
+  MJPL_TRY(e->d_push_f64.reserve(2 * rn + rk + rk * nplan));
+  MJPL_TRY(e->d_push_i32.reserve(3 * rows + 2 * rk + 2));
+  double *work[2] = {e->d_push_f64.p, e->d_push_f64.p + rn};
+  double *ndist = work[1] + rn, *ngrad = ndist + rk;
+  int *ids[2] = {e->d_push_i32.p, e->d_push_i32.p + rows};
+  int *ncount = ids[1] + rows, *npair = ncount + rows, *nstatus = npair + rk, *ctr = nstatus + rk;
+
+  // every row starts as its own answer: Q_out = Q, iters 0, no flag
+  HIP_TRY(hipMemcpyAsync(dQ_out, dQ, (size_t)N * nplan * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(diters, 0, (size_t)N * sizeof(int32_t), st));
+  HIP_TRY(hipMemsetAsync(dstatus, 0, (size_t)N * sizeof(int32_t), st));
+
+  for (int64_t i0 = 0; i0 < N; i0 += (int64_t)rows) {
+    int n = (int)std::min<int64_t>((int64_t)rows, N - i0);
+    hipLaunchKernelGGL(k_push_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dQ, N, i0, n, nplan, layout,
+                       work[0], ids[0]);
+    HIP_TRY(hipGetLastError());
+    for (int it = 0; it < d.max_iter && n > 0; it++) {
+      const int cur = it & 1, nxt = cur ^ 1;
+      MJPL_TRY(launch_distance(e, DM_NEAR, work[cur], n, MJPL_AOS, dstar, ndist, nullptr, npair, ngrad, nullptr, nullptr,
+                               nstatus, K, ncount));
+      HIP_TRY(hipMemsetAsync(ctr + nxt, 0, sizeof(int), st));
+      PushStep a = {};
+      a.rows = work[cur]; a.ids = ids[cur]; a.n = n;
+      a.next_rows = work[nxt]; a.next_ids = ids[nxt]; a.next_n = ctr + nxt;
+      a.K = K; a.count = ncount; a.pair = npair; a.slot_status = nstatus; a.dist = ndist; a.grad = ngrad;
+      a.cd = e->d_ct_dp;
+      a.d_min = d.d_min; a.overshoot = d.overshoot; a.damping = d.damping; a.step_max = d.step_max;
+      a.it = it; a.last = it + 1 == d.max_iter;
+      a.Q_out = dQ_out; a.N = N; a.i0 = i0; a.layout = layout; a.iters = diters; a.flag = dstatus;
+      MJPL_TRY(dispatch_nplan<1, kPushMaxPlan>(nplan, [&](auto NP) -> int {
+        PushBounds<NP()> bd;
+        for (int k = 0; k < NP(); k++) {
+          bd.lo[k] = d.lo ? d.lo[k] : -INFINITY;
+          bd.hi[k] = d.hi ? d.hi[k] : INFINITY;
+        }
+        hipLaunchKernelGGL(k_push_step<NP()>, dim3((unsigned)((n + kPushBlock - 1) / kPushBlock)), dim3(kPushBlock), 0, st, a, bd);
+        HIP_TRY(hipGetLastError());
+        return MJPL_OK;
+      }));
+      if (a.last) break;
+      HIP_TRY(hipMemcpyAsync(e->h_push_n, ctr + nxt, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      n = *e->h_push_n;
+    }
+  }
+  MJPL_TRY(launch_distance(e, DM_CLEAR, dQ_out, N, layout, dstar, nullptr, dclear, dpair));
+  hipLaunchKernelGGL(k_push_status, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, dclear, d.d_min, dstatus);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int mjpl_nearest_dev(mjpl_engine *e, const double *dnodes, int64_t n, int64_t cap, const double *dqueries,
@@ -2839,6 +2946,28 @@ int mjpl_near_pairs(mjpl_engine *e, const double *Q, int64_t N, int32_t layout, 
     return launch_distance(e, DM_NEAR, (const double *)in[0], N, layout, distmax, (double *)out[2], nullptr,
                            (int32_t *)out[1], (double *)out[3], (double *)out[4], (double *)out[5], (int32_t *)out[6], K,
                            (int32_t *)out[0]);
+  });
+}
+
+// ---- push out to a minimum clearance (mjpl_push.h)
+
+int mjpl_push_out_dev(mjpl_engine *e, const mjpl_push_desc *d, const double *dQ, int64_t N, int32_t layout, double *dQ_out,
+                      double *dclear, int32_t *dpair, int32_t *diters, int32_t *dstatus) {
+  int rc = check_push_args(e, d, dQ, N, layout, {dQ_out, dclear, dpair, diters, dstatus});
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_push(e, *d, dQ, N, layout, dQ_out, dclear, dpair, diters, dstatus);
+}
+
+int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *d, const double *Q, int64_t N, int32_t layout, double *Q_out,
+                  double *clear, int32_t *pair, int32_t *iters, int32_t *status) {
+  int rc = check_push_args(e, d, Q, N, layout, {Q_out, clear, pair, iters, status});
+  if (rc != MJPL_OK || N == 0) return rc;
+  const size_t n = N, db = sizeof(double), ib = sizeof(int32_t), qb = n * e->qidx.size() * db;
+  const HostOut outs[] = {{Q_out, qb}, {clear, n * db}, {pair, n * ib}, {iters, n * ib}, {status, n * ib}};
+  return staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
+    return launch_push(e, *d, (const double *)in[0], N, layout, (double *)out[0], (double *)out[1], (int32_t *)out[2],
+                       (int32_t *)out[3], (int32_t *)out[4]);
   });
 }
 

@@ -18,6 +18,8 @@ from .model import Model
 SOA, AOS = 0, 1
 # mjpl_clearance_grad* status values (include/mjpl_hip.h: MJPL_GRAD_*)
 GRAD_OK, GRAD_FLAT, GRAD_DEGENERATE, GRAD_NONFINITE = 0, 1, 2, 3
+# mjpl_push_out* status values (include/mjpl_hip.h: MJPL_PUSH_*)
+PUSH_OK, PUSH_STUCK, PUSH_DEGENERATE, PUSH_NONFINITE = 0, 1, 2, 3
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -84,6 +86,13 @@ class IKDesc(C.Structure):
     ]
 
 
+class PushDesc(C.Structure):
+    _fields_ = [
+        ("d_min", C.c_double), ("overshoot", C.c_double), ("damping", C.c_double), ("step_max", C.c_double),
+        ("max_iter", C.c_int32), ("max_pairs", C.c_int32), ("lo", _F64P), ("hi", _F64P),
+    ]
+
+
 class RrtDesc(C.Structure):
     _fields_ = [
         ("lanes", C.c_int32), ("capacity", C.c_int64), ("epsilon", C.c_double), ("interval_step", C.c_double),
@@ -136,6 +145,8 @@ ABI = {
                                   _F64P, _I32P]),
     "mjpl_near_pairs_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                       _VP]),
+    "mjpl_push_out": (C.c_int, [_VP, C.POINTER(PushDesc), _F64P, C.c_int64, C.c_int32, _F64P, _F64P, _I32P, _I32P, _I32P]),
+    "mjpl_push_out_dev": (C.c_int, [_VP, C.POINTER(PushDesc), _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -598,6 +609,49 @@ class Engine:
         stream."""
         self._ok(self.lib.mjpl_near_pairs_dev(self.h, dQ, n, layout, float(distmax), int(max_pairs), dcount, dpair, ddist,
                                               dgrad, dfromto, dnormal, dstatus))
+
+    # -- push out: configurations moved to a minimum clearance (include/mjpl_hip.h, mjpl_push_out*)
+    def push_desc(self, d_min, overshoot=1e-3, damping=1e-4, step_max=0.2, max_iter=16, max_pairs=16, lo=None, hi=None):
+        """The mjpl_push_desc of a call and the arrays it points into (keep both alive for the call)."""
+        keep = []
+        ptrs = []
+        for b in (lo, hi):
+            if b is None:
+                ptrs.append(None)
+                continue
+            b = _f64(b)
+            if b.shape != (self.nplan,):
+                raise ValueError(f"bounds must have {self.nplan} entries, got {b.shape}")
+            keep.append(b)
+            ptrs.append(b.ctypes.data_as(_F64P))
+        return PushDesc(float(d_min), float(overshoot), float(damping), float(step_max), int(max_iter), int(max_pairs),
+                        ptrs[0], ptrs[1]), keep
+
+    def push_out(self, Q, d_min, layout=AOS, **params):
+        """(Q_out like Q, clear float64 [N], pair int32 [N], iters int32 [N], status int32 [N]): every row moved by
+        damped least-squares steps on its near pairs until its clearance is at least d_min (include/mjpl_hip.h states
+        the iteration; params: overshoot, damping, step_max, max_iter, max_pairs, lo, hi).  clear and pair are
+        clearance(Q_out, d_min + the largest margin) bit for bit; status is PUSH_OK iff clear >= d_min, else
+        PUSH_DEGENERATE / PUSH_STUCK / PUSH_NONFINITE.  Rows that need no push come back byte for byte, iters 0."""
+        Q, n = self._batch(Q, layout)
+        desc, keep = self.push_desc(d_min, **params)
+        out = np.zeros_like(Q)
+        clear, pair = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        iters, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._ok(self.lib.mjpl_push_out(self.h, C.byref(desc), Q.ctypes.data_as(_F64P), n, layout,
+                                        out.ctypes.data_as(_F64P), clear.ctypes.data_as(_F64P),
+                                        pair.ctypes.data_as(_I32P), iters.ctypes.data_as(_I32P),
+                                        status.ctypes.data_as(_I32P)))
+        del keep
+        return out, clear, pair, iters, status
+
+    def push_out_dev(self, dQ, n, layout, d_min, dQ_out, dclear, dpair, diters, dstatus, **params):
+        """push_out() on device pointers: dQ_out n * nplan float64 in dQ's layout, dclear n float64, dpair / diters /
+        dstatus n int32 (lo / hi stay host arrays).  Enqueued on the engine's stream, which it synchronises between
+        iterations: the call returns once the last launches are enqueued, not before the loop has run."""
+        desc, keep = self.push_desc(d_min, **params)
+        self._ok(self.lib.mjpl_push_out_dev(self.h, C.byref(desc), dQ, n, layout, dQ_out, dclear, dpair, diters, dstatus))
+        del keep
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,
