@@ -432,7 +432,10 @@ int32_t mjpl_nearest_last_screen(mjpl_engine *e);
  * mjpl_set_option(e, name, value): MJPL_OK, or MJPL_E_ARG for an unknown name / a value out of range.  Options
  * that shape the compiled model (e.g. "filter") take effect at the next mjpl_set_planning / first launch; the rest
  * at the next call.  Names: the table in tools/README.md ("nn_cells", "nn_cells_min_nodes", "nn_mfma",
- * "nn_sample", "filter", "fused", ...).  mjpl_get_option reads one back. */
+ * "nn_sample", "filter", "fused", ...).  mjpl_get_option reads one back.  "prune_pairs" (default 1) shapes the compiled
+ * model like "filter": the program leaves out every enabled pair proved never to pass its bounding cull -- 1: pairs of a
+ * moving geom with a static geom or a plane, 2: pairs of two moving geoms of one chain as well, 0: none; the read-only
+ * "pairs_pruned" holds how many. */
 int mjpl_set_option(mjpl_engine *e, const char *name, double value);
 int mjpl_get_option(mjpl_engine *e, const char *name, double *value);
 /* the table itself: how many options there are, and option `index`'s name (NULL beyond the table; *writable = 0 for a
@@ -606,6 +609,16 @@ int mjpl_program_dump(const mjpl_model_desc *model, const int32_t *allowed_bodie
                       const int32_t *qidx, int32_t nplan, const double *qpos_base, double filter_tol,
                       int32_t *ip, int32_t *nip, float *fp, double *dp, int32_t *ntab,
                       mjpl_program_info *info);
+/* The same with the option "prune_pairs" as an argument (0, 1 or 2; mjpl_program_dump: 1, the default of an engine) and the
+ * pairs the program leaves out: *ndropped holds the room of `dropped` in pairs on entry (ignored when dropped is
+ * NULL) and the number of dropped pairs on return; `dropped` receives (g1 < g2) geom ids, as many as fit.  These are
+ * enabled pairs -- counted in mjpl_info.npairs -- proved never to come within their bounding radii and margin,
+ * whatever the hinge angles; the candidate tables of mjpl_contacts*, mjpl_distances*,
+ * mjpl_clearance* and mjpl_near_pairs* keep them. */
+int mjpl_program_dump_pruned(const mjpl_model_desc *model, const int32_t *allowed_bodies, int32_t nallowed,
+                             const int32_t *qidx, int32_t nplan, const double *qpos_base, double filter_tol,
+                             int32_t prune_pairs, int32_t *ip, int32_t *nip, float *fp, double *dp, int32_t *ntab,
+                             mjpl_program_info *info, int32_t *dropped, int32_t *ndropped);
 /* Host-only look-up, no device needed: is there a loadable library for this hash (mjpl_program_info.hash with
  * generic = 0, .robot_hash with generic = 1) that was built for this version of the engine?  1 / 0.  A
  * deployment step calls it after mjpl_amd/specialise.py; it is the look-up mjpl_create performs, and like it

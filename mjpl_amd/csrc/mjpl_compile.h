@@ -23,6 +23,7 @@ struct Fnv1a {
 double norm3(const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
 using BodyPairs = std::set<std::pair<int, int>>;  // sorted body-id pairs
+using GeomPairs = std::set<std::pair<int, int>>;  // sorted geom-id pairs (g1 < g2)
 
 bool pair_allowed(const HostModel &m, const BodyPairs &allowed, int g1, int g2) {
   const int b1 = m.geom_bodyid[g1], b2 = m.geom_bodyid[g2];
@@ -129,8 +130,10 @@ int layout_statics(const HostModel &m, const BodyPairs &allowed, ModelLayout *L)
 }
 
 // moving bodies in id order (parents precede children), where each takes its parent's pose from, LDS save slots;
-// moving geoms in processing order, their partners, and register-slot allocation
-int layout_moving(const HostModel &m, const BodyPairs &allowed, ModelLayout *L) {
+// moving geoms in processing order, their partners, and register-slot allocation.  `dropped`: enabled pairs the program
+// leaves out (prune_pairs, below): counted in npairs / npairs_world, on no partner list -- so slots, last_user, wbox /
+// mbox and the per-geom masks follow the reduced lists
+int layout_moving(const HostModel &m, const BodyPairs &allowed, const GeomPairs &dropped, ModelLayout *L) {
   const int ng = m.ngeom;
   for (int b = 1; b < m.nbody; b++)
     if (!L->body_static[b]) L->order.push_back(b);
@@ -159,17 +162,19 @@ int layout_moving(const HostModel &m, const BodyPairs &allowed, ModelLayout *L) 
     const int g = L->mgeoms[k];
     for (int s = 0; s < ng; s++)
       if (L->geom_static[s] && pair_enabled(m, allowed, std::min(g, s), std::max(g, s))) {
+        L->npairs++; L->npairs_world++;
+        if (dropped.count({std::min(g, s), std::max(g, s)})) { L->npruned++; continue; }
         L->world_partners[k].push_back(s);
         note_pair(g, s);
-        L->npairs++; L->npairs_world++;
       }
     for (int k2 = 0; k2 < k; k2++) {
       const int h = L->mgeoms[k2];
       if (!pair_enabled(m, allowed, std::min(g, h), std::max(g, h))) continue;
+      L->npairs++;
+      if (dropped.count({std::min(g, h), std::max(g, h)})) { L->npruned++; continue; }
       L->stored_partners[k].push_back(k2);
       note_pair(g, h);
       L->last_user[k2] = k;
-      L->npairs++;
     }
     if (m.geom_type[g] == GT_PLANE) return fail(MJPL_E_PAIRTYPE, "plane geom %d on a moving body", g);
   }
@@ -197,17 +202,238 @@ int layout_moving(const HostModel &m, const BodyPairs &allowed, ModelLayout *L) 
   return MJPL_OK;
 }
 
-int layout_model(const HostModel &m, const BodyPairs &allowed, const std::vector<int> &qidx, ModelLayout *L) {
+int layout_model(const HostModel &m, const BodyPairs &allowed, const GeomPairs &dropped, const std::vector<int> &qidx,
+                 ModelLayout *L) {
   *L = ModelLayout();
   for (int j = 0; j < m.njnt; j++)
     if (m.jnt_type[j] != JT_SLIDE && m.jnt_type[j] != JT_HINGE)
       return fail(MJPL_E_JOINT, "joint %d has type %d; only slide(2)/hinge(3) are supported", j,
                   m.jnt_type[j]);
   MJPL_TRY(layout_statics(m, allowed, L));
-  MJPL_TRY(layout_moving(m, allowed, L));
+  MJPL_TRY(layout_moving(m, allowed, dropped, L));
   L->col_of.assign(m.nq, -1);
   for (int c = 0; c < (int)qidx.size(); c++) L->col_of[qidx[c]] = c;
   return MJPL_OK;
+}
+
+// ---- stage 1b: enabled pairs whose bounding cull can never pass.  A pair is dropped only on a
+// PROOF over every hinge angle -- planned or not, so neither the planning selection nor the base configuration enters:
+//   the moving geom's centre c lies within rad_k of O_k, the origin of chain body k before its own joints, where
+//   rad_k = the body offsets, twice the joint offsets and the geom offset behind O_k (the ball of scene_table's
+//   `breach`, taken from every ancestor instead of the world origin alone); O_k depends on the hinges in front of it;
+//   with none O_k is a fixed point; with up to kPruneMaxHinges the hinge cube [-pi, pi]^h is bisected: in a cell of
+//   half widths w_i around a centre angle vector, O_k is within sum_i w_i lever_i of its place at the centre (a rotation
+//   by d about an axis moves a point at most d times its distance from a point of the axis, and lever_i bounds the
+//   distance of O_k from hinge i's anchor in every configuration).
+// Dropped when, for some k, in every cell:  |O_k - X| - rad_k - r1 - r2 - margin > kPruneSlack + widen (a plane: the
+// signed height of O_k instead of |O_k - X|), X = the partner's centre: a static geom in the world frame, or an earlier
+// moving geom of the same chain in its own body's frame (only the joints between the two count).  `widen` is what the
+// binary32 culls add to the float64 threshold (float_image, scene_table).  Slide joints on the chain, infinite bounds,
+// partners on another branch, more hinges than kPruneMaxHinges in front of every useful O_k, or a spent budget: kept.
+constexpr double kPruneSlack = 1e-3;        // metres of proved clearance beyond every cull threshold
+constexpr int kPruneMaxHinges = 3;          // hinges the bisection covers
+constexpr int kPrunePairEvals = 8192;       // cell evaluations one pair may spend ...
+constexpr int kPruneModelEvals = 1 << 18;  // ... and all pairs of a model together: the hard budget of a compile, once for
+                                           // the pairs with static geoms and once for the self pairs
+
+struct PruneChain {
+  double bpos[3] = {0, 0, 0}, bquat[4] = {1, 0, 0, 0};  // the frame the chain hangs in
+  std::vector<int> bodies;                               // from that frame down to the moving geom's body
+  double base_reach = 0;                                 // |bpos|
+};
+
+// forward kinematics of bodies[0 .. k) at hinge angles th (in chain order), then the offset `off` in the last frame;
+// line: per hinge its anchor and unit axis in the chain's frame
+void prune_point(const HostModel &m, const PruneChain &c, int k, const double *th, const double *off, double *out,
+                 double *line) {
+  double pos[3] = {c.bpos[0], c.bpos[1], c.bpos[2]}, quat[4] = {c.bquat[0], c.bquat[1], c.bquat[2], c.bquat[3]};
+  int h = 0;
+  for (int i = 0; i < k; i++) {
+    const int b = c.bodies[i];
+    double d[3], q[4];
+    rot_vec_quat(d, &m.body_pos[3 * b], quat);
+    for (int a = 0; a < 3; a++) pos[a] += d[a];
+    mul_quat(q, quat, &m.body_quat[4 * b]);
+    normalize4(q);
+    for (int a = 0; a < 4; a++) quat[a] = q[a];
+    for (int j = 0; j < m.body_jntnum[b]; j++, h++) {
+      const int jid = m.body_jntadr[b] + j;
+      const double *ax = &m.jnt_axis[3 * jid], n = norm3(ax), inv = 1.0 / (n > 0 ? n : 1.0), s = std::sin(0.5 * th[h]) * inv;
+      const double jq[4] = {std::cos(0.5 * th[h]), s * ax[0], s * ax[1], s * ax[2]};
+      double anchor[3], back[3], axw[3];
+      rot_vec_quat(anchor, &m.jnt_pos[3 * jid], quat);
+      rot_vec_quat(axw, ax, quat);
+      for (int a = 0; a < 3; a++) { line[6 * h + a] = pos[a] + anchor[a]; line[6 * h + 3 + a] = axw[a] * inv; }
+      mul_quat(q, quat, jq);
+      normalize4(q);
+      for (int a = 0; a < 4; a++) quat[a] = q[a];
+      rot_vec_quat(back, &m.jnt_pos[3 * jid], quat);
+      for (int a = 0; a < 3; a++) pos[a] += anchor[a] - back[a];
+    }
+  }
+  rot_vec_quat(out, off, quat);
+  for (int a = 0; a < 3; a++) out[a] += pos[a];
+}
+
+// true: proved.  X: the partner's centre in the chain's frame; nrm: a plane partner's normal (else nullptr); rsum: bounding
+// radii and margin; need: kPruneSlack + widen; *evals: the model's counter.  Cells are split worst first (the one
+// whose bound on the gap is lowest), so a pair that does come within reach is given up at the first cell centre that
+// shows it, and a proof ends when the worst cell left is clear.
+bool prune_prove(const HostModel &m, const PruneChain &c, int g, const double *X, const double *nrm, double rsum, double need,
+                 int *evals) {
+  const int n = (int)c.bodies.size();
+  auto jlen = [&](int b, int from) {  // twice the joint offsets of body b from its joint `from` on
+    double s = 0;
+    for (int j = from; j < m.body_jntnum[b]; j++) s += 2.0 * norm3(&m.jnt_pos[3 * (m.body_jntadr[b] + j)]);
+    return s;
+  };
+  int pair_evals = 0;
+  // k = n: the geom's centre itself (rad 0)
+  for (int k = 0, nh = 0; k <= n; nh += k < n ? m.body_jntnum[c.bodies[k]] : 0, k++) {
+    if (nh > kPruneMaxHinges) break;
+    const double *off = k < n ? &m.body_pos[3 * c.bodies[k]] : &m.geom_pos[3 * g];
+    double rad = 0;
+    if (k < n) {
+      rad = norm3(&m.geom_pos[3 * g]);
+      for (int i = k; i < n; i++) rad += jlen(c.bodies[i], 0) + (i > k ? norm3(&m.body_pos[3 * c.bodies[i]]) : 0.0);
+    }
+    double lever[kPruneMaxHinges] = {0, 0, 0};  // O_k from hinge i's anchor, at most, in every configuration
+    for (int i = 0, h = 0; i < k; i++)
+      for (int j = 0; j < m.body_jntnum[c.bodies[i]]; j++, h++) {
+        double l = norm3(&m.jnt_pos[3 * (m.body_jntadr[c.bodies[i]] + j)]) + jlen(c.bodies[i], j + 1);
+        for (int t = i + 1; t < k; t++) l += norm3(&m.body_pos[3 * c.bodies[t]]) + jlen(c.bodies[t], 0);
+        lever[h] = l + norm3(off);
+      }
+    struct Cell {
+      double th[kPruneMaxHinges], w[kPruneMaxHinges], low;  // low: a lower bound of the gap over the cell
+      int widest;
+      bool operator<(const Cell &o) const { return low > o.low; }
+    };
+    // false: the pair comes within reach at the cell's centre (no finer cell proves this k)
+    auto bound_cell = [&](Cell &cell) {
+      double O[3], line[6 * kPruneMaxHinges];
+      prune_point(m, c, k, cell.th, off, O, line);
+      const double d[3] = {O[0] - X[0], O[1] - X[1], O[2] - X[2]};
+      const double gap = (nrm ? nrm[0] * d[0] + nrm[1] * d[1] + nrm[2] * d[2] : norm3(d)) - rad - rsum - need;
+      // hinge i moves O_k by at most w_i times its distance from the axis: that distance at the centre plus what the
+      // hinges behind i can add to it inside the cell, and never more than the lever
+      double sway = 0, behind = 0, most = -1.0;
+      cell.widest = 0;
+      for (int h = nh - 1; h >= 0; h--) {
+        const double *a = &line[6 * h], r[3] = {O[0] - a[0], O[1] - a[1], O[2] - a[2]};
+        const double x[3] = {r[1] * a[5] - r[2] * a[4], r[2] * a[3] - r[0] * a[5], r[0] * a[4] - r[1] * a[3]};
+        const double arm = std::fmin(lever[h], norm3(x) + behind), part = cell.w[h] * arm;
+        sway += part;
+        behind += cell.w[h] * lever[h];
+        if (part > most) { most = part; cell.widest = h; }
+      }
+      cell.low = gap - sway;
+      return gap > 0;
+    };
+    std::priority_queue<Cell> todo;
+    Cell root;
+    for (int h = 0; h < kPruneMaxHinges; h++) { root.th[h] = 0.0; root.w[h] = h < nh ? 3.14159265358979323846 : 0.0; }
+    if (++pair_evals > kPrunePairEvals || ++*evals > kPruneModelEvals) return false;
+    bool ok = bound_cell(root);
+    todo.push(root);
+    while (ok && todo.top().low <= 0) {
+      const Cell cell = todo.top();
+      todo.pop();
+      if ((pair_evals += 2) > kPrunePairEvals || (*evals += 2) > kPruneModelEvals) return false;
+      Cell lo = cell, hi = cell;
+      lo.w[cell.widest] = hi.w[cell.widest] = 0.5 * cell.w[cell.widest];
+      lo.th[cell.widest] -= lo.w[cell.widest];
+      hi.th[cell.widest] += hi.w[cell.widest];
+      ok = bound_cell(lo) && bound_cell(hi);
+      todo.push(lo);
+      todo.push(hi);
+    }
+    if (ok) return true;
+  }
+  return false;
+}
+
+// the chain from `top` (exclusive: a static body, or the earlier geom's body) down to body b; false: b does not hang
+// below `top`, or a slide joint lies between
+bool prune_chain(const HostModel &m, const ModelLayout &L, int b, int top, PruneChain *c) {
+  c->bodies.clear();
+  for (int x = b; x != top; x = m.body_parentid[x]) {
+    if (x == 0 || L.body_static[x]) {
+      if (top >= 0) return false;
+      break;
+    }
+    for (int j = 0; j < m.body_jntnum[x]; j++)
+      if (m.jnt_type[m.body_jntadr[x] + j] != JT_HINGE) return false;
+    c->bodies.push_back(x);
+  }
+  if (c->bodies.empty()) return false;
+  std::reverse(c->bodies.begin(), c->bodies.end());
+  if (top < 0) {
+    const int p = m.body_parentid[c->bodies[0]];
+    for (int a = 0; a < 3; a++) c->bpos[a] = L.st_xpos[3 * p + a];
+    for (int a = 0; a < 4; a++) c->bquat[a] = L.st_xquat[4 * p + a];
+  }
+  c->base_reach = norm3(c->bpos);
+  return true;
+}
+
+// L: the layout with every enabled pair on its lists; tol, poison_slack: the band and the widening float_image applies
+// (upper bounds of what the reduced program will use); self_pairs: pairs of two moving geoms as well (option "prune_pairs"
+// = 2).  Returns the cell evaluations spent.
+int prune_pairs(const HostModel &m, const ModelLayout &L, double tol, double poison_slack, bool self_pairs,
+                GeomPairs *dropped) {
+  dropped->clear();
+  const int nm = (int)L.mgeoms.size();
+  const double u24 = std::ldexp(1.0, -24);
+  // (two counters, each with the model's budget: what the scene costs must not change which SELF pairs are proved -- the
+  //  robot hash of a scene-generic library covers them)
+  int evals = 0, self_evals = 0;
+  for (int k = 0; k < nm; k++) {
+    const int g = L.mgeoms[k], b = m.geom_bodyid[g];
+    // what the binary32 culls add to the float64 threshold thr of a partner at distance nx from the frame's origin:
+    // the band and the pose error (at most half of it) of float_image, the form's allowance of scene_table /
+    // expanded_threshold in squared distances (sqrt(thr^2 + a) <= thr + a / (2 thr)), the rounding of the thresholds
+    auto widen = [&](const PruneChain &c, double nx, double thr, bool plane) {
+      double reach = c.base_reach + norm3(&m.geom_pos[3 * g]);
+      for (int x : c.bodies) {
+        reach += norm3(&m.body_pos[3 * x]);
+        for (int j = 0; j < m.body_jntnum[x]; j++) reach += 2.0 * norm3(&m.jnt_pos[3 * (m.body_jntadr[x] + j)]);
+      }
+      const double s = 1.01 * reach + nx;
+      // (8 u s^2 is the allowance the threshold is raised by; the computed |c|^2 + a . c may fall short of the real value
+      //  by up to 6 u s^2 more -- three squares, three products, their sums: 14 u s^2 in all)
+      const double form = plane ? 4.0 * u24 * (s + thr) : 14.0 * u24 * s * s / (2.0 * thr);
+      return 2.0 * tol + poison_slack + form + 1e-5 * (thr + s);
+    };
+    PruneChain c;
+    if (!prune_chain(m, L, b, -1, &c)) continue;  // (a slide joint above the geom: unbounded reach, every pair kept)
+    {
+      for (int sgeom : L.world_partners[k]) {
+        const bool plane = m.geom_type[sgeom] == GT_PLANE;
+        const PairBound pb = pair_bound(m, std::min(g, sgeom), std::max(g, sgeom), plane ? sgeom : -1);
+        if (!std::isfinite(pb.bound)) continue;
+        const double rsum = plane ? pb.bound : std::sqrt(pb.bound);  // (radii and margin)
+        if (!(rsum > 0)) continue;
+        const double *X = &L.st_gxpos[3 * sgeom], *gm = &L.st_gxmat[9 * sgeom];
+        const double nrm[3] = {gm[2], gm[5], gm[8]};
+        if (prune_prove(m, c, g, X, plane ? nrm : nullptr, rsum, kPruneSlack + widen(c, norm3(X), rsum, plane), &evals))
+          dropped->insert({std::min(g, sgeom), std::max(g, sgeom)});
+      }
+    }
+    if (!self_pairs) continue;
+    for (int k2 : L.stored_partners[k]) {
+      const int h = L.mgeoms[k2];
+      const PairBound pb = pair_bound(m, std::min(g, h), std::max(g, h), -1);
+      if (!std::isfinite(pb.bound) || !(pb.bound > 0)) continue;
+      PruneChain cm;  // (the frame of h's body: identity)
+      if (!prune_chain(m, L, b, m.geom_bodyid[h], &cm)) continue;
+      // (the kernels compare the two centres in the world frame: the form's rounding is that of the world chain's reach)
+      const double rsum = std::sqrt(pb.bound);
+      if (prune_prove(m, cm, g, &m.geom_pos[3 * h], nullptr, rsum, kPruneSlack + widen(c, 0.0, rsum, false), &self_evals))
+        dropped->insert({std::min(g, h), std::max(g, h)});
+    }
+  }
+  return std::min(evals, kPruneModelEvals) + std::min(self_evals, kPruneModelEvals);  // cell evaluations spent
 }
 
 // ---- stage 2: ip / dp
@@ -469,14 +695,8 @@ FilterBound filter_error_bound(const HostModel &m, const ModelLayout &L, float t
   return fb;
 }
 
-// ---- stage 4: the filter's float32 image: same offsets; cull bounds widened by the tolerance so that
-// a pair culled in float32 is certainly culled (or contact-free) in float64
-void float_image(const std::vector<int> &ip, const std::vector<double> &dp, const BoundSites &sites, const FilterBound &fb,
-                 std::vector<float> &fp) {
-  fp.resize(dp.size());
-  for (size_t k = 0; k < dp.size(); k++) fp[k] = (float)dp[k];
-  // (a poisoned static geom's own rounding may exceed the band: its bounds are widened by that, too)
-  const double tol = fb.tol;
+// a poisoned static geom's own rounding may exceed the band: every cull bound of the float image is widened by that, too
+double poison_widening(const std::vector<int> &ip, const std::vector<double> &dp, const FilterBound &fb) {
   double poison_slack = 0;
   for (int w : fb.poison_rows) {
     const double *wt = &dp[(size_t)ip[H_OFF_WCULL]];
@@ -486,6 +706,16 @@ void float_image(const std::vector<int> &ip, const std::vector<double> &dp, cons
                        std::fabs(rn[WN_SIZE + 1]) + std::fabs(rn[WN_SIZE + 2]);
     poison_slack = std::fmax(poison_slack, 4 * std::ldexp(1.0, -24) * mag);
   }
+  return poison_slack;
+}
+
+// ---- stage 4: the filter's float32 image: same offsets; cull bounds widened by the tolerance so that
+// a pair culled in float32 is certainly culled (or contact-free) in float64
+void float_image(const std::vector<int> &ip, const std::vector<double> &dp, const BoundSites &sites, const FilterBound &fb,
+                 std::vector<float> &fp) {
+  fp.resize(dp.size());
+  for (size_t k = 0; k < dp.size(); k++) fp[k] = (float)dp[k];
+  const double tol = fb.tol, poison_slack = poison_widening(ip, dp, fb);
   for (size_t k : sites.sq_bound_at)
     if (std::isfinite(dp[k])) {
       const double r = std::sqrt(dp[k]) + tol + poison_slack;
@@ -659,12 +889,44 @@ void scene_table(const HostModel &m, const ModelLayout &L, const FilterBound &fb
   }
 }
 
+// Stage 1b's driver: e->pruned from the program with every enabled pair.  That program is compiled as far as its error
+// bound, because the proof's margin covers the band IT would run with -- the reduced program's band is no wider (the
+// floor of filter_error_bound is a maximum over the pairs left).  Nothing the result depends on changes with the
+// planning selection, so it is kept until the switch or the tolerance asked for changes.
+int find_pruned_pairs(mjpl_engine *e) {
+  if (!e->prune_pairs) {
+    e->pruned.clear();
+    e->pruned_valid = false;
+    return MJPL_OK;
+  }
+  if (e->pruned_valid && e->pruned_level == e->prune_pairs && e->pruned_tol_req == e->filter_tol_req &&
+      e->pruned_tol_user == e->filter_tol_user)
+    return MJPL_OK;
+  ModelLayout full;
+  MJPL_TRY(layout_model(e->m, e->allowed, GeomPairs(), e->qidx, &full));
+  std::vector<int> ip;
+  std::vector<double> dp;
+  BoundSites sites;
+  emit_program(e->m, full, e->qidx, e->qbase, ip, dp, &sites);
+  const FilterBound fb = filter_error_bound(e->m, full, e->filter_tol_req, e->filter_tol_user, ip, dp);
+  // (a filter that steps aside for the full program may serve the reduced one: then with the band asked for, or a default
+  //  one below the centimetre filter_error_bound gives up at)
+  const double tol = fb.usable ? fb.tol : (e->filter_tol_user ? e->filter_tol_req : 1e-2);
+  e->prune_evals = prune_pairs(e->m, full, tol, poison_widening(ip, dp, fb), e->prune_pairs >= 2, &e->pruned);
+  e->pruned_valid = true;
+  e->pruned_level = e->prune_pairs;
+  e->pruned_tol_req = e->filter_tol_req;
+  e->pruned_tol_user = e->filter_tol_user;
+  return MJPL_OK;
+}
+
 // Stages 1 to 6: the engine's host tables, bound and hashes from its model, allowed pairs, planning selection and
 // tolerance.  No HIP call, no device: mjpl_program_dump ends here; e->scene is non-empty exactly when the program
 // satisfies what a scene-generic library assumes.
 int compile_host(mjpl_engine *e) {
   const HostModel &m = e->m;
-  MJPL_TRY(layout_model(m, e->allowed, e->qidx, &e->lay));
+  MJPL_TRY(find_pruned_pairs(e));
+  MJPL_TRY(layout_model(m, e->allowed, e->pruned, e->qidx, &e->lay));
   BoundSites sites;
   emit_program(m, e->lay, e->qidx, e->qbase, e->ip, e->dp, &sites);
   e->fb = filter_error_bound(m, e->lay, e->filter_tol_req, e->filter_tol_user, e->ip, e->dp);

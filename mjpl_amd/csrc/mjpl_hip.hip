@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <queue>
 #include <set>
 #include <string>
 #include <type_traits>
@@ -268,6 +269,7 @@ struct ModelLayout {
   int nslots = 0, nsave = 0, maxs = 4;
   bool wbox = false, mbox = false;
   int npairs = 0, npairs_world = 0, nmoving = 0, nplanes = 0;  // (nmoving: moving geoms; nplanes: static planes)
+  int npruned = 0;  // enabled pairs (counted in npairs) on no partner list: proved never to pass their cull
   int nworld() const { return (int)winfo.size(); }  // static geoms: every one has a row
   int moving_base() const { return mgeoms.empty() ? 0 : mgeoms[0]; }  // model id of the first moving geom
 };
@@ -355,6 +357,14 @@ struct mjpl_engine {
   float filter_tol_req = 1e-4f;   // what the caller (or the default) asked for
   bool filter_tol_user = false;   // asked for through mjpl_set_filter / MJPL_FILTER_TOL
   FilterBound fb;                 // the band in force, and whether the filter serves this model at all
+  // option "prune_pairs": the program leaves out the enabled pairs proved never to pass their bounding cull (mjpl_compile.h:
+  // prune_pairs) -- 1: pairs of a moving geom with a static geom or a plane, 2: pairs of two moving geoms of one chain as well;
+  // `pruned` holds them as (g1 < g2), found once per model, level and tolerance asked for
+  int prune_pairs = 1, pruned_level = 0;
+  std::set<std::pair<int, int>> pruned;
+  bool pruned_valid = false, pruned_tol_user = false;
+  float pruned_tol_req = 0.0f;
+  int prune_evals = 0;  // cell evaluations the proofs took (of kPruneModelEvals); read-only option "prune_evals"
   uint64_t program_hash = 0;      // FNV-1a of the compiled tables (ip, fp, dp), the kernel variant and the header digest
   const SpecLib *spec = nullptr;  // this model's own filter kernels, if a library for program_hash was found
   // ... or, failing that, a scene-generic library of the ROBOT (robot_hash: moving bodies, their geoms and
@@ -1728,6 +1738,14 @@ void mjpl_destroy(mjpl_engine *e) {
 int mjpl_program_dump(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t nallowed, const int32_t *qidx,
                       int32_t nplan, const double *qpos_base, double filter_tol, int32_t *ip, int32_t *nip, float *fp,
                       double *dp, int32_t *ntab, mjpl_program_info *info) {
+  return mjpl_program_dump_pruned(d, allowed_bodies, nallowed, qidx, nplan, qpos_base, filter_tol, 1, ip, nip, fp, dp, ntab, info,
+                                  nullptr, nullptr);
+}
+
+int mjpl_program_dump_pruned(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t nallowed, const int32_t *qidx,
+                             int32_t nplan, const double *qpos_base, double filter_tol, int32_t prune_pairs, int32_t *ip,
+                             int32_t *nip, float *fp, double *dp, int32_t *ntab, mjpl_program_info *info, int32_t *dropped,
+                             int32_t *ndropped) {
   if (!d || !nip || !ntab || !info) return fail(MJPL_E_ARG, "mjpl_program_dump: NULL argument");
   if (d->nq < 0 || d->njnt < 0 || d->nbody < 1 || d->ngeom < 0 || nallowed < 0) return fail(MJPL_E_ARG, "negative size");
   if (d->nq != d->njnt) return fail(MJPL_E_JOINT, "nq != njnt: only 1-DoF joints are supported");
@@ -1741,7 +1759,18 @@ int mjpl_program_dump(const mjpl_model_desc *d, const int32_t *allowed_bodies, i
   }
   if (qpos_base) e->qbase.assign(qpos_base, qpos_base + d->nq);
   if (filter_tol > 0.0) { e->filter_tol_req = (float)filter_tol; e->filter_tol_user = true; }
+  if (prune_pairs < 0 || prune_pairs > 2) return fail(MJPL_E_ARG, "mjpl_program_dump_pruned: prune_pairs must be 0, 1 or 2");
+  e->prune_pairs = prune_pairs;
   if ((rc = compile_host(e.get())) != MJPL_OK) return rc;  // (host tables only: nothing is allocated or uploaded)
+  if (ndropped) {  // (in: room for that many pairs in `dropped`; out: how many the program leaves out)
+    const int32_t room = dropped ? *ndropped : 0;
+    int32_t n = 0;
+    for (const auto &gp : e->pruned) {
+      if (n < room) { dropped[2 * n] = gp.first; dropped[2 * n + 1] = gp.second; }
+      n++;
+    }
+    *ndropped = n;
+  }
   memset(info, 0, sizeof(*info));
   info->hash = e->program_hash;
   // (maxs: the slot-file width of the FILTER kernels a library is built around -- 24 for the queued build of models with
@@ -1983,6 +2012,9 @@ const EngineOption kEngineOptions[] = {
     // ---- what shapes the compiled model or the launch pipeline (take effect at the next mjpl_set_planning / mjpl_set_spec /
     //      mjpl_set_filter, which compile again; the launch-time ones at the next launch)
     MJPL_OPT_BOOL("filter", filter),
+    MJPL_OPT_INT("prune_pairs", prune_pairs, 0, 2),
+    {"pairs_pruned", [](mjpl_engine *e) { return (double)e->lay.npruned; }, nullptr},
+    {"prune_evals", [](mjpl_engine *e) { return (double)(e->prune_pairs ? e->prune_evals : 0); }, nullptr},
     MJPL_OPT_BOOL("two_pass", two_pass),
     MJPL_OPT_BOOL("force_immediate", force_immediate),
     MJPL_OPT_BOOL("expand", expand),

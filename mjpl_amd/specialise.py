@@ -63,10 +63,10 @@ class ProgramInfo(C.Structure):
                 ("robot_hash", C.c_uint64), ("scene_rows", C.c_int32), ("scene_ok", C.c_int32)]
 
 
-def dump_program(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0):
-    """Compile `model` on the host (no GPU) -> (ip int32[], fp float32[], dp float64[], ProgramInfo)."""
+def _dump(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, prune_pairs):
+    """mjpl_program_dump (prune_pairs None) or mjpl_program_dump_pruned -> (ip, fp, dp, ProgramInfo, dropped int32 [n, 2])."""
     lib = _engine.load_library()
-    f = lib.mjpl_program_dump
+    f = lib.mjpl_program_dump if prune_pairs is None else lib.mjpl_program_dump_pruned
     f.restype = C.c_int
     d = _engine._ModelDesc()
     d.nq, d.njnt, d.nbody, d.ngeom = model.nq, model.njnt, model.nbody, model.ngeom
@@ -80,22 +80,42 @@ def dump_program(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, 
     q = None if qidx is None else _engine._i32(qidx)
     base = None if qpos_base is None else _engine._f64(qpos_base)
     info = ProgramInfo()
-    nip, ntab = C.c_int32(0), C.c_int32(0)
+    nip, ntab, ndrop = C.c_int32(0), C.c_int32(0), C.c_int32(0)
 
-    def call(ip, fp, dp):
-        rc = f(C.byref(d), pairs.ctypes.data_as(_engine._I32P), len(pairs),
-               None if q is None else q.ctypes.data_as(_engine._I32P), 0 if q is None else len(q),
-               None if base is None else base.ctypes.data_as(_engine._F64P), C.c_double(filter_tol),
-               None if ip is None else ip.ctypes.data_as(_engine._I32P), C.byref(nip),
-               None if fp is None else fp.ctypes.data_as(C.POINTER(C.c_float)),
-               None if dp is None else dp.ctypes.data_as(_engine._F64P), C.byref(ntab), C.byref(info))
+    def call(ip, fp, dp, dropped=None):
+        args = [C.byref(d), pairs.ctypes.data_as(_engine._I32P), len(pairs),
+                None if q is None else q.ctypes.data_as(_engine._I32P), 0 if q is None else len(q),
+                None if base is None else base.ctypes.data_as(_engine._F64P), C.c_double(filter_tol)]
+        if prune_pairs is not None:
+            args.append(C.c_int32(int(prune_pairs)))
+        args += [None if ip is None else ip.ctypes.data_as(_engine._I32P), C.byref(nip),
+                 None if fp is None else fp.ctypes.data_as(C.POINTER(C.c_float)),
+                 None if dp is None else dp.ctypes.data_as(_engine._F64P), C.byref(ntab), C.byref(info)]
+        if prune_pairs is not None:
+            ndrop.value = 0 if dropped is None else len(dropped)
+            args += [None if dropped is None else dropped.ctypes.data_as(_engine._I32P), C.byref(ndrop)]
+        rc = f(*args)
         if rc != 0:
             raise _engine.MjplError(rc, lib.mjpl_last_error().decode())
 
     call(None, None, None)
     ip, fp, dp = np.zeros(nip.value, np.int32), np.zeros(ntab.value, np.float32), np.zeros(ntab.value, np.float64)
-    call(ip, fp, dp)
-    return ip, fp, dp, info
+    dropped = np.zeros((ndrop.value, 2), np.int32)
+    call(ip, fp, dp, dropped)
+    return ip, fp, dp, info, dropped
+
+
+def dump_program(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0):
+    """Compile `model` on the host (no GPU) -> (ip int32[], fp float32[], dp float64[], ProgramInfo): the program an
+    engine runs by default."""
+    return _dump(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, None)[:4]
+
+
+def dump_program_pruned(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, prune_pairs: int = 1):
+    """dump_program with the option "prune_pairs" forced (0: every enabled pair stays in the program, 1: the default, 2: self
+    pairs are dropped as well) -> (ip, fp, dp, ProgramInfo, dropped): dropped = the geom pairs the program leaves out,
+    int32 [n, 2], g1 < g2."""
+    return _dump(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, int(prune_pairs))
 
 
 # ----------------------------------------------------------------------------- expression helpers
