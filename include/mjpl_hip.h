@@ -435,7 +435,10 @@ int32_t mjpl_nearest_last_screen(mjpl_engine *e);
  * "nn_sample", "filter", "fused", ...).  mjpl_get_option reads one back.  "prune_pairs" (default 1) shapes the compiled
  * model like "filter": the program leaves out every enabled pair proved never to pass its bounding cull -- 1: pairs of a
  * moving geom with a static geom or a plane, 2: pairs of two moving geoms of one chain as well, 0: none; the read-only
- * "pairs_pruned" holds how many. */
+ * "pairs_pruned" holds how many.  "prune_contacts" (default 1; 0: off) likewise: pairs of a moving geom with a static geom
+ * or a plane proved never to come within their margin are left out of a per-program library's generated check -- the
+ * tables keep them, the program hash covers the set when it is not empty; read-only "pairs_never_touch",
+ * "prune_contact_evals". */
 int mjpl_set_option(mjpl_engine *e, const char *name, double value);
 int mjpl_get_option(mjpl_engine *e, const char *name, double *value);
 /* the table itself: how many options there are, and option `index`'s name (NULL beyond the table; *writable = 0 for a
@@ -619,6 +622,18 @@ int mjpl_program_dump_pruned(const mjpl_model_desc *model, const int32_t *allowe
                              const int32_t *qidx, int32_t nplan, const double *qpos_base, double filter_tol,
                              int32_t prune_pairs, int32_t *ip, int32_t *nip, float *fp, double *dp, int32_t *ntab,
                              mjpl_program_info *info, int32_t *dropped, int32_t *ndropped);
+/* The side set of the program compiled with the options "prune_pairs" and "prune_contacts" as given: the enabled pairs of
+ * a moving geom with a static geom or a plane proved never to come within their contact margin, whatever the hinge angles
+ * (DESIGN.md section 5.1d).  They stay in ip / fp / dp and in every table; a per-program library's generated check leaves
+ * them out, and the program hash (*hash) covers the set when it is not empty.  *npairs: room of `pairs` in pairs on entry
+ * (ignored when pairs is NULL), the size of the set on return; `pairs` receives (g1 < g2) geom ids, as many as fit;
+ * *evals: cell evaluations the proofs took; *tables_hash: the hash of ip / fp / dp alone, which is the program hash of an
+ * empty set.  prune_contacts: 0 the empty set, 1 an engine's default, >= 2 that many cell
+ * evaluations per pair at most (tests). */
+int mjpl_program_dump_never_touch(const mjpl_model_desc *model, const int32_t *allowed_bodies, int32_t nallowed,
+                                  const int32_t *qidx, int32_t nplan, const double *qpos_base, double filter_tol,
+                                  int32_t prune_pairs, int32_t prune_contacts, int32_t *pairs, int32_t *npairs,
+                                  int32_t *evals, uint64_t *hash, uint64_t *tables_hash);
 /* Host-only look-up, no device needed: is there a loadable library for this hash (mjpl_program_info.hash with
  * generic = 0, .robot_hash with generic = 1) that was built for this version of the engine?  1 / 0.  A
  * deployment step calls it after mjpl_amd/specialise.py; it is the look-up mjpl_create performs, and like it

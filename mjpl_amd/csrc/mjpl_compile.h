@@ -245,7 +245,7 @@ struct PruneChain {
 // forward kinematics of bodies[0 .. k) at hinge angles th (in chain order), then the offset `off` in the last frame;
 // line: per hinge its anchor and unit axis in the chain's frame
 void prune_point(const HostModel &m, const PruneChain &c, int k, const double *th, const double *off, double *out,
-                 double *line) {
+                 double *line, double *quat_out = nullptr) {
   double pos[3] = {c.bpos[0], c.bpos[1], c.bpos[2]}, quat[4] = {c.bquat[0], c.bquat[1], c.bquat[2], c.bquat[3]};
   int h = 0;
   for (int i = 0; i < k; i++) {
@@ -273,6 +273,58 @@ void prune_point(const HostModel &m, const PruneChain &c, int k, const double *t
   }
   rot_vec_quat(out, off, quat);
   for (int a = 0; a < 3; a++) out[a] += pos[a];
+  if (quat_out)  // (the last frame's orientation: stage 1c places a whole geom with it)
+    for (int a = 0; a < 4; a++) quat_out[a] = quat[a];
+}
+
+// twice the joint offsets of body b from its joint `from` on
+double prune_jlen(const HostModel &m, int b, int from) {
+  double s = 0;
+  for (int j = from; j < m.body_jntnum[b]; j++) s += 2.0 * norm3(&m.jnt_pos[3 * (m.body_jntadr[b] + j)]);
+  return s;
+}
+
+// lever[h]: how far a point at most `tail` from the origin of chain body k's frame (before its joints; k = n: the last
+// body's frame) can be from the anchor of hinge h, a hinge of bodies[0 .. k), in every configuration
+void prune_levers(const HostModel &m, const PruneChain &c, int k, double tail, double *lever) {
+  for (int i = 0, h = 0; i < k; i++)
+    for (int j = 0; j < m.body_jntnum[c.bodies[i]]; j++, h++) {
+      double l = norm3(&m.jnt_pos[3 * (m.body_jntadr[c.bodies[i]] + j)]) + prune_jlen(m, c.bodies[i], j + 1);
+      for (int t = i + 1; t < k; t++) l += norm3(&m.body_pos[3 * c.bodies[t]]) + prune_jlen(m, c.bodies[t], 0);
+      lever[h] = l + tail;
+    }
+}
+
+// The worst-first bisection of the hinge cube [-pi, pi]^nh, shared by stages 1b and 1c.  bound_cell(cell) sets cell.low, a
+// lower bound of the gap over the cell, and cell.widest, the hinge to split next; it returns false when the cell's centre
+// itself is within the bound (no finer cell helps).  1: the worst cell left is clear -- proved; 0: a centre refused;
+// -1: the pair's budget or the model's is spent (*pair_evals and *evals count the cell evaluations).
+struct PruneCell {
+  double th[kPruneMaxHinges], w[kPruneMaxHinges], low;
+  int widest;
+  bool operator<(const PruneCell &o) const { return low > o.low; }
+};
+template <class BoundCell>
+int prune_bisect(int nh, int *pair_evals, int pair_budget, int *evals, int model_budget, BoundCell &&bound_cell) {
+  std::priority_queue<PruneCell> todo;
+  PruneCell root;
+  for (int h = 0; h < kPruneMaxHinges; h++) { root.th[h] = 0.0; root.w[h] = h < nh ? 3.14159265358979323846 : 0.0; }
+  if (++*pair_evals > pair_budget || ++*evals > model_budget) return -1;
+  bool ok = bound_cell(root);
+  todo.push(root);
+  while (ok && todo.top().low <= 0) {
+    const PruneCell cell = todo.top();
+    todo.pop();
+    if ((*pair_evals += 2) > pair_budget || (*evals += 2) > model_budget) return -1;
+    PruneCell lo = cell, hi = cell;
+    lo.w[cell.widest] = hi.w[cell.widest] = 0.5 * cell.w[cell.widest];
+    lo.th[cell.widest] -= lo.w[cell.widest];
+    hi.th[cell.widest] += hi.w[cell.widest];
+    ok = bound_cell(lo) && bound_cell(hi);
+    todo.push(lo);
+    todo.push(hi);
+  }
+  return ok ? 1 : 0;
 }
 
 // true: proved.  X: the partner's centre in the chain's frame; nrm: a plane partner's normal (else nullptr); rsum: bounding
@@ -282,11 +334,6 @@ void prune_point(const HostModel &m, const PruneChain &c, int k, const double *t
 bool prune_prove(const HostModel &m, const PruneChain &c, int g, const double *X, const double *nrm, double rsum, double need,
                  int *evals) {
   const int n = (int)c.bodies.size();
-  auto jlen = [&](int b, int from) {  // twice the joint offsets of body b from its joint `from` on
-    double s = 0;
-    for (int j = from; j < m.body_jntnum[b]; j++) s += 2.0 * norm3(&m.jnt_pos[3 * (m.body_jntadr[b] + j)]);
-    return s;
-  };
   int pair_evals = 0;
   // k = n: the geom's centre itself (rad 0)
   for (int k = 0, nh = 0; k <= n; nh += k < n ? m.body_jntnum[c.bodies[k]] : 0, k++) {
@@ -295,22 +342,12 @@ bool prune_prove(const HostModel &m, const PruneChain &c, int g, const double *X
     double rad = 0;
     if (k < n) {
       rad = norm3(&m.geom_pos[3 * g]);
-      for (int i = k; i < n; i++) rad += jlen(c.bodies[i], 0) + (i > k ? norm3(&m.body_pos[3 * c.bodies[i]]) : 0.0);
+      for (int i = k; i < n; i++) rad += prune_jlen(m, c.bodies[i], 0) + (i > k ? norm3(&m.body_pos[3 * c.bodies[i]]) : 0.0);
     }
     double lever[kPruneMaxHinges] = {0, 0, 0};  // O_k from hinge i's anchor, at most, in every configuration
-    for (int i = 0, h = 0; i < k; i++)
-      for (int j = 0; j < m.body_jntnum[c.bodies[i]]; j++, h++) {
-        double l = norm3(&m.jnt_pos[3 * (m.body_jntadr[c.bodies[i]] + j)]) + jlen(c.bodies[i], j + 1);
-        for (int t = i + 1; t < k; t++) l += norm3(&m.body_pos[3 * c.bodies[t]]) + jlen(c.bodies[t], 0);
-        lever[h] = l + norm3(off);
-      }
-    struct Cell {
-      double th[kPruneMaxHinges], w[kPruneMaxHinges], low;  // low: a lower bound of the gap over the cell
-      int widest;
-      bool operator<(const Cell &o) const { return low > o.low; }
-    };
+    prune_levers(m, c, k, norm3(off), lever);
     // false: the pair comes within reach at the cell's centre (no finer cell proves this k)
-    auto bound_cell = [&](Cell &cell) {
+    auto bound_cell = [&](PruneCell &cell) {
       double O[3], line[6 * kPruneMaxHinges];
       prune_point(m, c, k, cell.th, off, O, line);
       const double d[3] = {O[0] - X[0], O[1] - X[1], O[2] - X[2]};
@@ -330,25 +367,8 @@ bool prune_prove(const HostModel &m, const PruneChain &c, int g, const double *X
       cell.low = gap - sway;
       return gap > 0;
     };
-    std::priority_queue<Cell> todo;
-    Cell root;
-    for (int h = 0; h < kPruneMaxHinges; h++) { root.th[h] = 0.0; root.w[h] = h < nh ? 3.14159265358979323846 : 0.0; }
-    if (++pair_evals > kPrunePairEvals || ++*evals > kPruneModelEvals) return false;
-    bool ok = bound_cell(root);
-    todo.push(root);
-    while (ok && todo.top().low <= 0) {
-      const Cell cell = todo.top();
-      todo.pop();
-      if ((pair_evals += 2) > kPrunePairEvals || (*evals += 2) > kPruneModelEvals) return false;
-      Cell lo = cell, hi = cell;
-      lo.w[cell.widest] = hi.w[cell.widest] = 0.5 * cell.w[cell.widest];
-      lo.th[cell.widest] -= lo.w[cell.widest];
-      hi.th[cell.widest] += hi.w[cell.widest];
-      ok = bound_cell(lo) && bound_cell(hi);
-      todo.push(lo);
-      todo.push(hi);
-    }
-    if (ok) return true;
+    const int res = prune_bisect(nh, &pair_evals, kPrunePairEvals, evals, kPruneModelEvals, bound_cell);
+    if (res != 0) return res > 0;  // (proved, or a budget spent; a centre within reach: the next k)
   }
   return false;
 }
@@ -434,6 +454,214 @@ int prune_pairs(const HostModel &m, const ModelLayout &L, double tol, double poi
     }
   }
   return std::min(evals, kPruneModelEvals) + std::min(self_evals, kPruneModelEvals);  // cell evaluations spent
+}
+
+// ---- stage 1c: enabled pairs of a moving geom with a static geom or plane that pass their bounding cull somewhere but
+// can never come within their contact margin.  The same domain, chain, forward kinematics and
+// worst-first bisection as stage 1b; what differs:
+//   the gap at a cell's centre is the float64 distance between the two CORES (sphere: a point, capsule: a segment, box:
+//   the solid box, plane: the half space) minus both radii and the margin, the moving geom placed with ALL hinges above
+//   it (the ball around an ancestor's origin says nothing about where a capsule's ends are);
+//   inside a cell hinge i moves any point of the moving core by at most w_i times that point's distance from the axis.
+//   The distance from a line is convex, so over a core it is largest at one of the core's extreme points (the point, the
+//   segment's two ends, the box's eight corners): arm_i = the largest of them at the cell's centre plus what the hinges
+//   behind i add inside the cell, and never more than lever_i + the core's half extent (half length, half diagonal, 0).
+// A pair is proved when in every cell  gap - sum_i w_i arm_i > slack,  slack = kPruneSlack + 2 tol + the poison widening:
+// the filter classifies a pair by ITS distance against margin +- tol (classify), and that distance is within the band tol
+// of the float64 one (filter_error_bound: that is what the band is), so a real gap above 2 tol is called neither contact
+// nor unsure -- and a routine that is more cautious than that only hands the pair to the exact re-check, which clears it:
+// verdicts never depend on the set.  kPruneSlack (1 mm) is far above the float64 rounding of the routines below and the
+// 1e-9 the segment-box minimisation stops at.  A poisoned static partner (NaN rows: always unsure), box against box, a
+// slide joint on the chain, an infinite size, more than kPruneMaxHinges hinges above the geom, a spent budget: kept.
+// The proved pairs stay in ip / fp / dp, the masks and every table: only a per-program generated check leaves them out.
+constexpr int kContactPairEvals = 8192;      // cell evaluations one pair may spend (option "prune_contacts" >= 2: that many) ...
+constexpr int kContactModelEvals = 1 << 18;  // ... and all pairs of a model together
+
+struct PruneCore {
+  int type = GT_SPHERE;
+  double c[3] = {0, 0, 0}, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, size[3] = {0, 0, 0};  // R: row-major, its columns the axes
+  double radius() const { return type == GT_SPHERE || type == GT_CAPSULE ? size[0] : 0.0; }
+  double half_extent() const { return type == GT_CAPSULE ? size[1] : (type == GT_BOX ? norm3(size) : 0.0); }
+  // the extreme points of the core: 1, 2 or 8 (a plane: none)
+  int points(double (*p)[3]) const {
+    if (type == GT_SPHERE) { for (int a = 0; a < 3; a++) p[0][a] = c[a]; return 1; }
+    if (type == GT_CAPSULE) {
+      for (int a = 0; a < 3; a++) { p[0][a] = c[a] - size[1] * R[3 * a + 2]; p[1][a] = c[a] + size[1] * R[3 * a + 2]; }
+      return 2;
+    }
+    if (type != GT_BOX) return 0;
+    for (int k = 0; k < 8; k++)
+      for (int a = 0; a < 3; a++)
+        p[k][a] = c[a] + (k & 1 ? 1 : -1) * size[0] * R[3 * a] + (k & 2 ? 1 : -1) * size[1] * R[3 * a + 1] +
+                  (k & 4 ? 1 : -1) * size[2] * R[3 * a + 2];
+    return 8;
+  }
+};
+
+double dist_point_point(const double *p, const double *q) {
+  const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  return norm3(d);
+}
+
+double dist_point_segment(const double *p, const double *a, const double *b) {
+  const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
+  const double len2 = ab[0] * ab[0] + ab[1] * ab[1] + ab[2] * ab[2];
+  double t = len2 > 0 ? (ap[0] * ab[0] + ap[1] * ab[1] + ap[2] * ab[2]) / len2 : 0.0;
+  t = std::fmin(1.0, std::fmax(0.0, t));
+  const double q[3] = {a[0] + t * ab[0], a[1] + t * ab[1], a[2] + t * ab[2]};
+  return dist_point_point(p, q);
+}
+
+// closest points of two segments, clamped; near-parallel segments leave the parameter of the first ill-conditioned, so
+// the four end-against-segment distances (exact in that case) are taken in as well
+double dist_segment_segment(const double *a0, const double *a1, const double *b0, const double *b1) {
+  const double d1[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]}, d2[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
+  const double r[3] = {a0[0] - b0[0], a0[1] - b0[1], a0[2] - b0[2]};
+  auto dot = [](const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+  auto clamp01 = [](double v) { return std::fmin(1.0, std::fmax(0.0, v)); };
+  const double a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r), c = dot(d1, r), b = dot(d1, d2);
+  double best = std::fmin(std::fmin(dist_point_segment(a0, b0, b1), dist_point_segment(a1, b0, b1)),
+                          std::fmin(dist_point_segment(b0, a0, a1), dist_point_segment(b1, a0, a1)));
+  const double denom = a * e - b * b;
+  if (a > 0 && e > 0 && denom > 0) {
+    double s = clamp01((b * f - c * e) / denom), t = (b * s + f) / e;
+    if (t < 0) { t = 0; s = clamp01(-c / a); }
+    else if (t > 1) { t = 1; s = clamp01((b - c) / a); }
+    const double p[3] = {a0[0] + s * d1[0], a0[1] + s * d1[1], a0[2] + s * d1[2]};
+    const double q[3] = {b0[0] + t * d2[0], b0[1] + t * d2[1], b0[2] + t * d2[2]};
+    best = std::fmin(best, dist_point_point(p, q));
+  }
+  return best;
+}
+
+double dist_point_box(const double *p, const PruneCore &box) {
+  const double d[3] = {p[0] - box.c[0], p[1] - box.c[1], p[2] - box.c[2]};
+  double out2 = 0;
+  for (int k = 0; k < 3; k++) {
+    const double x = std::fabs(d[0] * box.R[k] + d[1] * box.R[3 + k] + d[2] * box.R[6 + k]) - box.size[k];
+    if (x > 0) out2 += x * x;
+  }
+  return std::sqrt(out2);
+}
+
+// the distance of the segment's point at t from the box is convex in t: a ternary search to 1e-9 of the segment's length
+double dist_segment_box(const double *a, const double *b, const PruneCore &box) {
+  auto at = [&](double t) {
+    const double p[3] = {a[0] + t * (b[0] - a[0]), a[1] + t * (b[1] - a[1]), a[2] + t * (b[2] - a[2])};
+    return dist_point_box(p, box);
+  };
+  double lo = 0.0, hi = 1.0;
+  for (int it = 0; it < 52; it++) {  // ((2/3)^52 < 1e-9)
+    const double m1 = lo + (hi - lo) / 3.0, m2 = hi - (hi - lo) / 3.0;
+    if (at(m1) <= at(m2)) hi = m2; else lo = m1;
+  }
+  return std::fmin(at(0.5 * (lo + hi)), std::fmin(at(0.0), at(1.0)));
+}
+
+// distance between the cores of a moving geom A and a static geom or plane S; NaN: no routine (box against box)
+double core_distance(const PruneCore &A, const PruneCore &S) {
+  double pa[8][3], ps[8][3];
+  const int na = A.points(pa);
+  if (S.type == GT_PLANE) {  // the lowest extreme point above the plane (negative: below it)
+    double low = std::numeric_limits<double>::infinity();
+    for (int k = 0; k < na; k++) {
+      double h = 0;
+      for (int a = 0; a < 3; a++) h += S.R[3 * a + 2] * (pa[k][a] - S.c[a]);
+      low = std::fmin(low, h);
+    }
+    return na ? low : std::numeric_limits<double>::quiet_NaN();
+  }
+  const int ns = S.points(ps);
+  if (na == 0 || ns == 0 || (na == 8 && ns == 8)) return std::numeric_limits<double>::quiet_NaN();
+  if (na == 8) return ns == 1 ? dist_point_box(ps[0], A) : dist_segment_box(ps[0], ps[1], A);
+  if (ns == 8) return na == 1 ? dist_point_box(pa[0], S) : dist_segment_box(pa[0], pa[1], S);
+  if (na == 1 && ns == 1) return dist_point_point(pa[0], ps[0]);
+  if (na == 1) return dist_point_segment(pa[0], ps[0], ps[1]);
+  if (ns == 1) return dist_point_segment(ps[0], pa[0], pa[1]);
+  return dist_segment_segment(pa[0], pa[1], ps[0], ps[1]);
+}
+
+// true: proved.  c: the chain from the world down to geom g's body; S: the partner in the world frame; rsum: both radii
+// and the margin; need: the slack; budget: cell evaluations this pair may spend; *evals: the model's counter.
+bool contact_prove(const HostModel &m, const PruneChain &c, int g, const PruneCore &S, double rsum, double need, int budget,
+                   int *evals) {
+  const int n = (int)c.bodies.size();
+  int nh = 0;
+  for (int b : c.bodies) nh += m.body_jntnum[b];
+  if (nh > kPruneMaxHinges) return false;
+  PruneCore A;
+  A.type = m.geom_type[g];
+  for (int a = 0; a < 3; a++) A.size[a] = m.geom_size[3 * g + a];
+  const double ext = A.half_extent();
+  double lever[kPruneMaxHinges] = {0, 0, 0};  // any point of the core from hinge i's anchor, at most, in every configuration
+  prune_levers(m, c, n, norm3(&m.geom_pos[3 * g]) + ext, lever);
+  // false: within the slack of contact at the cell's centre (or no routine for the pair)
+  auto bound_cell = [&](PruneCell &cell) {
+    double line[6 * kPruneMaxHinges], bq[4], gq[4], pts[8][3];
+    prune_point(m, c, n, cell.th, &m.geom_pos[3 * g], A.c, line, bq);
+    mul_quat(gq, bq, &m.geom_quat[4 * g]);
+    normalize4(gq);
+    quat2mat(A.R, gq);
+    const double gap = core_distance(A, S) - rsum - need;
+    const int np = A.points(pts);
+    double sway = 0, behind = 0, most = -1.0;
+    cell.widest = 0;
+    for (int h = nh - 1; h >= 0; h--) {
+      const double *a = &line[6 * h];
+      double far = 0;
+      for (int k = 0; k < np; k++) {
+        const double r[3] = {pts[k][0] - a[0], pts[k][1] - a[1], pts[k][2] - a[2]};
+        const double x[3] = {r[1] * a[5] - r[2] * a[4], r[2] * a[3] - r[0] * a[5], r[0] * a[4] - r[1] * a[3]};
+        far = std::fmax(far, norm3(x));
+      }
+      const double arm = std::fmin(lever[h], far + behind), part = cell.w[h] * arm;
+      sway += part;
+      behind += cell.w[h] * lever[h];
+      if (part > most) { most = part; cell.widest = h; }
+    }
+    cell.low = gap - sway;
+    return gap > 0;  // (NaN: false)
+  };
+  int pair_evals = 0;
+  return prune_bisect(nh, &pair_evals, budget, evals, kContactModelEvals, bound_cell) > 0;
+}
+
+// L: the layout the program is compiled from (the pairs stage 1b dropped are on no list and are not looked at again);
+// tol, poison_slack, poison_rows: of the program's own filter bound; pair_budget: cell evaluations per pair.  Returns the
+// cell evaluations spent.
+int prune_contacts(const HostModel &m, const ModelLayout &L, double tol, double poison_slack, const std::vector<int> &poison_rows,
+                   int pair_budget, GeomPairs *never) {
+  never->clear();
+  int evals = 0;
+  const double need = kPruneSlack + 2.0 * tol + poison_slack;
+  for (int k = 0; k < (int)L.mgeoms.size(); k++) {
+    const int g = L.mgeoms[k];
+    PruneChain c;
+    if (!prune_chain(m, L, m.geom_bodyid[g], -1, &c)) continue;
+    bool finite = true;
+    for (int a = 0; a < 3; a++) finite = finite && std::isfinite(m.geom_size[3 * g + a]);
+    if (!finite) continue;
+    for (int sgeom : L.world_partners[k]) {
+      if (std::find(poison_rows.begin(), poison_rows.end(), L.world_row[sgeom]) != poison_rows.end()) continue;
+      PruneCore S;
+      S.type = m.geom_type[sgeom];
+      bool ok = true;
+      for (int a = 0; a < 3; a++) {
+        S.c[a] = L.st_gxpos[3 * sgeom + a];
+        S.size[a] = m.geom_size[3 * sgeom + a];
+        ok = ok && (S.type == GT_PLANE || std::isfinite(S.size[a]));
+      }
+      if (!ok) continue;
+      for (int a = 0; a < 9; a++) S.R[a] = L.st_gxmat[9 * sgeom + a];
+      PruneCore A;
+      A.type = m.geom_type[g];
+      A.size[0] = m.geom_size[3 * g];
+      const double margin = std::fmax(m.geom_margin[g], m.geom_margin[sgeom]);
+      if (contact_prove(m, c, g, S, A.radius() + S.radius() + margin, need, pair_budget, &evals))
+        never->insert({std::min(g, sgeom), std::max(g, sgeom)});
+    }
+  }
+  return std::min(evals, kContactModelEvals);
 }
 
 // ---- stage 2: ip / dp
@@ -731,7 +959,8 @@ void float_image(const std::vector<int> &ip, const std::vector<double> &dp, cons
 }
 
 // ---- stage 5: identity of the compiled program: what a per-model specialised library is keyed by
-uint64_t hash_program(const ModelLayout &L, const std::vector<int> &ip, const std::vector<float> &fp, const std::vector<double> &dp) {
+uint64_t hash_program(const ModelLayout &L, const std::vector<int> &ip, const std::vector<float> &fp, const std::vector<double> &dp,
+                      const GeomPairs &never_touch) {
   Fnv1a f;
   f.mix(ip.data(), ip.size() * sizeof(int));
   f.mix(fp.data(), fp.size() * sizeof(float));
@@ -741,6 +970,12 @@ uint64_t hash_program(const ModelLayout &L, const std::vector<int> &ip, const st
   const int shape[4] = {L.maxs, L.wbox ? 1 : 0, L.mbox ? 1 : 0, MJPL_SPEC_ABI};
   f.mix(shape, sizeof(shape));
   f.mix_stamp();
+  // the pairs a per-program library leaves out of its generated check (stage 1c), only when there are any: a model where
+  // nothing is proved keeps the hash it had without the stage
+  if (!never_touch.empty()) {
+    f.mixi(-3);
+    for (const auto &gp : never_touch) { f.mixi(gp.first); f.mixi(gp.second); }
+  }
   return f.h;
 }
 
@@ -920,6 +1155,29 @@ int find_pruned_pairs(mjpl_engine *e) {
   return MJPL_OK;
 }
 
+// Stage 1c's driver: e->never_touch from the layout the program is compiled from and its own filter bound (a model the
+// filter does not serve runs no generated check: nothing to leave out).  Like stage 1b's decisions the set does not change
+// with the planning selection: kept until the switches, the dropped pairs or the band change.
+void find_never_touch(mjpl_engine *e) {
+  if (!e->prune_contacts || !e->fb.usable) {
+    e->never_touch.clear();
+    e->never_valid = false;
+    return;
+  }
+  const double poison_slack = poison_widening(e->ip, e->dp, e->fb);
+  if (e->never_valid && e->never_level == e->prune_contacts && e->never_from == e->pruned && e->never_tol == (double)e->fb.tol &&
+      e->never_poison_slack == poison_slack && e->never_poison_rows == e->fb.poison_rows)
+    return;
+  const int budget = e->prune_contacts >= 2 ? e->prune_contacts : kContactPairEvals;
+  e->prune_contact_evals = prune_contacts(e->m, e->lay, (double)e->fb.tol, poison_slack, e->fb.poison_rows, budget, &e->never_touch);
+  e->never_valid = true;
+  e->never_level = e->prune_contacts;
+  e->never_from = e->pruned;
+  e->never_tol = (double)e->fb.tol;
+  e->never_poison_slack = poison_slack;
+  e->never_poison_rows = e->fb.poison_rows;
+}
+
 // Stages 1 to 6: the engine's host tables, bound and hashes from its model, allowed pairs, planning selection and
 // tolerance.  No HIP call, no device: mjpl_program_dump ends here; e->scene is non-empty exactly when the program
 // satisfies what a scene-generic library assumes.
@@ -931,7 +1189,8 @@ int compile_host(mjpl_engine *e) {
   emit_program(m, e->lay, e->qidx, e->qbase, e->ip, e->dp, &sites);
   e->fb = filter_error_bound(m, e->lay, e->filter_tol_req, e->filter_tol_user, e->ip, e->dp);
   float_image(e->ip, e->dp, sites, e->fb, e->fp);
-  e->program_hash = hash_program(e->lay, e->ip, e->fp, e->dp);
+  find_never_touch(e);
+  e->program_hash = hash_program(e->lay, e->ip, e->fp, e->dp, e->never_touch);
   e->robot_hash = hash_robot(m, e->lay, e->qbase, (int)e->qidx.size(), e->fb.tol);
   e->scene.clear();
   if (scene_generic_ok(e->lay, e->fb, !e->immediate()))

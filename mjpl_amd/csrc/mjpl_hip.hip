@@ -365,7 +365,16 @@ struct mjpl_engine {
   bool pruned_valid = false, pruned_tol_user = false;
   float pruned_tol_req = 0.0f;
   int prune_evals = 0;  // cell evaluations the proofs took (of kPruneModelEvals); read-only option "prune_evals"
-  uint64_t program_hash = 0;      // FNV-1a of the compiled tables (ip, fp, dp), the kernel variant and the header digest
+  // option "prune_contacts": pairs of a moving geom with a static geom or a plane proved never to come within their margin
+  // (mjpl_compile.h: prune_contacts) -- a side set of the program: in no table, mixed into program_hash when non-empty, left
+  // out by a per-program library's generated check only.  1: on, >= 2: on with that many cell evaluations per pair (tests)
+  int prune_contacts = 1, never_level = 0;
+  std::set<std::pair<int, int>> never_touch, never_from;  // (never_from: the dropped pairs the set was found beside)
+  bool never_valid = false;
+  double never_tol = 0, never_poison_slack = 0;
+  std::vector<int> never_poison_rows;
+  int prune_contact_evals = 0;  // cell evaluations (of kContactModelEvals); read-only option "prune_contact_evals"
+  uint64_t program_hash = 0;      // FNV-1a of the compiled tables (ip, fp, dp), the kernel variant, the header digest and the never-touch set when it is not empty
   const SpecLib *spec = nullptr;  // this model's own filter kernels, if a library for program_hash was found
   // ... or, failing that, a scene-generic library of the ROBOT (robot_hash: moving bodies, their geoms and
   // self pairs, planning set, tolerance -- nothing of the static geoms): its generated code takes every
@@ -1794,6 +1803,41 @@ int mjpl_program_dump_pruned(const mjpl_model_desc *d, const int32_t *allowed_bo
   return MJPL_OK;
 }
 
+int mjpl_program_dump_never_touch(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t nallowed, const int32_t *qidx,
+                                  int32_t nplan, const double *qpos_base, double filter_tol, int32_t prune_pairs,
+                                  int32_t prune_contacts, int32_t *pairs, int32_t *npairs, int32_t *evals, uint64_t *hash,
+                                  uint64_t *tables_hash) {
+  if (!d || !npairs) return fail(MJPL_E_ARG, "mjpl_program_dump_never_touch: NULL argument");
+  if (d->nq < 0 || d->njnt < 0 || d->nbody < 1 || d->ngeom < 0 || nallowed < 0) return fail(MJPL_E_ARG, "negative size");
+  if (d->nq != d->njnt) return fail(MJPL_E_JOINT, "nq != njnt: only 1-DoF joints are supported");
+  if (prune_pairs < 0 || prune_pairs > 2 || prune_contacts < 0 || prune_contacts > (1 << 24))
+    return fail(MJPL_E_ARG, "mjpl_program_dump_never_touch: prune_pairs must be 0, 1 or 2, prune_contacts 0 .. 2^24");
+  std::unique_ptr<mjpl_engine> e(new mjpl_engine());
+  int rc = engine_from_desc(e.get(), d, allowed_bodies, nallowed);
+  if (rc != MJPL_OK) return rc;
+  if (qidx) {
+    e->qidx.assign(qidx, qidx + nplan);
+    for (int c : e->qidx)
+      if (c < 0 || c >= d->nq) return fail(MJPL_E_ARG, "planning index %d out of range", c);
+  }
+  if (qpos_base) e->qbase.assign(qpos_base, qpos_base + d->nq);
+  if (filter_tol > 0.0) { e->filter_tol_req = (float)filter_tol; e->filter_tol_user = true; }
+  e->prune_pairs = prune_pairs;
+  e->prune_contacts = prune_contacts;
+  if ((rc = compile_host(e.get())) != MJPL_OK) return rc;
+  const int32_t room = pairs ? *npairs : 0;  // (in: room for that many pairs; out: how many there are)
+  int32_t n = 0;
+  for (const auto &gp : e->never_touch) {
+    if (n < room) { pairs[2 * n] = gp.first; pairs[2 * n + 1] = gp.second; }
+    n++;
+  }
+  *npairs = n;
+  if (evals) *evals = e->never_valid ? e->prune_contact_evals : 0;
+  if (hash) *hash = e->program_hash;
+  if (tables_hash) *tables_hash = hash_program(e->lay, e->ip, e->fp, e->dp, GeomPairs());
+  return MJPL_OK;
+}
+
 int mjpl_spec_probe(uint64_t hash, int32_t generic) {
   return find_spec(hash, generic != 0) ? 1 : 0;
 }
@@ -2015,6 +2059,9 @@ const EngineOption kEngineOptions[] = {
     MJPL_OPT_INT("prune_pairs", prune_pairs, 0, 2),
     {"pairs_pruned", [](mjpl_engine *e) { return (double)e->lay.npruned; }, nullptr},
     {"prune_evals", [](mjpl_engine *e) { return (double)(e->prune_pairs ? e->prune_evals : 0); }, nullptr},
+    MJPL_OPT_INT("prune_contacts", prune_contacts, 0, 1 << 24),
+    {"pairs_never_touch", [](mjpl_engine *e) { return (double)e->never_touch.size(); }, nullptr},
+    {"prune_contact_evals", [](mjpl_engine *e) { return (double)(e->never_valid ? e->prune_contact_evals : 0); }, nullptr},
     MJPL_OPT_BOOL("two_pass", two_pass),
     MJPL_OPT_BOOL("force_immediate", force_immediate),
     MJPL_OPT_BOOL("expand", expand),

@@ -195,6 +195,7 @@ ABI = {
     "mjpl_allgather_dev": (C.c_int, [_VP, _VP, _VP, C.c_size_t]),
     "mjpl_program_dump": (C.c_int, None),   # bound in mjpl_amd/specialise.py
     "mjpl_program_dump_pruned": (C.c_int, None),   # likewise
+    "mjpl_program_dump_never_touch": (C.c_int, None),   # likewise
     "mjpl_spec_probe": (C.c_int, [C.c_uint64, C.c_int32]),
     "mjpl_spec_loaded": (C.c_int, [_VP]),
     "mjpl_set_spec": (C.c_int, [_VP, C.c_int32]),

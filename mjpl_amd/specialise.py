@@ -118,6 +118,37 @@ def dump_program_pruned(model, allowed_collision_bodies=(), qidx=None, qpos_base
     return _dump(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, int(prune_pairs))
 
 
+def dump_never_touch(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, prune_pairs: int = 1,
+                     prune_contacts: int = 1):
+    """The side set of the program dump_program_pruned(..., prune_pairs) compiles (mjpl_program_dump_never_touch; DESIGN.md
+    5.1d) -> (pairs int32 [n, 2] with g1 < g2, cell evaluations spent, program hash, hash of ip / fp / dp alone): enabled pairs of a moving geom with a
+    static geom or a plane proved never to come within their contact margin.  ip / fp / dp keep them; `generate` leaves
+    them out of a per-program library.  prune_contacts: 0 the empty set, 1 the default, >= 2 that many cell evaluations per
+    pair at most (tests)."""
+    lib = _engine.load_library()
+    f = lib.mjpl_program_dump_never_touch
+    f.restype = C.c_int
+    d, keep = _model_desc(model)
+    allowed = _engine._i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
+    q = None if qidx is None else _engine._i32(qidx)
+    base = None if qpos_base is None else _engine._f64(qpos_base)
+    n, evals, h, th = C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(pairs):
+        n.value = 0 if pairs is None else len(pairs)
+        rc = f(C.byref(d), allowed.ctypes.data_as(_engine._I32P), len(allowed), None if q is None else q.ctypes.data_as(_engine._I32P),
+               0 if q is None else len(q), None if base is None else base.ctypes.data_as(_engine._F64P), C.c_double(filter_tol),
+               C.c_int32(int(prune_pairs)), C.c_int32(int(prune_contacts)), None if pairs is None else pairs.ctypes.data_as(_engine._I32P),
+               C.byref(n), C.byref(evals), C.byref(h), C.byref(th))
+        if rc != 0:
+            raise _engine.MjplError(rc, lib.mjpl_last_error().decode())
+
+    call(None)
+    pairs = np.zeros((n.value, 2), np.int32)
+    call(pairs)
+    return pairs, int(evals.value), int(h.value), int(th.value)
+
+
 # ----------------------------------------------------------------------------- expression helpers
 def lit(x: float) -> str:
     """Exact C literal of a binary32 value."""
@@ -230,17 +261,18 @@ class _SharedAxesReused(ValueError):
     """Boxes share an axes slot that the program's slot allocation reuses while they still refer to it."""
 
 
-def generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, report: dict | None = None) -> str:
+def generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, report: dict | None = None, never_touch=()) -> str:
     """Straight-line filter code of one program (see _generate).  Moving boxes of one body with one orientation share
     the slot of their x and y axes; where the program's own slot allocation gets in the way of that, every box keeps
     its own."""
     try:
-        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=True, report=report)
+        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=True, report=report, never_touch=never_touch)
     except _SharedAxesReused:
-        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=False, report=report)
+        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=False, report=report, never_touch=never_touch)
 
 
-def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, share_axes: bool = True, report: dict | None = None) -> str:
+def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, share_axes: bool = True, report: dict | None = None,
+              never_touch=()) -> str:
     """HIP source of `struct Spec` for one compiled program.
     generic: the ROBOT's code only -- forward kinematics, geom poses, the culls against earlier moving geoms --
     as literals; every static partner (floor, obstacles, the robot's own world-welded base) is a row of the
@@ -251,6 +283,9 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
     fused multiply-adds and a compare per partner on top of one |c|^2 per geom -- with the threshold
     raised by a bound of the form's own rounding (see `expanded_threshold`); "difference" is the
     interpreter's |c - X|^2 <= bound (six operations and a compare, two partners per packed instruction)."""
+    # never_touch (dump_never_touch of THIS program -- its hash covers the set): static or plane partners a per-program library
+    # does not test at all; a scene-generic library tests whatever its scene table holds
+    skip = set() if generic else {(int(a), int(b)) for a, b in never_touch}
     cull_form = cull_form or os.environ.get("MJPL_SPEC_CULL", "expanded")
     if info.immediate or not info.filter_usable:
         raise ValueError("this model runs the immediate interpreter / has no usable filter: nothing to specialise")
@@ -470,6 +505,9 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
             for wrow in range(64):
                 if not (pmask >> wrow) & 1:
                     continue
+                pgid_ = int(np.frombuffer(np.float32(fp[wc_at(wrow, 3)]).tobytes(), dtype=np.int32)[0]) >> 8
+                if (min(geom_id, pgid_), max(geom_id, pgid_)) in skip:
+                    continue
                 ppos = [float(fp[wc_at(wrow, f)]) for f in range(3)]
                 pz = [float(x) for x in fp[off_wnarrow + wrow * WN_LEN + WN_ZAXIS: off_wnarrow + wrow * WN_LEN + WN_ZAXIS + 3]]
                 k = len(partners)
@@ -486,6 +524,8 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
                     continue
                 info_word = int(np.frombuffer(np.float32(fp[wc_at(wrow, 3)]).tobytes(), dtype=np.int32)[0])
                 ptype, pgid = info_word & 255, info_word >> 8
+                if (min(geom_id, pgid), max(geom_id, pgid)) in skip:
+                    continue
                 pfirst = 1 if (ptype < gtype or (ptype == gtype and pgid < geom_id)) else 0
                 X, Y, Z = (float(fp[wc_at(wrow, f)]) for f in range(3))
                 statics.append((len(partners), X, Y, Z, wbound[wrow]))
@@ -1531,14 +1571,20 @@ def spec_path(hash_: int, generic: bool = False) -> str:
 
 
 def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, force: bool = False,
-          keep_source: bool = True, extra_flags=(), output: str | None = None, generic: bool = False) -> str | None:
+          keep_source: bool = True, extra_flags=(), output: str | None = None, generic: bool = False, prune_contacts: int = 1) -> str | None:
     """Generate and compile the specialised library of (model, planning set, tolerance).  Returns the
     path of the library, or None if the model cannot be specialised (immediate interpreter).
     generic: the ROBOT's scene-generic library instead (named by the robot hash): built from any scene that
-    holds the robot, it serves every scene with it -- the static geoms come from the engine's scene table."""
+    holds the robot, it serves every scene with it -- the static geoms come from the engine's scene table.
+    prune_contacts: the engine option of that name the library is for (0: the program without its never-touch set, which
+    an engine with the option off looks for -- A/B measurements)."""
     ip, fp, dp, info = dump_program(model, allowed_collision_bodies, qidx, qpos_base, filter_tol)
     if info.immediate or not info.filter_usable or (generic and not info.scene_ok):
         return None
+    never_touch, _, never_hash, _ = dump_never_touch(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, prune_contacts=prune_contacts)
+    if prune_contacts == 1 and never_hash != int(info.hash):
+        raise RuntimeError("dump_never_touch and dump_program disagree on the program hash")
+    info.hash = never_hash
     os.makedirs(SPEC_DIR, exist_ok=True)
     key = info.robot_hash if generic else info.hash
     target = output or spec_path(key, generic)  # (output, extra_flags: timing-only variants, tools/time_variants.sh)
@@ -1552,7 +1598,7 @@ def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_
             nj, ng = int(ip[pc + B_NJNT]), int(ip[pc + B_NGEOM])
             pc += B_SIZE + nj * J_SIZE + ng * (G_SIZE + MAX_SLOTS)
             nstage += ng
-    src = translation_unit(generate(ip, fp, dp, info, generic=generic), generate_exact(ip, dp, info, generic=generic), key, info,
+    src = translation_unit(generate(ip, fp, dp, info, generic=generic, never_touch=never_touch), generate_exact(ip, dp, info, generic=generic), key, info,
                            (SCENE_ROWS << 8 | nstage) if generic else 0,  # (kSceneRows, moving geoms)
                            pose=generate_pose_section(model, int(ip[H_NPLAN]), qidx=(None if qidx is None else [int(x) for x in qidx])),
                            # (an experiment, off by default: see generate_full_exact / mjpl_fused.h)
