@@ -389,6 +389,79 @@ int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *desc, const double *Q, i
 int mjpl_push_out_dev(mjpl_engine *e, const mjpl_push_desc *desc, const double *dQ, int64_t N, int32_t layout,
                       double *dQ_out, double *dclear, int32_t *dpair, int32_t *diters, int32_t *dstatus);
 
+/* ---- certified edge checks: no contact anywhere along an edge ------------------------------
+ * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
+ * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md
+ * section 5.11 has the proof).
+ *
+ * The lever table W[P][nplan] over the candidate pairs of mjpl_contact_pairs: one unit of planning
+ * column c changes the distance of pair p by at most W[p][c].  It is made at mjpl_create and by
+ * mjpl_set_planning without bounds, and again by mjpl_sweep_bounds or by a mjpl_sweep_edges* call whose
+ * bounds differ from those in force.  A planning SLIDE joint needs finite bounds: without them every
+ * hinge above it has lever +inf for the geoms below the slide.  mjpl_sweep_bounds(e, lo, hi): HOST arrays
+ * of nplan bounds, either may be NULL (none); NaN and lo > hi are refused.  mjpl_sweep_levers computes the
+ * table on the host only -- no device needed, like mjpl_program_dump: W receives P * nplan doubles if
+ * cap >= P * nplan, and the call returns P (or a negative error).
+ *
+ * mjpl_sweep_measure: the bubble measurement at N rows.  HD[i][c] >= 0 (Q's layout): how far column c may
+ * move from q_i; cap > 0.  With D_p = min(d_p, cap) and B_p = sum_c HD[i][c] W[p][c] (ascending c, terms
+ * with W = 0 or HD = 0 skipped, inf stays inf):
+ *   gap[i]   = min over non-allowed p of (D_p - margin_p), gap_pair[i] its lowest index: bit-identical
+ *              to mjpl_clearance(q_i, distmax = cap);
+ *   slack[i] = min over non-allowed p of (D_p - margin_p - B_p), slack_pair[i] its lowest index.
+ * Without a non-allowed pair: cap and -1.  A non-finite row of Q: NaN and -1.  slack[i] > 0 means: no
+ * configuration of the box |q_c - q_i,c| <= HD[i][c] is in contact (given that the box lies inside the
+ * bounds in force).  HD itself is not checked: a negative or non-finite entry gives a meaningless slack.
+ *
+ * mjpl_sweep_edges: E edges.  Descriptor: d_min >= 0, the clearance every configuration of a FREE edge
+ * keeps (0: no contact); cap > d_min + the largest margin of a non-allowed pair, where distances stop
+ * being measured (and clear_lb saturates); max_depth 0..16 (8 is a good default); lo, hi as above.
+ * A node (t, h) of an edge is the row q(t) with travel HD_c = h |QB_c - QA_c|.  Round 0 holds the end
+ * points (0, 0), (1, 0) and the root (1/2, 1/2); depth k has h = 2^-(k+1).  Per node, on the outputs
+ * of the measurement:
+ *   hit        iff gap <= 0 or gap < d_min;
+ *   certified  iff otherwise slack - d_min >= 1e-9;
+ *   otherwise it is split into (t -+ h/2, h/2) -- or, at max_depth or for an end point, the edge is
+ *   flagged undecided.
+ * Rounds are breadth-first; an edge hit in a round opens no further nodes.
+ *   status[i]   MJPL_SWEEP_HIT if any node hit, else UNDECIDED if flagged, else FREE: no configuration of
+ *               the segment is in contact or nearer than d_min.  NONFINITE: the edge holds NaN / inf.
+ *               RANGE: an end point lies outside the bounds given; the edge is not measured.
+ *   t_hit[i]    the least t among the hit nodes of the first depth that has one; NaN unless HIT.
+ *   pair[i]     that node's gap_pair; -1 unless HIT.
+ *   clear_lb[i] the least certified slack over the edge's leaves: clearance(q(t)) >= clear_lb for all t,
+ *               capped at cap; NaN unless FREE.
+ *   depth[i], nodes[i]  the deepest depth evaluated and the number of nodes evaluated on the edge.
+ * All outputs are deterministic.  MJPL_E_ARG: a parameter outside its range, NaN anywhere in the
+ * descriptor, lo > hi, NULL descriptor, a NULL output with E > 0, an unknown layout.  MJPL_E_PAIRTYPE
+ * as for mjpl_clearance.  The host forms synchronise; mjpl_sweep_edges_dev enqueues on the engine's
+ * stream but synchronises it once per round to read how many nodes are open (4 bytes).  The results
+ * depend on no option and no MJPL_* variable. */
+#define MJPL_SWEEP_FREE       0
+#define MJPL_SWEEP_HIT        1
+#define MJPL_SWEEP_UNDECIDED  2
+#define MJPL_SWEEP_NONFINITE  3
+#define MJPL_SWEEP_RANGE      4
+typedef struct {
+  double d_min, cap;
+  int32_t max_depth;
+  const double *lo, *hi; /* host, [nplan], may be NULL, both forms */
+} mjpl_sweep_desc;
+int mjpl_sweep_levers(const mjpl_model_desc *model, const int32_t *allowed_bodies, int32_t nallowed,
+                      const int32_t *qidx, int32_t nplan, const double *qpos_base, const double *lo,
+                      const double *hi, double *W, int64_t cap);
+int mjpl_sweep_bounds(mjpl_engine *e, const double *lo, const double *hi);
+int mjpl_sweep_measure(mjpl_engine *e, const double *Q, const double *HD, int64_t N, int32_t layout, double cap,
+                       double *slack, int32_t *slack_pair, double *gap, int32_t *gap_pair);
+int mjpl_sweep_measure_dev(mjpl_engine *e, const double *dQ, const double *dHD, int64_t N, int32_t layout,
+                           double cap, double *dslack, int32_t *dslack_pair, double *dgap, int32_t *dgap_pair);
+int mjpl_sweep_edges(mjpl_engine *e, const mjpl_sweep_desc *desc, const double *QA, const double *QB, int64_t E,
+                     int32_t layout, int32_t *status, double *t_hit, double *clear_lb, int32_t *pair,
+                     int32_t *nodes, int32_t *depth);
+int mjpl_sweep_edges_dev(mjpl_engine *e, const mjpl_sweep_desc *desc, const double *dQA, const double *dQB,
+                         int64_t E, int32_t layout, int32_t *dstatus, double *dt_hit, double *dclear_lb,
+                         int32_t *dpair, int32_t *dnodes, int32_t *ddepth);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,

@@ -2,7 +2,7 @@
 planner plug-in surface.  The compute path is ``libmjpl_hip.so``
 (mjpl_amd/csrc, C ABI in include/mjpl_hip.h); there is no CPU fallback in this package.
 """
-from .constraint import (ClearanceConstraint, CollisionConstraint, CollisionRuleset, Constraint, JointLimitConstraint,
+from .constraint import (CertifiedIntervals, ClearanceConstraint, CollisionConstraint, CollisionRuleset, Constraint, JointLimitConstraint,
                          PoseConstraint, apply_constraints, obeys_constraints)
 from .inverse_kinematics import HipIKSolver, IKSolver
 from .lie import SE3, SO3
@@ -18,7 +18,7 @@ def comm_unique_id() -> bytes:
     return _f()
 
 __all__ = (
-    "ClearanceConstraint", "CollisionConstraint", "CollisionRuleset", "Constraint", "JointLimitConstraint", "PoseConstraint",
+    "CertifiedIntervals", "ClearanceConstraint", "CollisionConstraint", "CollisionRuleset", "Constraint", "JointLimitConstraint", "PoseConstraint",
     "SE3", "SO3", "site_pose", "HipIKSolver", "IKSolver", "cartesian_plan",
     "apply_constraints", "obeys_constraints", "Model", "ModelBuilder", "load_mjcf", "parse_mjcf",
     "RRT", "Node", "Tree", "path_length", "smooth_path", "ParallelBiRRT", "DeviceBiRRT", "EdgeValidator", "HipEdgeValidator",

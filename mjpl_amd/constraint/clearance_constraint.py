@@ -83,3 +83,18 @@ class ClearanceConstraint(Constraint):
         lo = None if self.lower is None else self.lower[idx]
         hi = None if self.upper is None else self.upper[idx]
         return self.engine.push_out(Qp, self.min_clearance, layout, lo=lo, hi=hi, **self.params)
+
+    # ---- the edge form: the margin between the nodes too (include/mjpl_hip.h, mjpl_sweep_edges) --------------------
+    def certified_interval(self, start: np.ndarray, end: np.ndarray, **params):
+        """The segment between two full-nq configurations with ``d_min = min_clearance`` and this constraint's bounds
+        -> ``CertifiedEdge``: ``status == engine.SWEEP_FREE`` iff every configuration of it keeps the clearance."""
+        return self.collision.certified_interval(start, end, self.min_clearance, **self._sweep_params(params))
+
+    def certified_intervals(self, starts: np.ndarray, ends: np.ndarray, **params):
+        """Row-wise ``certified_interval`` over full-nq edges [N, nq], one call."""
+        return self.collision.certified_intervals(starts, ends, self.min_clearance, **self._sweep_params(params))
+
+    def _sweep_params(self, params: dict) -> dict:
+        out = dict(lo=self.lower, hi=self.upper)
+        out.update(params)
+        return out

@@ -60,6 +60,16 @@ class NearPair(NamedTuple):
     status: int                        # engine.GRAD_OK / GRAD_DEGENERATE
 
 
+class CertifiedEdge(NamedTuple):
+    """One edge decided as a whole (``CollisionConstraint.certified_interval``)."""
+    status: int                        # engine.SWEEP_FREE / SWEEP_HIT / SWEEP_UNDECIDED / SWEEP_NONFINITE / SWEEP_RANGE
+    t_hit: float                       # where a configuration in contact was found (NaN unless HIT)
+    clear_lb: float                    # clearance >= this all along the edge (NaN unless FREE)
+    pair: tuple[int, int] | None       # the closest geom pair at t_hit (None unless HIT)
+    nodes: int                         # bubble measurements spent
+    depth: int                         # deepest bisection depth evaluated
+
+
 class CollisionRuleset:
     """Which body pairs may touch (reference collision_constraint.py:36-95).
 
@@ -292,6 +302,32 @@ class CollisionConstraint(Constraint):
         self._ensure_full()
         return self.engine.check_edges(np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64),
                                        step_dist, _engine.AOS, interior_only=True).astype(bool)
+
+    # ---- certified edge checks: the whole segment, not samples of it (include/mjpl_hip.h, mjpl_sweep_edges) --------
+    def certified_interval(self, start: np.ndarray, end: np.ndarray, d_min: float = 0.0, **params) -> "CertifiedEdge":
+        """The straight segment between two full-nq configurations, decided as a whole -> :class:`CertifiedEdge`.
+        ``status == engine.SWEEP_FREE``: no configuration of it is in contact (or nearer than ``d_min``), whatever lies
+        between two waypoints of ``valid_interval``.  params: cap, max_depth, lo, hi (full nq; a model with slide
+        joints needs finite bounds for them)."""
+        status, t_hit, clear_lb, pair, nodes, depth = self.certified_intervals(
+            self._full_q(start), self._full_q(end), d_min, **params)
+        geoms = None
+        if pair[0] >= 0:
+            g1, g2 = self.engine.contact_pairs()[0][pair[0]]
+            geoms = (int(g1), int(g2))
+        return CertifiedEdge(int(status[0]), float(t_hit[0]), float(clear_lb[0]), geoms, int(nodes[0]), int(depth[0]))
+
+    def certified_intervals(self, starts: np.ndarray, ends: np.ndarray, d_min: float = 0.0, **params):
+        """``certified_interval`` for every row of full-nq edges [N, nq], one call -> (status [N], t_hit [N], clear_lb
+        [N], candidate-pair index [N], nodes [N], depth [N])."""
+        return self.engine.sweep_edges(self._full_batch(starts), self._full_batch(ends), d_min, _engine.AOS, **params)
+
+    def certified_edges_planning(self, QA: np.ndarray, QB: np.ndarray, d_min: float = 0.0, layout: int = _engine.AOS,
+                                 **params):
+        """``certified_intervals`` over the columns of ``set_planning`` (every other joint at its base value; lo / hi
+        over those columns)."""
+        self._ensure_planning()
+        return self.engine.sweep_edges(QA, QB, d_min, layout, **params)
 
     def valid_configs_planning(self, Q: np.ndarray, layout: int = _engine.AOS) -> np.ndarray:
         self._ensure_planning()

@@ -1267,18 +1267,15 @@ std::vector<double> build_distance_table(const mjpl_engine *e) {
   return dt;
 }
 
-// The tables of k_distance<DM_GRAD> (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
-// the number of later joints on that body and the body's subtree as DFS times; per model joint its type, axis,
-// position and where its dq comes from (as the FK program computes it); per geom the DFS entry time of its body.
-// Depends on the model and the planning selection: made at mjpl_create and by mjpl_set_planning.
-int build_grad_table(const mjpl_engine *e, std::vector<double> &t) {
-  const HostModel &m = e->m;
-  const std::vector<int> &col_of = e->lay.col_of;
-  const int nplan = (int)e->qidx.size(), nj = m.njnt, ng = m.ngeom, nb = m.nbody;
-  // DFS entry / exit times of the body tree (children in id order)
+// DFS entry / exit times of the body tree (children in id order): body a is b or above it iff
+// tin[a] <= tin[b] < tout[a]
+void body_dfs_times(const HostModel &m, std::vector<int> &tin, std::vector<int> &tout) {
+  const int nb = m.nbody;
   std::vector<std::vector<int>> kids(nb);
   for (int b = 1; b < nb; b++) kids[m.body_parentid[b]].push_back(b);
-  std::vector<int> tin(nb, 0), tout(nb, 0), stack = {0};
+  tin.assign(nb, 0);
+  tout.assign(nb, 0);
+  std::vector<int> stack = {0};
   std::vector<size_t> next(nb, 0);
   int clock = 0;
   tin[0] = clock++;
@@ -1293,6 +1290,18 @@ int build_grad_table(const mjpl_engine *e, std::vector<double> &t) {
       stack.pop_back();
     }
   }
+}
+
+// The tables of k_distance<DM_GRAD> (mjpl_distance_grad.h): per planning column its joint's body, model joint id,
+// the number of later joints on that body and the body's subtree as DFS times; per model joint its type, axis,
+// position and where its dq comes from (as the FK program computes it); per geom the DFS entry time of its body.
+// Depends on the model and the planning selection: made at mjpl_create and by mjpl_set_planning.
+int build_grad_table(const mjpl_engine *e, std::vector<double> &t) {
+  const HostModel &m = e->m;
+  const std::vector<int> &col_of = e->lay.col_of;
+  const int nplan = (int)e->qidx.size(), nj = m.njnt, ng = m.ngeom, nb = m.nbody;
+  std::vector<int> tin, tout;
+  body_dfs_times(m, tin, tout);
   std::vector<int> jnt_body(nj, 0);
   for (int b = 0; b < nb; b++)
     for (int j = 0; j < m.body_jntnum[b]; j++) jnt_body[m.body_jntadr[b] + j] = b;
@@ -1324,6 +1333,76 @@ int build_grad_table(const mjpl_engine *e, std::vector<double> &t) {
   }
   for (int g = 0; g < ng; g++) gt[g] = tin[m.geom_bodyid[g]];
   return MJPL_OK;
+}
+
+// The pair lever table of k_distance<DM_SWEEP> (mjpl_distance.h): W[p][c] bounds how far one
+// unit of planning column c can change the distance of candidate pair p.  rho_c(g), the lever of a planning hinge c
+// for a geom g below it: the longest the chain can stretch from the hinge's anchor to the geom's centre -- body
+// offsets, 2 |jnt_pos| per hinge passed, a slide held at its base as |qbase - q0|, a planning slide as
+// max(|lo - q0|, |hi - q0|) (+inf without finite bounds), |geom_pos| -- plus geom_rbound[g]; a planning slide above g
+// has lever 1.  W[p][c] is the lever for the one geom of the pair that c moves, 0 when it moves both or neither.
+// lo, hi: bounds per planning column, either may be null (none).  Depends on the model, the planning selection and
+// the bounds; not part of the hashed program.
+std::vector<double> build_sweep_table(const mjpl_engine *e, const double *lo, const double *hi) {
+  const HostModel &m = e->m;
+  const std::vector<int> &col_of = e->lay.col_of;
+  const int nplan = (int)e->qidx.size(), nb = m.nbody, P = (int)e->ct_g1.size();
+  auto norm3 = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+  // per body: the stretch from every planning hinge above it to the body's origin (-1: not above), and the planning
+  // slides above it
+  std::vector<double> reach((size_t)nb * nplan, -1.0);
+  std::vector<char> slide((size_t)nb * nplan, 0);
+  for (int b = 1; b < nb; b++) {
+    double *r = &reach[(size_t)b * nplan];
+    char *s = &slide[(size_t)b * nplan];
+    const int parent = m.body_parentid[b];
+    const double blen = norm3(&m.body_pos[3 * b]);
+    for (int c = 0; c < nplan; c++) {
+      r[c] = reach[(size_t)parent * nplan + c];
+      s[c] = slide[(size_t)parent * nplan + c];
+      if (r[c] >= 0) r[c] += blen;
+    }
+    for (int k = 0; k < m.body_jntnum[b]; k++) {
+      const int j = m.body_jntadr[b] + k, qadr = m.jnt_qposadr[j], col = col_of[qadr];
+      const double jp = norm3(&m.jnt_pos[3 * j]), q0 = m.qpos0[qadr];
+      double add = 2.0 * jp;  // a hinge: the body's origin moves by at most twice its offset
+      if (m.jnt_type[j] == JT_SLIDE && col < 0) add = std::fabs(e->qbase[qadr] - q0);  // held at its base
+      if (m.jnt_type[j] == JT_SLIDE && col >= 0)  // planned: its travel inside the bounds
+        add = std::max(std::fabs((lo ? lo[col] : -INFINITY) - q0), std::fabs((hi ? hi[col] : INFINITY) - q0));
+      for (int c = 0; c < nplan; c++)
+        if (r[c] >= 0) r[c] += add;
+      if (col >= 0) {
+        if (m.jnt_type[j] == JT_SLIDE) s[col] = 1;
+        else r[col] = jp;
+      }
+    }
+  }
+  // rho_c(g), 0 when c is not above g
+  auto lever = [&](int g, int c) {
+    const int b = m.geom_bodyid[g];
+    if (slide[(size_t)b * nplan + c]) return 1.0;
+    const double r = reach[(size_t)b * nplan + c];
+    return r < 0 ? 0.0 : r + norm3(&m.geom_pos[3 * g]) + m.geom_rbound[g];
+  };
+  std::vector<int> tin, tout, col_body(nplan, 0);
+  body_dfs_times(m, tin, tout);
+  for (int b = 0; b < nb; b++)
+    for (int k = 0; k < m.body_jntnum[b]; k++) {
+      const int col = col_of[m.jnt_qposadr[m.body_jntadr[b] + k]];
+      if (col >= 0) col_body[col] = b;
+    }
+  auto above = [&](int c, int g) {
+    const int a = col_body[c], b = m.geom_bodyid[g];
+    return tin[a] <= tin[b] && tin[b] < tout[a];
+  };
+  std::vector<double> W((size_t)P * nplan, 0.0);
+  for (int p = 0; p < P; p++)
+    for (int c = 0; c < nplan; c++) {
+      const int g1 = e->ct_g1[p], g2 = e->ct_g2[p];
+      const bool a1 = above(c, g1), a2 = above(c, g2);
+      if (a1 != a2) W[(size_t)p * nplan + c] = lever(a1 ? g1 : g2, c);
+    }
+  return W;
 }
 
 // ---- chain program shared by the pose and IK handles: per body {njnt}, per joint {type, qadr, jid}

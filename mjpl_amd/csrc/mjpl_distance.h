@@ -15,8 +15,12 @@
 //      (min over non-allowed pairs of D - margin, its pair index) in registers and stores 12 bytes per
 //      configuration; k_distance<DM_GRAD> (clearance gradients) does the same, then runs the epilogue of
 //      mjpl_distance_grad.h once per lane; k_distance<DM_NEAR> (near pairs) lists every non-allowed pair below
-//      distmax with its distance, witnesses and gradient (mjpl_distance_grad.h: near_step), up to K per lane.
-// The walks of all four modes and of k_contacts load a pair's geoms with contact_load_pair (mjpl_contacts.h).
+//      distmax with its distance, witnesses and gradient (mjpl_distance_grad.h: near_step), up to K per lane;
+//      k_distance<DM_SWEEP> (the bubble measurement of the certified edge checks, mjpl_sweep.h) is DM_CLEAR's walk
+//      without the "cannot beat the best so far" skip and with two minima: D - margin, and D - margin minus how far
+//      the pair can move while every planning column c travels at most HD[c] from q (the lever table W of
+//      mjpl_compile.h: build_sweep_table).
+// The walks of all five modes and of k_contacts load a pair's geoms with contact_load_pair (mjpl_contacts.h).
 //
 // The routines reduce every non-plane pair to core distance minus radii (sphere = point, capsule = segment,
 // box = box).  Disjoint cores: the minimum over the feature pairs that can hold the closest points (end
@@ -318,8 +322,9 @@ __device__ __forceinline__ double pair_distance(int tcur, const GeomT<double> &c
   return core_core_distance(cur, scur, tcur == GT_CAPSULE, par, spar, tpar == GT_CAPSULE);
 }
 
-// The kernel's four modes: distances, clearance, clearance with the gradient epilogue, and the list of near pairs.
-enum : int { DM_DIST = 0, DM_CLEAR, DM_GRAD, DM_NEAR };
+// The kernel's five modes: distances, clearance, clearance with the gradient epilogue, the list of near pairs, and
+// the bubble measurement.
+enum : int { DM_DIST = 0, DM_CLEAR, DM_GRAD, DM_NEAR, DM_SWEEP };
 
 // DM_GRAD's and DM_NEAR's scratch, tables and outputs (mjpl_distance_grad.h)
 struct GradOut {
@@ -340,6 +345,14 @@ struct NearOut {
   double *dist;    // [N][K]
 };
 
+// DM_SWEEP's inputs and outputs beside clear / pair (which hold gap and its pair)
+struct SweepIO {
+  const double *W;   // lever table [P][nplan], read wave-uniformly
+  const double *HD;  // [N][nplan] in the batch's layout: how far column c may move from q, >= 0
+  double *slack;     // [N]
+  int *slack_pair;   // [N]
+};
+
 // DM_GRAD's epilogue (mjpl_distance_grad.h)
 __device__ __forceinline__ void grad_epilogue(const GradOut &go, const Carve<double> &c, IP ct, DP cd, DP wcull,
                                               DP wnarrow, const double *rx, const double *rm, int64_t i, int64_t row,
@@ -356,22 +369,28 @@ __device__ __forceinline__ void near_step(const GradOut &go, const NearOut &no, 
 // pair as DM_CLEAR, the body poses also written to go's scratch rows, then go's outputs at row i.  A row with a
 // non-finite planning column gives NaN (and pair -1).  DM_NEAR: the non-allowed pairs with d_p < distmax in
 // ascending p: no.count[i] of them (-1 for a non-finite row), the first no.K in slots i * K + k of no.pair, no.dist and
-// go's outputs, no.pair = -1 in the row's remaining slots (nothing else of those is written).
+// go's outputs, no.pair = -1 in the row's remaining slots (nothing else of those is written).  DM_SWEEP: with
+// B_p = sum over c in ascending order of HD[i][c] * W[p][c] (terms with W == 0 or HD == 0 skipped, so inf times 0 never
+// arises; inf stays inf), clear[i] = min over non-allowed p of (min(d_p, distmax) - margin_p) and pair[i] exactly as
+// DM_CLEAR gives them, sw.slack[i] = min over non-allowed p of (min(d_p, distmax) - margin_p - B_p) and sw.slack_pair[i]
+// its lowest index (distmax, -1 without such a pair; NaN, -1 for a non-finite row).  HD sits in the second column set
+// of the LDS carve.
 template <int MODE>
 __global__ void __launch_bounds__(kBlock)
 k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp, int ndp,
            const int *__restrict__ gct, const double *__restrict__ gcd, const double *__restrict__ gdt, int P,
            const double *__restrict__ Q, int64_t N, int64_t i0, int64_t n, int layout, double distmax,
            double *__restrict__ gx, double *__restrict__ gm, int ngeom, double *__restrict__ dist,
-           double *__restrict__ clear, int *__restrict__ pair, GradOut go, NearOut no) {
+           double *__restrict__ clear, int *__restrict__ pair, GradOut go, NearOut no, SweepIO sw) {
   extern __shared__ double smem[];
   const int B = blockDim.x;
   const int nplan = gip[H_NPLAN];
-  Carve<double> c = carve_lds<double>(smem, gip, nip, gdp, ndp, nplan, 1, B);
+  Carve<double> c = carve_lds<double>(smem, gip, nip, gdp, ndp, nplan, MODE == DM_SWEEP ? 2 : 1, B);
   const int64_t r = (int64_t)blockIdx.x * B + threadIdx.x;
   const bool active = r < n;
   const int64_t i = i0 + (active ? r : 0);
   load_columns(c.col0 + threadIdx.x, B, Q, N, i, nplan, layout, active);
+  if constexpr (MODE == DM_SWEEP) load_columns(c.col1 + threadIdx.x, B, sw.HD, N, i, nplan, layout, active);
   __syncthreads();
   bool finite = true;
   for (int k = 0; k < nplan; k++) finite = finite && __builtin_isfinite(c.col0[k * B + threadIdx.x]);
@@ -404,6 +423,8 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
   int bestp = -1;
   bool bestcap = true;  // DM_GRAD: the winner's D is distmax (a cap: no geometry to differentiate)
   int cnt = 0;          // DM_NEAR: near pairs so far
+  double sbest = distmax;  // DM_SWEEP: least D - margin - B so far, at pair index sbestp
+  int sbestp = -1;
   for (int p = 0; p < P; p++) {
     // (uniform: allowed pairs take no part in the clearance)
     if (MODE != DM_DIST && uni((int)dt[p * DT_LEN + DT_ALLOWED]) != 0) continue;
@@ -439,6 +460,25 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
       const bool put = near && cnt < no.K;
       if (__builtin_amdgcn_ballot_w64(put) != 0ull) near_step(go, no, g, p, D, i * no.K + cnt, active ? r : 0, nplan, put);
       if (near) cnt++;
+    } else if constexpr (MODE == DM_SWEEP) {
+      const double v = D - margin;
+      double bp = 0.0;
+      for (int k = 0; k < nplan; k++) {
+        const double w = sw.W[(int64_t)p * nplan + k];
+        if (w != 0.0) {  // (uniform)
+          const double hd = c.col1[k * B + threadIdx.x];
+          if (hd != 0.0) bp += hd * w;
+        }
+      }
+      const double s = v - bp;
+      if (live && (bestp < 0 || v < best)) {
+        best = v;
+        bestp = p;
+      }
+      if (live && (sbestp < 0 || s < sbest)) {
+        sbest = s;
+        sbestp = p;
+      }
     } else {
       const double v = D - margin;
       if (live && (need || far) && (bestp < 0 || v < best)) {
@@ -456,6 +496,10 @@ k_distance(const int *__restrict__ gip, int nip, const double *__restrict__ gdp,
     if (!active) return;
     clear[i] = live ? best : NAN;
     pair[i] = live ? bestp : -1;
+    if constexpr (MODE == DM_SWEEP) {
+      sw.slack[i] = live ? sbest : NAN;
+      sw.slack_pair[i] = live ? sbestp : -1;
+    }
     // 3. DM_GRAD: the epilogue (lanes diverge from here on)
     if constexpr (MODE == DM_GRAD)
       grad_epilogue(go, c, ct, cd, wcull, wnarrow, rx, rm, i, r, nplan, live, bestp, bestcap);

@@ -36,6 +36,7 @@
 #include "mjpl_distance.h"
 #include "mjpl_distance_grad.h"
 #include "mjpl_push.h"
+#include "mjpl_sweep.h"
 
 namespace {
 
@@ -506,6 +507,14 @@ struct mjpl_engine {
   DevBuf<double> d_push_f64;
   DevBuf<int> d_push_i32;
   int *h_push_n = nullptr;
+  // mjpl_sweep_* (mjpl_sweep.h): the bounds in force over the planning columns (empty: none) and the device table
+  // [lo | hi | W] made from them (mjpl_compile.h: build_sweep_table; not part of the hashed program); per chunk the two
+  // work buffers of nodes, the measurements of a round and the per-edge hit keys (grow-only)
+  std::vector<double> sweep_lo, sweep_hi;
+  double *d_sweep_tab = nullptr;
+  DevBuf<double> d_sweep_rows[2], d_sweep_hd[2], d_sweep_f64;
+  DevBuf<int> d_sweep_meta[2], d_sweep_i32;
+  DevBuf<unsigned long long> d_sweep_key;
 };
 
 namespace {
@@ -693,6 +702,21 @@ int make_grad_table(mjpl_engine *e) {
   std::vector<double> t;
   MJPL_TRY(build_grad_table(e, t));
   return upload_table(&e->d_gr, t);
+}
+
+// ... and the lever table of the certified edge checks, which follows the planning selection and the bounds given:
+// mjpl_create, mjpl_set_planning (no bounds), mjpl_sweep_bounds and a mjpl_sweep_edges* call with other bounds
+int make_sweep_table(mjpl_engine *e, const double *lo, const double *hi) {
+  const size_t nplan = e->qidx.size();
+  e->sweep_lo.assign(nplan, -INFINITY);
+  e->sweep_hi.assign(nplan, INFINITY);
+  if (lo) e->sweep_lo.assign(lo, lo + nplan);
+  if (hi) e->sweep_hi.assign(hi, hi + nplan);
+  std::vector<double> t(e->sweep_lo);
+  t.insert(t.end(), e->sweep_hi.begin(), e->sweep_hi.end());
+  const std::vector<double> W = build_sweep_table(e, e->sweep_lo.data(), e->sweep_hi.data());
+  t.insert(t.end(), W.begin(), W.end());
+  return upload_table(&e->d_sweep_tab, t);
 }
 
 size_t lds_bytes(const mjpl_engine *e, int ncolsets, size_t scalar = sizeof(double), int block = kBlock,
@@ -1394,7 +1418,7 @@ struct PairLaunch {
 
 // What every pair-query launch needs first: the pair-type check, the FK scratch and the kernel's LDS grant.
 template <class K>
-int pair_query_prologue(mjpl_engine *e, K kernel, int64_t N, PairLaunch *pl) {
+int pair_query_prologue(mjpl_engine *e, K kernel, int64_t N, PairLaunch *pl, int ncolsets = 1) {
   int rc = check_pair_types(e);
   if (rc != MJPL_OK) return rc;
   const size_t ng = e->m.ngeom;
@@ -1403,7 +1427,7 @@ int pair_query_prologue(mjpl_engine *e, K kernel, int64_t N, PairLaunch *pl) {
   if (rc != MJPL_OK) return rc;
   pl->gx = e->d_ct_scratch.p;
   pl->gm = e->d_ct_scratch.p + (size_t)pl->rows * ng * 3;
-  pl->lds = lds_bytes(e, 1);
+  pl->lds = lds_bytes(e, ncolsets);
   return allow_lds(kernel, pl->lds);
 }
 
@@ -1429,21 +1453,31 @@ int launch_contacts(mjpl_engine *e, const double *dQ, int64_t N, int layout, uns
 // One k_distance<mode> launch per kContactRows configurations: D [N][P] (DM_DIST), (C, pair) [N] (DM_CLEAR),
 // (C, pair), grad [N][nplan], fromto [N][6], normal [N][3] and status [N] (DM_GRAD; fromto / normal may be null), or
 // count [N] and K slots per configuration of pair, D (ddist), grad, fromto, normal and status (DM_NEAR: K = near_k,
-// dcount; fromto / normal may be null).
+// dcount; fromto / normal may be null), or gap and its pair (dclear, dpair) with slack and its pair (DM_SWEEP: dHD the
+// travels beside dQ, dslack, dslack_pair; HD takes a second column set of the LDS carve).
 int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int layout, double distmax, double *ddist,
                     double *dclear, int32_t *dpair, double *dgrad = nullptr, double *dfromto = nullptr,
-                    double *dnormal = nullptr, int32_t *dstatus = nullptr, int near_k = 0, int32_t *dcount = nullptr) {
+                    double *dnormal = nullptr, int32_t *dstatus = nullptr, int near_k = 0, int32_t *dcount = nullptr,
+                    const double *dHD = nullptr, double *dslack = nullptr, int32_t *dslack_pair = nullptr) {
   const int P = (int)e->ct_g1.size();
   if (N == 0 || (mode == DM_DIST && P == 0)) return MJPL_OK;
   const auto kernel = mode == DM_DIST    ? k_distance<DM_DIST>
                       : mode == DM_CLEAR ? k_distance<DM_CLEAR>
                       : mode == DM_GRAD  ? k_distance<DM_GRAD>
-                                         : k_distance<DM_NEAR>;
+                      : mode == DM_NEAR  ? k_distance<DM_NEAR>
+                                         : k_distance<DM_SWEEP>;
   PairLaunch pl;
-  int rc = pair_query_prologue(e, kernel, N, &pl);
+  int rc = pair_query_prologue(e, kernel, N, &pl, mode == DM_SWEEP ? 2 : 1);
   if (rc != MJPL_OK) return rc;
   GradOut go = {};
   NearOut no = {};
+  SweepIO sw = {};
+  if (mode == DM_SWEEP) {
+    sw.W = e->d_sweep_tab + 2 * e->qidx.size();
+    sw.HD = dHD;
+    sw.slack = dslack;
+    sw.slack_pair = dslack_pair;
+  }
   if (mode == DM_NEAR) {
     rc = e->d_nr_frames.reserve((size_t)pl.rows * e->qidx.size() * 6);
     if (rc != MJPL_OK) return rc;
@@ -1474,7 +1508,7 @@ int launch_distance(mjpl_engine *e, int mode, const double *dQ, int64_t N, int l
     // (all outputs are indexed by the batch row i: whole arrays)
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), pl.lds, e->stream, e->d_ip, (int)e->ip.size(), e->d_dp,
                        (int)e->dp.size(), e->d_ct_ip, e->d_ct_dp, e->d_dt, P, dQ, N, i0, n, layout, distmax, pl.gx,
-                       pl.gm, e->m.ngeom, ddist, dclear, dpair, go, no);
+                       pl.gm, e->m.ngeom, ddist, dclear, dpair, go, no, sw);
     HIP_TRY(hipGetLastError());
   }
   return MJPL_OK;
@@ -1706,7 +1740,8 @@ int mjpl_create(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t
   int rc = engine_from_desc(e, d, allowed_bodies, nallowed);
   if (rc != MJPL_OK) return bail(rc);
   apply_debug_environment(e);
-  if ((rc = compile_program(e)) != MJPL_OK || (rc = make_pair_tables(e)) != MJPL_OK || (rc = make_grad_table(e)) != MJPL_OK)
+  if ((rc = compile_program(e)) != MJPL_OK || (rc = make_pair_tables(e)) != MJPL_OK || (rc = make_grad_table(e)) != MJPL_OK ||
+      (rc = make_sweep_table(e, nullptr, nullptr)) != MJPL_OK)
     return bail(rc);
   *out = e;
   return MJPL_OK;
@@ -1739,6 +1774,7 @@ void mjpl_destroy(mjpl_engine *e) {
   if (e->d_ct_dp) (void)hipFree(e->d_ct_dp);
   if (e->d_dt) (void)hipFree(e->d_dt);
   if (e->d_gr) (void)hipFree(e->d_gr);
+  if (e->d_sweep_tab) (void)hipFree(e->d_sweep_tab);
   const hipStream_t stream = e->stream;
   delete e;  // (frees its DevBufs: with the device set, and before the stream goes)
   if (stream) (void)hipStreamDestroy(stream);
@@ -1838,6 +1874,35 @@ int mjpl_program_dump_never_touch(const mjpl_model_desc *d, const int32_t *allow
   return MJPL_OK;
 }
 
+int mjpl_sweep_levers(const mjpl_model_desc *d, const int32_t *allowed_bodies, int32_t nallowed, const int32_t *qidx,
+                      int32_t nplan, const double *qpos_base, const double *lo, const double *hi, double *W, int64_t cap) {
+  if (!d) return fail(MJPL_E_ARG, "mjpl_sweep_levers: NULL argument");
+  if (d->nq < 0 || d->njnt < 0 || d->nbody < 1 || d->ngeom < 0 || nallowed < 0) return fail(MJPL_E_ARG, "negative size");
+  if (d->nq != d->njnt) return fail(MJPL_E_JOINT, "nq != njnt: only 1-DoF joints are supported");
+  std::unique_ptr<mjpl_engine> e(new mjpl_engine());
+  int rc = engine_from_desc(e.get(), d, allowed_bodies, nallowed);
+  if (rc != MJPL_OK) return rc;
+  if (qidx) {
+    e->qidx.assign(qidx, qidx + nplan);
+    for (int c : e->qidx)
+      if (c < 0 || c >= d->nq) return fail(MJPL_E_ARG, "planning index %d out of range", c);
+  }
+  if (qpos_base) e->qbase.assign(qpos_base, qpos_base + d->nq);
+  for (size_t k = 0; k < e->qidx.size(); k++) {
+    const double l = lo ? lo[k] : -INFINITY, h = hi ? hi[k] : INFINITY;
+    if (!(l <= h)) return fail(MJPL_E_ARG, "bounds of planning column %d: lo %g, hi %g (NaN and lo > hi are refused)", (int)k, l, h);
+  }
+  if ((rc = compile_host(e.get())) != MJPL_OK) return rc;  // (host tables only: nothing is allocated or uploaded)
+  std::vector<int> cip;
+  std::vector<double> cdp;
+  build_contact_table(e.get(), cip, cdp);
+  const std::vector<double> t = build_sweep_table(e.get(), lo, hi);
+  const int64_t P = (int64_t)e->ct_g1.size();
+  if (W && cap >= (int64_t)t.size()) memcpy(W, t.data(), t.size() * sizeof(double));
+  else if (W) return fail(MJPL_E_CAPACITY, "mjpl_sweep_levers: room for %lld doubles, the table has %zu", (long long)cap, t.size());
+  return (int)P;
+}
+
 int mjpl_spec_probe(uint64_t hash, int32_t generic) {
   return find_spec(hash, generic != 0) ? 1 : 0;
 }
@@ -1867,7 +1932,8 @@ int mjpl_set_planning(mjpl_engine *e, const int32_t *qidx, int32_t nplan, const 
   if (qpos_base) e->qbase.assign(qpos_base, qpos_base + e->m.nq);
   const int rc = compile_program(e);
   if (rc != MJPL_OK) return rc;
-  return make_grad_table(e);
+  MJPL_TRY(make_grad_table(e));
+  return make_sweep_table(e, nullptr, nullptr);
 }
 
 int mjpl_set_filter(mjpl_engine *e, int32_t enable, double tol) {
@@ -2788,6 +2854,129 @@ int launch_push(mjpl_engine *e, const mjpl_push_desc &d, const double *dQ, int64
 
 }  // namespace
 
+// ---- certified edge checks (mjpl_sweep.h)
+namespace {
+
+int check_bounds(const mjpl_engine *e, const double *lo, const double *hi) {
+  for (size_t k = 0; k < e->qidx.size(); k++) {
+    const double l = lo ? lo[k] : -INFINITY, h = hi ? hi[k] : INFINITY;
+    if (!(l <= h)) return fail(MJPL_E_ARG, "bounds of planning column %d: lo %g, hi %g (NaN and lo > hi are refused)", (int)k, l, h);
+  }
+  return MJPL_OK;
+}
+
+// the lever table for these bounds, made again only when they differ from those in force
+int sweep_use_bounds(mjpl_engine *e, const double *lo, const double *hi) {
+  bool same = e->d_sweep_tab != nullptr || e->qidx.empty();
+  for (size_t k = 0; k < e->qidx.size() && same; k++)
+    same = (lo ? lo[k] : -INFINITY) == e->sweep_lo[k] && (hi ? hi[k] : INFINITY) == e->sweep_hi[k];
+  if (same) return MJPL_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return make_sweep_table(e, lo, hi);
+}
+
+int check_measure_args(const mjpl_engine *e, const void *Q, const void *HD, int64_t N, int layout, double cap,
+                       std::initializer_list<const void *> outs) {
+  MJPL_TRY(check_query_args(e, Q, N, layout, cap, outs));
+  if (N > 0 && !HD) return fail(MJPL_E_ARG, "NULL batch pointer");
+  if (!(cap < INFINITY)) return fail(MJPL_E_ARG, "cap must be finite, got %g", cap);
+  return MJPL_OK;
+}
+
+// Argument checks of mjpl_sweep_edges*: check_common on both ends, the ranges of the descriptor (NaN refused
+// everywhere), lo <= hi per planning column, every output non-null when E > 0.
+int check_sweep_args(const mjpl_engine *e, const mjpl_sweep_desc *d, const void *QA, const void *QB, int64_t E, int layout,
+                     std::initializer_list<const void *> outs) {
+  MJPL_TRY(check_common(e, QA, E, layout));
+  MJPL_TRY(check_common(e, QB, E, layout));
+  if (!d) return fail(MJPL_E_ARG, "mjpl_sweep_edges: NULL descriptor");
+  if (!(d->d_min >= 0) || !(d->d_min < INFINITY)) return fail(MJPL_E_ARG, "d_min must be >= 0 and finite (NaN is refused), got %g", d->d_min);
+  if (!(d->cap > d->d_min + e->ct_margin_max) || !(d->cap < INFINITY))
+    return fail(MJPL_E_ARG, "cap must be finite and > d_min + the largest margin of a non-allowed pair = %g (NaN is refused), got %g",
+                d->d_min + e->ct_margin_max, d->cap);
+  if (d->max_depth < 0 || d->max_depth > kSweepMaxDepth) return fail(MJPL_E_ARG, "max_depth must be 0..%d, got %d", kSweepMaxDepth, d->max_depth);
+  MJPL_TRY(check_bounds(e, d->lo, d->hi));
+  if (E > 0)
+    for (const void *o : outs)
+      if (!o) return fail(MJPL_E_ARG, "NULL output pointer");
+  return MJPL_OK;
+}
+
+// The loop of mjpl_sweep_edges* on device pointers (include/mjpl_hip.h states the node rule).  Edges go in chunks of
+// clamp(kSweepNodes >> max_depth, 64, 2^14), so that a chunk's deepest round holds kSweepNodes nodes at most.  Per chunk:
+// k_sweep_init writes round 0 into work buffer 0; then per round one k_distance<DM_SWEEP> launch over the open nodes, one
+// k_sweep_step launch, and one 4-byte read of the other buffer's fill counter, which sizes the next round (0: the chunk
+// is done); k_sweep_finish turns the per-edge state into the verdicts.
+int launch_sweep(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dQA, const double *dQB, int64_t E, int layout,
+                 int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes, int32_t *ddepth) {
+  MJPL_TRY(check_pair_types(e));
+  MJPL_TRY(sweep_use_bounds(e, d.lo, d.hi));
+  const int nplan = (int)e->qidx.size();
+  const hipStream_t st = e->stream;
+  if (!e->h_push_n) HIP_TRY(hipHostMalloc((void **)&e->h_push_n, sizeof(int)));
+  const int64_t chunk = std::min<int64_t>(std::max<int64_t>(kSweepNodes >> d.max_depth, 64), (int64_t)1 << 14);
+  const size_t np = (size_t)std::max(nplan, 1);
+  // a work buffer for n nodes; its fill counter sits behind the (edge, ordinal) words
+  auto reserve_work = [&](int k, size_t n) -> int {
+    MJPL_TRY(e->d_sweep_rows[k].reserve(n * np));
+    MJPL_TRY(e->d_sweep_hd[k].reserve(n * np));
+    return e->d_sweep_meta[k].reserve(2 * n + 1);
+  };
+  auto work = [&](int k) {
+    return SweepWork{e->d_sweep_rows[k].p, e->d_sweep_hd[k].p, e->d_sweep_meta[k].p, e->d_sweep_meta[k].p + e->d_sweep_meta[k].cap - 1};
+  };
+  auto read_count = [&](const SweepWork &w, int *n) -> int {
+    HIP_TRY(hipMemcpyAsync(e->h_push_n, w.n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n = *e->h_push_n;
+    return MJPL_OK;
+  };
+  MJPL_TRY(e->d_sweep_key.reserve((size_t)std::min<int64_t>(chunk, E)));
+  SweepArgs a = {};
+  a.QA = dQA; a.QB = dQB; a.E = E; a.layout = layout; a.nplan = nplan;
+  a.lo = e->d_sweep_tab; a.hi = e->d_sweep_tab + nplan;
+  a.d_min = d.d_min; a.max_depth = d.max_depth;
+  a.key = e->d_sweep_key.p;
+  a.status = dstatus; a.nodes = dnodes; a.depth = ddepth; a.pair = dpair; a.t_hit = dt_hit;
+  a.clear_bits = reinterpret_cast<unsigned long long *>(dclear_lb);
+  for (int64_t i0 = 0; i0 < E; i0 += chunk) {
+    const int ne = (int)std::min<int64_t>(chunk, E - i0);
+    a.i0 = i0;
+    MJPL_TRY(reserve_work(0, 3 * (size_t)ne));
+    SweepWork cur = work(0);
+    HIP_TRY(hipMemsetAsync(cur.n, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_sweep_init, dim3((unsigned)((ne + kSweepBlock - 1) / kSweepBlock)), dim3(kSweepBlock), 0, st, a, ne, cur);
+    HIP_TRY(hipGetLastError());
+    int n = 0;
+    MJPL_TRY(read_count(cur, &n));
+    for (int round = 0; round <= d.max_depth && n > 0; round++) {
+      const int nxt = (round & 1) ^ 1;
+      MJPL_TRY(e->d_sweep_f64.reserve(2 * (size_t)n));
+      MJPL_TRY(e->d_sweep_i32.reserve(2 * (size_t)n));
+      double *gap = e->d_sweep_f64.p, *slack = gap + n;
+      int *gap_pair = e->d_sweep_i32.p, *slack_pair = gap_pair + n;
+      MJPL_TRY(launch_distance(e, DM_SWEEP, cur.rows, n, MJPL_AOS, d.cap, nullptr, gap, gap_pair, nullptr, nullptr, nullptr,
+                               nullptr, 0, nullptr, cur.hd, slack, slack_pair));
+      // (the other buffer at twice the active count: every node may open two)
+      const bool last = round == d.max_depth;
+      MJPL_TRY(reserve_work(nxt, last ? 1 : 2 * (size_t)n));
+      SweepWork next = work(nxt);
+      HIP_TRY(hipMemsetAsync(next.n, 0, sizeof(int), st));
+      hipLaunchKernelGGL(k_sweep_step, dim3((unsigned)((n + kSweepBlock - 1) / kSweepBlock)), dim3(kSweepBlock), 0, st, a, round, n,
+                         cur, gap, gap_pair, slack, next);
+      HIP_TRY(hipGetLastError());
+      if (last) break;
+      MJPL_TRY(read_count(next, &n));
+      cur = next;
+    }
+    hipLaunchKernelGGL(k_sweep_finish, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, a, ne);
+    HIP_TRY(hipGetLastError());
+  }
+  return MJPL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int mjpl_nearest_dev(mjpl_engine *e, const double *dnodes, int64_t n, int64_t cap, const double *dqueries,
@@ -3047,6 +3236,58 @@ int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *d, const double *Q, int6
   return staged(e, false, {{Q, qb}}, outs, [&](void **in, void **out) {
     return launch_push(e, *d, (const double *)in[0], N, layout, (double *)out[0], (double *)out[1], (int32_t *)out[2],
                        (int32_t *)out[3], (int32_t *)out[4]);
+  });
+}
+
+// ---- certified edge checks (mjpl_sweep.h)
+
+int mjpl_sweep_bounds(mjpl_engine *e, const double *lo, const double *hi) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  MJPL_TRY(check_bounds(e, lo, hi));
+  HIP_TRY(hipSetDevice(e->device));
+  return sweep_use_bounds(e, lo, hi);
+}
+
+int mjpl_sweep_measure_dev(mjpl_engine *e, const double *dQ, const double *dHD, int64_t N, int32_t layout, double cap,
+                           double *dslack, int32_t *dslack_pair, double *dgap, int32_t *dgap_pair) {
+  int rc = check_measure_args(e, dQ, dHD, N, layout, cap, {dslack, dslack_pair, dgap, dgap_pair});
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_distance(e, DM_SWEEP, dQ, N, layout, cap, nullptr, dgap, dgap_pair, nullptr, nullptr, nullptr, nullptr, 0,
+                         nullptr, dHD, dslack, dslack_pair);
+}
+
+int mjpl_sweep_measure(mjpl_engine *e, const double *Q, const double *HD, int64_t N, int32_t layout, double cap, double *slack,
+                       int32_t *slack_pair, double *gap, int32_t *gap_pair) {
+  int rc = check_measure_args(e, Q, HD, N, layout, cap, {slack, slack_pair, gap, gap_pair});
+  if (rc != MJPL_OK || N == 0) return rc;
+  const size_t n = N, db = sizeof(double), ib = sizeof(int32_t), qb = n * e->qidx.size() * db;
+  const HostOut outs[] = {{slack, n * db}, {slack_pair, n * ib}, {gap, n * db}, {gap_pair, n * ib}};
+  return staged(e, false, {{Q, qb}, {HD, qb}}, outs, [&](void **in, void **out) {
+    return launch_distance(e, DM_SWEEP, (const double *)in[0], N, layout, cap, nullptr, (double *)out[2], (int32_t *)out[3],
+                           nullptr, nullptr, nullptr, nullptr, 0, nullptr, (const double *)in[1], (double *)out[0],
+                           (int32_t *)out[1]);
+  });
+}
+
+int mjpl_sweep_edges_dev(mjpl_engine *e, const mjpl_sweep_desc *d, const double *dQA, const double *dQB, int64_t E,
+                         int32_t layout, int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes,
+                         int32_t *ddepth) {
+  int rc = check_sweep_args(e, d, dQA, dQB, E, layout, {dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth});
+  if (rc != MJPL_OK || E == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_sweep(e, *d, dQA, dQB, E, layout, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth);
+}
+
+int mjpl_sweep_edges(mjpl_engine *e, const mjpl_sweep_desc *d, const double *QA, const double *QB, int64_t E, int32_t layout,
+                     int32_t *status, double *t_hit, double *clear_lb, int32_t *pair, int32_t *nodes, int32_t *depth) {
+  int rc = check_sweep_args(e, d, QA, QB, E, layout, {status, t_hit, clear_lb, pair, nodes, depth});
+  if (rc != MJPL_OK || E == 0) return rc;
+  const size_t n = E, db = sizeof(double), ib = sizeof(int32_t), qb = n * e->qidx.size() * db;
+  const HostOut outs[] = {{status, n * ib}, {t_hit, n * db}, {clear_lb, n * db}, {pair, n * ib}, {nodes, n * ib}, {depth, n * ib}};
+  return staged(e, false, {{QA, qb}, {QB, qb}}, outs, [&](void **in, void **out) {
+    return launch_sweep(e, *d, (const double *)in[0], (const double *)in[1], E, layout, (int32_t *)out[0], (double *)out[1],
+                        (double *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
   });
 }
 

@@ -20,6 +20,8 @@ SOA, AOS = 0, 1
 GRAD_OK, GRAD_FLAT, GRAD_DEGENERATE, GRAD_NONFINITE = 0, 1, 2, 3
 # mjpl_push_out* status values (include/mjpl_hip.h: MJPL_PUSH_*)
 PUSH_OK, PUSH_STUCK, PUSH_DEGENERATE, PUSH_NONFINITE = 0, 1, 2, 3
+# mjpl_sweep_edges* status values (include/mjpl_hip.h: MJPL_SWEEP_*)
+SWEEP_FREE, SWEEP_HIT, SWEEP_UNDECIDED, SWEEP_NONFINITE, SWEEP_RANGE = 0, 1, 2, 3, 4
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -93,6 +95,10 @@ class PushDesc(C.Structure):
     ]
 
 
+class SweepDesc(C.Structure):
+    _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
+
+
 class RrtDesc(C.Structure):
     _fields_ = [
         ("lanes", C.c_int32), ("capacity", C.c_int64), ("epsilon", C.c_double), ("interval_step", C.c_double),
@@ -147,6 +153,15 @@ ABI = {
                                       _VP]),
     "mjpl_push_out": (C.c_int, [_VP, C.POINTER(PushDesc), _F64P, C.c_int64, C.c_int32, _F64P, _F64P, _I32P, _I32P, _I32P]),
     "mjpl_push_out_dev": (C.c_int, [_VP, C.POINTER(PushDesc), _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
+                                    C.c_int64]),
+    "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
+    "mjpl_sweep_measure": (C.c_int, [_VP, _F64P, _F64P, C.c_int64, C.c_int32, C.c_double, _F64P, _I32P, _F64P, _I32P]),
+    "mjpl_sweep_measure_dev": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, _VP, _VP, _VP, _VP]),
+    "mjpl_sweep_edges": (C.c_int, [_VP, C.POINTER(SweepDesc), _F64P, _F64P, C.c_int64, C.c_int32, _I32P, _F64P, _F64P, _I32P,
+                                   _I32P, _I32P]),
+    "mjpl_sweep_edges_dev": (C.c_int, [_VP, C.POINTER(SweepDesc), _VP, _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                       _VP]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -283,6 +298,54 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _model_desc(model: Model):
+    """(mjpl_model_desc of `model`, the arrays it points into)."""
+    d = _ModelDesc()
+    d.nq, d.njnt, d.nbody, d.ngeom = model.nq, model.njnt, model.nbody, model.ngeom
+    keep = []
+    for name, typ in _ModelDesc._fields_[4:]:
+        arr = getattr(model, name)
+        arr = _i32(arr) if typ is _I32P else _f64(arr)
+        keep.append(arr)
+        setattr(d, name, arr.ctypes.data_as(typ))
+    return d, keep
+
+
+def _opt_f64(a, n, what):
+    if a is None:
+        return None, None
+    a = _f64(a)
+    if a.shape != (n,):
+        raise ValueError(f"{what} must have {n} entries, got {a.shape}")
+    return a, a.ctypes.data_as(_F64P)
+
+
+def sweep_levers(model: Model, allowed_collision_bodies=(), qidx=None, qpos_base=None, lo=None, hi=None) -> np.ndarray:
+    """The pair lever table of the certified edge checks, on the host alone (mjpl_sweep_levers: no GPU needed) ->
+    float64 [P, nplan] over the candidate pairs of Engine.contact_pairs(): one unit of planning column c changes the
+    distance of pair p by at most W[p, c].  lo / hi: bounds per planning column (a planning slide joint without finite
+    bounds gives inf for the hinges above it)."""
+    lib = load_library()
+    d, keep = _model_desc(model)
+    pairs = _i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
+    q = None if qidx is None else _i32(qidx)
+    nplan = model.nq if q is None else len(q)
+    base = None if qpos_base is None else _f64(qpos_base)
+    lo, plo = _opt_f64(lo, nplan, "lo")
+    hi, phi = _opt_f64(hi, nplan, "hi")
+    args = [C.byref(d), pairs.ctypes.data_as(_I32P), len(pairs), None if q is None else q.ctypes.data_as(_I32P), nplan,
+            None if base is None else base.ctypes.data_as(_F64P), plo, phi]
+    P = lib.mjpl_sweep_levers(*args, None, 0)
+    if P < 0:
+        raise MjplError(P, lib.mjpl_last_error().decode())
+    W = np.zeros((P, nplan), np.float64)
+    rc = lib.mjpl_sweep_levers(*args, W.ctypes.data_as(_F64P), W.size)
+    if rc < 0:
+        raise MjplError(rc, lib.mjpl_last_error().decode())
+    del keep
+    return W
+
+
 class DeviceBuffer:
     """A hipMalloc'ed block owned by an :class:`Engine`."""
 
@@ -321,14 +384,7 @@ class Engine:
         self.lib = load_library(lib_path)
         self.model = model
         self.h = None
-        d = _ModelDesc()
-        d.nq, d.njnt, d.nbody, d.ngeom = model.nq, model.njnt, model.nbody, model.ngeom
-        keep = []
-        for name, typ in _ModelDesc._fields_[4:]:
-            arr = getattr(model, name)
-            arr = _i32(arr) if typ is _I32P else _f64(arr)
-            keep.append(arr)
-            setattr(d, name, arr.ctypes.data_as(typ))
+        d, keep = _model_desc(model)
         # body names -> ids (unknown names raise KeyError from model.body, as mujoco does)
         pairs = _i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]
                      ).reshape(-1, 2)
@@ -337,6 +393,8 @@ class Engine:
         self._ok(rc)
         self.h = h
         self.nplan = model.nq
+        self._allowed_bodies = tuple(allowed_collision_bodies)
+        self._qidx, self._qbase = None, None
         self._projectors: "weakref.WeakSet[PoseProjector]" = weakref.WeakSet()
         self._apply_start_options(options)
 
@@ -452,6 +510,7 @@ class Engine:
         self._ok(self.lib.mjpl_set_planning(self.h, qidx.ctypes.data_as(_I32P), len(qidx),
                                             base.ctypes.data_as(_F64P)))
         self.nplan = len(qidx)
+        self._qidx, self._qbase = qidx.copy(), base.copy()
 
     def _batch(self, Q, layout):
         Q = _f64(Q)
@@ -653,6 +712,85 @@ class Engine:
         iterations: the call returns once the last launches are enqueued, not before the loop has run."""
         desc, keep = self.push_desc(d_min, **params)
         self._ok(self.lib.mjpl_push_out_dev(self.h, C.byref(desc), dQ, n, layout, dQ_out, dclear, dpair, diters, dstatus))
+        del keep
+
+    # -- certified edge checks: no contact anywhere along an edge (include/mjpl_hip.h, mjpl_sweep_*)
+    def sweep_levers(self, lo=None, hi=None) -> np.ndarray:
+        """The lever table this engine would use with the bounds lo / hi -> float64 [P, nplan] (computed on the host:
+        module-level sweep_levers)."""
+        return sweep_levers(self.model, self._allowed_bodies, self._qidx, self._qbase, lo, hi)
+
+    def sweep_bounds(self, lo=None, hi=None):
+        """Bounds over the planning columns for the lever table of sweep_measure (sweep_edges takes its own)."""
+        lo, plo = _opt_f64(lo, self.nplan, "lo")
+        hi, phi = _opt_f64(hi, self.nplan, "hi")
+        self._ok(self.lib.mjpl_sweep_bounds(self.h, plo, phi))
+
+    def sweep_measure(self, Q, HD, cap, layout=AOS):
+        """The bubble measurement -> (slack float64 [N], slack_pair int32 [N], gap float64 [N], gap_pair int32 [N]).
+        HD (shaped like Q, >= 0): how far each planning column may move from the row.  gap, gap_pair = clearance(Q, cap)
+        bit for bit; slack = min over non-allowed pairs of (distance - margin - sum_c HD[c] W[p, c]).  slack > 0: no
+        configuration of the box around the row is in contact."""
+        Q, n = self._batch(Q, layout)
+        HD, n2 = self._batch(HD, layout)
+        if n != n2:
+            raise ValueError("Q and HD must hold the same number of rows")
+        slack, gap = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        sp, gp = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._ok(self.lib.mjpl_sweep_measure(self.h, Q.ctypes.data_as(_F64P), HD.ctypes.data_as(_F64P), n, layout, float(cap),
+                                             slack.ctypes.data_as(_F64P), sp.ctypes.data_as(_I32P),
+                                             gap.ctypes.data_as(_F64P), gp.ctypes.data_as(_I32P)))
+        return slack, sp, gap, gp
+
+    def sweep_measure_dev(self, dQ, dHD, n, layout, cap, dslack, dslack_pair, dgap, dgap_pair):
+        """sweep_measure() on device pointers: dslack / dgap n float64, dslack_pair / dgap_pair n int32 (asynchronous)."""
+        self._ok(self.lib.mjpl_sweep_measure_dev(self.h, dQ, dHD, n, layout, float(cap), dslack, dslack_pair, dgap, dgap_pair))
+
+    def sweep_desc(self, d_min=0.0, cap=None, max_depth=8, lo=None, hi=None):
+        """The mjpl_sweep_desc of a call and the arrays it points into (keep both alive for the call).  cap None: d_min +
+        the largest margin of a non-allowed pair + 0.1."""
+        lo, plo = _opt_f64(lo, self.nplan, "lo")
+        hi, phi = _opt_f64(hi, self.nplan, "hi")
+        if cap is None:
+            cap = float(d_min) + self.sweep_margin_max() + 0.1
+        return SweepDesc(float(d_min), float(cap), int(max_depth), plo, phi), (lo, hi)
+
+    def sweep_margin_max(self) -> float:
+        """The largest margin of a non-allowed candidate pair (0 without one): a sweep's cap must exceed d_min + this."""
+        if getattr(self, "_sweep_margin_max", None) is None:
+            pairs, allowed = self.contact_pairs()
+            m = np.asarray(self.model.geom_margin, np.float64)
+            pm = np.maximum(m[pairs[:, 0]], m[pairs[:, 1]])[~allowed]
+            self._sweep_margin_max = float(pm.max()) if len(pm) else 0.0
+        return self._sweep_margin_max
+
+    def sweep_edges(self, QA, QB, d_min=0.0, layout=AOS, **params):
+        """Certified edge checks -> (status int32 [E], t_hit float64 [E], clear_lb float64 [E], pair int32 [E], nodes int32
+        [E], depth int32 [E]); params: cap, max_depth, lo, hi.  status SWEEP_FREE: no configuration of the segment
+        QA -> QB is in contact or nearer than d_min, and clearance >= clear_lb all along it; SWEEP_HIT: the configuration
+        at t_hit is (pair: its closest pair); SWEEP_UNDECIDED: max_depth spent; SWEEP_NONFINITE; SWEEP_RANGE: an end
+        point outside lo / hi."""
+        QA, n = self._batch(QA, layout)
+        QB, n2 = self._batch(QB, layout)
+        if n != n2:
+            raise ValueError("QA and QB must hold the same number of edges")
+        desc, keep = self.sweep_desc(d_min, **params)
+        status, pair = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        nodes, depth = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        t_hit, clear_lb = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        self._ok(self.lib.mjpl_sweep_edges(self.h, C.byref(desc), QA.ctypes.data_as(_F64P), QB.ctypes.data_as(_F64P), n, layout,
+                                           status.ctypes.data_as(_I32P), t_hit.ctypes.data_as(_F64P),
+                                           clear_lb.ctypes.data_as(_F64P), pair.ctypes.data_as(_I32P),
+                                           nodes.ctypes.data_as(_I32P), depth.ctypes.data_as(_I32P)))
+        del keep
+        return status, t_hit, clear_lb, pair, nodes, depth
+
+    def sweep_edges_dev(self, dQA, dQB, n, layout, d_min, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth, **params):
+        """sweep_edges() on device pointers (lo / hi stay host arrays).  Enqueued on the engine's stream, which it
+        synchronises once per round."""
+        desc, keep = self.sweep_desc(d_min, **params)
+        self._ok(self.lib.mjpl_sweep_edges_dev(self.h, C.byref(desc), dQA, dQB, n, layout, dstatus, dt_hit, dclear_lb, dpair,
+                                               dnodes, ddepth))
         del keep
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
