@@ -320,30 +320,47 @@ def _opt_f64(a, n, what):
     return a, a.ctypes.data_as(_F64P)
 
 
+def _ptr(a, typ):
+    return None if a is None else a.ctypes.data_as(typ)
+
+
+def _compile_args(model: Model, allowed_collision_bodies=(), qidx=None, qpos_base=None):
+    """What every host-side compile entry point of the library takes first -> ([model descriptor, allowed body pairs and
+    their number, planning indices and their number (NULL, 0: every joint), base configuration], the arrays these point into)."""
+    d, keep = _model_desc(model)
+    # body names -> ids (unknown names raise KeyError from model.body, as mujoco does)
+    pairs = _i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
+    q = None if qidx is None else _i32(qidx)
+    base = None if qpos_base is None else _f64(qpos_base)
+    return [C.byref(d), _ptr(pairs, _I32P), len(pairs), _ptr(q, _I32P), 0 if q is None else len(q), _ptr(base, _F64P)], (d, keep, pairs, q, base)
+
+
+def _sized_call(lib, f, args_for, alloc):
+    """The protocol of the host-side dump functions: called with NULL buffers, f reports how much there is (its return
+    value, or counters that args_for passes by reference); alloc(that return value) makes the arrays, the second call
+    fills them.  args_for(arrays or None) -> f's arguments.  -> the arrays."""
+    def call(bufs):
+        rc = f(*args_for(bufs))
+        if rc < 0:
+            raise MjplError(rc, lib.mjpl_last_error().decode())
+        return rc
+    bufs = alloc(call(None))
+    call(bufs)
+    return bufs
+
+
 def sweep_levers(model: Model, allowed_collision_bodies=(), qidx=None, qpos_base=None, lo=None, hi=None) -> np.ndarray:
     """The pair lever table of the certified edge checks, on the host alone (mjpl_sweep_levers: no GPU needed) ->
     float64 [P, nplan] over the candidate pairs of Engine.contact_pairs(): one unit of planning column c changes the
     distance of pair p by at most W[p, c].  lo / hi: bounds per planning column (a planning slide joint without finite
     bounds gives inf for the hinges above it)."""
     lib = load_library()
-    d, keep = _model_desc(model)
-    pairs = _i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
-    q = None if qidx is None else _i32(qidx)
-    nplan = model.nq if q is None else len(q)
-    base = None if qpos_base is None else _f64(qpos_base)
+    args, keep = _compile_args(model, allowed_collision_bodies, qidx, qpos_base)
+    nplan = args[4] = model.nq if qidx is None else args[4]
     lo, plo = _opt_f64(lo, nplan, "lo")
     hi, phi = _opt_f64(hi, nplan, "hi")
-    args = [C.byref(d), pairs.ctypes.data_as(_I32P), len(pairs), None if q is None else q.ctypes.data_as(_I32P), nplan,
-            None if base is None else base.ctypes.data_as(_F64P), plo, phi]
-    P = lib.mjpl_sweep_levers(*args, None, 0)
-    if P < 0:
-        raise MjplError(P, lib.mjpl_last_error().decode())
-    W = np.zeros((P, nplan), np.float64)
-    rc = lib.mjpl_sweep_levers(*args, W.ctypes.data_as(_F64P), W.size)
-    if rc < 0:
-        raise MjplError(rc, lib.mjpl_last_error().decode())
-    del keep
-    return W
+    return _sized_call(lib, lib.mjpl_sweep_levers, lambda W: [*args, plo, phi, _ptr(W, _F64P), 0 if W is None else W.size],
+                       lambda P: np.zeros((P, nplan), np.float64))
 
 
 class DeviceBuffer:

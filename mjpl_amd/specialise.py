@@ -24,36 +24,28 @@ touches the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import math
 import os
 import subprocess
 import threading
+from typing import NamedTuple
 
 import numpy as np
 
 from . import build as _build
 from . import engine as _engine
+from .engine import _ptr
+from .fold import Fold, dlit
+# (the layout constants stay names of this module: tools and tests walk the layout through them)
+from .program import (B_BODYID, B_DOFF, B_NGEOM, B_NJNT, B_PARENT, B_SAVE, B_SIZE, EK_PLANE, EK_SLOT, EK_STATIC, FC_MAXANGLE,  # noqa: F401
+                      FC_MAXCOORD, G_DOFF, G_FLAGS, G_GEOMID, G_PMASK_HI, G_PMASK_LO, G_SIZE, G_SMASK, G_STORE, G_TYPE, G_WMASK_HI,
+                      G_WMASK_LO, GD_SIZE, GD_WBOUND, GF_SAMEPOS, GF_SAMEROT, GT_BOX, GT_CAPSULE, GT_PLANE, GT_SPHERE, H_NBODYOPS,
+                      H_NPLAN, H_NSAVE, H_NSLOTS, H_NWORLD, H_NWPAD, H_OFF_BODYOPS, H_OFF_FCONST, H_OFF_PERM, H_OFF_WCULL,
+                      H_OFF_WNARROW, H_SIZE, J_DOFF, J_FLAGS, J_QSRC, J_SIZE, J_TYPE, JF_POS_NONZERO, JT_HINGE, JT_SLIDE, MAX_SLOTS,
+                      P_FIRST, PARENT_CUR, PARENT_STATIC, SLOT_NONE, WN_LEN, WN_ZAXIS, Geom, decode)
 
 SPEC_DIR = os.path.join(_build.CSRC, "spec")
-
-# program layout (mjpl_device.h)
-H_NBODYOPS, H_NPLAN, H_NSAVE, H_NSLOTS, H_OFF_BODYOPS, H_OFF_PERM, H_OFF_WCULL, H_OFF_WNARROW, H_NWORLD, H_NWPAD, \
-    H_OFF_FCONST, H_SIZE = range(12)
-B_PARENT, B_DOFF, B_BODYID, B_NJNT, B_SAVE, B_NGEOM, B_SIZE = range(7)
-J_TYPE, J_QSRC, J_FLAGS, J_DOFF, J_SIZE = range(5)
-G_TYPE, G_FLAGS, G_DOFF, G_STORE, G_GEOMID, G_SMASK, G_WMASK_LO, G_WMASK_HI, G_PMASK_LO, G_PMASK_HI, G_SIZE = range(11)
-MAX_SLOTS = 32
-GD_SIZE, GD_WBOUND = 7, 12
-GF_SAMEPOS, GF_SAMEROT = 1, 2
-JF_POS_NONZERO = 1
-PARENT_CUR, PARENT_STATIC = 0, -1
-JT_SLIDE, JT_HINGE = 2, 3
-GT_PLANE, GT_SPHERE, GT_CAPSULE, GT_BOX = 0, 2, 3, 6
-EK_PLANE, EK_STATIC, EK_SLOT = 0, 1, 2
-WN_ZAXIS, WN_LEN = 0, 12
-P_FIRST = 1 << 17
-SLOT_NONE = 63
-FC_MAXCOORD, FC_MAXANGLE = 0, 1
 
 
 class ProgramInfo(C.Structure):
@@ -66,42 +58,21 @@ class ProgramInfo(C.Structure):
 def _dump(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, prune_pairs):
     """mjpl_program_dump (prune_pairs None) or mjpl_program_dump_pruned -> (ip, fp, dp, ProgramInfo, dropped int32 [n, 2])."""
     lib = _engine.load_library()
-    f = lib.mjpl_program_dump if prune_pairs is None else lib.mjpl_program_dump_pruned
-    f.restype = C.c_int
-    d = _engine._ModelDesc()
-    d.nq, d.njnt, d.nbody, d.ngeom = model.nq, model.njnt, model.nbody, model.ngeom
-    keep = []
-    for name, typ in _engine._ModelDesc._fields_[4:]:
-        arr = getattr(model, name)
-        arr = _engine._i32(arr) if typ is _engine._I32P else _engine._f64(arr)
-        keep.append(arr)
-        setattr(d, name, arr.ctypes.data_as(typ))
-    pairs = _engine._i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
-    q = None if qidx is None else _engine._i32(qidx)
-    base = None if qpos_base is None else _engine._f64(qpos_base)
+    head, keep = _engine._compile_args(model, allowed_collision_bodies, qidx, qpos_base)
     info = ProgramInfo()
     nip, ntab, ndrop = C.c_int32(0), C.c_int32(0), C.c_int32(0)
 
-    def call(ip, fp, dp, dropped=None):
-        args = [C.byref(d), pairs.ctypes.data_as(_engine._I32P), len(pairs),
-                None if q is None else q.ctypes.data_as(_engine._I32P), 0 if q is None else len(q),
-                None if base is None else base.ctypes.data_as(_engine._F64P), C.c_double(filter_tol)]
-        if prune_pairs is not None:
-            args.append(C.c_int32(int(prune_pairs)))
-        args += [None if ip is None else ip.ctypes.data_as(_engine._I32P), C.byref(nip),
-                 None if fp is None else fp.ctypes.data_as(C.POINTER(C.c_float)),
-                 None if dp is None else dp.ctypes.data_as(_engine._F64P), C.byref(ntab), C.byref(info)]
-        if prune_pairs is not None:
-            ndrop.value = 0 if dropped is None else len(dropped)
-            args += [None if dropped is None else dropped.ctypes.data_as(_engine._I32P), C.byref(ndrop)]
-        rc = f(*args)
-        if rc != 0:
-            raise _engine.MjplError(rc, lib.mjpl_last_error().decode())
+    def args(bufs):
+        ip, fp, dp, dropped = bufs or (None, None, None, None)
+        ndrop.value = 0 if dropped is None else len(dropped)
+        tables = [_ptr(ip, _engine._I32P), C.byref(nip), _ptr(fp, C.POINTER(C.c_float)), _ptr(dp, _engine._F64P), C.byref(ntab), C.byref(info)]
+        if prune_pairs is None:
+            return [*head, C.c_double(filter_tol), *tables]
+        return [*head, C.c_double(filter_tol), C.c_int32(int(prune_pairs)), *tables, _ptr(dropped, _engine._I32P), C.byref(ndrop)]
 
-    call(None, None, None)
-    ip, fp, dp = np.zeros(nip.value, np.int32), np.zeros(ntab.value, np.float32), np.zeros(ntab.value, np.float64)
-    dropped = np.zeros((ndrop.value, 2), np.int32)
-    call(ip, fp, dp, dropped)
+    def alloc(_):
+        return np.zeros(nip.value, np.int32), np.zeros(ntab.value, np.float32), np.zeros(ntab.value, np.float64), np.zeros((ndrop.value, 2), np.int32)
+    ip, fp, dp, dropped = _engine._sized_call(lib, lib.mjpl_program_dump if prune_pairs is None else lib.mjpl_program_dump_pruned, args, alloc)
     return ip, fp, dp, info, dropped
 
 
@@ -126,26 +97,14 @@ def dump_never_touch(model, allowed_collision_bodies=(), qidx=None, qpos_base=No
     them out of a per-program library.  prune_contacts: 0 the empty set, 1 the default, >= 2 that many cell evaluations per
     pair at most (tests)."""
     lib = _engine.load_library()
-    f = lib.mjpl_program_dump_never_touch
-    f.restype = C.c_int
-    d, keep = _model_desc(model)
-    allowed = _engine._i32([(model.body(a).id, model.body(b).id) for a, b in allowed_collision_bodies]).reshape(-1, 2)
-    q = None if qidx is None else _engine._i32(qidx)
-    base = None if qpos_base is None else _engine._f64(qpos_base)
+    head, keep = _engine._compile_args(model, allowed_collision_bodies, qidx, qpos_base)
     n, evals, h, th = C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
 
-    def call(pairs):
+    def args(pairs):
         n.value = 0 if pairs is None else len(pairs)
-        rc = f(C.byref(d), allowed.ctypes.data_as(_engine._I32P), len(allowed), None if q is None else q.ctypes.data_as(_engine._I32P),
-               0 if q is None else len(q), None if base is None else base.ctypes.data_as(_engine._F64P), C.c_double(filter_tol),
-               C.c_int32(int(prune_pairs)), C.c_int32(int(prune_contacts)), None if pairs is None else pairs.ctypes.data_as(_engine._I32P),
-               C.byref(n), C.byref(evals), C.byref(h), C.byref(th))
-        if rc != 0:
-            raise _engine.MjplError(rc, lib.mjpl_last_error().decode())
-
-    call(None)
-    pairs = np.zeros((n.value, 2), np.int32)
-    call(pairs)
+        return [*head, C.c_double(filter_tol), C.c_int32(int(prune_pairs)), C.c_int32(int(prune_contacts)), _ptr(pairs, _engine._I32P),
+                C.byref(n), C.byref(evals), C.byref(h), C.byref(th)]
+    pairs = _engine._sized_call(lib, lib.mjpl_program_dump_never_touch, args, lambda _: np.zeros((n.value, 2), np.int32))
     return pairs, int(evals.value), int(h.value), int(th.value)
 
 
@@ -202,13 +161,6 @@ def quat_mul_np(a, b):
                      a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
 
 
-def quat_mat_np(q):
-    w, x, y, z = q
-    return np.array([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
-                     2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
-                     2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z])
-
-
 def expanded_threshold(X, bound, reach: float) -> float:
     """Threshold of the expanded bounding cull of a static partner at X (binary32 coordinates) whose
     difference-form bound is `bound` (already widened by the filter's tolerance): the test
@@ -233,14 +185,28 @@ def expanded_threshold(X, bound, reach: float) -> float:
     return float(f)
 
 
-class _Gen:
-    def __init__(self, ip, fp, dp, info):
-        self.ip, self.fp, self.dp, self.info = ip, fp, dp, info
-        self.lines: list[str] = []
-        self.ind = 3
+class Options(NamedTuple):
+    """The generation switches.  The environment is their outside interface: the public entry points (generate,
+    generate_full_exact, translation_unit, build) read it once, here, and pass the value down."""
+    cull: str = "expanded"     # MJPL_SPEC_CULL: the form of the static culls (see generate)
+    cert: bool = False         # MJPL_SPEC_CERT=1: the edge certificate, where the program admits one
+    f64: bool = False          # MJPL_SPEC_F64=1: libraries carry the generated float64 check (generate_full_exact)
+    f64_inline: bool = False   # MJPL_SPEC_F64_INLINE=1: ... inlined, for tools/f64_inline_probe.py
+    mbox_waves: int = 2        # MJPL_SPEC_MBOX_WAVES: waves per SIMD the kernels of a model with moving boxes are built for (A/B builds)
 
-    def w(self, s=""):
-        self.lines.append("  " * self.ind + s)
+    @classmethod
+    def from_env(cls) -> "Options":
+        e = os.environ.get
+        return cls(e("MJPL_SPEC_CULL", "expanded"), e("MJPL_SPEC_CERT", "0") == "1", e("MJPL_SPEC_F64") == "1",
+                   e("MJPL_SPEC_F64_INLINE") == "1", max(1, min(3, int(e("MJPL_SPEC_MBOX_WAVES", "2")))))
+
+
+class _Gen:
+    def __init__(self):
+        self.lines: list[str] = []
+
+    def w(self, s="", ind=3):
+        self.lines.append("  " * ind + s)
 
     # rot_vec_quat(res, const vec, quat expr): v + 2 * cross(q_xyz, q_w v + cross(q_xyz, v))
     def rot_vec_quat(self, dst, vec, qn):
@@ -257,23 +223,399 @@ SCENE_ROWS, SCENE_HEADER, SCENE_SLOT_LANE0 = 32, 32, 40  # (mjpl_filter.h: kScen
 SCENE_PLANE_ROWS, SCENE_STAGE = 2, 32 * 4 + 32              # (kScenePlaneRows, kSceneStageFloats)
 
 
-class _SharedAxesReused(ValueError):
-    """Boxes share an axes slot that the program's slot allocation reuses while they still refer to it."""
+def pack_desc(kind, index, ptype, pfirst, boxq, index2=0, lvl=0) -> int:
+    """The descriptor of one partner of a stage (kSpecDesc / kExactDesc): what the rolled push loop reads per hit."""
+    return (kind << 0) | (index << 2) | (ptype << 10) | (pfirst << 14) | (boxq << 15) | (index2 << 16) | (lvl << 22)
 
 
-def generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, report: dict | None = None, never_touch=()) -> str:
-    """Straight-line filter code of one program (see _generate).  Moving boxes of one body with one orientation share
-    the slot of their x and y axes; where the program's own slot allocation gets in the way of that, every box keeps
-    its own."""
-    try:
-        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=True, report=report, never_touch=never_touch)
-    except _SharedAxesReused:
-        return _generate(ip, fp, dp, info, cull_form, generic, share_axes=False, report=report, never_touch=never_touch)
+# ----------------------------------------------------------------------------- analyses of a decoded program (no text)
+def _along_chain(prog, init, root, step) -> list:
+    """One value per body op, handed down the tree the way the poses are: step(body, the parent's value) with the parent
+    the body before (PARENT_CUR; `init` in front of the first), a static one (root(body)) or a saved one."""
+    cur, saved, out = init, {}, []
+    for b in prog.bodies:
+        cur = step(b, root(b) if b.parent == PARENT_STATIC else (cur if b.parent == PARENT_CUR else saved[b.parent - 1]))
+        out.append(cur)
+        if b.save >= 0:
+            saved[b.save] = cur
+    return out
 
 
-def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, share_axes: bool = True, report: dict | None = None,
-              never_touch=()) -> str:
-    """HIP source of `struct Spec` for one compiled program.
+def _body_reach(prog, fp, dp) -> list:
+    """How far from the world origin can a moving geom's centre be while its lane is still alive?  Per body op: the body
+    origins by the triangle inequality along the chain (hinges keep lengths; an off-centre hinge adds
+    twice its offset), or -- below a slide joint, whose travel the program does not know -- by the
+    per-lane range check: a lane whose body origin leaves [-maxcoord, maxcoord]^3 is dead from there on."""
+    box_reach = math.sqrt(3.0) * float(fp[prog.off_fconst + FC_MAXCOORD])
+
+    def step(b, parent_reach):
+        reach = parent_reach + float(np.linalg.norm(dp[b.doff: b.doff + 3]))
+        for j in b.joints:
+            reach = math.inf if j.type == JT_SLIDE else reach + 2.0 * float(np.linalg.norm(dp[j.doff + 3: j.doff + 6]))
+        return min(reach, box_reach)
+    return _along_chain(prog, 0.0, lambda b: float(np.linalg.norm(dp[b.doff + 7: b.doff + 10])), step)
+
+
+def _body_levers(prog, dp) -> tuple:
+    """The edge certificate (mjpl_fused.h): how far can any point of a moving geom travel while the
+    planning joints go from one end of an edge to the other?  At most  sum_j |dq_j| rho_j  over the planning hinges j
+    above it, rho_j = the longest the chain can stretch from joint j's anchor to the geom's centre + the geom's
+    bounding radius (hinges keep lengths: a triangle inequality along the chain, as `_body_reach`).
+    -> (per body op `anc`: [(planning column, that length up to the body's origin)] root first, False where a planning
+    SLIDE joint rules the certificate out)."""
+    ok = True
+
+    def step(b, anc_parent):
+        nonlocal ok
+        blen = float(np.linalg.norm(dp[b.doff: b.doff + 3]))
+        anc = [(qs, d + blen) for qs, d in anc_parent]
+        for j in b.joints:
+            jp = float(np.linalg.norm(dp[j.doff + 3: j.doff + 6]))
+            if j.type == JT_SLIDE:
+                if j.qsrc >= 0:
+                    ok = False
+                else:  # a slide joint held at its constant: a fixed offset along its axis
+                    off = abs(float(dp[j.doff + 7]) - float(dp[j.doff + 6]))
+                    anc = [(qs, d + off) for qs, d in anc]
+            else:
+                anc = [(qs, d + 2.0 * jp) for qs, d in anc]
+                if j.qsrc >= 0:
+                    anc.append((j.qsrc, jp))
+        return anc
+    return _along_chain(prog, [], lambda b: [], step), ok
+
+
+def _slot_levels(prog, anc, maxs) -> tuple:
+    """Per stage {slot: certificate level of the geom stored there}: the planning joints above a stored geom must be a
+    prefix of those above the geom tested against it, and at most 7 -- the level is their number (0: relative to the
+    world).  -> (levels, False where some moving pair does not nest so: level 0 there, and no certificate)."""
+    slot_anc, out, ok = {}, [], True   # slot -> planning columns above the geom stored there
+    for g in prog.geoms:
+        mine, lv = [qs for qs, _ in anc[g.body]], {}
+        for n, _ in g.slots(maxs):
+            theirs = slot_anc.get(n)
+            nested = theirs is not None and mine[:len(theirs)] == theirs and len(theirs) <= 7
+            ok, lv[n] = ok and nested, len(theirs) if nested else 0
+        out.append(lv)
+        if g.store >= 0:
+            slot_anc[g.slot] = mine
+    return out, ok
+
+
+def _axes_slots(prog, dp, mbox: bool, share: bool, statics: list):
+    """Moving boxes: boxes of one body with one orientation (the Panda's five pads per finger) have ONE frame --
+    the x and y axes are kept once, in the second slot of the first of them.  Per stage (`axes_of` at its culls: each
+    stored box's own second slot -> the slot that holds the values, the slot this geom stores its axes in or 63).
+    None: the program's own slot allocation reuses a shared slot while boxes still refer to it (never without sharing).
+    statics: the static partners per stage (_world_partners).  The generator has always named a frame's owner by the last
+    static partner its body's geoms so far tested in a pair of two, where there is one, and by the body otherwise: two boxes
+    of a body share only where that partner (lane, centre, bound) is the same, which is less often than they could.
+    Kept, because generated text follows from it."""
+    axes_of: dict[int, int] = {}
+    axes_key: dict[int, tuple] = {}   # whose axes a slot holds right now
+    out = []
+
+    def referred(slot):
+        return any(v == slot and k != v for k, v in axes_of.items())
+    owner = None
+    for g in prog.geoms:
+        if g.stage == prog.bodies[g.body].geoms[0].stage:  # (the first geom of its body)
+            owner = g.body
+        if len(statics[g.stage]) >= 2:
+            owner = statics[g.stage][len(statics[g.stage]) // 2 * 2 - 1]
+        at_culls = dict(axes_of)
+        store2 = ((g.store >> 6) & 63) if (g.store >= 0 and mbox) else 63
+        if g.store >= 0 and g.slot in axes_key:  # (a slot that held shared axes is written again: nobody may still read them)
+            if referred(g.slot):
+                return None
+            del axes_key[g.slot]
+        if store2 != 63:
+            key = (owner, bool(g.flags & GF_SAMEROT), tuple(np.float32(dp[g.doff + 3: g.doff + 7]).tolist()))
+            held = [sl for sl, k_ in axes_key.items() if k_ == key] if share else []
+            if held:           # the frame is in the slot file already
+                axes_of[store2] = held[0]
+                store2 = 63
+            else:
+                if referred(store2):
+                    return None
+                axes_of[store2] = store2
+                axes_key[store2] = key
+        out.append((at_culls, store2))
+    return out
+
+
+class _Stage(NamedTuple):
+    """One moving geom with the partners its bounding sphere is tested against; k: the lane its hit mask is parked in."""
+    geom: Geom
+    curbox: bool    # a moving box: the whole frame is kept
+    planes: list    # [(k, world row, bound)]
+    statics: list   # [(k, X, Y, Z, bound)]
+    slots: list     # [(k, slot, bound, certificate level)]
+    desc: list      # the packed descriptors, lane by lane
+    reach: float    # how far from the origin the centre can be (_body_reach + the geom's offset)
+    store2: int     # slot its x and y axes are stored in, or 63
+
+
+def _world_partners(prog, g, fp, info, generic, skip) -> tuple:
+    """The static partners of moving geom g -> (planes, statics, their descriptors: see _Stage), without the never-touch
+    pairs `skip`; none in a scene-generic library, where they are rows of the scene table."""
+    curbox = bool(info.mbox) and g.type == GT_BOX
+    wbound = fp[g.doff + GD_WBOUND:]
+    planes, statics, desc = [], [], []
+    for wrow in ([] if generic else g.world_rows(planes=True)):
+        pgid = prog.row_info(fp, wrow)[1]
+        if (min(g.geom_id, pgid), max(g.geom_id, pgid)) in skip:
+            continue
+        planes.append((len(desc), wrow, wbound[wrow]))
+        desc.append(pack_desc(EK_PLANE, wrow, GT_PLANE, 1, 1 if curbox else 0, 63))
+    for wrow in ([] if generic else g.world_rows(planes=False)):
+        ptype, pgid = prog.row_info(fp, wrow)
+        if (min(g.geom_id, pgid), max(g.geom_id, pgid)) in skip:
+            continue
+        pfirst = 1 if (ptype < g.type or (ptype == g.type and pgid < g.geom_id)) else 0
+        statics.append((len(desc), *(float(fp[prog.wc_at(wrow, f)]) for f in range(3)), wbound[wrow]))
+        desc.append(pack_desc(EK_STATIC, wrow, ptype, pfirst, 1 if (ptype == GT_BOX or curbox) else 0, 63))
+    return planes, statics, desc
+
+
+def _partners(prog, g, fp, dp, info, generic, world, levels, axes, body_reach) -> _Stage:
+    """The partner list of moving geom g: its static partners `world`, then the earlier moving geoms in the slot file
+    (from lane 40 on in a scene-generic library)."""
+    mbox = bool(info.mbox)  # moving boxes: full frames in the box queue, two register slots per stored box
+    curbox = mbox and g.type == GT_BOX
+    sbound = fp[g.doff + GD_WBOUND + 2 * prog.nwpad:]
+    (planes, statics, desc), slots = world, []
+    axes_of, store2 = axes
+    for n, pw in g.slots(int(info.maxs)):
+        if generic:  # (lanes 0 .. 31 belong to the scene rows)
+            desc += [0] * (SCENE_SLOT_LANE0 - len(desc))
+        sptype = (pw >> 12) & 15
+        # (a stored box keeps its x and y axes in a second slot, pw & 63; with a box on either side the pair
+        # takes the box queue, whose records carry full frames)
+        n2 = (pw & 63) if mbox else 63
+        if n2 != 63:
+            n2 = axes_of[n2]
+        slots.append((len(desc), n, sbound[n], levels[n]))
+        desc.append(pack_desc(EK_SLOT, n, sptype, 1 if (pw & P_FIRST) else 0, 1 if (mbox and (curbox or sptype == GT_BOX)) else 0, n2, levels[n]))
+    if len(desc) > 64:
+        raise ValueError("a geom with more than 64 enabled partners cannot be specialised")
+    reach = body_reach + float(np.linalg.norm(np.asarray(dp[g.doff: g.doff + 3], dtype=np.float64)))
+    return _Stage(g, curbox, planes, statics, slots, desc, reach, store2)
+
+
+def _certificate(st: _Stage, dp, anc) -> tuple:
+    """The certificate block of a stage: suffix sums of |dq_j| rho_j from the deepest planning joint up; level c =
+    the motion relative to a geom that hangs on the first c of them (0: to the world).
+    -> (False where the geom has no bounding radius or more than 7 planning joints above it, the block's lines,
+    (geom id, [(planning column, rho)], bounding radius): an entry of report["cert_levers"])."""
+    g = st.geom
+    sizes = [float(x) for x in dp[g.doff + GD_SIZE: g.doff + GD_SIZE + 3]]
+    rbound = {GT_SPHERE: sizes[0], GT_CAPSULE: sizes[0] + sizes[1], GT_BOX: math.sqrt(sum(x * x for x in sizes))}.get(g.type, math.inf)
+    lp = float(np.linalg.norm(np.asarray(dp[g.doff: g.doff + 3], dtype=np.float64)))
+    levers = [(qs, d + lp + (rbound if math.isfinite(rbound) else 0.0)) for qs, d in anc]
+    k2w = max([2.0 * math.sqrt(max(float(bound), 0.0)) for _, _, _, _, bound in st.statics] + [0.0])
+    slot_k2 = max([2.0 * math.sqrt(max(float(bound), 0.0)) for _, _, bound, _ in st.slots] + [0.0])
+    slot_levels = {lvl for _, _, _, lvl in st.slots}
+    cb = ["float s_ = 0.0f;"]
+    for lv in range(len(anc), -1, -1):
+        if lv < len(anc):
+            cb.append(f"s_ = __builtin_fmaf((float)adq[{levers[lv][0]} * 64], {lit(levers[lv][1] * (1.0 + 1e-6))}, s_);")
+        if lv in slot_levels | {0}:
+            cb.append(f"dm{lv} = __builtin_fmaf(s_, 1.001f, 2.0f * tol);")
+    cb.append(f"wc0 = __builtin_fmaf({lit(k2w * (1.0 + 1e-6))}, dm0, dm0 * dm0); deadp = dead - dm0;")
+    for lv in sorted(slot_levels):
+        cb.append(f"ws{lv} = __builtin_fmaf({lit(slot_k2 * (1.0 + 1e-6))}, dm{lv}, dm{lv} * dm{lv});")
+    return math.isfinite(rbound) and len(anc) <= 7, cb, (g.geom_id, levers, rbound)
+
+
+# ----------------------------------------------------------------------------- emitters (text from analysed data)
+def _emit_body_fk(g: _Gen, body, dp):
+    """Forward kinematics of one body op: the parent's pose, the joints, normalisation, range check, save."""
+    w = g.w
+    bd = dp[body.doff:]
+    if body.parent == PARENT_STATIC:
+        pp, pq, pR = bd[7:10].copy(), bd[10:14].copy(), bd[14:23].copy()
+        npc = pp + pR.reshape(3, 3) @ bd[0:3]
+        nqc = quat_mul_np(pq, bd[3:7])
+        w(f"float np0 = {lit(npc[0])}, np1 = {lit(npc[1])}, np2 = {lit(npc[2])};")
+        w(f"float nq0 = {lit(nqc[0])}, nq1 = {lit(nqc[1])}, nq2 = {lit(nqc[2])}, nq3 = {lit(nqc[3])};")
+    else:
+        if body.parent != PARENT_CUR:  # restore a saved pose
+            w(f"{{ const float *sv = save + (size_t){body.parent - 1} * 7 * sstride;")
+            w("  p0 = sv[0]; p1 = sv[sstride]; p2 = sv[2 * sstride];")
+            w("  q0 = sv[3 * sstride]; q1 = sv[4 * sstride]; q2 = sv[5 * sstride]; q3 = sv[6 * sstride];")
+            w("  MJPL_SPEC_QUAT2MAT(); }")
+        bp, bq = bd[0:3], bd[3:7]
+        for r in range(3):
+            w(f"float np{r} = p{r} + {lin([(bp[0], f'R{3 * r}'), (bp[1], f'R{3 * r + 1}'), (bp[2], f'R{3 * r + 2}')])};")
+        e = quat_mul_const_right(["q0", "q1", "q2", "q3"], bq)
+        w(f"float nq0 = {e[0]}, nq1 = {e[1]}, nq2 = {e[2]}, nq3 = {e[3]};")
+    for jtype, qsrc, jflags, jdoff in body.joints:
+        jd = dp[jdoff:]
+        axis, jpos, qpos0, qconst = jd[0:3], jd[3:6], float(jd[6]), float(jd[7])
+        if qsrc >= 0:
+            w(f"{{ const float dq = (float)q[{qsrc} * qstride] - {lit(qpos0)};")
+        else:
+            w(f"{{ const float dq = {lit(np.float32(qconst) - np.float32(qpos0))};")
+        nqn = ["nq0", "nq1", "nq2", "nq3"]
+        if jtype == JT_SLIDE:
+            w("  float xa0, xa1, xa2;")
+            g.rot_vec_quat("xa", axis, nqn)
+            w("  np0 += xa0 * dq; np1 += xa1 * dq; np2 += xa2 * dq; }")
+        else:
+            if jflags & JF_POS_NONZERO:
+                w("  float an0, an1, an2;")
+                g.rot_vec_quat("an", jpos, nqn)
+                w("  an0 += np0; an1 += np1; an2 += np2;")
+            w("  far = far || !(fabsf(dq) <= maxangle);  // binary32(q) is off by eps |q|")
+            w("  float sn, cs; sincosf(dq * 0.5f, &sn, &cs);")
+            # nq = nq (x) (cs, ax sn, ay sn, az sn)
+            a = [float(np.float32(x)) for x in axis]
+            sx = [f"{lit(a[k])} * sn" if a[k] not in (0.0, 1.0, -1.0) else ("sn" if a[k] == 1.0 else ("(-sn)" if a[k] == -1.0 else None))
+                  for k in range(3)]
+
+            def term(sign, left, right):
+                return None if right is None else (sign, f"{left} * {right}")
+
+            comps = [
+                [("+", "nq0 * cs"), term("-", "nq1", sx[0]), term("-", "nq2", sx[1]), term("-", "nq3", sx[2])],
+                [term("+", "nq0", sx[0]), ("+", "nq1 * cs"), term("+", "nq2", sx[2]), term("-", "nq3", sx[1])],
+                [term("+", "nq0", sx[1]), term("-", "nq1", sx[2]), ("+", "nq2 * cs"), term("+", "nq3", sx[0])],
+                [term("+", "nq0", sx[2]), term("+", "nq1", sx[1]), term("-", "nq2", sx[0]), ("+", "nq3 * cs")],
+            ]
+            exprs = []
+            for comp in comps:
+                ts = [t for t in comp if t is not None]
+                out = ("-" if ts[0][0] == "-" else "") + ts[0][1]
+                for sgn, ex in ts[1:]:
+                    out += f" {sgn} {ex}"
+                exprs.append(out)
+            w(f"  const float t0 = {exprs[0]}, t1 = {exprs[1]}, t2 = {exprs[2]}, t3 = {exprs[3]};")
+            w("  nq0 = t0; nq1 = t1; nq2 = t2; nq3 = t3;")
+            if jflags & JF_POS_NONZERO:
+                w("  float vv0, vv1, vv2;")
+                g.rot_vec_quat("vv", jpos, nqn)
+                w("  np0 = an0 - vv0; np1 = an1 - vv1; np2 = an2 - vv2;")
+            w("}")
+    # ---- normalise, rotation matrix, range check, save
+    w("{ const float inv = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(nq0 * nq0 + nq1 * nq1 + nq2 * nq2 + nq3 * nq3));")
+    w("  q0 = nq0 * inv; q1 = nq1 * inv; q2 = nq2 * inv; q3 = nq3 * inv; }")
+    w("p0 = np0; p1 = np1; p2 = np2;")
+    w("MJPL_SPEC_QUAT2MAT();")
+    w("far = far || !(fmaxf(fabsf(p0), fmaxf(fabsf(p1), fabsf(p2))) <= maxcoord);")
+    w("if (far) dead = kInf;")
+    if body.save >= 0:
+        w(f"{{ float *sv = save + (size_t){body.save} * 7 * sstride;")
+        w("  sv[0] = p0; sv[sstride] = p1; sv[2 * sstride] = p2;")
+        w("  sv[3 * sstride] = q0; sv[4 * sstride] = q1; sv[5 * sstride] = q2; sv[6 * sstride] = q3; }")
+
+
+def _emit_geom_pose(g: _Gen, st: _Stage, dp):
+    """Centre and z axis of a moving geom (a moving box: its whole frame) from its body's pose."""
+    w = g.w
+    lpos, lquat = dp[st.geom.doff: st.geom.doff + 3], dp[st.geom.doff + 3: st.geom.doff + 7]
+    if st.geom.flags & GF_SAMEPOS:
+        w("cx = p0; cy = p1; cz = p2;")
+    else:
+        for r, nm in enumerate(("cx", "cy", "cz")):
+            w(f"{nm} = p{r} + {lin([(lpos[0], f'R{3 * r}'), (lpos[1], f'R{3 * r + 1}'), (lpos[2], f'R{3 * r + 2}')])};")
+    if st.geom.flags & GF_SAMEROT:
+        w("zx = R2; zy = R5; zz = R8;")
+        if st.curbox:
+            w("xx = R0; xy = R3; xz = R6; yx = R1; yy = R4; yz = R7;")
+    else:
+        e = quat_mul_const_right(["q0", "q1", "q2", "q3"], lquat)
+        w(f"{{ const float g0 = {e[0]}, g1 = {e[1]}, g2 = {e[2]}, g3 = {e[3]};")
+        if st.curbox:  # the whole frame, by the interpreter's own routine (same binary32 values)
+            w("  const float gq_[4] = {g0, g1, g2, g3}; float mm_[9]; mjpl::quat2mat(mm_, gq_);")
+            w("  zx = mm_[2]; zy = mm_[5]; zz = mm_[8]; xx = mm_[0]; xy = mm_[3]; xz = mm_[6]; yx = mm_[1]; yy = mm_[4]; yz = mm_[7]; }")
+        else:
+            w("  zx = 2.0f * (g1 * g3 + g0 * g2); zy = 2.0f * (g2 * g3 - g0 * g1); zz = g0 * g0 - g1 * g1 - g2 * g2 + g3 * g3; }")
+
+
+def _emit_culls(g: _Gen, st: _Stage, prog, fp, cull_form: str, generic: bool, cert_lines):
+    """The stage's certificate block (cert_lines; None: a library without the certificate, which carries none of its
+    text) and one bounding cull per partner."""
+    w = g.w
+    cert = cert_lines is not None
+    if cert:
+        w("deadp = dead;", 2)
+        w("if (cert) {", 2)
+        for cl in cert_lines:
+            w(cl)
+        w("}", 2)
+    for k, wrow, bound in st.planes:
+        ppos = [float(fp[prog.wc_at(wrow, f)]) for f in range(3)]
+        at = prog.off_wnarrow + wrow * WN_LEN + WN_ZAXIS
+        pz = [float(x) for x in fp[at: at + 3]]
+        dot = lin([(pz[0], "cx"), (pz[1], "cy"), (pz[2], "cz")], -(np.float32(pz[0]) * np.float32(ppos[0]) + np.float32(pz[1]) * np.float32(ppos[1]) + np.float32(pz[2]) * np.float32(ppos[2])))
+        w(f"MJPL_SPEC_HIT({k}, !({dot} + {'deadp' if cert else 'dead'} > {lit(bound)}));")
+    w("const float ux = cx + dead;")
+    if cull_form == "expanded" and not generic:
+        w(f"const float cc = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, ux * ux)){' - wc0' if cert else ''};  // (wc0: the certificate's widening, 0 without)")
+    statics = st.statics
+    if cull_form == "expanded" and statics:
+        for a, b in zip(statics[0::2], statics[1::2]):
+            ta, tb = expanded_threshold(a[1:4], a[4], st.reach), expanded_threshold(b[1:4], b[4], st.reach)
+            w(f"MJPL_SPEC_CULLX2({a[0]}, {b[0]}, {lit(-2 * a[1])}, {lit(-2 * a[2])}, {lit(-2 * a[3])}, {lit(ta)}, "
+              f"{lit(-2 * b[1])}, {lit(-2 * b[2])}, {lit(-2 * b[3])}, {lit(tb)});")
+        if len(statics) % 2:
+            k, X, Y, Z, bound = statics[-1]
+            w(f"MJPL_SPEC_CULLX({k}, {lit(-2 * X)}, {lit(-2 * Y)}, {lit(-2 * Z)}, {lit(expanded_threshold((X, Y, Z), bound, st.reach))});")
+    else:
+        for a, b in zip(statics[0::2], statics[1::2]):
+            w(f"MJPL_SPEC_CULL2({a[0]}, {b[0]}, {lit(a[1])}, {lit(b[1])}, {lit(a[2])}, {lit(b[2])}, {lit(a[3])}, {lit(b[3])}, "
+              f"{lit(a[4])}, {lit(b[4])});")
+        if len(statics) % 2:
+            k, X, Y, Z, bound = statics[-1]
+            w(f"MJPL_SPEC_CULL({k}, {lit(X)}, {lit(Y)}, {lit(Z)}, {lit(bound)});")
+    for k, n, bound, lvl in st.slots:
+        w(f"MJPL_SPEC_SLOTCULL({k}, {n}, {lit(bound)}{f' + ws{lvl}' if cert else ''});")
+
+
+# the fixed macros of every generated check
+_MACROS = r"""#define MJPL_SPEC_QUAT2MAT() \
+  do { R0 = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; R4 = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3; \
+       R8 = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3; R1 = 2.0f * (q1 * q2 - q0 * q3); R2 = 2.0f * (q1 * q3 + q0 * q2); \
+       R3 = 2.0f * (q1 * q2 + q0 * q3); R5 = 2.0f * (q2 * q3 - q0 * q1); R6 = 2.0f * (q1 * q3 - q0 * q2); \
+       R7 = 2.0f * (q2 * q3 + q0 * q1); } while (0)
+typedef float spec_v2f __attribute__((ext_vector_type(2)));
+// (a scalar branch around the two v_writelane -- most culls pass for no lane of the wave -- measured
+//  3 % SLOWER than parking unconditionally: 213 more branches per configuration)
+#define MJPL_SPEC_HIT(k, pass) \
+  do { const unsigned long long m_ = __builtin_amdgcn_ballot_w64(pass); \
+       mjpl::park_mask<k>(mlo, mhi, m_); } while (0)
+// ux = cx, or +inf on a lane that is not to report anything (inactive / decided / out of range)
+#define MJPL_SPEC_CULL(k, X, Y, Z, BOUND) \
+  do { const float dx_ = ux - (X), dy_ = cy - (Y), dz_ = cz - (Z); \
+       MJPL_SPEC_HIT(k, !(mjpl::sqnorm3(dx_, dy_, dz_) > (BOUND))); } while (0)
+// two static partners at once: packed float32 arithmetic
+#define MJPL_SPEC_CULL2(ka, kb, XA, XB, YA, YB, ZA, ZB, BOUNDA, BOUNDB) \
+  do { const spec_v2f dx_ = (spec_v2f){ux, ux} - (spec_v2f){XA, XB}, dy_ = (spec_v2f){cy, cy} - (spec_v2f){YA, YB}, \
+                      dz_ = (spec_v2f){cz, cz} - (spec_v2f){ZA, ZB}; \
+       const spec_v2f s_ = __builtin_elementwise_fma(dx_, dx_, __builtin_elementwise_fma(dy_, dy_, dz_ * dz_)); \
+       const unsigned long long ma_ = __builtin_amdgcn_ballot_w64(!(s_.x > (BOUNDA))); \
+       const unsigned long long mb_ = __builtin_amdgcn_ballot_w64(!(s_.y > (BOUNDB))); \
+       mjpl::park_mask2<ka, kb>(mlo, mhi, ma_, mb_); } while (0)
+// expanded form: t = |c|^2 - 2 c.X against THR = bound - |X|^2 (+ the form's rounding allowance); cc = |c|^2 with
+// ux in it, so a lane that is not to report anything carries +inf or NaN here and fails the ordered compare
+#define MJPL_SPEC_CULLX(k, M2X, M2Y, M2Z, THR) \
+  do { const float t_ = __builtin_fmaf(cz, (M2Z), __builtin_fmaf(cy, (M2Y), __builtin_fmaf(ux, (M2X), cc))); \
+       MJPL_SPEC_HIT(k, t_ <= (THR)); } while (0)
+#define MJPL_SPEC_CULLX2(ka, kb, AX, AY, AZ, ATHR, BX, BY, BZ, BTHR) \
+  do { const float ta_ = __builtin_fmaf(cz, (AZ), __builtin_fmaf(cy, (AY), __builtin_fmaf(ux, (AX), cc))); \
+       const float tb_ = __builtin_fmaf(cz, (BZ), __builtin_fmaf(cy, (BY), __builtin_fmaf(ux, (BX), cc))); \
+       const unsigned long long ma_ = __builtin_amdgcn_ballot_w64(ta_ <= (ATHR)); \
+       const unsigned long long mb_ = __builtin_amdgcn_ballot_w64(tb_ <= (BTHR)); \
+       mjpl::park_mask2<ka, kb>(mlo, mhi, ma_, mb_); } while (0)
+#define MJPL_SPEC_SLOTCULL(k, n, BOUND) \
+  do { const float dx_ = ux - sf.f[0][n], dy_ = cy - sf.f[1][n], dz_ = cz - sf.f[2][n]; \
+       MJPL_SPEC_HIT(k, !(mjpl::sqnorm3(dx_, dy_, dz_) > (BOUND))); } while (0)"""
+
+
+def generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, report: dict | None = None, never_touch=(),
+             opts: Options | None = None) -> str:
+    """HIP source of `struct Spec` for one compiled program: straight-line filter code.
     generic: the ROBOT's code only -- forward kinematics, geom poses, the culls against earlier moving geoms --
     as literals; every static partner (floor, obstacles, the robot's own world-welded base) is a row of the
     scene table the engine keeps in front of the float32 tables (`tp[-S ...]`, scalar loads): [a0 a1 a2 thr
@@ -282,397 +624,114 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
     cull_form: "expanded" (default) tests a static partner as  |c|^2 - 2 c.X <= bound - |X|^2  -- three
     fused multiply-adds and a compare per partner on top of one |c|^2 per geom -- with the threshold
     raised by a bound of the form's own rounding (see `expanded_threshold`); "difference" is the
-    interpreter's |c - X|^2 <= bound (six operations and a compare, two partners per packed instruction)."""
-    # never_touch (dump_never_touch of THIS program -- its hash covers the set): static or plane partners a per-program library
-    # does not test at all; a scene-generic library tests whatever its scene table holds
-    skip = set() if generic else {(int(a), int(b)) for a, b in never_touch}
-    cull_form = cull_form or os.environ.get("MJPL_SPEC_CULL", "expanded")
+    interpreter's |c - X|^2 <= bound (six operations and a compare, two partners per packed instruction).
+    never_touch (dump_never_touch of THIS program -- its hash covers the set): static or plane partners a per-program
+    library does not test at all; a scene-generic library tests whatever its scene table holds.
+    Moving boxes of one body with one orientation share the slot of their x and y axes; where the program's own slot
+    allocation gets in the way of that, every box keeps its own."""
+    return _generate(ip, fp, dp, info, cull_form, generic, True, report, never_touch, opts or Options.from_env())
+
+
+def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = False, share_axes: bool = True, report: dict | None = None,
+              never_touch=(), opts: Options = Options()) -> str:
+    """generate with the switches as a value; share_axes=False: every moving box keeps its own axes slot from the start."""
     if info.immediate or not info.filter_usable:
         raise ValueError("this model runs the immediate interpreter / has no usable filter: nothing to specialise")
-    mbox = bool(info.mbox)  # moving boxes: full frames in the box queue, two register slots per stored box
-    g = _Gen(ip, fp, dp, info)
-    w = g.w
-    nbody = int(ip[H_NBODYOPS])
-    nwpad = int(ip[H_NWPAD])
-    off_wcull, off_wnarrow = int(ip[H_OFF_WCULL]), int(ip[H_OFF_WNARROW])
-    fconst = int(ip[H_OFF_FCONST])
-    maxs = int(info.maxs)
-
-    def wc_at(wrow, f):
-        return off_wcull + ((wrow >> 2) << 4) + (f << 2) + (wrow & 3)
-
-    nstage_total = 0
-    _pc = int(ip[H_OFF_BODYOPS])
-    for _b in range(nbody):
-        _nj, _ng = int(ip[_pc + B_NJNT]), int(ip[_pc + B_NGEOM])
-        _pc += B_SIZE + _nj * J_SIZE + _ng * (G_SIZE + MAX_SLOTS)
-        nstage_total += _ng
-    SC = -(SCENE_HEADER + nstage_total * SCENE_STAGE + 16)  # where the scene table starts, relative to tp
-    stages = []       # (case body lines, gtype, gdoff, store)
-    desc = []         # per stage: list of packed partner descriptors
-    pending_fk: list[str] = []   # FK of bodies since the last stage (bodies without geoms)
-    pc = int(ip[H_OFF_BODYOPS])
-    state_known = None  # (p, q) as numpy constants while the chain so far is constant (static parent, fixed joints)
-
-    # How far from the world origin can a moving geom's centre be while its lane is still alive?  The body
-    # origins by the triangle inequality along the chain (hinges keep lengths; an off-centre hinge adds
-    # twice its offset), or -- below a slide joint, whose travel the program does not know -- by the
-    # per-lane range check: a lane whose body origin leaves [-maxcoord, maxcoord]^3 is dead from there on.
-    maxcoord = float(fp[fconst + FC_MAXCOORD])
-    box_reach = math.sqrt(3.0) * maxcoord
-    body_reach_cur = 0.0      # of the body the walk is at (PARENT_CUR refers to it)
-    saved_reach: dict[int, float] = {}
-    # Moving boxes: boxes of one body with one orientation (the Panda's five pads per finger) have ONE frame --
-    # the x and y axes are kept once, in the second slot of the first of them; `axes_of` maps each box's own second
-    # slot to the slot that holds the values, `axes_key` says whose axes a slot holds right now.
-    axes_of: dict[int, int] = {}
-    axes_key: dict[int, tuple] = {}
-    # The edge certificate (mjpl_fused.h; DESIGN.md 5.4g): how far can any point of a moving geom travel while the
-    # planning joints go from one end of an edge to the other?  At most  sum_j |dq_j| rho_j  over the planning hinges j
-    # above it, rho_j = the longest the chain can stretch from joint j's anchor to the geom's centre + the geom's
-    # bounding radius (hinges keep lengths: a triangle inequality along the chain, as `geom_reach` above).  `anc` of a
-    # body: [(planning column, that length up to the body's origin)] root first.  A planning SLIDE joint, or a moving
-    # pair whose earlier geom does not hang on a prefix of the later one's joints, and the library is built without.
-    cert_ok = not generic
-    anc_cur: list = []
-    saved_anc: dict[int, list] = {}
-    slot_anc: dict[int, list] = {}   # slot -> planning columns above the geom stored there
-    cert_stage: list = []            # per stage: the lines of its certificate block
-    cert_levers: list = []           # per stage: (geom id, [(planning column, rho)], bounding radius) -- report["cert_levers"]
-
-    for b in range(nbody):
-        parent, bdoff, njnt, save_slot, ngeom = (int(ip[pc + k]) for k in (B_PARENT, B_DOFF, B_NJNT, B_SAVE, B_NGEOM))
-        pc += B_SIZE
-        bd = dp[bdoff:]
-        g.lines, body_lines = [], None
-        if parent == PARENT_STATIC:
-            parent_reach = float(np.linalg.norm(bd[7:10]))
-        elif parent == PARENT_CUR:
-            parent_reach = body_reach_cur
-        else:
-            parent_reach = saved_reach[parent - 1]
-        geom_reach = parent_reach + float(np.linalg.norm(bd[0:3]))
-        for j in range(njnt):
-            jtype_, jdoff_ = int(ip[pc + j * J_SIZE + J_TYPE]), int(ip[pc + j * J_SIZE + J_DOFF])
-            if jtype_ == JT_SLIDE:
-                geom_reach = math.inf
-            else:
-                geom_reach += 2.0 * float(np.linalg.norm(dp[jdoff_ + 3: jdoff_ + 6]))
-        geom_reach = min(geom_reach, box_reach)
-        body_reach_cur = geom_reach
-        # ... and the planning joints above this body with their lever arms
-        anc_parent = [] if parent == PARENT_STATIC else (anc_cur if parent == PARENT_CUR else saved_anc[parent - 1])
-        blen = float(np.linalg.norm(bd[0:3]))
-        anc_body = [(qs, d + blen) for qs, d in anc_parent]
-        for j in range(njnt):
-            jt_, qs_, jd_ = (int(ip[pc + j * J_SIZE + k]) for k in (J_TYPE, J_QSRC, J_DOFF))
-            jp_ = float(np.linalg.norm(dp[jd_ + 3: jd_ + 6]))
-            if jt_ == JT_SLIDE:
-                if qs_ >= 0:
-                    cert_ok = False
-                else:  # a slide joint held at its constant: a fixed offset along its axis
-                    off_ = abs(float(dp[jd_ + 7]) - float(dp[jd_ + 6]))
-                    anc_body = [(qs, d + off_) for qs, d in anc_body]
-            else:
-                anc_body = [(qs, d + 2.0 * jp_) for qs, d in anc_body]
-                if qs_ >= 0:
-                    anc_body.append((qs_, jp_))
-        anc_cur = anc_body
-        if save_slot >= 0:
-            saved_anc[save_slot] = anc_body
-        if save_slot >= 0:
-            saved_reach[save_slot] = geom_reach
-        # ---- parent pose
-        if parent == PARENT_STATIC:
-            pp, pq, pR = bd[7:10].copy(), bd[10:14].copy(), bd[14:23].copy()
-            npc = pp + pR.reshape(3, 3) @ bd[0:3]
-            nqc = quat_mul_np(pq, bd[3:7])
-            w(f"float np0 = {lit(npc[0])}, np1 = {lit(npc[1])}, np2 = {lit(npc[2])};")
-            w(f"float nq0 = {lit(nqc[0])}, nq1 = {lit(nqc[1])}, nq2 = {lit(nqc[2])}, nq3 = {lit(nqc[3])};")
-        else:
-            if parent != PARENT_CUR:  # restore a saved pose
-                k = parent - 1
-                w(f"{{ const float *sv = save + (size_t){k} * 7 * sstride;")
-                w("  p0 = sv[0]; p1 = sv[sstride]; p2 = sv[2 * sstride];")
-                w("  q0 = sv[3 * sstride]; q1 = sv[4 * sstride]; q2 = sv[5 * sstride]; q3 = sv[6 * sstride];")
-                w("  MJPL_SPEC_QUAT2MAT(); }")
-            bp, bq = bd[0:3], bd[3:7]
-            for r in range(3):
-                w(f"float np{r} = p{r} + {lin([(bp[0], f'R{3 * r}'), (bp[1], f'R{3 * r + 1}'), (bp[2], f'R{3 * r + 2}')])};")
-            e = quat_mul_const_right(["q0", "q1", "q2", "q3"], bq)
-            w(f"float nq0 = {e[0]}, nq1 = {e[1]}, nq2 = {e[2]}, nq3 = {e[3]};")
-        # ---- joints
-        for j in range(njnt):
-            jtype, qsrc, jflags, jdoff = (int(ip[pc + k]) for k in (J_TYPE, J_QSRC, J_FLAGS, J_DOFF))
-            pc += J_SIZE
-            jd = dp[jdoff:]
-            axis, jpos, qpos0, qconst = jd[0:3], jd[3:6], float(jd[6]), float(jd[7])
-            if qsrc >= 0:
-                w(f"{{ const float dq = (float)q[{qsrc} * qstride] - {lit(qpos0)};")
-            else:
-                w(f"{{ const float dq = {lit(np.float32(qconst) - np.float32(qpos0))};")
-            nqn = ["nq0", "nq1", "nq2", "nq3"]
-            if jtype == JT_SLIDE:
-                w("  float xa0, xa1, xa2;")
-                g.rot_vec_quat("xa", axis, nqn)
-                w("  np0 += xa0 * dq; np1 += xa1 * dq; np2 += xa2 * dq; }")
-            else:
-                if jflags & JF_POS_NONZERO:
-                    w("  float an0, an1, an2;")
-                    g.rot_vec_quat("an", jpos, nqn)
-                    w("  an0 += np0; an1 += np1; an2 += np2;")
-                w("  far = far || !(fabsf(dq) <= maxangle);  // binary32(q) is off by eps |q|")
-                w("  float sn, cs; sincosf(dq * 0.5f, &sn, &cs);")
-                # nq = nq (x) (cs, ax sn, ay sn, az sn)
-                a = [float(np.float32(x)) for x in axis]
-                sx = [f"{lit(a[k])} * sn" if a[k] not in (0.0, 1.0, -1.0) else ("sn" if a[k] == 1.0 else ("(-sn)" if a[k] == -1.0 else None))
-                      for k in range(3)]
-
-                def term(sign, left, right):
-                    return None if right is None else (sign, f"{left} * {right}")
-
-                comps = [
-                    [("+", "nq0 * cs"), term("-", "nq1", sx[0]), term("-", "nq2", sx[1]), term("-", "nq3", sx[2])],
-                    [term("+", "nq0", sx[0]), ("+", "nq1 * cs"), term("+", "nq2", sx[2]), term("-", "nq3", sx[1])],
-                    [term("+", "nq0", sx[1]), term("-", "nq1", sx[2]), ("+", "nq2 * cs"), term("+", "nq3", sx[0])],
-                    [term("+", "nq0", sx[2]), term("+", "nq1", sx[1]), term("-", "nq2", sx[0]), ("+", "nq3 * cs")],
-                ]
-                exprs = []
-                for comp in comps:
-                    ts = [t for t in comp if t is not None]
-                    out = ("-" if ts[0][0] == "-" else "") + ts[0][1]
-                    for sgn, ex in ts[1:]:
-                        out += f" {sgn} {ex}"
-                    exprs.append(out)
-                w(f"  const float t0 = {exprs[0]}, t1 = {exprs[1]}, t2 = {exprs[2]}, t3 = {exprs[3]};")
-                w("  nq0 = t0; nq1 = t1; nq2 = t2; nq3 = t3;")
-                if jflags & JF_POS_NONZERO:
-                    w("  float vv0, vv1, vv2;")
-                    g.rot_vec_quat("vv", jpos, nqn)
-                    w("  np0 = an0 - vv0; np1 = an1 - vv1; np2 = an2 - vv2;")
-                w("}")
-        # ---- normalise, rotation matrix, range check, save
-        w("{ const float inv = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(nq0 * nq0 + nq1 * nq1 + nq2 * nq2 + nq3 * nq3));")
-        w("  q0 = nq0 * inv; q1 = nq1 * inv; q2 = nq2 * inv; q3 = nq3 * inv; }")
-        w("p0 = np0; p1 = np1; p2 = np2;")
-        w("MJPL_SPEC_QUAT2MAT();")
-        w("far = far || !(fmaxf(fabsf(p0), fmaxf(fabsf(p1), fabsf(p2))) <= maxcoord);")
-        w("if (far) dead = kInf;")
-        if save_slot >= 0:
-            w(f"{{ float *sv = save + (size_t){save_slot} * 7 * sstride;")
-            w("  sv[0] = p0; sv[sstride] = p1; sv[2 * sstride] = p2;")
-            w("  sv[3 * sstride] = q0; sv[4 * sstride] = q1; sv[5 * sstride] = q2; sv[6 * sstride] = q3; }")
-        body_lines = g.lines
-        pending_fk.extend(["{"] + body_lines + ["}"])
-        # ---- geoms
-        for gi in range(ngeom):
-            gtype, gflags, gdoff, store, geom_id, smask = (int(ip[pc + k]) for k in (G_TYPE, G_FLAGS, G_DOFF, G_STORE, G_GEOMID, G_SMASK))
-            wmask = (int(ip[pc + G_WMASK_LO]) & 0xFFFFFFFF) | ((int(ip[pc + G_WMASK_HI]) & 0xFFFFFFFF) << 32)
-            pmask = (int(ip[pc + G_PMASK_LO]) & 0xFFFFFFFF) | ((int(ip[pc + G_PMASK_HI]) & 0xFFFFFFFF) << 32)
-            swords = [int(x) for x in ip[pc + G_SIZE: pc + G_SIZE + MAX_SLOTS]]
-            pc += G_SIZE + MAX_SLOTS
-            gd = dp[gdoff:]
-            fgd = fp[gdoff:]
-            g.lines = []
-            lpos, lquat = gd[0:3], gd[3:7]
-            if gflags & GF_SAMEPOS:
-                w("cx = p0; cy = p1; cz = p2;")
-            else:
-                for r, nm in enumerate(("cx", "cy", "cz")):
-                    w(f"{nm} = p{r} + {lin([(lpos[0], f'R{3 * r}'), (lpos[1], f'R{3 * r + 1}'), (lpos[2], f'R{3 * r + 2}')])};")
-            curbox = mbox and gtype == GT_BOX
-            if gflags & GF_SAMEROT:
-                w("zx = R2; zy = R5; zz = R8;")
-                if curbox:
-                    w("xx = R0; xy = R3; xz = R6; yx = R1; yy = R4; yz = R7;")
-            else:
-                e = quat_mul_const_right(["q0", "q1", "q2", "q3"], lquat)
-                w(f"{{ const float g0 = {e[0]}, g1 = {e[1]}, g2 = {e[2]}, g3 = {e[3]};")
-                if curbox:  # the whole frame, by the interpreter's own routine (same binary32 values)
-                    w("  const float gq_[4] = {g0, g1, g2, g3}; float mm_[9]; mjpl::quat2mat(mm_, gq_);")
-                    w("  zx = mm_[2]; zy = mm_[5]; zz = mm_[8]; xx = mm_[0]; xy = mm_[3]; xz = mm_[6]; yx = mm_[1]; yy = mm_[4]; yz = mm_[7]; }")
-                else:
-                    w("  zx = 2.0f * (g1 * g3 + g0 * g2); zy = 2.0f * (g2 * g3 - g0 * g1); zz = g0 * g0 - g1 * g1 - g2 * g2 + g3 * g3; }")
-            w("/*CERT*/")  # (the stage's certificate block goes here once its partners are known)
-            partners = []
-            slot_levels: set = set()
-            slot_k2 = 0.0
-            if generic:
-                pmask = wmask = 0  # (static partners: rows of the scene table, tested after the switch)
-            wbound = fgd[GD_WBOUND: GD_WBOUND + nwpad]
-            sbound = fgd[GD_WBOUND + 2 * nwpad: GD_WBOUND + 2 * nwpad + MAX_SLOTS]
-            # static planes
-            for wrow in range(64):
-                if not (pmask >> wrow) & 1:
-                    continue
-                pgid_ = int(np.frombuffer(np.float32(fp[wc_at(wrow, 3)]).tobytes(), dtype=np.int32)[0]) >> 8
-                if (min(geom_id, pgid_), max(geom_id, pgid_)) in skip:
-                    continue
-                ppos = [float(fp[wc_at(wrow, f)]) for f in range(3)]
-                pz = [float(x) for x in fp[off_wnarrow + wrow * WN_LEN + WN_ZAXIS: off_wnarrow + wrow * WN_LEN + WN_ZAXIS + 3]]
-                k = len(partners)
-                dot = lin([(pz[0], "cx"), (pz[1], "cy"), (pz[2], "cz")], -(np.float32(pz[0]) * np.float32(ppos[0]) + np.float32(pz[1]) * np.float32(ppos[1]) + np.float32(pz[2]) * np.float32(ppos[2])))
-                w(f"MJPL_SPEC_HIT({k}, !({dot} + deadp > {lit(wbound[wrow])}));")
-                partners.append((EK_PLANE, wrow, GT_PLANE, 1, 1 if curbox else 0, 63, 0))
-            # other static geoms
-            w("const float ux = cx + dead;")
-            if cull_form == "expanded" and not generic:
-                w("const float cc = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, ux * ux)) - wc0;  // (wc0: the certificate's widening, 0 without)")
-            statics = []
-            for wrow in range(64):
-                if not (wmask >> wrow) & 1:
-                    continue
-                info_word = int(np.frombuffer(np.float32(fp[wc_at(wrow, 3)]).tobytes(), dtype=np.int32)[0])
-                ptype, pgid = info_word & 255, info_word >> 8
-                if (min(geom_id, pgid), max(geom_id, pgid)) in skip:
-                    continue
-                pfirst = 1 if (ptype < gtype or (ptype == gtype and pgid < geom_id)) else 0
-                X, Y, Z = (float(fp[wc_at(wrow, f)]) for f in range(3))
-                statics.append((len(partners), X, Y, Z, wbound[wrow]))
-                partners.append((EK_STATIC, wrow, ptype, pfirst, 1 if (ptype == GT_BOX or curbox) else 0, 63, 0))
-            if cull_form == "expanded" and statics:
-                reach = geom_reach + float(np.linalg.norm(np.asarray(lpos, dtype=np.float64)))
-                for a, b in zip(statics[0::2], statics[1::2]):
-                    ta, tb = expanded_threshold(a[1:4], a[4], reach), expanded_threshold(b[1:4], b[4], reach)
-                    w(f"MJPL_SPEC_CULLX2({a[0]}, {b[0]}, {lit(-2 * a[1])}, {lit(-2 * a[2])}, {lit(-2 * a[3])}, {lit(ta)}, "
-                      f"{lit(-2 * b[1])}, {lit(-2 * b[2])}, {lit(-2 * b[3])}, {lit(tb)});")
-                if len(statics) % 2:
-                    k, X, Y, Z, bound = statics[-1]
-                    w(f"MJPL_SPEC_CULLX({k}, {lit(-2 * X)}, {lit(-2 * Y)}, {lit(-2 * Z)}, {lit(expanded_threshold((X, Y, Z), bound, reach))});")
-            else:
-                for a, b in zip(statics[0::2], statics[1::2]):
-                    w(f"MJPL_SPEC_CULL2({a[0]}, {b[0]}, {lit(a[1])}, {lit(b[1])}, {lit(a[2])}, {lit(b[2])}, {lit(a[3])}, {lit(b[3])}, "
-                      f"{lit(a[4])}, {lit(b[4])});")
-                if len(statics) % 2:
-                    k, X, Y, Z, bound = statics[-1]
-                    w(f"MJPL_SPEC_CULL({k}, {lit(X)}, {lit(Y)}, {lit(Z)}, {lit(bound)});")
-            # earlier moving geoms in the slot file
-            for n in range(maxs):
-                if not (smask >> n) & 1:
-                    continue
-                pw = swords[n]
-                if generic:  # (lanes 0 .. 31 belong to the scene rows)
-                    while len(partners) < SCENE_SLOT_LANE0:
-                        partners.append((0, 0, 0, 0, 0, 0, 0))
-                k = len(partners)
-                # the planning joints above the stored geom must be a prefix of those above this one (else: no certificate)
-                mine_, theirs_ = [qs for qs, _ in anc_cur], slot_anc.get(n, None)
-                if theirs_ is None or mine_[:len(theirs_)] != theirs_ or len(theirs_) > 7:
-                    cert_ok = False
-                    lvl = 0
-                else:
-                    lvl = len(theirs_)
-                slot_levels.add(lvl)
-                slot_k2 = max(slot_k2, 2.0 * math.sqrt(max(float(sbound[n]), 0.0)))
-                w(f"MJPL_SPEC_SLOTCULL({k}, {n}, {lit(sbound[n])} + ws{lvl});")
-                sptype = (pw >> 12) & 15
-                # (a stored box keeps its x and y axes in a second slot, pw & 63; with a box on either side the pair
-                # takes the box queue, whose records carry full frames)
-                n2 = (pw & 63) if mbox else 63
-                if n2 != 63:
-                    n2 = axes_of[n2]
-                partners.append((EK_SLOT, n, sptype, 1 if (pw & P_FIRST) else 0, 1 if (mbox and (curbox or sptype == GT_BOX)) else 0, n2, lvl))
-            if len(partners) > 64:
-                raise ValueError("a geom with more than 64 enabled partners cannot be specialised")
-            store2 = ((store >> 6) & 63) if (store >= 0 and mbox) else 63
-            if store >= 0 and (store & 63) in axes_key:  # (a slot that held shared axes is written again: nobody may still read them)
-                if any(v == (store & 63) and k != v for k, v in axes_of.items()):
-                    raise _SharedAxesReused("a shared axes slot is reused while boxes still refer to it")
-                del axes_key[store & 63]
-            if store2 != 63:
-                key = (b, bool(gflags & GF_SAMEROT), tuple(np.float32(lquat).tolist()))
-                held = [sl for sl, k_ in axes_key.items() if k_ == key] if share_axes else []
-                if held:           # the frame is in the slot file already
-                    axes_of[store2] = held[0]
-                    store2 = 63
-                else:
-                    if any(v == store2 and k != v for k, v in axes_of.items()):
-                        raise _SharedAxesReused("a shared axes slot is reused while boxes still refer to it")
-                    axes_of[store2] = store2
-                    axes_key[store2] = key
-            # the certificate block of the stage: suffix sums of |dq_j| rho_j from the deepest planning joint up; level c =
-            # the motion relative to a geom that hangs on the first c of them (0: to the world)
-            sizes_ = [float(x) for x in gd[GD_SIZE: GD_SIZE + 3]]
-            rbound_ = {GT_SPHERE: sizes_[0], GT_CAPSULE: sizes_[0] + sizes_[1], GT_BOX: math.sqrt(sum(x * x for x in sizes_))}.get(gtype, math.inf)
-            lp_ = float(np.linalg.norm(np.asarray(lpos, dtype=np.float64)))
-            k2w = max([2.0 * math.sqrt(max(float(st_[4]), 0.0)) for st_ in statics] + [0.0])
-            if not math.isfinite(rbound_) or len(anc_cur) > 7:
-                cert_ok = False
-            cb = ["float s_ = 0.0f;"]
-            need = sorted(slot_levels | {0})
-            for lv in range(len(anc_cur), -1, -1):
-                if lv < len(anc_cur):
-                    qs_, d_ = anc_cur[lv]
-                    rho_ = (d_ + lp_ + (rbound_ if math.isfinite(rbound_) else 0.0)) * (1.0 + 1e-6)
-                    cb.append(f"s_ = __builtin_fmaf((float)adq[{qs_} * 64], {lit(rho_)}, s_);")
-                if lv in need:
-                    cb.append(f"dm{lv} = __builtin_fmaf(s_, 1.001f, 2.0f * tol);")
-            cb.append(f"wc0 = __builtin_fmaf({lit(k2w * (1.0 + 1e-6))}, dm0, dm0 * dm0); deadp = dead - dm0;")
-            for lv in sorted(slot_levels):
-                cb.append(f"ws{lv} = __builtin_fmaf({lit(slot_k2 * (1.0 + 1e-6))}, dm{lv}, dm{lv} * dm{lv});")
-            cert_stage.append(cb)
-            cert_levers.append((geom_id, [(qs_, d_ + lp_ + (rbound_ if math.isfinite(rbound_) else 0.0)) for qs_, d_ in anc_cur], rbound_))
-            if store >= 0:
-                slot_anc[store & 63] = [qs for qs, _ in anc_cur]
-            stages.append((pending_fk + g.lines, gtype, gdoff, store & 63 if store >= 0 else -1, store2))
-            pending_fk = []
-            desc.append([(kind << 0) | (index << 2) | (ptype << 10) | (pfirst << 14) | (boxq << 15) | (index2 << 16) | (lvl << 22)
-                         for kind, index, ptype, pfirst, boxq, index2, lvl in partners])
-    if pending_fk:  # trailing bodies without geoms influence nothing: drop them
-        pending_fk = []
+    prog = decode(ip)
+    cull_form = cull_form or opts.cull
+    skip = set() if generic else {(int(a), int(b)) for a, b in never_touch}
+    reach = _body_reach(prog, fp, dp)
+    anc, hinges_only = _body_levers(prog, dp)
+    levels, nested = _slot_levels(prog, anc, int(info.maxs))
+    world = [_world_partners(prog, g, fp, info, generic, skip) for g in prog.geoms]
+    statics = [w[1] for w in world]
+    axes = (_axes_slots(prog, dp, bool(info.mbox), True, statics) if share_axes else None) or _axes_slots(prog, dp, bool(info.mbox), False, statics)
+    stages = [_partners(prog, g, fp, dp, info, generic, world[g.stage], levels[g.stage], axes[g.stage], reach[g.body]) for g in prog.geoms]
+    cert = [_certificate(st, dp, anc[st.geom.body]) for st in stages]
     # The certificate is an opt-in build (MJPL_SPEC_CERT=1): measured on the headline batch it halves the waypoint checks and
     # gains 3 % -- a workgroup's two rounds of endpoint tiles bound the launch -- while the lines it adds to the code every
     # tile runs cost 8 % without it (profiles/README.md, round 5).  Without it the generated code carries none of it.
-    cert_ok = cert_ok and cull_form == "expanded" and os.environ.get("MJPL_SPEC_CERT", "0") == "1"
+    cert_ok = not generic and hinges_only and nested and all(ok for ok, _, _ in cert) and cull_form == "expanded" and opts.cert
     if report is not None:
-        report["cert_ok"], report["cert_levers"] = bool(cert_ok), cert_levers
-    if not cert_ok:
-        import re
-        stages = [([re.sub(r" \+ ws\d\)", ")", ln).replace(") - wc0;", ");").replace("deadp", "dead") for ln in lines], gt_, gd_, st_, st2_)
-                  for lines, gt_, gd_, st_, st2_ in stages]
-    nstage = len(stages)
+        report["cert_ok"], report["cert_levers"] = bool(cert_ok), [levers for _, _, levers in cert]
+    # the text of a stage: FK of the bodies since the last stage (trailing bodies without geoms influence nothing: never
+    # emitted), the geom's pose, its culls
+    text, nbody_done = [], 0
+    for st, (_, cert_lines, _) in zip(stages, cert):
+        g = _Gen()
+        for body in prog.bodies[nbody_done: st.geom.body + 1]:
+            g.lines.append("{")
+            _emit_body_fk(g, body, dp)
+            g.lines.append("}")
+        nbody_done = st.geom.body + 1
+        _emit_geom_pose(g, st, dp)
+        _emit_culls(g, st, prog, fp, cull_form, generic, cert_lines if cert_ok else None)
+        text.append(g.lines)
+    return _emit_spec(prog, fp, info, stages, text, generic, cert_ok)
+
+
+def _emit_scene_rows(o):
+    """The static partners of a stage of a scene-generic library: the rows of its scene table."""
+    o("      {  // static partners: one row [a0 a1 a2 thr] of the scene table each, two rows per scalar load, the next")
+    o("         // pair fetched while this one is tested (two buffers taking turns: no copies, 16 scalar registers).")
+    o("         // The planes (the last rows): a . c <= thr; the others: |c|^2 + a . c <= thr; a row that is no partner: thr = -inf.")
+    o("         // One straight line over all rows, entered at the first pair in use: row offsets and the lanes")
+    o("         // the masks are parked in are literals, and what a stage pays beside the tests is the one dispatch (a")
+    o("         // rolled loop spent thirty scalar instructions per four rows: addresses, the lane select in M0, the counter).")
+    o("        const float ux = cx + dead;")
+    o("        const float cc = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, ux * ux));")
+    o("        const float zd = 0.0f * ux;  // 0, or NaN on a lane that is not to report anything")
+    o("        const float acc_a = sc_nplane >= 2 ? zd : cc, acc_b = sc_nplane >= 1 ? zd : cc;  // (the last two rows)")
+    o(f"        FP rows = sc + ({SCENE_HEADER} + g * {SCENE_STAGE});")
+    # rows per scalar load: two (two buffers of 8 registers).  Four (2 x 16 registers) measured slower, item pass 0.142 vs
+    # 0.137 ms: the kernels sit at the scalar-register limit and spill into vector lanes
+    o("        float ra[8], rb[8];")
+    o("#define MJPL_SCENE_LOAD(dst, at, n) _Pragma(\"unroll\") for (int k_ = 0; k_ < (n); k_++) dst[k_] = rows[4 * (at) + k_]")
+    o("        // (a fetch is waited for behind the arithmetic of the rows before it: scalar loads return out of order, so")
+    o("        //  a wait at its first use -- after the NEXT fetch has gone out -- would drain that one, too; `rows` passes")
+    o("        //  through the wait so that the next fetch cannot be moved above it, the scheduling barriers keep fetch,")
+    o("        //  arithmetic and wait in this order)")
+    o("#define MJPL_SCENE_WAIT(buf, n) asm volatile(\"\" : \"+s\"(rows) : \"s\"(buf[0]), \"s\"(buf[(n) - 1]))")
+    o("#define MJPL_SCENE_PAIR(buf, acca, accb, ka, kb) do { \\")
+    o("          const float t0_ = __builtin_fmaf(cz, (buf)[2], __builtin_fmaf(cy, (buf)[1], __builtin_fmaf(ux, (buf)[0], acca))); \\")
+    o("          const float t1_ = __builtin_fmaf(cz, (buf)[6], __builtin_fmaf(cy, (buf)[5], __builtin_fmaf(ux, (buf)[4], accb))); \\")
+    o("          const unsigned long long m0_ = __builtin_amdgcn_ballot_w64(t0_ <= (buf)[3]); \\")
+    o("          const unsigned long long m1_ = __builtin_amdgcn_ballot_w64(t1_ <= (buf)[7]); \\")
+    o("          mjpl::park_mask2<ka, kb>(mlo, mhi, m0_, m1_); } while (0)")
+    o("        // (one copy of the line per entry point: falling through case labels, the buffers would arrive at every")
+    o("        //  label from two places and the compiler would copy the registers there)")
+    o("        switch (sc_first) {")
+    for first in range(0, SCENE_ROWS, 2):
+        o(f"          {'default' if first == SCENE_ROWS - 2 else f'case {first}'}: {{")
+        o(f"        MJPL_SCENE_LOAD(ra, {first}, 8);")
+        for k, r in enumerate(range(first, SCENE_ROWS, 2)):  # the rows from `first` on, a pair per fetch
+            cur, nxt = ("ra", "rb") if k % 2 == 0 else ("rb", "ra")
+            o(f"        MJPL_SCENE_WAIT({cur}, 8);")
+            o("        __builtin_amdgcn_sched_barrier(0);")
+            if r + 2 < SCENE_ROWS:
+                o(f"        MJPL_SCENE_LOAD({nxt}, {r + 2}, 8);")
+            o("        __builtin_amdgcn_sched_barrier(0);")
+            acc = ("acc_a", "acc_b") if r == SCENE_ROWS - 2 else ("cc", "cc")
+            o(f"        MJPL_SCENE_PAIR({cur} + 0, {acc[0]}, {acc[1]}, {r}, {r + 1});")
+            o("        __builtin_amdgcn_sched_barrier(0);")
+        o("          } break;")
+    o("        }")
+    o("#undef MJPL_SCENE_LOAD")
+    o("#undef MJPL_SCENE_WAIT")
+    o("#undef MJPL_SCENE_PAIR")
+    o("      }")
+
+
+def _emit_spec(prog, fp, info, stages, text, generic: bool, cert_ok: bool) -> str:
+    """The library's float32 check: the fixed macros, the descriptor table, `struct Spec` with the loop around the stages."""
+    mbox, maxs, nstage = bool(info.mbox), int(info.maxs), len(stages)
+    desc = [st.desc for st in stages]
     out = []
     o = out.append
     o("// GENERATED by mjpl_amd/specialise.py -- straight-line per-configuration check of ONE compiled program.")
-    o(f"// program hash {info.hash:016x}, {nbody} moving bodies, {nstage} moving geoms, "
+    o(f"// program hash {info.hash:016x}, {len(prog.bodies)} moving bodies, {nstage} moving geoms, "
       f"{sum(1 for d in desc for x in d if x)} literal pairs{' (static partners: scene table)' if generic else ''}, slot file width {maxs}")
-    o("#define MJPL_SPEC_QUAT2MAT() \\")
-    o("  do { R0 = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; R4 = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3; \\")
-    o("       R8 = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3; R1 = 2.0f * (q1 * q2 - q0 * q3); R2 = 2.0f * (q1 * q3 + q0 * q2); \\")
-    o("       R3 = 2.0f * (q1 * q2 + q0 * q3); R5 = 2.0f * (q2 * q3 - q0 * q1); R6 = 2.0f * (q1 * q3 - q0 * q2); \\")
-    o("       R7 = 2.0f * (q2 * q3 + q0 * q1); } while (0)")
-    o("typedef float spec_v2f __attribute__((ext_vector_type(2)));")
-    o("// (a scalar branch around the two v_writelane -- most culls pass for no lane of the wave -- measured")
-    o("//  3 % SLOWER than parking unconditionally: 213 more branches per configuration)")
-    o("#define MJPL_SPEC_HIT(k, pass) \\")
-    o("  do { const unsigned long long m_ = __builtin_amdgcn_ballot_w64(pass); \\")
-    o("       mjpl::park_mask<k>(mlo, mhi, m_); } while (0)")
-    o("// ux = cx, or +inf on a lane that is not to report anything (inactive / decided / out of range)")
-    o("#define MJPL_SPEC_CULL(k, X, Y, Z, BOUND) \\")
-    o("  do { const float dx_ = ux - (X), dy_ = cy - (Y), dz_ = cz - (Z); \\")
-    o("       MJPL_SPEC_HIT(k, !(mjpl::sqnorm3(dx_, dy_, dz_) > (BOUND))); } while (0)")
-    o("// two static partners at once: packed float32 arithmetic")
-    o("#define MJPL_SPEC_CULL2(ka, kb, XA, XB, YA, YB, ZA, ZB, BOUNDA, BOUNDB) \\")
-    o("  do { const spec_v2f dx_ = (spec_v2f){ux, ux} - (spec_v2f){XA, XB}, dy_ = (spec_v2f){cy, cy} - (spec_v2f){YA, YB}, \\")
-    o("                      dz_ = (spec_v2f){cz, cz} - (spec_v2f){ZA, ZB}; \\")
-    o("       const spec_v2f s_ = __builtin_elementwise_fma(dx_, dx_, __builtin_elementwise_fma(dy_, dy_, dz_ * dz_)); \\")
-    o("       const unsigned long long ma_ = __builtin_amdgcn_ballot_w64(!(s_.x > (BOUNDA))); \\")
-    o("       const unsigned long long mb_ = __builtin_amdgcn_ballot_w64(!(s_.y > (BOUNDB))); \\")
-    o("       mjpl::park_mask2<ka, kb>(mlo, mhi, ma_, mb_); } while (0)")
-    o("// expanded form: t = |c|^2 - 2 c.X against THR = bound - |X|^2 (+ the form's rounding allowance); cc = |c|^2 with")
-    o("// ux in it, so a lane that is not to report anything carries +inf or NaN here and fails the ordered compare")
-    o("#define MJPL_SPEC_CULLX(k, M2X, M2Y, M2Z, THR) \\")
-    o("  do { const float t_ = __builtin_fmaf(cz, (M2Z), __builtin_fmaf(cy, (M2Y), __builtin_fmaf(ux, (M2X), cc))); \\")
-    o("       MJPL_SPEC_HIT(k, t_ <= (THR)); } while (0)")
-    o("#define MJPL_SPEC_CULLX2(ka, kb, AX, AY, AZ, ATHR, BX, BY, BZ, BTHR) \\")
-    o("  do { const float ta_ = __builtin_fmaf(cz, (AZ), __builtin_fmaf(cy, (AY), __builtin_fmaf(ux, (AX), cc))); \\")
-    o("       const float tb_ = __builtin_fmaf(cz, (BZ), __builtin_fmaf(cy, (BY), __builtin_fmaf(ux, (BX), cc))); \\")
-    o("       const unsigned long long ma_ = __builtin_amdgcn_ballot_w64(ta_ <= (ATHR)); \\")
-    o("       const unsigned long long mb_ = __builtin_amdgcn_ballot_w64(tb_ <= (BTHR)); \\")
-    o("       mjpl::park_mask2<ka, kb>(mlo, mhi, ma_, mb_); } while (0)")
-    o("#define MJPL_SPEC_SLOTCULL(k, n, BOUND) \\")
-    o("  do { const float dx_ = ux - sf.f[0][n], dy_ = cy - sf.f[1][n], dz_ = cz - sf.f[2][n]; \\")
-    o("       MJPL_SPEC_HIT(k, !(mjpl::sqnorm3(dx_, dy_, dz_) > (BOUND))); } while (0)")
+    o(_MACROS)
     o("")
     o(f"__constant__ int kSpecDesc[{nstage} * 64] = {{")
     for d in desc:
@@ -695,7 +754,7 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
         o("}")
         o("")
     o("struct Spec {")
-    o(f"  static constexpr int kNplan = {int(ip[H_NPLAN])};")
+    o(f"  static constexpr int kNplan = {prog.nplan};")
     o("  // the edge certificate: with ps.adq = this lane's |dq| per planning column, run() widens every bounding cull by what")
     o("  // the pair can move along the edge, every candidate carries that margin to its narrowphase routine, and a lane")
     o("  // none of whose candidates came closer returns V_CLEAR instead of V_NONE (mjpl_fused.h)")
@@ -718,16 +777,16 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
     o("    const bool cert = adq != nullptr;  // (wave-uniform)")
     if generic:
         o(f"    // the scene table in front of the float32 tables: header, then per moving geom {SCENE_ROWS} cull rows and {SCENE_ROWS} descriptors")
-        o(f"    const FP sc = tp + ({SC});")
+        o(f"    const FP sc = tp + ({-(SCENE_HEADER + nstage * SCENE_STAGE + 16)});")  # (where the scene table starts, relative to tp)
         o("    const int sc_nplane = info_bits(sc[0]);  // the last 0 .. 2 rows of a geom are planes")
         o("    const int sc_first = info_bits(sc[1]);   // first pair of rows in use (the rows of a geom fill its table from the end)")
         o("    const float maxcoord = sc[4], maxangle = sc[5];")
         o("    const int nwpad = info_bits(sc[2]);")
         o("    const float *lwcull = ltab, *lwnarrow = ltab + info_bits(sc[3]);")
     else:
-        o(f"    const float maxcoord = {lit(fp[fconst + FC_MAXCOORD])}, maxangle = {lit(fp[fconst + FC_MAXANGLE])};")
-        o(f"    const int nwpad = {nwpad};")
-        o(f"    const float *lwcull = ltab + {off_wcull}, *lwnarrow = ltab + {off_wnarrow};")
+        o(f"    const float maxcoord = {lit(fp[prog.off_fconst + FC_MAXCOORD])}, maxangle = {lit(fp[prog.off_fconst + FC_MAXANGLE])};")
+        o(f"    const int nwpad = {prog.nwpad};")
+        o(f"    const float *lwcull = ltab + {prog.off_wcull}, *lwnarrow = ltab + {prog.off_wnarrow};")
     o("#pragma nounroll")
     o(f"    for (int g = 0; g < {nstage}; g++) {{")
     o("      if (__builtin_amdgcn_ballot_w64(dead == 0.0f) == 0ull && qn == 0 && qb == 0) break;  // every lane decided")
@@ -747,83 +806,15 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
         o("      const int dv = kSpecDesc[64 * g + lane];")
     o("      int gtype = 0, gdoff = 0;")
     o("      switch (g) {")
-    for si, (lines, gtype, gdoff, store, store2) in enumerate(stages):
+    for si, (st, lines) in enumerate(zip(stages, text)):
         o(f"        case {si}: {{")
-        for ln in lines:
-            if ln.strip() == "/*CERT*/":
-                if cert_ok:
-                    o("          deadp = dead;")
-                    o("          if (cert) {")
-                    for cl in cert_stage[si]:
-                        o("            " + cl)
-                    o("          }")
-                continue
-            o("      " + ln)
-        if generic:
-            o(f"          gtype = {gtype}; gdoff = info_bits(sc[8 + {si}]);")
-        else:
-            o(f"          gtype = {gtype}; gdoff = {gdoff};")
+        out.extend("      " + ln for ln in lines)
+        o(f"          gtype = {st.geom.type}; gdoff = {f'info_bits(sc[8 + {si}])' if generic else st.geom.doff};")
         o("        } break;")
     o("        default: break;")
     o("      }")
     if generic:
-        o("      {  // static partners: one row [a0 a1 a2 thr] of the scene table each, two rows per scalar load, the next")
-        o("         // pair fetched while this one is tested (two buffers taking turns: no copies, 16 scalar registers).")
-        o("         // The planes (the last rows): a . c <= thr; the others: |c|^2 + a . c <= thr; a row that is no partner: thr = -inf.")
-        o("         // One straight line over all rows, entered at the first pair in use: row offsets and the lanes")
-        o("         // the masks are parked in are literals, and what a stage pays beside the tests is the one dispatch (a")
-        o("         // rolled loop spent thirty scalar instructions per four rows: addresses, the lane select in M0, the counter).")
-        o("        const float ux = cx + dead;")
-        o("        const float cc = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, ux * ux));")
-        o("        const float zd = 0.0f * ux;  // 0, or NaN on a lane that is not to report anything")
-        o("        const float acc_a = sc_nplane >= 2 ? zd : cc, acc_b = sc_nplane >= 1 ? zd : cc;  // (the last two rows)")
-        o(f"        FP rows = sc + ({SCENE_HEADER} + g * {SCENE_STAGE});")
-        # rows per scalar load: two (two buffers of 8 registers); MJPL_GEN_SCENE_WIDE=1: four (2 x 16 registers) -- measured
-        # slower, item pass 0.142 vs 0.137 ms: the kernels sit at the scalar-register limit and spill into vector lanes
-        wide = int(os.environ.get("MJPL_GEN_SCENE_WIDE", "0"))
-        o(f"        float ra[{16 if wide else 8}], rb[{16 if wide else 8}];")
-        o("#define MJPL_SCENE_LOAD(dst, at, n) _Pragma(\"unroll\") for (int k_ = 0; k_ < (n); k_++) dst[k_] = rows[4 * (at) + k_]")
-        o("        // (a fetch is waited for behind the arithmetic of the rows before it: scalar loads return out of order, so")
-        o("        //  a wait at its first use -- after the NEXT fetch has gone out -- would drain that one, too; `rows` passes")
-        o("        //  through the wait so that the next fetch cannot be moved above it, the scheduling barriers keep fetch,")
-        o("        //  arithmetic and wait in this order)")
-        o("#define MJPL_SCENE_WAIT(buf, n) asm volatile(\"\" : \"+s\"(rows) : \"s\"(buf[0]), \"s\"(buf[(n) - 1]))")
-        o("#define MJPL_SCENE_PAIR(buf, acca, accb, ka, kb) do { \\")
-        o("          const float t0_ = __builtin_fmaf(cz, (buf)[2], __builtin_fmaf(cy, (buf)[1], __builtin_fmaf(ux, (buf)[0], acca))); \\")
-        o("          const float t1_ = __builtin_fmaf(cz, (buf)[6], __builtin_fmaf(cy, (buf)[5], __builtin_fmaf(ux, (buf)[4], accb))); \\")
-        o("          const unsigned long long m0_ = __builtin_amdgcn_ballot_w64(t0_ <= (buf)[3]); \\")
-        o("          const unsigned long long m1_ = __builtin_amdgcn_ballot_w64(t1_ <= (buf)[7]); \\")
-        o("          mjpl::park_mask2<ka, kb>(mlo, mhi, m0_, m1_); } while (0)")
-        o("        // (one copy of the line per entry point: falling through case labels, the buffers would arrive at every")
-        o("        //  label from two places and the compiler would copy the registers there)")
-        o("        switch (sc_first) {")
-        for first in range(0, SCENE_ROWS, 2):
-            o(f"          {'default' if first == SCENE_ROWS - 2 else f'case {first}'}: {{")
-            # the rows from `first` on, in fetches of four (a leading pair where `first` is not a multiple of four) or of two
-            chunks = []
-            r = first
-            while r < SCENE_ROWS:
-                nr = 4 if (wide and r % 4 == 0) else 2
-                chunks.append((r, nr))
-                r += nr
-            o(f"        MJPL_SCENE_LOAD(ra, {chunks[0][0]}, {4 * chunks[0][1]});")
-            for k, (r, nr) in enumerate(chunks):
-                cur, nxt = ("ra", "rb") if k % 2 == 0 else ("rb", "ra")
-                o(f"        MJPL_SCENE_WAIT({cur}, {4 * nr});")
-                o("        __builtin_amdgcn_sched_barrier(0);")
-                if k + 1 < len(chunks):
-                    o(f"        MJPL_SCENE_LOAD({nxt}, {chunks[k + 1][0]}, {4 * chunks[k + 1][1]});")
-                o("        __builtin_amdgcn_sched_barrier(0);")
-                for j in range(0, nr, 2):
-                    last = r + j == SCENE_ROWS - 2
-                    o(f"        MJPL_SCENE_PAIR({cur} + {4 * j}, {'acc_a' if last else 'cc'}, {'acc_b' if last else 'cc'}, {r + j}, {r + j + 1});")
-                o("        __builtin_amdgcn_sched_barrier(0);")
-            o("          } break;")
-        o("        }")
-        o("#undef MJPL_SCENE_LOAD")
-        o("#undef MJPL_SCENE_WAIT")
-        o("#undef MJPL_SCENE_PAIR")
-        o("      }")
+        _emit_scene_rows(o)
     o("      const float cur6[6] = {cx, cy, cz, zx, zy, zz};")
     if mbox:
         o("      const float cur6b[6] = {xx, xy, xz, yx, yy, yz};")
@@ -849,52 +840,33 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
         o("        float t6b[6] = {0, 0, 0, 0, 0, 0};")
         o("        const int index2 = (d >> 16) & 63;  // a stored box: the slot of its x and y axes")
         o("        if (kind == EK_SLOT) {")
-        o("          switch (index) {")
-        for n in used1:
-            o(f"            case {n}: spec_get6(sf, {n}, t6); break;")
-        o("            default: break;")
-        o("          }")
-        o("          switch (index2) {")
-        for n in used2:
-            o(f"            case {n}: spec_get6(sf, {n}, t6b); break;")
-        o("            default: break;")
-        o("          }")
+        for var, used, dst in (("index", used1, "t6"), ("index2", used2, "t6b")):
+            o(f"          switch ({var}) {{")
+            out.extend(f"            case {n}: spec_get6(sf, {n}, {dst}); break;" for n in used)
+            o("            default: break;")
+            o("          }")
         o("        }")
     else:
         o("        if (kind == EK_SLOT) slot_get6(sf, index, t6);")
-    if mbox:
-        o("        if ((d >> 15) & 1)")
-        o("          queue_push<float, true, true>(wq, qb, dead, fl, active, far, ltab, lwcull, lwnarrow, nwpad, tol, ps, pm, kind, index,")
-        o("                                        gtype, ptype, pfirst, gdoff, cur6, t6, cur6b, t6b, mc_);")
-        o("        else")
-        o("          queue_push<float, false, true>(wq, qn, dead, fl, active, far, ltab, lwcull, lwnarrow, nwpad, tol, ps, pm, kind, index,")
-        o("                                         gtype, ptype, pfirst, gdoff, cur6, t6, nullptr, nullptr, mc_);")
-    else:
-        o("        if ((d >> 15) & 1)")
-        o("          queue_push<float, true>(wq, qb, dead, fl, active, far, ltab, lwcull, lwnarrow, nwpad, tol, ps, pm, kind, index,")
-        o("                                  gtype, ptype, pfirst, gdoff, cur6, t6, nullptr, nullptr, mc_);")
-        o("        else")
-        o("          queue_push<float, false>(wq, qn, dead, fl, active, far, ltab, lwcull, lwnarrow, nwpad, tol, ps, pm, kind, index,")
-        o("                                   gtype, ptype, pfirst, gdoff, cur6, t6, nullptr, nullptr, mc_);")
+    for cond, box, qv in (("if ((d >> 15) & 1)", "true", "qb"), ("else", "false", "qn")):  # (the box queue's records carry full frames)
+        call = f"          queue_push<float, {box}{', true' if mbox else ''}>("
+        o("        " + cond)
+        o(f"{call}wq, {qv}, dead, fl, active, far, ltab, lwcull, lwnarrow, nwpad, tol, ps, pm, kind, index,")
+        o(" " * len(call) + f"gtype, ptype, pfirst, gdoff, cur6, t6, {'cur6b, t6b' if (mbox and box == 'true') else 'nullptr, nullptr'}, mc_);")
     o("      }")
     o("      switch (g) {  // (a literal slot index keeps the slot file in registers)")
     put = "spec_put6" if mbox else "slot_put6"
-    for si, (_, _, _, store, store2) in enumerate(stages):
-        if store >= 0:
-            if mbox and store2 != 63:
-                o(f"        case {si}: {put}(sf, {store}, cur6); {put}(sf, {store2}, cur6b); break;")
-            else:
-                o(f"        case {si}: {put}(sf, {store}, cur6); break;")
+    for si, st in enumerate(stages):
+        if st.geom.store >= 0:
+            axes = f" {put}(sf, {st.store2}, cur6b);" if (mbox and st.store2 != 63) else ""
+            o(f"        case {si}: {put}(sf, {st.geom.slot}, cur6);{axes} break;")
     o("        default: break;")
     o("      }")
     o("    }")
-    if mbox:
-        o("    if (qn > 0) queue_drain<float, false, true, true>(wq, qn, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
-        o("    if (qb > 0) queue_drain<float, true, true, true>(wq, qb, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
-    else:
-        o("    if (qn > 0) queue_drain<float, false, true>(wq, qn, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
-    if (info.wbox or generic) and not mbox:  # (a scene-generic library serves scenes with static boxes whatever scene it was generated from)
-        o("    if (qb > 0) queue_drain<float, true, true>(wq, qb, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
+    m3 = ", true" if mbox else ""
+    o(f"    if (qn > 0) queue_drain<float, false, true{m3}>(wq, qn, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
+    if mbox or info.wbox or generic:  # (a scene-generic library serves scenes with static boxes whatever scene it was generated from)
+        o(f"    if (qb > 0) queue_drain<float, true, true{m3}>(wq, qb, ltab, lwcull, lwnarrow, nwpad, tol, ps);")
     o("    fl = wq.flags[lane] & 7;")
     o("    if (active && far) return V_UNSURE;  // nothing this lane's candidates said can be trusted")
     o("    return !active ? V_NONE : ((fl & 1) ? V_CONTACT : ((fl & 2) ? V_UNSURE : ((cert && !(fl & 4)) ? V_CLEAR : V_NONE)));")
@@ -903,10 +875,54 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
     return "\n".join(out) + "\n"
 
 
-
-def dlit(x) -> str:
-    """An exact C++17 hexadecimal literal of a float64."""
-    return float(x).hex()
+def _exact_body_fk(f, body, dp, p, qt, R, sv_prefix: str, sin_tag):
+    """mj_kinematics of ONE body op as folded straight-line float64 code (the statements of run_config_queued<double> /
+    patch_pairs_body, mjpl_device.h).  (p, qt, R): the walk's current state as Fold values; sv_prefix, sin_tag(joint number):
+    how the caller wants a restored pose's values and a hinge's sine and cosine named.  -> new (p, qt, R)."""
+    c, v = f.c, f.v
+    bd = dp[body.doff:]
+    if body.parent == PARENT_CUR:
+        pp, pq, pR = p, qt, R
+    elif body.parent == PARENT_STATIC:
+        pp, pq, pR = [c(x) for x in bd[7:10]], [c(x) for x in bd[10:14]], [c(x) for x in bd[14:23]]
+    else:
+        k0 = f.n
+        f.n += 1
+        f.emit(f"const double *sv{k0} = save + (size_t){body.parent - 1} * 7 * sstride;")
+        names = [f"{sv_prefix}sv{k0}_{k}" for k in range(7)]
+        f.emit("const double " + ", ".join(f"{names[k]} = sv{k0}[{k} * sstride]" for k in range(7)) + ";")
+        pp, pq = [v(n) for n in names[:3]], [v(n) for n in names[3:]]
+        pR = f.quat2mat(pq)
+    np_ = [f.add(x, y) for x, y in zip(f.mul_mat_vec3(pR, [c(x) for x in bd[0:3]]), pp)]
+    nq_ = f.mul_quat(pq, [c(x) for x in bd[3:7]])
+    for j, (jtype, qsrc, jflags, jdoff) in enumerate(body.joints):
+        jd = dp[jdoff:]
+        qv = v(f"q[{qsrc} * qstride]") if qsrc >= 0 else c(jd[7])
+        dq = f.sub(qv, c(jd[6]))
+        jaxis, jpos = [c(x) for x in jd[0:3]], [c(x) for x in jd[3:6]]
+        if jtype == JT_SLIDE:
+            xaxis = f.rot_vec_quat(jaxis, nq_)
+            np_ = [f.add(np_[r], f.mul(xaxis[r], dq)) for r in range(3)]
+        else:
+            xanchor = np_
+            if jflags & JF_POS_NONZERO:
+                xanchor = [f.add(x, y) for x, y in zip(f.rot_vec_quat(jpos, nq_), np_)]
+            half = f.mul(dq, c(0.5))
+            tag = sin_tag(j)
+            f.emit(f"double sn{tag}, cs{tag};")
+            f.emit(f"sincos_half({f.text(half)}, &sn{tag}, &cs{tag});")
+            sn, cs = v(f"sn{tag}"), v(f"cs{tag}")
+            nq_ = f.mul_quat(nq_, [cs, f.mul(jaxis[0], sn), f.mul(jaxis[1], sn), f.mul(jaxis[2], sn)])
+            if jflags & JF_POS_NONZERO:
+                vec = f.rot_vec_quat(jpos, nq_)
+                np_ = [f.sub(xanchor[r], vec[r]) for r in range(3)]
+    nq_ = f.normalize4(nq_)
+    Rn = f.quat2mat(nq_)
+    if body.save >= 0:
+        f.emit(f"{{ double *sv = save + (size_t){body.save} * 7 * sstride;")
+        f.emit("  " + " ".join(f"sv[{k} * sstride] = {f.text(np_[k])};" for k in range(3)))
+        f.emit("  " + " ".join(f"sv[{3 + k} * sstride] = {f.text(nq_[k])};" for k in range(4)) + " }")
+    return np_, nq_, Rn
 
 
 def generate_exact(ip, dp, info, generic: bool = False, fold: bool = True) -> str:
@@ -917,13 +933,10 @@ def generate_exact(ip, dp, info, generic: bool = False, fold: bool = True) -> st
     verdicts are the interpreter's, bit for bit; what goes away is ~700 scalar loads per wave and more than half of the
     chain's float64 instructions -- the latency of this chain is what a launch's tail kernel costs.
     fold=False: every operation of the statement (tests)."""
-    from .fold import Fold
     out = []
     o = out.append
-    nbody = int(ip[H_NBODYOPS])
-    pc = int(ip[H_OFF_BODYOPS])
     f = Fold(indent="    ", fold=fold)
-    c, v = f.c, f.v
+    c = f.c
     o("struct ExactSpec {")
     o("  // 1: geoms are numbered from the first moving one (a scene-generic library: model ids shift with the scene)")
     o(f"  static constexpr int kRelative = {1 if generic else 0};")
@@ -932,72 +945,21 @@ def generate_exact(ip, dp, info, generic: bool = False, fold: bool = True) -> st
     o("    using namespace mjpl;")
     p, qt = [c(0), c(0), c(0)], [c(1), c(0), c(0), c(0)]
     R = [c(x) for x in (1, 0, 0, 0, 1, 0, 0, 0, 1)]
-    stage = 0
-    nsin = 0
-    for b in range(nbody):
-        parent, bdoff, njnt, save_slot, ngeom = (int(ip[pc + k]) for k in (B_PARENT, B_DOFF, B_NJNT, B_SAVE, B_NGEOM))
-        pc += B_SIZE
-        bd = dp[bdoff:]
-        f.emit(f"// body op {b}")
-        if parent == PARENT_CUR:
-            pp, pq, pR = p, qt, R
-        elif parent == PARENT_STATIC:
-            pp, pq, pR = [c(x) for x in bd[7:10]], [c(x) for x in bd[10:14]], [c(x) for x in bd[14:23]]
-        else:
-            k0 = f.n
-            f.n += 1
-            f.emit(f"const double *sv{k0} = save + (size_t){parent - 1} * 7 * sstride;")
-            names = [f"sv{k0}_{k}" for k in range(7)]
-            f.emit("const double " + ", ".join(f"{names[k]} = sv{k0}[{k} * sstride]" for k in range(7)) + ";")
-            pp, pq = [v(n) for n in names[:3]], [v(n) for n in names[3:]]
-            pR = f.quat2mat(pq)
-        np_ = [f.add(x, y) for x, y in zip(f.mul_mat_vec3(pR, [c(x) for x in bd[0:3]]), pp)]
-        nq_ = f.mul_quat(pq, [c(x) for x in bd[3:7]])
-        for j in range(njnt):
-            jtype, qsrc, jflags, jdoff = (int(ip[pc + k]) for k in (J_TYPE, J_QSRC, J_FLAGS, J_DOFF))
-            pc += J_SIZE
-            jd = dp[jdoff:]
-            qv = v(f"q[{qsrc} * qstride]") if qsrc >= 0 else c(jd[7])
-            dq = f.sub(qv, c(jd[6]))
-            jaxis, jpos = [c(x) for x in jd[0:3]], [c(x) for x in jd[3:6]]
-            if jtype == JT_SLIDE:
-                xaxis = f.rot_vec_quat(jaxis, nq_)
-                np_ = [f.add(np_[r], f.mul(xaxis[r], dq)) for r in range(3)]
-            else:
-                xanchor = np_
-                if jflags & JF_POS_NONZERO:
-                    xanchor = [f.add(x, y) for x, y in zip(f.rot_vec_quat(jpos, nq_), np_)]
-                half = f.mul(dq, c(0.5))
-                f.emit(f"double sn{nsin}, cs{nsin};")
-                f.emit(f"sincos_half({f.text(half)}, &sn{nsin}, &cs{nsin});")
-                sn, cs = v(f"sn{nsin}"), v(f"cs{nsin}")
-                nsin += 1
-                nq_ = f.mul_quat(nq_, [cs, f.mul(jaxis[0], sn), f.mul(jaxis[1], sn), f.mul(jaxis[2], sn)])
-                if jflags & JF_POS_NONZERO:
-                    vec = f.rot_vec_quat(jpos, nq_)
-                    np_ = [f.sub(xanchor[r], vec[r]) for r in range(3)]
-        nq_ = f.normalize4(nq_)
-        p, qt = np_, nq_
-        R = f.quat2mat(qt)
-        if save_slot >= 0:
-            f.emit(f"{{ double *sv = save + (size_t){save_slot} * 7 * sstride;")
-            f.emit("  " + " ".join(f"sv[{k} * sstride] = {f.text(p[k])};" for k in range(3)))
-            f.emit("  " + " ".join(f"sv[{3 + k} * sstride] = {f.text(qt[k])};" for k in range(4)) + " }")
-        for gi in range(ngeom):
-            gflags, gdoff, geom_id = (int(ip[pc + k]) for k in (G_FLAGS, G_DOFF, G_GEOMID))
-            pc += G_SIZE + MAX_SLOTS
-            gd = dp[gdoff:]
-            if generic:
-                geom_id = stage
-            stage += 1
+    nsin = itertools.count()  # (the hinges' sines and cosines: numbered through the whole chain)
+    for body in decode(ip).bodies:
+        f.emit(f"// body op {body.index}")
+        p, qt, R = _exact_body_fk(f, body, dp, p, qt, R, "", lambda j: next(nsin))
+        for g in body.geoms:
+            gd = dp[g.doff:]
+            geom_id = g.stage if generic else g.geom_id
             f.emit(f"if (__ballot(active && (ga == {geom_id} || gb == {geom_id})) != 0ull) {{")
             with f.scope():
                 ind, f.ind = f.ind, f.ind + "  "
-                if gflags & GF_SAMEPOS:
+                if g.flags & GF_SAMEPOS:
                     cpos = p
                 else:
                     cpos = [f.add(x, y) for x, y in zip(f.mul_mat_vec3(R, [c(x) for x in gd[0:3]]), p)]
-                cm = R if gflags & GF_SAMEROT else f.quat2mat(f.mul_quat(qt, [c(x) for x in gd[3:7]]))
+                cm = R if g.flags & GF_SAMEROT else f.quat2mat(f.mul_quat(qt, [c(x) for x in gd[3:7]]))
                 f.emit(f"const bool isa = ga == {geom_id}, isb = gb == {geom_id};")
                 for k in range(3):
                     t = f.text(cpos[k])
@@ -1012,61 +974,8 @@ def generate_exact(ip, dp, info, generic: bool = False, fold: bool = True) -> st
     o("};")
     return "\n".join(out) + "\n"
 
-def _exact_body_fk(f, ip, dp, pc, p, qt, R, sin_tag: str):
-    """mj_kinematics of ONE body op as folded straight-line float64 code (the statements of run_config_queued<double> /
-    patch_pairs_body, mjpl_device.h): `pc` at the body op's header.  (p, qt, R): the walk's current state as Fold values.
-    -> (pc behind the joints, new p, qt, R, save slot, number of geoms)."""
-    c, v = f.c, f.v
-    parent, bdoff, njnt, save_slot, ngeom = (int(ip[pc + k]) for k in (B_PARENT, B_DOFF, B_NJNT, B_SAVE, B_NGEOM))
-    pc += B_SIZE
-    bd = dp[bdoff:]
-    if parent == PARENT_CUR:
-        pp, pq, pR = p, qt, R
-    elif parent == PARENT_STATIC:
-        pp, pq, pR = [c(x) for x in bd[7:10]], [c(x) for x in bd[10:14]], [c(x) for x in bd[14:23]]
-    else:
-        k0 = f.n
-        f.n += 1
-        f.emit(f"const double *sv{k0} = save + (size_t){parent - 1} * 7 * sstride;")
-        names = [f"{f.prefix}sv{k0}_{k}" for k in range(7)]
-        f.emit("const double " + ", ".join(f"{names[k]} = sv{k0}[{k} * sstride]" for k in range(7)) + ";")
-        pp, pq = [v(n) for n in names[:3]], [v(n) for n in names[3:]]
-        pR = f.quat2mat(pq)
-    np_ = [f.add(x, y) for x, y in zip(f.mul_mat_vec3(pR, [c(x) for x in bd[0:3]]), pp)]
-    nq_ = f.mul_quat(pq, [c(x) for x in bd[3:7]])
-    for j in range(njnt):
-        jtype, qsrc, jflags, jdoff = (int(ip[pc + k]) for k in (J_TYPE, J_QSRC, J_FLAGS, J_DOFF))
-        pc += J_SIZE
-        jd = dp[jdoff:]
-        qv = v(f"q[{qsrc} * qstride]") if qsrc >= 0 else c(jd[7])
-        dq = f.sub(qv, c(jd[6]))
-        jaxis, jpos = [c(x) for x in jd[0:3]], [c(x) for x in jd[3:6]]
-        if jtype == JT_SLIDE:
-            xaxis = f.rot_vec_quat(jaxis, nq_)
-            np_ = [f.add(np_[r], f.mul(xaxis[r], dq)) for r in range(3)]
-        else:
-            xanchor = np_
-            if jflags & JF_POS_NONZERO:
-                xanchor = [f.add(x, y) for x, y in zip(f.rot_vec_quat(jpos, nq_), np_)]
-            half = f.mul(dq, c(0.5))
-            tag = f"{sin_tag}{j}"
-            f.emit(f"double sn{tag}, cs{tag};")
-            f.emit(f"sincos_half({f.text(half)}, &sn{tag}, &cs{tag});")
-            sn, cs = v(f"sn{tag}"), v(f"cs{tag}")
-            nq_ = f.mul_quat(nq_, [cs, f.mul(jaxis[0], sn), f.mul(jaxis[1], sn), f.mul(jaxis[2], sn)])
-            if jflags & JF_POS_NONZERO:
-                vec = f.rot_vec_quat(jpos, nq_)
-                np_ = [f.sub(xanchor[r], vec[r]) for r in range(3)]
-    nq_ = f.normalize4(nq_)
-    Rn = f.quat2mat(nq_)
-    if save_slot >= 0:
-        f.emit(f"{{ double *sv = save + (size_t){save_slot} * 7 * sstride;")
-        f.emit("  " + " ".join(f"sv[{k} * sstride] = {f.text(np_[k])};" for k in range(3)))
-        f.emit("  " + " ".join(f"sv[{3 + k} * sstride] = {f.text(nq_[k])};" for k in range(4)) + " }")
-    return pc, np_, nq_, Rn, save_slot, ngeom
 
-
-def generate_full_exact(ip, fp, dp, info) -> str | None:
+def generate_full_exact(ip, fp, dp, info, opts: Options | None = None) -> str | None:
     """HIP source of `struct ExactFull`: the float64 check of one configuration through the candidate queues
     (run_config_queued<double>, mjpl_device.h -- what k_edges_fused_f64 calls for every endpoint and waypoint when the
     filter is off or refused) as straight-line code for ONE compiled program: forward kinematics and geom poses with the
@@ -1080,41 +989,30 @@ def generate_full_exact(ip, fp, dp, info) -> str | None:
     is two scalar moves, and the kernel spills 222 scalar registers.  So libraries carry it only when built with
     MJPL_SPEC_F64=1; what a generated float64 path would need is the partners' rows from the table (scalar loads) around
     the folded FK -- the FK is a tenth of the check."""
-    from .fold import Fold
+    opts = opts or Options.from_env()
     if info.immediate or info.mbox or int(info.maxs) > 16:
         return None
-    nbody, nwpad, maxs = int(ip[H_NBODYOPS]), int(ip[H_NWPAD]), int(info.maxs)
-    off_wcull, off_wnarrow = int(ip[H_OFF_WCULL]), int(ip[H_OFF_WNARROW])
-
-    def wc_at(wrow, f_):
-        return off_wcull + ((wrow >> 2) << 4) + (f_ << 2) + (wrow & 3)
+    prog = decode(ip)
+    nwpad, maxs, off_wcull, off_wnarrow = prog.nwpad, int(info.maxs), prog.off_wcull, prog.off_wnarrow
     state = ["p0", "p1", "p2", "q0", "q1", "q2", "q3"] + [f"R{k}" for k in range(9)]
     stages, desc, pending = [], [], []
-    pc = int(ip[H_OFF_BODYOPS])
-    known = True  # the walk's state is still a generation-time constant (nothing assigned to the variables yet)
-    cp, cq, cR = None, None, None
-    for b in range(nbody):
+    for body in prog.bodies:
+        b = body.index
         f = Fold(indent="          ", prefix=f"b{b}_")
-        if known and b == 0:
+        if b == 0:  # the walk's state is still a generation-time constant (nothing assigned to the variables yet)
             p, qt, R = [f.c(0)] * 3, [f.c(1), f.c(0), f.c(0), f.c(0)], [f.c(x) for x in (1, 0, 0, 0, 1, 0, 0, 0, 1)]
         else:
             p, qt, R = [f.v(n) for n in state[:3]], [f.v(n) for n in state[3:7]], [f.v(n) for n in state[7:]]
-        pc, p, qt, R, save_slot, ngeom = _exact_body_fk(f, ip, dp, pc, p, qt, R, f"b{b}j")
+        p, qt, R = _exact_body_fk(f, body, dp, p, qt, R, f.prefix, lambda j: f"b{b}j{j}")
         for name, val in zip(state, p + qt + R):
             f.emit(f"{name} = {f.text(val)};")
-        known = False
         pending.extend(["        {"] + f.lines + ["        }"])
-        for gi in range(ngeom):
-            gtype, gflags, gdoff, store, geom_id, smask = (int(ip[pc + k]) for k in (G_TYPE, G_FLAGS, G_DOFF, G_STORE, G_GEOMID, G_SMASK))
-            wmask = (int(ip[pc + G_WMASK_LO]) & 0xFFFFFFFF) | ((int(ip[pc + G_WMASK_HI]) & 0xFFFFFFFF) << 32)
-            pmask = (int(ip[pc + G_PMASK_LO]) & 0xFFFFFFFF) | ((int(ip[pc + G_PMASK_HI]) & 0xFFFFFFFF) << 32)
-            swords = [int(x) for x in ip[pc + G_SIZE: pc + G_SIZE + MAX_SLOTS]]
-            pc += G_SIZE + MAX_SLOTS
-            gd = dp[gdoff:]
+        for gm in body.geoms:
+            gd = dp[gm.doff:]
             g = Fold(indent="          ", prefix=f"g{len(stages)}_")
             sp_, sq_, sR_ = [g.v(n) for n in state[:3]], [g.v(n) for n in state[3:7]], [g.v(n) for n in state[7:]]
-            cpos = sp_ if gflags & GF_SAMEPOS else [g.add(x, y) for x, y in zip(g.mul_mat_vec3(sR_, [g.c(x) for x in gd[0:3]]), sp_)]
-            if gflags & GF_SAMEROT:
+            cpos = sp_ if gm.flags & GF_SAMEPOS else [g.add(x, y) for x, y in zip(g.mul_mat_vec3(sR_, [g.c(x) for x in gd[0:3]]), sp_)]
+            if gm.flags & GF_SAMEROT:
                 zax = [sR_[2], sR_[5], sR_[8]]
             else:  # quat2zaxis(qt (x) lq): the third column of quat2mat, its expressions
                 gq = g.mul_quat(sq_, [g.c(x) for x in gd[3:7]])
@@ -1129,36 +1027,28 @@ def generate_full_exact(ip, fp, dp, info) -> str | None:
             partners = []
             wbound = gd[GD_WBOUND: GD_WBOUND + nwpad]
             sbound = gd[GD_WBOUND + 2 * nwpad: GD_WBOUND + 2 * nwpad + MAX_SLOTS]
-            for wrow in range(64):  # static planes
-                if not (pmask >> wrow) & 1:
-                    continue
-                ppos = [g.c(dp[wc_at(wrow, k)]) for k in range(3)]
+            for wrow in gm.world_rows(planes=True):
+                ppos = [g.c(dp[prog.wc_at(wrow, k)]) for k in range(3)]
                 pz = [g.c(dp[off_wnarrow + wrow * WN_LEN + WN_ZAXIS + k]) for k in range(3)]
                 dif = [g.sub(cv[k], ppos[k]) for k in range(3)]
                 dot = g.sum([g.mul(dif[k], pz[k]) for k in range(3)])
                 g.emit(f"MJPL_X64_HIT({len(partners)}, !({g.text(dot)} + dead > {dlit(wbound[wrow])}));")
-                partners.append((EK_PLANE, wrow, GT_PLANE, 1, 0))
-            for wrow in range(64):  # other static geoms
-                if not (wmask >> wrow) & 1:
-                    continue
-                info_word = int(np.frombuffer(np.float64(dp[wc_at(wrow, 3)]).tobytes(), dtype=np.int32)[0])
-                ptype, pgid = info_word & 255, info_word >> 8
-                pfirst = 1 if (ptype < gtype or (ptype == gtype and pgid < geom_id)) else 0
-                dd = [g.sub(cv[k], g.c(dp[wc_at(wrow, k)])) for k in range(3)]
+                partners.append(pack_desc(EK_PLANE, wrow, GT_PLANE, 1, 0))
+            for wrow in gm.world_rows(planes=False):  # other static geoms
+                ptype, pgid = prog.row_info(dp, wrow)
+                pfirst = 1 if (ptype < gm.type or (ptype == gm.type and pgid < gm.geom_id)) else 0
+                dd = [g.sub(cv[k], g.c(dp[prog.wc_at(wrow, k)])) for k in range(3)]
                 sq = g.sum([g.mul(x, x) for x in dd])
                 g.emit(f"MJPL_X64_HIT({len(partners)}, !({g.text(sq)} + dead > {dlit(wbound[wrow])}));")
-                partners.append((EK_STATIC, wrow, ptype, pfirst, 1 if ptype == GT_BOX else 0))
-            for n in range(maxs):  # earlier moving geoms in the slot file
-                if not (smask >> n) & 1:
-                    continue
-                pw = swords[n]
+                partners.append(pack_desc(EK_STATIC, wrow, ptype, pfirst, 1 if ptype == GT_BOX else 0))
+            for n, pw in gm.slots(maxs):  # earlier moving geoms in the slot file
                 g.emit(f"MJPL_X64_SLOTCULL({len(partners)}, {n}, {dlit(sbound[n])});")
-                partners.append((EK_SLOT, n, (pw >> 12) & 15, 1 if (pw & P_FIRST) else 0, 0))
+                partners.append(pack_desc(EK_SLOT, n, (pw >> 12) & 15, 1 if (pw & P_FIRST) else 0, 0))
             if len(partners) > 64:
                 return None
-            stages.append((pending + g.lines, gtype, gdoff, store & 63 if store >= 0 else -1))
+            stages.append((pending + g.lines, gm.type, gm.doff, gm.slot))
             pending = []
-            desc.append([(kind << 0) | (index << 2) | (ptype << 10) | (pfirst << 14) | (boxq << 15) for kind, index, ptype, pfirst, boxq in partners])
+            desc.append(partners)
     nstage = len(stages)
     wbox = any((x >> 15) & 1 for d in desc for x in d)
     out = []
@@ -1181,7 +1071,7 @@ def generate_full_exact(ip, fp, dp, info) -> str | None:
     #  tiles were right -- every variant with a second call site, and this outlined form, return the interpreter's verdicts on
     #  all edges; observed with ROCm 7.2's compiler at 222 spilled scalar registers, not explained)
     # (MJPL_SPEC_F64_INLINE=1: the inlined form, for tools/f64_inline_probe.py -- the experiment that looks for what breaks it)
-    attr = "always_inline" if os.environ.get("MJPL_SPEC_F64_INLINE") == "1" else "noinline"
+    attr = "always_inline" if opts.f64_inline else "noinline"
     o(f"  static __device__ __attribute__(({attr})) int run(const double *ltab, const double *q, int qstride, double *save, int sstride, bool active,")
     o("                                            const mjpl::WaveQueue<double, false> &wq, int item, const mjpl::PatchSink &ps) {")
     o("    using namespace mjpl;")
@@ -1349,34 +1239,17 @@ int mjpl_spec_launch_patch(hipStream_t st, unsigned grid, unsigned block, size_t
 PH_NBODY, PH_NJOINT, PH_NQ, PH_SIZE = 0, 1, 2, 6  # (mjpl_pose.h)
 
 
-def _model_desc(model):
-    d = _engine._ModelDesc()
-    d.nq, d.njnt, d.nbody, d.ngeom = model.nq, model.njnt, model.nbody, model.ngeom
-    keep = []
-    for name, typ in _engine._ModelDesc._fields_[4:]:
-        arr = getattr(model, name)
-        arr = _engine._i32(arr) if typ is _engine._I32P else _engine._f64(arr)
-        keep.append(arr)
-        setattr(d, name, arr.ctypes.data_as(typ))
-    return d, keep
-
-
 def dump_pose_chain(model, site_body: int):
-    """The chain program mjpl_pose_create compiles for (model, site body), on the host (no GPU)
+    """The chain program mjpl_pose_chain_dump compiles for (model, site body), on the host (no GPU)
     -> (pi int32[], pd float64[], hash)."""
     lib = _engine.load_library()
-    d, keep = _model_desc(model)
+    d, keep = _engine._model_desc(model)
     npi, npd, h = C.c_int32(0), C.c_int32(0), C.c_uint64(0)
 
-    def call(pi, pd):
-        rc = lib.mjpl_pose_chain_dump(C.byref(d), int(site_body), None if pi is None else pi.ctypes.data_as(_engine._I32P), C.byref(npi),
-                                      None if pd is None else pd.ctypes.data_as(_engine._F64P), C.byref(npd), C.byref(h))
-        if rc != 0:
-            raise _engine.MjplError(rc, lib.mjpl_last_error().decode())
-
-    call(None, None)
-    pi, pd = np.zeros(npi.value, np.int32), np.zeros(npd.value, np.float64)
-    call(pi, pd)
+    def args(bufs):
+        pi, pd = bufs or (None, None)
+        return [C.byref(d), int(site_body), _ptr(pi, _engine._I32P), C.byref(npi), _ptr(pd, _engine._F64P), C.byref(npd), C.byref(h)]
+    pi, pd = _engine._sized_call(lib, lib.mjpl_pose_chain_dump, args, lambda _: (np.zeros(npi.value, np.int32), np.zeros(npd.value, np.float64)))
     return pi, pd, int(h.value)
 
 
@@ -1393,7 +1266,6 @@ def generate_pose(pi, pd, hash_: int, index: int, qualifier: str = "static __dev
     or one joint per lane of a row's group (mjpl_project.h).  What goes away against the interpreting kernel: the
     reading of the chain program, the loop control, the trip through LDS of the joints' axes and anchors, and about
     half of the chain's arithmetic.  qualifier: how the member functions are declared (tests compile a chain for the host)."""
-    from .fold import Fold
     nb, nj, nq = int(pi[PH_NBODY]), int(pi[PH_NJOINT]), int(pi[PH_NQ])
     f = Fold(indent="    ", fold=fold)  # (fold=False: every operation of the statement, for tests)
     c, v = f.c, f.v
@@ -1533,11 +1405,6 @@ def generate_pose_section(model, nplan: int = 0, qidx=None) -> str:
     return "\n".join(src) + "\n"
 
 
-def _mbox_waves() -> int:
-    """Waves per SIMD the kernels of a model with moving boxes are built for (MJPL_SPEC_MBOX_WAVES: A/B builds)."""
-    return max(1, min(3, int(os.environ.get("MJPL_SPEC_MBOX_WAVES", "2"))))
-
-
 _FUSED_F64 = """// the float64 checks of an edge launch through the pool (filter off or refused) around this model's generated check
 int mjpl_spec_launch_fused_f64(hipStream_t st, int nwaves, size_t lds, FusedArgs a) {
   if (nwaves != kFusedF64Waves) return -1;
@@ -1547,27 +1414,54 @@ int mjpl_spec_launch_fused_f64(hipStream_t st, int nwaves, size_t lds, FusedArgs
 }"""
 
 
-def translation_unit(spec: str, exact: str, key: int, info, generic_word: int = 0, pose: str | None = None, exact_full: str | None = None) -> str:
+def translation_unit(spec: str, exact: str, key: int, info, generic_word: int = 0, pose: str | None = None, exact_full: str | None = None,
+                     opts: Options | None = None) -> str:
     """The source of a library: the kernels of mjpl_filter.h / mjpl_fused.h instantiated around `spec` / `exact`,
     and the projections of `pose` (generate_pose_section; None: a library without any)."""
+    opts = opts or Options.from_env()
     mbox = bool(info.mbox)
     if pose is None:
         pose = 'extern "C" int mjpl_spec_pose_count(void) { return 0; }\n'
     wbox_s = "true" if (info.wbox or generic_word or mbox) else "false"
     return _TU % dict(spec=spec, exact=exact, hash=key, maxs=info.maxs, pose=pose, exact_full=exact_full or "",
-                      fused_f64=(_FUSED_F64 % dict(wbox=wbox_s)) if exact_full else "",
-                      wbox="true" if (info.wbox or generic_word or mbox) else "false", mbox="true" if mbox else "false",
+                      fused_f64=(_FUSED_F64 % dict(wbox=wbox_s)) if exact_full else "", wbox=wbox_s, mbox="true" if mbox else "false",
                       maxsd=32 if mbox else info.maxs,  # (the exact kernels of a model with moving boxes: the general build)
                       # a model with moving boxes keeps whole frames in its slot file and in the box queue's records: built for
                       # two waves per SIMD (256 VGPRs), eight waves per workgroup of the fused kernel -- at three the kernels
                       # spill 60 .. 90 registers and the fused kernel's LDS no longer fits: 0.56 against 0.42 ms on Franka-P
                       # with the ten pad boxes (profiles/r04_pads.json)
-                      fwaves=(4 * _mbox_waves()) if mbox else 12, waves_define=f"#define MJPL_SPEC_WAVES {_mbox_waves()}\n" if mbox else "",
+                      fwaves=(4 * opts.mbox_waves) if mbox else 12, waves_define=f"#define MJPL_SPEC_WAVES {opts.mbox_waves}\n" if mbox else "",
                       generic=generic_word)
 
 
 def spec_path(hash_: int, generic: bool = False) -> str:
     return os.path.join(SPEC_DIR, f"libmjpl_spec{'g' if generic else ''}_{hash_:016x}.so")
+
+
+# every Python file the generated text depends on: a library older than one of them is stale
+GENERATOR_SOURCES = tuple(os.path.join(os.path.dirname(os.path.abspath(__file__)), f) for f in ("specialise.py", "program.py", "fold.py"))
+
+
+def library_source(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, generic: bool = False,
+                   prune_contacts: int = 1, opts: Options | None = None) -> tuple | None:
+    """The source half of build(): (the hash the library is named by, its translation unit), or None if the model cannot
+    be specialised.  Host Python over the program tables: no compiler, no GPU."""
+    opts = opts or Options.from_env()
+    ip, fp, dp, info = dump_program(model, allowed_collision_bodies, qidx, qpos_base, filter_tol)
+    if info.immediate or not info.filter_usable or (generic and not info.scene_ok):
+        return None
+    never_touch, _, never_hash, _ = dump_never_touch(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, prune_contacts=prune_contacts)
+    if prune_contacts == 1 and never_hash != int(info.hash):
+        raise RuntimeError("dump_never_touch and dump_program disagree on the program hash")
+    info.hash = never_hash
+    key = info.robot_hash if generic else info.hash
+    prog = decode(ip)
+    src = translation_unit(generate(ip, fp, dp, info, generic=generic, never_touch=never_touch, opts=opts), generate_exact(ip, dp, info, generic=generic),
+                           key, info, (SCENE_ROWS << 8 | prog.nstage) if generic else 0,  # (kSceneRows, moving geoms)
+                           pose=generate_pose_section(model, prog.nplan, qidx=(None if qidx is None else [int(x) for x in qidx])),
+                           # (an experiment, off by default: see generate_full_exact / mjpl_fused.h)
+                           exact_full=generate_full_exact(ip, fp, dp, info, opts) if (not generic and opts.f64) else None, opts=opts)
+    return key, src
 
 
 def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, force: bool = False,
@@ -1578,35 +1472,23 @@ def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_
     holds the robot, it serves every scene with it -- the static geoms come from the engine's scene table.
     prune_contacts: the engine option of that name the library is for (0: the program without its never-touch set, which
     an engine with the option off looks for -- A/B measurements)."""
-    ip, fp, dp, info = dump_program(model, allowed_collision_bodies, qidx, qpos_base, filter_tol)
-    if info.immediate or not info.filter_usable or (generic and not info.scene_ok):
+    made = library_source(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, generic, prune_contacts)
+    if made is None:
         return None
-    never_touch, _, never_hash, _ = dump_never_touch(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, prune_contacts=prune_contacts)
-    if prune_contacts == 1 and never_hash != int(info.hash):
-        raise RuntimeError("dump_never_touch and dump_program disagree on the program hash")
-    info.hash = never_hash
+    key, src = made
     os.makedirs(SPEC_DIR, exist_ok=True)
-    key = info.robot_hash if generic else info.hash
     target = output or spec_path(key, generic)  # (output, extra_flags: timing-only variants, tools/time_variants.sh)
-    deps = [os.path.join(_build.CSRC, f) for f in _build.STAMPED_HEADERS] + [__file__, os.path.join(os.path.dirname(__file__), "fold.py")]
+    deps = [os.path.join(_build.CSRC, f) for f in _build.STAMPED_HEADERS] + list(GENERATOR_SOURCES)
     if not force and os.path.exists(target) and all(os.path.getmtime(d) <= os.path.getmtime(target) for d in deps):
         return target
-    nstage = 0
-    if generic:
-        pc = int(ip[H_OFF_BODYOPS])
-        for _ in range(int(ip[H_NBODYOPS])):
-            nj, ng = int(ip[pc + B_NJNT]), int(ip[pc + B_NGEOM])
-            pc += B_SIZE + nj * J_SIZE + ng * (G_SIZE + MAX_SLOTS)
-            nstage += ng
-    src = translation_unit(generate(ip, fp, dp, info, generic=generic, never_touch=never_touch), generate_exact(ip, dp, info, generic=generic), key, info,
-                           (SCENE_ROWS << 8 | nstage) if generic else 0,  # (kSceneRows, moving geoms)
-                           pose=generate_pose_section(model, int(ip[H_NPLAN]), qidx=(None if qidx is None else [int(x) for x in qidx])),
-                           # (an experiment, off by default: see generate_full_exact / mjpl_fused.h)
-                           exact_full=generate_full_exact(ip, fp, dp, info) if (not generic and os.environ.get("MJPL_SPEC_F64") == "1") else None)
+    return _compile(src, os.path.join(SPEC_DIR, f"spec{'g' if generic else ''}_{key:016x}.hip"), target, keep_source, extra_flags)
+
+
+def _compile(src: str, src_path: str, target: str, keep_source: bool, extra_flags) -> str:
+    """The compile half of build(): `src` through hipcc into `target`; with keep_source the text stays as `src_path`."""
     # Source and library appear under their final names complete or not at all (os.replace): an engine created
     # while a rebuild is running finds the old library or the new one, never half a file -- a failed dlopen would
     # be remembered as "no library" for the life of that process -- and two builds of one hash cannot interleave.
-    src_path = os.path.join(SPEC_DIR, f"spec{'g' if generic else ''}_{key:016x}.hip")
     tag = f".tmp{os.getpid()}_{threading.get_ident():x}"
     src_tmp = src_path[:-4] + tag + ".hip"
     lib_tmp = target + tag
