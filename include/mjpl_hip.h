@@ -389,6 +389,68 @@ int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *desc, const double *Q, i
 int mjpl_push_out_dev(mjpl_engine *e, const mjpl_push_desc *desc, const double *dQ, int64_t N, int32_t layout,
                       double *dQ_out, double *dclear, int32_t *dpair, int32_t *diters, int32_t *dstatus);
 
+/* ---- trajectories: time-optimal parameterisation of a batch of paths -----------------------
+ * A path is n >= 2 waypoints of nq columns (1..16); B paths are packed one after another in W, path b
+ * being rows wp_off[b] .. wp_off[b+1] - 1 (wp_off[0] = 0).  mjpl_topp_profile finds, per path, the fastest
+ * motion along the natural cubic spline through its waypoints under per-column limits
+ * vmin < 0 < vmax on velocity and amin < 0 < amax on acceleration (mjpl_topp_desc: HOST arrays of nq
+ * entries, in both forms of the calls; grid >= 2 intervals per waypoint segment, 8 is a good default).
+ * The engine gives its device, stream and staging slots; its model plays no part.
+ *
+ * Per path (tests/trajectory_reference.py states every operation; DESIGN.md section 5.12 derives it):
+ *   1. M[n][nq], the knot second derivatives of the natural spline at the knots s_k = k / (n-1)
+ *      (zero at both ends), by the Thomas recurrence per column.
+ *   2. A grid of N = (n-1) * grid intervals of width D = 1/N; a_i = q'(s_i), b_i = q''(s_i).
+ *   3. x_i = sdot^2 at grid point i, x_0 = x_N = 0; u_i = sddot on interval i, x_{i+1} = x_i + 2 D u_i.
+ *   4. Interval i: x_i <= min_j (v*_j / a_ij)^2 (v* = vmax where a_ij > 0, vmin where < 0); and per column at
+ *      BOTH ends of the interval amin_j <= a_ij u + b_ij x_i <= amax_j and
+ *      amin_j <= (a_{i+1,j} + 2 D b_{i+1,j}) u + b_{i+1,j} x_i <= amax_j (the second is the acceleration at
+ *      the right end with x_{i+1} written out); and 0 <= x_i + 2 D u <= K_{i+1}.  All are lines in (u, x).
+ *   5. Backward: K_N = 0, K_i = the largest x_i for which some u satisfies all of 4 = max(0, the least
+ *      intersection of a lower with an upper line), in closed form.
+ *   6. Forward: u_i = the largest u the upper lines allow at x_i, x_{i+1} = clamp(x_i + 2 D u_i, 0, K_{i+1});
+ *      then u_i = (x_{i+1} - x_i) / 2D.
+ *   7. t_0 = 0, t_{i+1} = t_i + 2 D / (sqrt x_i + sqrt x_{i+1}).
+ * Outputs: M like W; x, u, t packed at g_off[b] = grid (wp_off[b] - b) + b with N_b + 1 entries per path,
+ * u's last entry 0, t's last entry the duration.  status[b]:
+ *   MJPL_TOPP_OK         otherwise.  A single interior x_i = 0 is a stop, and OK.
+ *   MJPL_TOPP_STALLED    two consecutive x_i are 0: that interval takes for ever (t holds inf from there).
+ *   MJPL_TOPP_NONFINITE  a waypoint of the path holds NaN / inf: its M, x, u, t are NaN -- or a result is
+ *                        not finite.  Other paths of the batch are not affected.
+ * Two consecutive equal waypoints are not refused here (the Python binding raises ValueError).
+ *
+ * mjpl_topp_sample evaluates the motion: path b gets samp_off[b+1] - samp_off[b] samples (samp_off[0] = 0,
+ * non-decreasing), sample k = 1, 2, ... at t_k = min(k dt, duration).  The caller sizes them: m =
+ * ceil((duration - 1e-8) / dt) puts the last sample at the duration itself, where the position is the last
+ * waypoint and the velocity 0.  In the interval t_i <= t_k <= t_{i+1}, tau = t_k - t_i:
+ *   sdot = sqrt x_i + u_i tau,  s = s_i + sqrt x_i tau + u_i tau^2 / 2,
+ *   pos = q(s),  vel = q'(s) sdot,  acc = q''(s) sdot^2 + q'(s) u_i,     each [samp_off[B]][nq].
+ * Sampling a path that is not OK reads NaN / inf times and gives meaningless rows, never a fault.
+ *
+ * wp_off and samp_off are HOST arrays in both forms.  MJPL_E_ARG: a NULL pointer, grid < 2, a path with
+ * fewer than 2 waypoints or offsets that fall, a limit of the wrong sign, infinite or NaN, dt <= 0 or
+ * NaN.  MJPL_E_CAPACITY: nq outside 1..16, a path of more than 2^24 grid points.  B = 0 (and a sample call
+ * without samples) launches nothing.  All outputs are deterministic and depend on no option and no MJPL_*
+ * variable.  The host forms synchronise.  The device forms synchronise the engine's stream once on entry
+ * (before the offset tables of an earlier call are replaced) and return with their launches enqueued. */
+#define MJPL_TOPP_OK         0
+#define MJPL_TOPP_STALLED    1
+#define MJPL_TOPP_NONFINITE  2
+typedef struct {
+  int32_t nq, grid;
+  const double *vmin, *vmax, *amin, *amax; /* host, [nq], both forms */
+} mjpl_topp_desc;
+int mjpl_topp_profile(mjpl_engine *e, const mjpl_topp_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                      double *M, double *x, double *u, double *t, int32_t *status);
+int mjpl_topp_profile_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const double *dW, const int64_t *wp_off,
+                          int64_t B, double *dM, double *dx, double *du, double *dt, int32_t *dstatus);
+int mjpl_topp_sample(mjpl_engine *e, const mjpl_topp_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                     const double *M, const double *x, const double *u, const double *t, double dt,
+                     const int64_t *samp_off, double *pos, double *vel, double *acc);
+int mjpl_topp_sample_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const double *dW, const int64_t *wp_off,
+                         int64_t B, const double *dM, const double *dx, const double *du, const double *dt_grid,
+                         double dt, const int64_t *samp_off, double *dpos, double *dvel, double *dacc);
+
 /* ---- certified edge checks: no contact anywhere along an edge ------------------------------
  * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
  * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md
@@ -568,6 +630,13 @@ int mjpl_time_edges_dev(mjpl_engine *e, const double *dQA, const double *dQB, in
                         float *ms, float *ms_first);
 int mjpl_time_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,
                           uint8_t *dvalid, int32_t iters, float *ms);
+/* iters times mjpl_topp_profile_dev then mjpl_topp_sample_dev on the same device batches, each between two
+ * events: ms_profile[k], ms_sample[k] = what call k took on the stream, the upload of its offset tables
+ * included.  samp_off must fit the durations the profile gives (size it from an earlier call). */
+int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const double *dW, const int64_t *wp_off, int64_t B,
+                       double *dM, double *dx, double *du, double *dt_grid, int32_t *dstatus, double dt,
+                       const int64_t *samp_off, double *dpos, double *dvel, double *dacc, int32_t iters,
+                       float *ms_profile, float *ms_sample);
 
 /* ---- misc ------------------------------------------------------------------------ */
 

@@ -37,6 +37,7 @@
 #include "mjpl_distance_grad.h"
 #include "mjpl_push.h"
 #include "mjpl_sweep.h"
+#include "mjpl_topp.h"
 
 namespace {
 
@@ -515,6 +516,13 @@ struct mjpl_engine {
   DevBuf<double> d_sweep_rows[2], d_sweep_hd[2], d_sweep_f64;
   DevBuf<int> d_sweep_meta[2], d_sweep_i32;
   DevBuf<unsigned long long> d_sweep_key;
+  // mjpl_topp_* (mjpl_topp.h): the call's offset tables [wp_off | samp_off] and limits [vmin | vmax | amin | amax] on
+  // the host (what the uploads read: rewritten only after the stream has drained) and on the device; c' of the Thomas
+  // recurrence, grown to the longest path seen; the workspace of a chunk of paths (all grow-only)
+  std::vector<int64_t> topp_off_h;
+  std::vector<double> topp_lim_h, topp_cp_h;
+  DevBuf<int64_t> d_topp_off;
+  DevBuf<double> d_topp_lim, d_topp_cp, d_topp_ws;
 };
 
 namespace {
@@ -2854,6 +2862,134 @@ int launch_push(mjpl_engine *e, const mjpl_push_desc &d, const double *dQ, int64
 
 }  // namespace
 
+// ---- time-optimal path parameterisation (mjpl_topp.h)
+namespace {
+
+constexpr size_t kToppChunkBytes = (size_t)512 << 20;  // workspace of one chunk of paths (one path may exceed it)
+
+// first grid point of path b (the host's topp_g_off)
+int64_t topp_g_off_h(const int64_t *wp_off, int G, int64_t b) { return (int64_t)G * (wp_off[b] - b) + b; }
+
+// Argument checks shared by mjpl_topp_profile* and mjpl_topp_sample*: the descriptor, the offsets, non-null batches.
+int check_topp_args(const mjpl_engine *e, const mjpl_topp_desc *d, const void *W, const int64_t *wp_off, int64_t B,
+                    std::initializer_list<const void *> bufs) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (!d) return fail(MJPL_E_ARG, "mjpl_topp: NULL descriptor");
+  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_topp: batch size %lld out of range", (long long)B);
+  if (d->nq < 1 || d->nq > kToppMaxCols) return fail(MJPL_E_CAPACITY, "mjpl_topp: %d columns (1..%d supported)", d->nq, kToppMaxCols);
+  if (d->grid < 2 || d->grid > (1 << 16)) return fail(MJPL_E_ARG, "grid must be 2..65536 intervals per segment, got %d", d->grid);
+  if (!d->vmin || !d->vmax || !d->amin || !d->amax) return fail(MJPL_E_ARG, "mjpl_topp: NULL limit array");
+  for (int j = 0; j < d->nq; j++) {
+    if (!(d->vmin[j] < 0 && d->vmax[j] > 0 && d->vmin[j] > -INFINITY && d->vmax[j] < INFINITY))
+      return fail(MJPL_E_ARG, "velocity limits of column %d: [%g, %g] (finite vmin < 0 < vmax wanted, NaN is refused)", j, d->vmin[j], d->vmax[j]);
+    if (!(d->amin[j] < 0 && d->amax[j] > 0 && d->amin[j] > -INFINITY && d->amax[j] < INFINITY))
+      return fail(MJPL_E_ARG, "acceleration limits of column %d: [%g, %g] (finite amin < 0 < amax wanted, NaN is refused)", j, d->amin[j], d->amax[j]);
+  }
+  if (B == 0) return MJPL_OK;
+  if (!wp_off) return fail(MJPL_E_ARG, "mjpl_topp: NULL offsets");
+  if (wp_off[0] != 0) return fail(MJPL_E_ARG, "wp_off[0] must be 0, got %lld", (long long)wp_off[0]);
+  for (int64_t b = 0; b < B; b++) {
+    const int64_t n = wp_off[b + 1] - wp_off[b];
+    if (n < 2) return fail(MJPL_E_ARG, "path %lld has %lld waypoints (offsets must rise by at least 2)", (long long)b, (long long)n);
+    if (n > (1 << 24) / d->grid) return fail(MJPL_E_CAPACITY, "path %lld: %lld waypoints at grid %d exceed 2^24 grid points", (long long)b, (long long)n, d->grid);
+  }
+  if (!W) return fail(MJPL_E_ARG, "NULL batch pointer");
+  for (const void *o : bufs)
+    if (!o) return fail(MJPL_E_ARG, "NULL batch pointer");
+  return MJPL_OK;
+}
+
+// The call's tables on the device: [wp_off | samp_off] and the limits.  The stream is drained first: an earlier call's
+// launches read the same buffers.
+int topp_upload(mjpl_engine *e, const mjpl_topp_desc &d, const int64_t *wp_off, const int64_t *samp_off, int64_t B) {
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t nb = (size_t)B + 1, nd = d.nq;
+  e->topp_off_h.assign(2 * nb, 0);
+  std::copy(wp_off, wp_off + nb, e->topp_off_h.begin());
+  if (samp_off) std::copy(samp_off, samp_off + nb, e->topp_off_h.begin() + nb);
+  e->topp_lim_h.resize(4 * nd);
+  for (size_t j = 0; j < nd; j++) {
+    e->topp_lim_h[j] = d.vmin[j];
+    e->topp_lim_h[nd + j] = d.vmax[j];
+    e->topp_lim_h[2 * nd + j] = d.amin[j];
+    e->topp_lim_h[3 * nd + j] = d.amax[j];
+  }
+  MJPL_TRY(e->d_topp_off.reserve(2 * nb, 1024));
+  MJPL_TRY(e->d_topp_lim.reserve(4 * kToppMaxCols));
+  HIP_TRY(hipMemcpyAsync(e->d_topp_off.p, e->topp_off_h.data(), 2 * nb * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_topp_lim.p, e->topp_lim_h.data(), 4 * nd * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  return MJPL_OK;
+}
+
+// mjpl_topp_profile* on device batches (wp_off on the host): the spline of every path in one launch, then per chunk of
+// paths whose workspace fits kToppChunkBytes the two grid kernels and the sweeps.
+int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                        double *dx, double *du, double *dt, int32_t *dstatus) {
+  MJPL_TRY(topp_upload(e, d, wp_off, nullptr, B));
+  const hipStream_t st = e->stream;
+  int64_t nmax = 0;
+  for (int64_t b = 0; b < B; b++) nmax = std::max(nmax, wp_off[b + 1] - wp_off[b]);
+  if ((size_t)nmax > e->topp_cp_h.size()) {  // c'[0] = 0, c'[k] = 1 / (4 - c'[k-1])
+    e->topp_cp_h.assign(std::max<size_t>(nmax, 1024), 0.0);
+    for (size_t k = 1; k < e->topp_cp_h.size(); k++) e->topp_cp_h[k] = 1.0 / (4.0 - e->topp_cp_h[k - 1]);
+    MJPL_TRY(e->d_topp_cp.reserve(e->topp_cp_h.size()));
+    HIP_TRY(hipMemcpyAsync(e->d_topp_cp.p, e->topp_cp_h.data(), e->topp_cp_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  ToppBatch a = {};
+  a.W = dW; a.wp_off = e->d_topp_off.p; a.B = (int)B; a.d = d.nq; a.G = d.grid;
+  a.lim = e->d_topp_lim.p; a.cp = e->d_topp_cp.p; a.M = dM;
+  a.x = dx; a.u = du; a.t = dt; a.status = dstatus;
+  hipLaunchKernelGGL(k_topp_spline, dim3((unsigned)((B * d.nq + 255) / 256)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  const size_t rows = 2 * (size_t)d.nq, per_pt = (5 * rows + 1) * sizeof(double);
+  for (int64_t b0 = 0; b0 < B;) {
+    const int64_t g0 = topp_g_off_h(wp_off, d.grid, b0);
+    int64_t b1 = b0 + 1;
+    while (b1 < B && (size_t)(topp_g_off_h(wp_off, d.grid, b1 + 1) - g0) * per_pt <= kToppChunkBytes) b1++;
+    const int64_t pts = topp_g_off_h(wp_off, d.grid, b1) - g0;
+    MJPL_TRY(e->d_topp_ws.reserve((size_t)pts * (5 * rows + 1)));
+    const size_t span = (size_t)pts * rows;
+    a.b0 = (int)b0; a.b1 = (int)b1; a.g0 = g0; a.pts = pts;
+    a.wP = e->d_topp_ws.p; a.wrho = a.wP + span; a.wpp = a.wrho + span; a.wg = a.wpp + span; a.ws = a.wg + span;
+    a.wK = a.ws + span;
+    const dim3 grid((unsigned)((span + 255) / 256));
+    hipLaunchKernelGGL(k_topp_lines, grid, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_topp_pairs, grid, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_topp_sweep, dim3((unsigned)((b1 - b0 + kToppSweepWaves - 1) / kToppSweepWaves)), dim3(64 * kToppSweepWaves), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    b0 = b1;
+  }
+  return MJPL_OK;
+}
+
+int check_topp_sample_args(const mjpl_topp_desc *d, const int64_t *wp_off, int64_t B, double dt, const int64_t *samp_off) {
+  if (!(dt > 0) || !(dt < INFINITY)) return fail(MJPL_E_ARG, "dt must be > 0 and finite (NaN is refused), got %g", dt);
+  if (B == 0) return MJPL_OK;
+  if (!samp_off) return fail(MJPL_E_ARG, "mjpl_topp_sample: NULL offsets");
+  if (samp_off[0] != 0) return fail(MJPL_E_ARG, "samp_off[0] must be 0, got %lld", (long long)samp_off[0]);
+  for (int64_t b = 0; b < B; b++)
+    if (samp_off[b + 1] < samp_off[b]) return fail(MJPL_E_ARG, "samp_off falls at path %lld", (long long)b);
+  return MJPL_OK;
+}
+
+int launch_topp_sample(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B,
+                       const double *dM, const double *dx, const double *du, const double *dt_grid, double dt,
+                       const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
+  MJPL_TRY(topp_upload(e, d, wp_off, samp_off, B));
+  ToppSamples a = {};
+  a.W = dW; a.M = dM; a.x = dx; a.u = du; a.t = dt_grid;
+  a.wp_off = e->d_topp_off.p; a.samp_off = e->d_topp_off.p + (B + 1);
+  a.B = (int)B; a.d = d.nq; a.G = d.grid; a.dt = dt;
+  a.pos = dpos; a.vel = dvel; a.acc = dacc;
+  hipLaunchKernelGGL(k_topp_sample, dim3((unsigned)((samp_off[B] + 255) / 256)), dim3(256), 0, e->stream, a);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+}  // namespace
+
 // ---- certified edge checks (mjpl_sweep.h)
 namespace {
 
@@ -3239,6 +3375,55 @@ int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *d, const double *Q, int6
   });
 }
 
+// ---- time-optimal path parameterisation (mjpl_topp.h)
+
+int mjpl_topp_profile_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                          double *dx, double *du, double *dt, int32_t *dstatus) {
+  int rc = check_topp_args(e, d, dW, wp_off, B, {dM, dx, du, dt, dstatus});
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_topp_profile(e, *d, dW, wp_off, B, dM, dx, du, dt, dstatus);
+}
+
+int mjpl_topp_profile(mjpl_engine *e, const mjpl_topp_desc *d, const double *W, const int64_t *wp_off, int64_t B, double *M,
+                      double *x, double *u, double *t, int32_t *status) {
+  int rc = check_topp_args(e, d, W, wp_off, B, {M, x, u, t, status});
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
+  const HostOut outs[] = {{M, wb}, {x, gb}, {u, gb}, {t, gb}, {status, (size_t)B * sizeof(int32_t)}};
+  return staged(e, false, {{W, wb}}, outs, [&](void **in, void **out) {
+    return launch_topp_profile(e, *d, (const double *)in[0], wp_off, B, (double *)out[0], (double *)out[1], (double *)out[2],
+                               (double *)out[3], (int32_t *)out[4]);
+  });
+}
+
+int mjpl_topp_sample_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW, const int64_t *wp_off, int64_t B,
+                         const double *dM, const double *dx, const double *du, const double *dt_grid, double dt,
+                         const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
+  int rc = check_topp_args(e, d, dW, wp_off, B, {dM, dx, du, dt_grid});
+  if (rc == MJPL_OK) rc = check_topp_sample_args(d, wp_off, B, dt, samp_off);
+  if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
+  if (!dpos || !dvel || !dacc) return fail(MJPL_E_ARG, "NULL output pointer");
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_topp_sample(e, *d, dW, wp_off, B, dM, dx, du, dt_grid, dt, samp_off, dpos, dvel, dacc);
+}
+
+int mjpl_topp_sample(mjpl_engine *e, const mjpl_topp_desc *d, const double *W, const int64_t *wp_off, int64_t B, const double *M,
+                     const double *x, const double *u, const double *t, double dt, const int64_t *samp_off, double *pos,
+                     double *vel, double *acc) {
+  int rc = check_topp_args(e, d, W, wp_off, B, {M, x, u, t});
+  if (rc == MJPL_OK) rc = check_topp_sample_args(d, wp_off, B, dt, samp_off);
+  if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
+  if (!pos || !vel || !acc) return fail(MJPL_E_ARG, "NULL output pointer");
+  const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
+  const size_t sb = (size_t)samp_off[B] * d->nq * db;
+  return staged(e, false, {{W, wb}, {M, wb}, {x, gb}, {u, gb}, {t, gb}}, {{pos, sb}, {vel, sb}, {acc, sb}}, [&](void **in, void **out) {
+    return launch_topp_sample(e, *d, (const double *)in[0], wp_off, B, (const double *)in[1], (const double *)in[2],
+                              (const double *)in[3], (const double *)in[4], dt, samp_off, (double *)out[0], (double *)out[1],
+                              (double *)out[2]);
+  });
+}
+
 // ---- certified edge checks (mjpl_sweep.h)
 
 int mjpl_sweep_bounds(mjpl_engine *e, const double *lo, const double *hi) {
@@ -3408,6 +3593,30 @@ int mjpl_time_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t l
   }
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (int k = 0; k < iters && rc == MJPL_OK; k++) HIP_TRY(hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]));
+  for (auto &x : ev) (void)hipEventDestroy(x);
+  return rc;
+}
+
+int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                       double *dx, double *du, double *dt_grid, int32_t *dstatus, double dt, const int64_t *samp_off, double *dpos,
+                       double *dvel, double *dacc, int32_t iters, float *ms_profile, float *ms_sample) {
+  if (!e || iters < 0 || (iters > 0 && (!ms_profile || !ms_sample))) return fail(MJPL_E_ARG, "mjpl_time_topp_dev: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<hipEvent_t> ev(3 * (size_t)iters);
+  for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+  int rc = MJPL_OK;
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) {
+    HIP_TRY(hipEventRecord(ev[3 * k], e->stream));
+    rc = mjpl_topp_profile_dev(e, d, dW, wp_off, B, dM, dx, du, dt_grid, dstatus);
+    HIP_TRY(hipEventRecord(ev[3 * k + 1], e->stream));
+    if (rc == MJPL_OK) rc = mjpl_topp_sample_dev(e, d, dW, wp_off, B, dM, dx, du, dt_grid, dt, samp_off, dpos, dvel, dacc);
+    HIP_TRY(hipEventRecord(ev[3 * k + 2], e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) {
+    HIP_TRY(hipEventElapsedTime(&ms_profile[k], ev[3 * k], ev[3 * k + 1]));
+    HIP_TRY(hipEventElapsedTime(&ms_sample[k], ev[3 * k + 1], ev[3 * k + 2]));
+  }
   for (auto &x : ev) (void)hipEventDestroy(x);
   return rc;
 }

@@ -22,12 +22,15 @@ GRAD_OK, GRAD_FLAT, GRAD_DEGENERATE, GRAD_NONFINITE = 0, 1, 2, 3
 PUSH_OK, PUSH_STUCK, PUSH_DEGENERATE, PUSH_NONFINITE = 0, 1, 2, 3
 # mjpl_sweep_edges* status values (include/mjpl_hip.h: MJPL_SWEEP_*)
 SWEEP_FREE, SWEEP_HIT, SWEEP_UNDECIDED, SWEEP_NONFINITE, SWEEP_RANGE = 0, 1, 2, 3, 4
+# mjpl_topp_profile* status values (include/mjpl_hip.h: MJPL_TOPP_*)
+TOPP_OK, TOPP_STALLED, TOPP_NONFINITE = 0, 1, 2
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
 _F64P = C.POINTER(C.c_double)
 _U8P = C.POINTER(C.c_uint8)
 _U64P = C.POINTER(C.c_uint64)
+_I64P = C.POINTER(C.c_int64)
 
 
 class MjplError(RuntimeError):
@@ -95,6 +98,10 @@ class PushDesc(C.Structure):
     ]
 
 
+class ToppDesc(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("grid", C.c_int32), ("vmin", _F64P), ("vmax", _F64P), ("amin", _F64P), ("amax", _F64P)]
+
+
 class SweepDesc(C.Structure):
     _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
 
@@ -153,6 +160,12 @@ ABI = {
                                       _VP]),
     "mjpl_push_out": (C.c_int, [_VP, C.POINTER(PushDesc), _F64P, C.c_int64, C.c_int32, _F64P, _F64P, _I32P, _I32P, _I32P]),
     "mjpl_push_out_dev": (C.c_int, [_VP, C.POINTER(PushDesc), _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_topp_profile": (C.c_int, [_VP, C.POINTER(ToppDesc), _F64P, _I64P, C.c_int64, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "mjpl_topp_profile_dev": (C.c_int, [_VP, C.POINTER(ToppDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_topp_sample": (C.c_int, [_VP, C.POINTER(ToppDesc), _F64P, _I64P, C.c_int64, _F64P, _F64P, _F64P, _F64P, C.c_double,
+                                   _I64P, _F64P, _F64P, _F64P]),
+    "mjpl_topp_sample_dev": (C.c_int, [_VP, C.POINTER(ToppDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, C.c_double,
+                                       _I64P, _VP, _VP, _VP]),
     "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
                                     C.c_int64]),
     "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
@@ -177,6 +190,8 @@ ABI = {
                                              C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32P]),
     "mjpl_time_configs_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32,
                                         C.POINTER(C.c_float)]),
+    "mjpl_time_topp_dev": (C.c_int, [_VP, C.POINTER(ToppDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_double, _I64P,
+                                     _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mjpl_pose_create": (C.c_int, [_VP, C.POINTER(PoseDesc), C.POINTER(_VP)]),
     "mjpl_pose_destroy": (None, [_VP]),
     "mjpl_pose_spec_loaded": (C.c_int, [_VP]),
@@ -729,6 +744,99 @@ class Engine:
         iterations: the call returns once the last launches are enqueued, not before the loop has run."""
         desc, keep = self.push_desc(d_min, **params)
         self._ok(self.lib.mjpl_push_out_dev(self.h, C.byref(desc), dQ, n, layout, dQ_out, dclear, dpair, diters, dstatus))
+        del keep
+
+    # -- trajectories: time-optimal parameterisation of a batch of paths (include/mjpl_hip.h, mjpl_topp_*)
+    @staticmethod
+    def topp_desc(nq, grid, vmin, vmax, amin, amax):
+        """The mjpl_topp_desc of a call and the arrays it points into (keep both alive for the call)."""
+        keep = []
+        for v in (vmin, vmax, amin, amax):
+            v = _f64(v)
+            if v.shape != (nq,):
+                raise ValueError(f"limits must have {nq} entries, got {v.shape}")
+            keep.append(v)
+        return ToppDesc(int(nq), int(grid), *(v.ctypes.data_as(_F64P) for v in keep)), keep
+
+    @staticmethod
+    def topp_offsets(wp_off, grid):
+        """(wp_off int64 [B+1], g_off int64 [B+1]): where path b's x, u and t start, grid (wp_off[b] - b) + b."""
+        wp_off = np.ascontiguousarray(wp_off, dtype=np.int64)
+        return wp_off, int(grid) * (wp_off - np.arange(len(wp_off))) + np.arange(len(wp_off))
+
+    def topp_profile(self, W, wp_off, vmin, vmax, amin, amax, grid=8):
+        """(M like W, x, u, t float64 [g_off[B]], status int32 [B]) of the B paths packed in W [wp_off[B], nq] (path b:
+        rows wp_off[b] .. wp_off[b+1] - 1): knot second derivatives of the natural spline, sdot^2 at the grid points,
+        sddot on the intervals, the time of every grid point (last entry of a path: its duration); status TOPP_OK /
+        TOPP_STALLED / TOPP_NONFINITE.  Path b's entries start at topp_offsets(wp_off, grid)[1][b]."""
+        W = _f64(W)
+        if W.ndim != 2:
+            raise ValueError(f"W must be [rows, nq], got {W.shape}")
+        wp_off, g_off = self.topp_offsets(wp_off, grid)
+        B = len(wp_off) - 1
+        if B >= 0 and len(wp_off) and wp_off[-1] != len(W):
+            raise ValueError(f"wp_off ends at {wp_off[-1]}, W has {len(W)} rows")
+        desc, keep = self.topp_desc(W.shape[1], grid, vmin, vmax, amin, amax)
+        ng = max(int(g_off[-1]), 0) if B > 0 else 0
+        M = np.zeros_like(W)
+        x, u, t = (np.zeros(ng, np.float64) for _ in range(3))
+        status = np.zeros(max(B, 0), np.int32)
+        self._ok(self.lib.mjpl_topp_profile(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                            M.ctypes.data_as(_F64P), x.ctypes.data_as(_F64P), u.ctypes.data_as(_F64P),
+                                            t.ctypes.data_as(_F64P), status.ctypes.data_as(_I32P)))
+        del keep
+        return M, x, u, t, status
+
+    def topp_profile_dev(self, dW, wp_off, nq, vmin, vmax, amin, amax, grid, dM, dx, du, dt, dstatus):
+        """topp_profile() on device pointers (wp_off and the limits stay host arrays)."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        desc, keep = self.topp_desc(nq, grid, vmin, vmax, amin, amax)
+        self._ok(self.lib.mjpl_topp_profile_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dx,
+                                                du, dt, dstatus))
+        del keep
+
+    def topp_sample(self, W, wp_off, M, x, u, t, dt, samp_off, vmin, vmax, amin, amax, grid=8):
+        """(pos, vel, acc float64 [samp_off[B], nq]): path b sampled at min(k dt, duration), k = 1 .. samp_off[b+1] -
+        samp_off[b], from the outputs of topp_profile()."""
+        W, M = _f64(W), _f64(M)
+        x, u, t = _f64(x), _f64(u), _f64(t)
+        wp_off, g_off = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        B = len(wp_off) - 1
+        if len(samp_off) != len(wp_off):
+            raise ValueError("samp_off and wp_off must have the same length")
+        if W.ndim != 2 or M.shape != W.shape or wp_off[-1] != len(W) or not (len(x) == len(u) == len(t) == max(int(g_off[-1]), 0)):
+            raise ValueError("W, M, x, u, t do not have the sizes wp_off gives them")
+        desc, keep = self.topp_desc(W.shape[1], grid, vmin, vmax, amin, amax)
+        ns = max(int(samp_off[-1]), 0)
+        pos, vel, acc = (np.zeros((ns, W.shape[1]), np.float64) for _ in range(3))
+        self._ok(self.lib.mjpl_topp_sample(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                           M.ctypes.data_as(_F64P), x.ctypes.data_as(_F64P), u.ctypes.data_as(_F64P),
+                                           t.ctypes.data_as(_F64P), float(dt), samp_off.ctypes.data_as(_I64P),
+                                           pos.ctypes.data_as(_F64P), vel.ctypes.data_as(_F64P), acc.ctypes.data_as(_F64P)))
+        del keep
+        return pos, vel, acc
+
+    def time_topp_dev(self, dW, wp_off, nq, dM, dx, du, dt_grid, dstatus, dt, samp_off, vmin, vmax, amin, amax, grid, dpos, dvel,
+                      dacc, iters):
+        """(ms_profile, ms_sample) float32 [iters]: device-event times of `iters` topp_profile_dev + topp_sample_dev calls."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        desc, keep = self.topp_desc(nq, grid, vmin, vmax, amin, amax)
+        mp, ms = np.zeros(iters, np.float32), np.zeros(iters, np.float32)
+        self._ok(self.lib.mjpl_time_topp_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dx, du,
+                                             dt_grid, dstatus, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc, iters,
+                                             mp.ctypes.data_as(C.POINTER(C.c_float)), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        del keep
+        return mp, ms
+
+    def topp_sample_dev(self, dW, wp_off, nq, dM, dx, du, dt_grid, dt, samp_off, vmin, vmax, amin, amax, grid, dpos, dvel, dacc):
+        """topp_sample() on device pointers (wp_off, samp_off and the limits stay host arrays)."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        desc, keep = self.topp_desc(nq, grid, vmin, vmax, amin, amax)
+        self._ok(self.lib.mjpl_topp_sample_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dx,
+                                               du, dt_grid, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc))
         del keep
 
     # -- certified edge checks: no contact anywhere along an edge (include/mjpl_hip.h, mjpl_sweep_*)

@@ -1,0 +1,235 @@
+"""The NumPy statement of the trajectory kernels (tests/trajectory_reference.py) against closed forms, scipy and its own
+constraints, and the host-side trajectory helpers (mjpl_amd/trajectory/utils.py).  No GPU."""
+import numpy as np
+import pytest
+
+import trajectory_reference as R
+from mjpl_amd.constraint import Constraint
+from mjpl_amd.trajectory import Trajectory, TrajectoryGenerator, generate_constrained_trajectories, generate_constrained_trajectory
+from mjpl_amd.trajectory.topp_trajectory import sample_count
+from mjpl_amd.trajectory.utils import _add_intermediate_waypoint, _waypoint_timing
+
+CASES = R.parity_cases()
+IDS = [c[0] for c in CASES]
+
+
+@pytest.mark.parametrize("n", [2, 3, 5, 17, 64])
+def test_spline_matches_scipy_natural(n):
+    from scipy.interpolate import CubicSpline
+    W = np.random.default_rng(n).uniform(-1, 1, (n, 3))
+    M = R.spline_second_derivatives(W)
+    ref = CubicSpline(np.linspace(0, 1, n), W, bc_type="natural")
+    s = np.linspace(0, 1, 257)
+    got = [np.array([R.spline_at(W, M, x)[k] for x in s]) for k in range(3)]
+    for k in range(3):
+        want = ref(s, k)
+        assert np.abs(got[k] - want).max() <= 1e-12 * max(1.0, np.abs(want).max()), k
+    assert np.abs(M - ref(np.linspace(0, 1, n), 2)).max() <= 1e-12 * max(1.0, np.abs(M).max())
+
+
+@pytest.mark.parametrize("vmax, G, T", [(10.0, 2, 2.0), (10.0, 16, 2.0), (0.5, 8, 2.5), (0.5, 16, 2.5)])
+def test_closed_forms(vmax, G, T):
+    # 0 -> 1 with amax 1: triangular 2 sqrt(L / a), trapezoid L / v + v / a; the switch points fall on grid points
+    p = R.profile([[0.0], [1.0]], [-vmax], [vmax], [-1.0], [1.0], G)
+    assert p["status"] == R.OK
+    assert abs(p["t"][-1] - T) <= 1e-12
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=IDS)
+def test_statement_keeps_the_limits(k):
+    _, W, vmin, vmax, amin, amax = CASES[k]
+    p = R.parity_profile(k)
+    x, u, a, b = p["x"], p["u"], p["a"], p["b"]
+    N = len(x) - 1
+    assert p["status"] == R.OK
+    assert x[0] == 0 and x[N] == 0
+    assert np.abs(x[:-1] + (2.0 * (1.0 / N)) * u[:-1] - x[1:]).max() <= 4e-16 * x.max()  # x and u agree
+    vel = a * np.sqrt(x)[:, None]
+    assert np.all(vel <= vmax * (1 + 1e-12)) and np.all(vel >= vmin * (1 + 1e-12))
+    for acc in (a[:-1] * u[:N, None] + b[:-1] * x[:-1, None], a[1:] * u[:N, None] + b[1:] * x[1:, None]):
+        assert np.all(acc <= amax * (1 + 1e-12)) and np.all(acc >= amin * (1 + 1e-12))
+    pos, vel, _ = R.sample(W, p, 0.01)
+    assert len(pos) == R.sample_count(p["t"][-1], 0.01)
+    assert np.abs(pos[-1] - W[-1]).max() <= 1e-12
+    assert np.abs(vel[-1]).max() <= 1e-12
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=IDS)
+def test_conditioning_guard(k):
+    """A parity case must be one whose numbers rounding cannot move: float64 and longdouble agree to 1e-11 and no
+    interior x comes near 0 (where T depends on the square root of a rounding-level number)."""
+    p = R.parity_profile(k)
+    x, N = p["x"], len(p["x"]) - 1
+    assert x[1:N].min() >= 1e-6 * x.max()
+    if np.finfo(np.longdouble).eps >= np.finfo(np.float64).eps:
+        pytest.skip("np.longdouble is no wider than float64 on this machine")
+    _, W, vmin, vmax, amin, amax = CASES[k]
+    pl = R.profile(W, vmin, vmax, amin, amax, R.PARITY_GRID, np.longdouble)
+    assert abs(float(pl["t"][-1]) - p["t"][-1]) <= 1e-11 * p["t"][-1]
+    assert np.abs(pl["x"].astype(np.float64) - x).max() <= 1e-11 * x.max()
+
+
+def test_sample_count_rule():
+    p = R.profile([[0.0], [1.0]], [-10.0], [10.0], [-1.0], [1.0], 2)  # T = 2
+    assert p["t"][-1] == 2.0
+    assert R.sample_count(2.0, 0.25) == sample_count(2.0, 0.25) == 8
+    assert R.sample_count(2.0, 0.3) == sample_count(2.0, 0.3) == 7
+    assert R.sample_count(2.0, 3.0) == sample_count(2.0, 3.0) == 1
+    W = np.array([[0.0], [1.0]])
+    pos, vel, acc = R.sample(W, p, 0.3)
+    assert len(pos) == 7 and abs(pos[-1, 0] - 1.0) <= 1e-15 and abs(vel[-1, 0]) <= 1e-15
+    assert abs(pos[0, 0] - 0.5 * 0.3 ** 2) <= 1e-15 and abs(acc[0, 0] - 1.0) <= 1e-15
+
+
+def test_nonfinite_status():
+    p = R.profile([[0.0, 0.0], [np.nan, 1.0], [1.0, 2.0]], [-1, -1], [1, 1], [-1, -1], [1, 1], 4)
+    assert p["status"] == R.NONFINITE and np.all(np.isnan(p["x"]))
+
+
+# ---- the helpers of generate_constrained_trajectory, on the reference's own cases
+
+WAYPOINTS = [np.array([0.0, 0.0]), np.array([1.0, 1.0]), np.array([2.0, 1.0]), np.array([2.0, 0.0])]
+
+
+def spline_trajectory(waypoints, count=100):
+    W = np.array(waypoints, dtype=np.float64)
+    M = R.spline_second_derivatives(W)
+    dt = 1.0 / count
+    pos = [R.spline_at(W, M, (k + 1) * dt)[0] for k in range(count)]
+    zero = [np.zeros(W.shape[1])] * count
+    return Trajectory(dt, W[0], pos, zero, zero)
+
+
+def test_waypoint_timing():
+    traj = spline_trajectory(WAYPOINTS)
+    with pytest.raises(ValueError):
+        _waypoint_timing(WAYPOINTS[:1], traj)
+    timing = _waypoint_timing(WAYPOINTS, traj)
+    assert len(timing) == 4 and timing[0] == 0.0 and timing[-1] == 100 * traj.dt
+    P = np.stack(traj.positions)
+    for wp, ts in zip(WAYPOINTS[1:-1], timing[1:-1]):
+        assert ts == (np.argmin(((P - wp) ** 2).sum(axis=1)) + 1) * traj.dt
+    assert timing == sorted(timing)
+    assert _waypoint_timing(WAYPOINTS[:2], traj) == [0.0, 100 * traj.dt]
+
+
+def test_add_intermediate_waypoint():
+    traj = spline_trajectory(WAYPOINTS)
+    timing = _waypoint_timing(WAYPOINTS, traj)
+    with pytest.raises(ValueError):
+        _add_intermediate_waypoint(list(WAYPOINTS), timing[:-1], 0.5)
+    for outside in (-0.1, timing[-1] + 0.1):
+        wps = list(WAYPOINTS)
+        assert not _add_intermediate_waypoint(wps, timing, outside) and len(wps) == 4
+    # inside segment 1 -> its midpoint, after waypoint 1
+    wps = list(WAYPOINTS)
+    assert _add_intermediate_waypoint(wps, timing, 0.5 * (timing[1] + timing[2]))
+    assert len(wps) == 5 and np.array_equal(wps[2], [1.5, 1.0])
+    # a timestamp equal to an interior waypoint's time picks the earlier segment
+    wps = list(WAYPOINTS)
+    assert _add_intermediate_waypoint(wps, timing, timing[1])
+    assert len(wps) == 5 and np.array_equal(wps[1], [0.5, 0.5])
+
+
+class PolylineGenerator(TrajectoryGenerator):
+    """A fake: `per_segment` states per segment along a rounded polyline that overshoots every interior waypoint
+    outwards by `bulge` (a stand-in for a spline's overshoot), dt = 1."""
+
+    def __init__(self, per_segment=10, bulge=0.2):
+        self.per_segment, self.bulge, self.calls = per_segment, bulge, 0
+
+    def generate_trajectory(self, waypoints):
+        self.calls += 1
+        W = np.array(waypoints, dtype=np.float64)
+        pos = []
+        for i in range(len(W) - 1):
+            for k in range(1, self.per_segment + 1):
+                f = k / self.per_segment
+                q = W[i] + f * (W[i + 1] - W[i])
+                if i + 2 < len(W) and k < self.per_segment:  # lean out of the corner ahead, more the nearer it is
+                    out = 2 * W[i + 1] - W[i] - W[i + 2]
+                    if np.linalg.norm(out) > 0:  # (by a share of the segment's own length: shorter segments lean less)
+                        q = q + self.bulge * f * f * np.linalg.norm(W[i + 1] - W[i]) * out / np.linalg.norm(out)
+                pos.append(q)
+        zero = [np.zeros(W.shape[1])] * len(pos)
+        return Trajectory(1.0, W[0], pos, zero, zero)
+
+
+class BatchedPolylineGenerator(PolylineGenerator):
+    def generate_trajectories(self, paths):
+        self.batches = getattr(self, "batches", 0) + 1
+        return [PolylineGenerator.generate_trajectory(self, p) for p in paths]
+
+
+class Ceiling(Constraint):
+    """y <= top; a midpoint is repaired by clamping unless `repair` is off."""
+
+    def __init__(self, top, repair=True):
+        self.top, self.repair = top, repair
+
+    def valid_config(self, q):
+        return bool(q[1] <= self.top)
+
+    def apply(self, q_old, q):
+        if not self.repair:
+            return q if self.valid_config(q) else None
+        return np.array([q[0], min(q[1], self.top)])
+
+
+class BatchedCeiling(Ceiling):
+    def valid_configs(self, Q):
+        self.batch_calls = getattr(self, "batch_calls", 0) + 1
+        return np.asarray(Q)[:, 1] <= self.top
+
+
+ROOF = [np.array([0.0, 0.0]), np.array([1.0, 1.0]), np.array([2.0, 0.0])]
+
+
+def test_constrained_trajectory_inserts_in_the_violating_segment():
+    gen = PolylineGenerator()
+    first = gen.generate_trajectory(ROOF)
+    bad = [i for i, q in enumerate(first.positions) if q[1] > 1.05]
+    assert bad and bad[0] < 10  # the overshoot is in segment 0, before the corner
+    waypoints = list(ROOF)
+    traj = generate_constrained_trajectory(waypoints, gen, [Ceiling(1.05)], max_rounds=50)
+    assert traj is not None and all(q[1] <= 1.05 for q in traj.positions)
+    assert len(waypoints) == 3  # the caller's list is left alone
+    assert len(traj.positions) > len(first.positions)  # waypoints were added
+    # one round adds the midpoint of segment 0
+    one = PolylineGenerator()
+    assert generate_constrained_trajectory(list(ROOF), one, [Ceiling(1.05)], max_rounds=1) is None and one.calls == 1
+    t2 = _waypoint_timing(ROOF, first)
+    wps = list(ROOF)
+    assert _add_intermediate_waypoint(wps, t2, (bad[0] + 1) * first.dt, [Ceiling(1.05)])
+    assert np.array_equal(wps[1], [0.5, 0.5])
+
+
+def test_constrained_trajectory_none_when_midpoint_cannot_be_repaired():
+    # the midpoint of segment 0 itself violates y <= 0.4 and the constraint does not repair
+    assert generate_constrained_trajectory(list(ROOF), PolylineGenerator(), [Ceiling(0.4, repair=False)], max_rounds=50) is None
+
+
+def test_constrained_trajectory_max_rounds():
+    gen = PolylineGenerator()
+    full = generate_constrained_trajectory(list(ROOF), gen, [Ceiling(1.05)], max_rounds=50)
+    need = gen.calls
+    assert full is not None and need >= 2
+    short = PolylineGenerator()
+    assert generate_constrained_trajectory(list(ROOF), short, [Ceiling(1.05)], max_rounds=need - 1) is None
+    assert short.calls == need - 1
+    exact = PolylineGenerator()
+    assert generate_constrained_trajectory(list(ROOF), exact, [Ceiling(1.05)], max_rounds=need) is not None
+
+
+def test_constrained_trajectories_batched_equals_scalar():
+    paths = [list(ROOF), [np.array([0.0, 0.0]), np.array([2.0, 0.5])], [w * np.array([1.0, 0.9]) + 0.05 for w in ROOF],
+             [np.array([0.0, 0.0]), np.array([1.0, 1.3]), np.array([2.0, 0.0])]]
+    want = [generate_constrained_trajectory(list(p), PolylineGenerator(), [Ceiling(1.05)], max_rounds=50) for p in paths]
+    gen, con = BatchedPolylineGenerator(), BatchedCeiling(1.05)
+    got = generate_constrained_trajectories(paths, gen, [con], max_rounds=50)
+    assert con.batch_calls == gen.batches  # one validation per round, whatever the number of open paths
+    assert [w is None for w in want] == [g is None for g in got]
+    assert any(w is not None for w in want)
+    for w, g in zip(want, got):
+        if w is not None:
+            assert np.array_equal(np.stack(w.positions), np.stack(g.positions))
