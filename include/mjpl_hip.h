@@ -524,6 +524,50 @@ int mjpl_sweep_edges_dev(mjpl_engine *e, const mjpl_sweep_desc *desc, const doub
                          int64_t E, int32_t layout, int32_t *dstatus, double *dt_hit, double *dclear_lb,
                          int32_t *dpair, int32_t *dnodes, int32_t *ddepth);
 
+/* ---- certified trajectories: no contact anywhere along the spline ----------------------------
+ * mjpl_topp_* moves along the natural cubic spline through the waypoints, not along the polyline that
+ * mjpl_sweep_edges certifies; the spline can leave the polyline, and the bounds, between its waypoints.
+ * mjpl_sweep_splines decides the PIECES of B splines the way mjpl_sweep_edges decides edges (DESIGN.md
+ * section 5.13; tests/spline_sweep_reference.py states every operation).
+ *
+ * W is packed [wp_off[B]][nplan] over the engine's planning columns and wp_off is a HOST array in both
+ * forms, as for mjpl_topp_profile.  A path of n waypoints has n - 1 pieces; piece k of path b is
+ *   q_k(B) = the spline on [k / (n-1), (k+1) / (n-1)] at the local coordinate B in [0, 1]
+ * and its outputs sit at index wp_off[b] - b + k: wp_off[B] - B pieces in all.  M (may be NULL: not
+ * wanted) receives the knot second derivatives, bit-identical to mjpl_topp_profile's M on the same W.
+ *
+ * A node (t, h) of a piece stands for B in [a, b] = [t - h, t + h].  Its row is q_k(t) -- for the end
+ * points (0, 0) and (1, 0) the waypoint itself -- and its travel per column c, with r = n - 1 and q' the
+ * derivative with respect to the path coordinate s:
+ *   P0 = q_k(a), P3 = q_k(b), P1 = P0 + (b - a)/3 q_k'(a)/r, P2 = P3 - (b - a)/3 q_k'(b)/r,
+ *   HD_c = max_j |P_j,c - row_c| (1 + 2^-30) + 2^-40 (|W_k,c| + |W_k+1,c| + (|M_k,c| + |M_k+1,c|) / (6 r^2)),
+ * 0 when h = 0.  A cubic lies in the hull of its Bezier control points P0..P3, so every q_k(B) of the node
+ * lies in the box row +- HD; the inflation covers the rounding of the control points.
+ *
+ * Rounds, depths, the measurement and the rule per node are those of mjpl_sweep_edges, with two
+ * additions, tested in this order:
+ *   a node whose ROW lies outside [lo, hi] in a column counts as a hit with pair -2, before contact is
+ *     looked at: if it decides the piece, status is MJPL_SWEEP_RANGE, t_hit where it left, pair -2;
+ *   a node whose BOX leaves [lo, hi] while its row does not is never certified (the lever table holds
+ *     inside the bounds only): it is split -- or, at max_depth, the piece is undecided.  So a piece that
+ *     touches a bound, at a waypoint or between two, is never FREE.
+ * A piece with a waypoint outside the bounds is RANGE and is not measured (t_hit NaN, pair -1), as an
+ * edge is.  A path with a non-finite waypoint has every piece NONFINITE (and a non-finite M); the other
+ * paths of the batch are not affected.  status, t_hit (the local B), clear_lb, pair, nodes and depth per
+ * piece are otherwise those of mjpl_sweep_edges, and FREE means: no configuration q_k(B), B in [0, 1], is
+ * in contact or nearer than d_min, and clearance >= clear_lb all along the piece.
+ * MJPL_E_ARG: what mjpl_sweep_edges refuses in the descriptor, a NULL W, wp_off or output with B > 0, a
+ * path with fewer than 2 waypoints or offsets that fall, B < 0.  B = 0 launches nothing.  All outputs
+ * are deterministic and depend on no option and no MJPL_* variable.  The host form synchronises; the
+ * device form synchronises the engine's stream on entry (before the tables of an earlier call are
+ * replaced) and once per round. */
+int mjpl_sweep_splines(mjpl_engine *e, const mjpl_sweep_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                       double *M, int32_t *status, double *t_hit, double *clear_lb, int32_t *pair, int32_t *nodes,
+                       int32_t *depth);
+int mjpl_sweep_splines_dev(mjpl_engine *e, const mjpl_sweep_desc *desc, const double *dW, const int64_t *wp_off,
+                           int64_t B, double *dM, int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair,
+                           int32_t *dnodes, int32_t *ddepth);
+
 /* ---- device-resident entry points (asynchronous on the engine's stream) --------- */
 
 int mjpl_check_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t layout,
@@ -637,6 +681,12 @@ int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const double 
                        double *dM, double *dx, double *du, double *dt_grid, int32_t *dstatus, double dt,
                        const int64_t *samp_off, double *dpos, double *dvel, double *dacc, int32_t iters,
                        float *ms_profile, float *ms_sample);
+/* iters times one sweep call between two events: with wp_off NULL mjpl_sweep_edges_dev(dA, dB, n edges, layout), else
+ * mjpl_sweep_splines_dev(W = dA, wp_off, n paths, M = dB, which may be NULL); ms[k] = what call k took on the
+ * stream, its table uploads and its per-round synchronisations included. */
+int mjpl_time_sweep_dev(mjpl_engine *e, const mjpl_sweep_desc *desc, const double *dA, double *dB, const int64_t *wp_off,
+                        int64_t n, int32_t layout, int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair,
+                        int32_t *dnodes, int32_t *ddepth, int32_t iters, float *ms);
 
 /* ---- misc ------------------------------------------------------------------------ */
 

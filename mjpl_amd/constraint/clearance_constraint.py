@@ -94,6 +94,16 @@ class ClearanceConstraint(Constraint):
         """Row-wise ``certified_interval`` over full-nq edges [N, nq], one call."""
         return self.collision.certified_intervals(starts, ends, self.min_clearance, **self._sweep_params(params))
 
+    # ---- the trajectory form: the margin all along the spline (include/mjpl_hip.h, mjpl_sweep_splines) ------------
+    def certified_spline(self, waypoints, **params):
+        """The natural cubic spline through full-nq ``waypoints`` with ``d_min = min_clearance`` and this constraint's
+        bounds -> ``CertifiedPath``: ``status == engine.SWEEP_FREE`` iff every configuration of it keeps the clearance."""
+        return self.collision.certified_spline(waypoints, self.min_clearance, **self._sweep_params(params))
+
+    def certified_splines(self, paths, **params):
+        """``certified_spline`` for every path, one call."""
+        return self.collision.certified_splines(paths, self.min_clearance, **self._sweep_params(params))
+
     def _sweep_params(self, params: dict) -> dict:
         out = dict(lo=self.lower, hi=self.upper)
         out.update(params)

@@ -70,6 +70,26 @@ class CertifiedEdge(NamedTuple):
     depth: int                         # deepest bisection depth evaluated
 
 
+class CertifiedPath(NamedTuple):
+    """One path's spline decided as a whole (``CollisionConstraint.certified_spline``)."""
+    status: int                        # engine.SWEEP_*: HIT if any piece is, else RANGE / NONFINITE, else UNDECIDED, else FREE
+    piece: int                         # the lowest piece with that status (-1 when the path is FREE)
+    s_hit: float                       # (piece + t_hit) / (n - 1) where the spline is in contact or leaves the bounds (else NaN)
+    q_hit: np.ndarray | None           # the configuration there, full nq (None where s_hit is NaN)
+    clear_lb: float                    # clearance >= this all along the spline (NaN unless FREE)
+    pair: tuple[int, int] | None       # the closest geom pair at s_hit (None unless HIT)
+    nodes: int                         # bubble measurements spent on the path
+    piece_status: np.ndarray           # engine.SWEEP_* of every piece, int32 [n - 1]
+
+
+def spline_piece_point(W: np.ndarray, M: np.ndarray, k: int, B: float) -> np.ndarray:
+    """q_k(B): piece k of the natural cubic spline through W [n, d] with knot second derivatives M, at the local
+    coordinate B in [0, 1] (include/mjpl_hip.h, mjpl_sweep_splines)."""
+    r = float(len(W) - 1)
+    A = 1.0 - B
+    return (A * W[k] + B * W[k + 1]) + ((A * A * A - A) * M[k] + (B * B * B - B) * M[k + 1]) / (6.0 * r * r)
+
+
 class CollisionRuleset:
     """Which body pairs may touch (reference collision_constraint.py:36-95).
 
@@ -328,6 +348,47 @@ class CollisionConstraint(Constraint):
         over those columns)."""
         self._ensure_planning()
         return self.engine.sweep_edges(QA, QB, d_min, layout, **params)
+
+    # ---- certified trajectories: the whole spline, not its samples (include/mjpl_hip.h, mjpl_sweep_splines) --------
+    def certified_spline(self, waypoints, d_min: float = 0.0, **params) -> "CertifiedPath":
+        """The natural cubic spline through full-nq ``waypoints`` -- the curve ``HipToppTrajectoryGenerator`` moves
+        along -- decided as a whole -> :class:`CertifiedPath`.  ``status == engine.SWEEP_FREE``: no configuration of it is
+        in contact (or nearer than ``d_min``), whatever lies between two samples of a trajectory.  params: cap,
+        max_depth, lo, hi (full nq)."""
+        return self.certified_splines([waypoints], d_min, **params)[0]
+
+    def certified_splines(self, paths, d_min: float = 0.0, **params) -> "list[CertifiedPath]":
+        """``certified_spline`` for every path (each a sequence of at least two full-nq configurations), one call."""
+        packed = [self._full_batch(np.array([np.asarray(w, dtype=np.float64).reshape(-1) for w in p])) for p in paths]
+        if not packed:
+            return []
+        if any(len(W) < 2 for W in packed):
+            raise ValueError("every path needs at least two waypoints")
+        off = np.concatenate([[0], np.cumsum([len(W) for W in packed])]).astype(np.int64)
+        status, t_hit, clear_lb, pair, nodes, _depth, M = self.engine.sweep_splines(np.concatenate(packed), off, d_min, **params)
+        cand = self.engine.contact_pairs()[0]
+        out = []
+        for b, W in enumerate(packed):
+            p = slice(int(off[b]) - b, int(off[b + 1]) - b - 1)
+            st, Mb = status[p], M[off[b]:off[b + 1]]
+            verdict, k = _engine.SWEEP_FREE, -1
+            for group in ((_engine.SWEEP_HIT,), (_engine.SWEEP_RANGE, _engine.SWEEP_NONFINITE), (_engine.SWEEP_UNDECIDED,)):
+                at = np.flatnonzero(np.isin(st, group))
+                if len(at):
+                    k = int(at[0])
+                    verdict = int(st[k])
+                    break
+            s_hit, q_hit, geoms, lb = float("nan"), None, None, float("nan")
+            if k >= 0 and np.isfinite(t_hit[p][k]):
+                tk = float(t_hit[p][k])
+                s_hit = (k + tk) / (len(W) - 1)
+                q_hit = W[k].copy() if tk == 0.0 else W[k + 1].copy() if tk == 1.0 else spline_piece_point(W, Mb, k, tk)
+                if pair[p][k] >= 0:
+                    geoms = tuple(int(g) for g in cand[pair[p][k]])
+            if verdict == _engine.SWEEP_FREE:
+                lb = float(clear_lb[p].min())
+            out.append(CertifiedPath(verdict, k, s_hit, q_hit, lb, geoms, int(nodes[p].sum()), st.copy()))
+        return out
 
     def valid_configs_planning(self, Q: np.ndarray, layout: int = _engine.AOS) -> np.ndarray:
         self._ensure_planning()

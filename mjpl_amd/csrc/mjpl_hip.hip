@@ -516,6 +516,11 @@ struct mjpl_engine {
   DevBuf<double> d_sweep_rows[2], d_sweep_hd[2], d_sweep_f64;
   DevBuf<int> d_sweep_meta[2], d_sweep_i32;
   DevBuf<unsigned long long> d_sweep_key;
+  // mjpl_sweep_splines*: the call's tables [wp_off | per piece: first row, n - 1] on the host (what the upload reads:
+  // rewritten only after the stream has drained) and on the device; M for a caller that wants none (grow-only)
+  std::vector<int64_t> sweep_piece_h;
+  DevBuf<int64_t> d_sweep_piece;
+  DevBuf<double> d_sweep_M;
   // mjpl_topp_* (mjpl_topp.h): the call's offset tables [wp_off | samp_off] and limits [vmin | vmax | amin | amax] on
   // the host (what the uploads read: rewritten only after the stream has drained) and on the device; c' of the Thomas
   // recurrence, grown to the longest path seen; the workspace of a chunk of paths (all grow-only)
@@ -2921,20 +2926,27 @@ int topp_upload(mjpl_engine *e, const mjpl_topp_desc &d, const int64_t *wp_off, 
   return MJPL_OK;
 }
 
-// mjpl_topp_profile* on device batches (wp_off on the host): the spline of every path in one launch, then per chunk of
-// paths whose workspace fits kToppChunkBytes the two grid kernels and the sweeps.
-int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
-                        double *dx, double *du, double *dt, int32_t *dstatus) {
-  MJPL_TRY(topp_upload(e, d, wp_off, nullptr, B));
-  const hipStream_t st = e->stream;
+// c' of the Thomas recurrence on the device, for the longest of these paths (k_topp_spline reads it; the stream is drained)
+int topp_cp_table(mjpl_engine *e, const int64_t *wp_off, int64_t B) {
   int64_t nmax = 0;
   for (int64_t b = 0; b < B; b++) nmax = std::max(nmax, wp_off[b + 1] - wp_off[b]);
   if ((size_t)nmax > e->topp_cp_h.size()) {  // c'[0] = 0, c'[k] = 1 / (4 - c'[k-1])
     e->topp_cp_h.assign(std::max<size_t>(nmax, 1024), 0.0);
     for (size_t k = 1; k < e->topp_cp_h.size(); k++) e->topp_cp_h[k] = 1.0 / (4.0 - e->topp_cp_h[k - 1]);
     MJPL_TRY(e->d_topp_cp.reserve(e->topp_cp_h.size()));
-    HIP_TRY(hipMemcpyAsync(e->d_topp_cp.p, e->topp_cp_h.data(), e->topp_cp_h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_topp_cp.p, e->topp_cp_h.data(), e->topp_cp_h.size() * sizeof(double), hipMemcpyHostToDevice,
+                           e->stream));
   }
+  return MJPL_OK;
+}
+
+// mjpl_topp_profile* on device batches (wp_off on the host): the spline of every path in one launch, then per chunk of
+// paths whose workspace fits kToppChunkBytes the two grid kernels and the sweeps.
+int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                        double *dx, double *du, double *dt, int32_t *dstatus) {
+  MJPL_TRY(topp_upload(e, d, wp_off, nullptr, B));
+  const hipStream_t st = e->stream;
+  MJPL_TRY(topp_cp_table(e, wp_off, B));
   ToppBatch a = {};
   a.W = dW; a.wp_off = e->d_topp_off.p; a.B = (int)B; a.d = d.nq; a.G = d.grid;
   a.lim = e->d_topp_lim.p; a.cp = e->d_topp_cp.p; a.M = dM;
@@ -3019,22 +3031,46 @@ int check_measure_args(const mjpl_engine *e, const void *Q, const void *HD, int6
   return MJPL_OK;
 }
 
-// Argument checks of mjpl_sweep_edges*: check_common on both ends, the ranges of the descriptor (NaN refused
-// everywhere), lo <= hi per planning column, every output non-null when E > 0.
-int check_sweep_args(const mjpl_engine *e, const mjpl_sweep_desc *d, const void *QA, const void *QB, int64_t E, int layout,
-                     std::initializer_list<const void *> outs) {
-  MJPL_TRY(check_common(e, QA, E, layout));
-  MJPL_TRY(check_common(e, QB, E, layout));
+// The descriptor of mjpl_sweep_edges* and mjpl_sweep_splines*: its ranges (NaN refused everywhere), lo <= hi per column
+int check_sweep_desc(const mjpl_engine *e, const mjpl_sweep_desc *d) {
   if (!d) return fail(MJPL_E_ARG, "mjpl_sweep_edges: NULL descriptor");
   if (!(d->d_min >= 0) || !(d->d_min < INFINITY)) return fail(MJPL_E_ARG, "d_min must be >= 0 and finite (NaN is refused), got %g", d->d_min);
   if (!(d->cap > d->d_min + e->ct_margin_max) || !(d->cap < INFINITY))
     return fail(MJPL_E_ARG, "cap must be finite and > d_min + the largest margin of a non-allowed pair = %g (NaN is refused), got %g",
                 d->d_min + e->ct_margin_max, d->cap);
   if (d->max_depth < 0 || d->max_depth > kSweepMaxDepth) return fail(MJPL_E_ARG, "max_depth must be 0..%d, got %d", kSweepMaxDepth, d->max_depth);
-  MJPL_TRY(check_bounds(e, d->lo, d->hi));
+  return check_bounds(e, d->lo, d->hi);
+}
+
+// Argument checks of mjpl_sweep_edges*: check_common on both ends, the descriptor, every output non-null when E > 0.
+int check_sweep_args(const mjpl_engine *e, const mjpl_sweep_desc *d, const void *QA, const void *QB, int64_t E, int layout,
+                     std::initializer_list<const void *> outs) {
+  MJPL_TRY(check_common(e, QA, E, layout));
+  MJPL_TRY(check_common(e, QB, E, layout));
+  MJPL_TRY(check_sweep_desc(e, d));
   if (E > 0)
     for (const void *o : outs)
       if (!o) return fail(MJPL_E_ARG, "NULL output pointer");
+  return MJPL_OK;
+}
+
+// Argument checks of mjpl_sweep_splines*: the descriptor as for the edges, the offsets as for mjpl_topp_profile, W and
+// every listed output non-null when B > 0.
+int check_spline_sweep_args(const mjpl_engine *e, const mjpl_sweep_desc *d, const void *W, const int64_t *wp_off, int64_t B,
+                            std::initializer_list<const void *> outs) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_sweep_splines: batch size %lld out of range", (long long)B);
+  MJPL_TRY(check_sweep_desc(e, d));
+  if (B == 0) return MJPL_OK;
+  if (!wp_off) return fail(MJPL_E_ARG, "mjpl_sweep_splines: NULL offsets");
+  if (wp_off[0] != 0) return fail(MJPL_E_ARG, "wp_off[0] must be 0, got %lld", (long long)wp_off[0]);
+  for (int64_t b = 0; b < B; b++) {
+    const int64_t n = wp_off[b + 1] - wp_off[b];
+    if (n < 2) return fail(MJPL_E_ARG, "path %lld has %lld waypoints (offsets must rise by at least 2)", (long long)b, (long long)n);
+  }
+  if (!W) return fail(MJPL_E_ARG, "NULL batch pointer");
+  for (const void *o : outs)
+    if (!o) return fail(MJPL_E_ARG, "NULL output pointer");
   return MJPL_OK;
 }
 
@@ -3042,9 +3078,11 @@ int check_sweep_args(const mjpl_engine *e, const mjpl_sweep_desc *d, const void 
 // clamp(kSweepNodes >> max_depth, 64, 2^14), so that a chunk's deepest round holds kSweepNodes nodes at most.  Per chunk:
 // k_sweep_init writes round 0 into work buffer 0; then per round one k_distance<DM_SWEEP> launch over the open nodes, one
 // k_sweep_step launch, and one 4-byte read of the other buffer's fill counter, which sizes the next round (0: the chunk
-// is done); k_sweep_finish turns the per-edge state into the verdicts.
+// is done); k_sweep_finish turns the per-edge state into the verdicts.  With `sp` the E "edges" are the pieces of a call's
+// splines (launch_sweep_splines): the same loop, with the round-0 and step kernels of the cubic nodes.
 int launch_sweep(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dQA, const double *dQB, int64_t E, int layout,
-                 int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes, int32_t *ddepth) {
+                 int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes, int32_t *ddepth,
+                 const SweepSpline *sp = nullptr) {
   MJPL_TRY(check_pair_types(e));
   MJPL_TRY(sweep_use_bounds(e, d.lo, d.hi));
   const int nplan = (int)e->qidx.size();
@@ -3081,7 +3119,9 @@ int launch_sweep(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dQA, co
     MJPL_TRY(reserve_work(0, 3 * (size_t)ne));
     SweepWork cur = work(0);
     HIP_TRY(hipMemsetAsync(cur.n, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_sweep_init, dim3((unsigned)((ne + kSweepBlock - 1) / kSweepBlock)), dim3(kSweepBlock), 0, st, a, ne, cur);
+    const dim3 init_grid((unsigned)((ne + kSweepBlock - 1) / kSweepBlock));
+    if (sp) hipLaunchKernelGGL(k_sweep_spline_init, init_grid, dim3(kSweepBlock), 0, st, a, *sp, ne, cur);
+    else hipLaunchKernelGGL(k_sweep_init, init_grid, dim3(kSweepBlock), 0, st, a, ne, cur);
     HIP_TRY(hipGetLastError());
     int n = 0;
     MJPL_TRY(read_count(cur, &n));
@@ -3098,8 +3138,9 @@ int launch_sweep(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dQA, co
       MJPL_TRY(reserve_work(nxt, last ? 1 : 2 * (size_t)n));
       SweepWork next = work(nxt);
       HIP_TRY(hipMemsetAsync(next.n, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_sweep_step, dim3((unsigned)((n + kSweepBlock - 1) / kSweepBlock)), dim3(kSweepBlock), 0, st, a, round, n,
-                         cur, gap, gap_pair, slack, next);
+      const dim3 step_grid((unsigned)((n + kSweepBlock - 1) / kSweepBlock));
+      if (sp) hipLaunchKernelGGL(k_sweep_spline_step, step_grid, dim3(kSweepBlock), 0, st, a, *sp, round, n, cur, gap, gap_pair, slack, next);
+      else hipLaunchKernelGGL(k_sweep_step, step_grid, dim3(kSweepBlock), 0, st, a, round, n, cur, gap, gap_pair, slack, next);
       HIP_TRY(hipGetLastError());
       if (last) break;
       MJPL_TRY(read_count(next, &n));
@@ -3109,6 +3150,39 @@ int launch_sweep(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dQA, co
     HIP_TRY(hipGetLastError());
   }
   return MJPL_OK;
+}
+
+// mjpl_sweep_splines* on device batches (wp_off on the host).  The stream is drained, then the call's tables go up:
+// wp_off for k_topp_spline and per piece the row of its first waypoint and n - 1.  k_topp_spline writes M (into the
+// engine's own buffer when the caller wants none); launch_sweep runs the loop over the pieces.
+int launch_sweep_splines(mjpl_engine *e, const mjpl_sweep_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                         int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes, int32_t *ddepth) {
+  const int nplan = (int)e->qidx.size();
+  if (nplan < 1) return fail(MJPL_E_ARG, "mjpl_sweep_splines: no planning columns");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t nb = (size_t)B + 1, pieces = (size_t)(wp_off[B] - B);
+  e->sweep_piece_h.resize(nb + 2 * pieces);
+  std::copy(wp_off, wp_off + nb, e->sweep_piece_h.begin());
+  int64_t *piece = e->sweep_piece_h.data() + nb;
+  for (int64_t b = 0; b < B; b++)
+    for (int64_t k = wp_off[b]; k < wp_off[b + 1] - 1; k++) {
+      piece[2 * (k - b)] = k;
+      piece[2 * (k - b) + 1] = wp_off[b + 1] - wp_off[b] - 1;
+    }
+  MJPL_TRY(e->d_sweep_piece.reserve(e->sweep_piece_h.size(), 1024));
+  HIP_TRY(hipMemcpyAsync(e->d_sweep_piece.p, e->sweep_piece_h.data(), e->sweep_piece_h.size() * sizeof(int64_t),
+                         hipMemcpyHostToDevice, e->stream));
+  MJPL_TRY(topp_cp_table(e, wp_off, B));
+  if (!dM) {
+    MJPL_TRY(e->d_sweep_M.reserve((size_t)wp_off[B] * nplan));
+    dM = e->d_sweep_M.p;
+  }
+  ToppBatch t = {};
+  t.W = dW; t.wp_off = e->d_sweep_piece.p; t.B = (int)B; t.d = nplan; t.cp = e->d_topp_cp.p; t.M = dM;
+  hipLaunchKernelGGL(k_topp_spline, dim3((unsigned)((B * nplan + 255) / 256)), dim3(256), 0, e->stream, t);
+  HIP_TRY(hipGetLastError());
+  const SweepSpline sp = {dW, dM, e->d_sweep_piece.p + nb};
+  return launch_sweep(e, d, nullptr, nullptr, (int64_t)pieces, MJPL_AOS, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth, &sp);
 }
 
 }  // namespace
@@ -3476,6 +3550,28 @@ int mjpl_sweep_edges(mjpl_engine *e, const mjpl_sweep_desc *d, const double *QA,
   });
 }
 
+int mjpl_sweep_splines_dev(mjpl_engine *e, const mjpl_sweep_desc *d, const double *dW, const int64_t *wp_off, int64_t B,
+                           double *dM, int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes,
+                           int32_t *ddepth) {
+  int rc = check_spline_sweep_args(e, d, dW, wp_off, B, {dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth});
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_sweep_splines(e, *d, dW, wp_off, B, dM, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth);
+}
+
+int mjpl_sweep_splines(mjpl_engine *e, const mjpl_sweep_desc *d, const double *W, const int64_t *wp_off, int64_t B, double *M,
+                       int32_t *status, double *t_hit, double *clear_lb, int32_t *pair, int32_t *nodes, int32_t *depth) {
+  int rc = check_spline_sweep_args(e, d, W, wp_off, B, {status, t_hit, clear_lb, pair, nodes, depth});
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t n = (size_t)(wp_off[B] - B), db = sizeof(double), ib = sizeof(int32_t), wb = (size_t)wp_off[B] * e->qidx.size() * db;
+  const HostOut outs[] = {{M, wb},         {status, n * ib}, {t_hit, n * db}, {clear_lb, n * db},
+                          {pair, n * ib},  {nodes, n * ib},  {depth, n * ib}};
+  return staged(e, false, {{W, wb}}, outs, [&](void **in, void **out) {
+    return launch_sweep_splines(e, *d, (const double *)in[0], wp_off, B, (double *)out[0], (int32_t *)out[1], (double *)out[2],
+                                (double *)out[3], (int32_t *)out[4], (int32_t *)out[5], (int32_t *)out[6]);
+  });
+}
+
 // ---- memory / stream helpers
 
 int mjpl_dev_alloc(mjpl_engine *e, size_t bytes, void **out) {
@@ -3617,6 +3713,26 @@ int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW
     HIP_TRY(hipEventElapsedTime(&ms_profile[k], ev[3 * k], ev[3 * k + 1]));
     HIP_TRY(hipEventElapsedTime(&ms_sample[k], ev[3 * k + 1], ev[3 * k + 2]));
   }
+  for (auto &x : ev) (void)hipEventDestroy(x);
+  return rc;
+}
+
+int mjpl_time_sweep_dev(mjpl_engine *e, const mjpl_sweep_desc *d, const double *dA, double *dB, const int64_t *wp_off, int64_t n,
+                        int32_t layout, int32_t *dstatus, double *dt_hit, double *dclear_lb, int32_t *dpair, int32_t *dnodes,
+                        int32_t *ddepth, int32_t iters, float *ms) {
+  if (!e || iters < 0 || (iters > 0 && !ms)) return fail(MJPL_E_ARG, "mjpl_time_sweep_dev: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<hipEvent_t> ev(2 * (size_t)iters);
+  for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+  int rc = MJPL_OK;
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) {
+    HIP_TRY(hipEventRecord(ev[2 * k], e->stream));
+    rc = wp_off ? mjpl_sweep_splines_dev(e, d, dA, wp_off, n, dB, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth)
+                : mjpl_sweep_edges_dev(e, d, dA, dB, n, layout, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth);
+    HIP_TRY(hipEventRecord(ev[2 * k + 1], e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) HIP_TRY(hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]));
   for (auto &x : ev) (void)hipEventDestroy(x);
   return rc;
 }

@@ -175,6 +175,12 @@ ABI = {
                                    _I32P, _I32P]),
     "mjpl_sweep_edges_dev": (C.c_int, [_VP, C.POINTER(SweepDesc), _VP, _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP,
                                        _VP]),
+    "mjpl_sweep_splines": (C.c_int, [_VP, C.POINTER(SweepDesc), _F64P, _I64P, C.c_int64, _F64P, _I32P, _F64P, _F64P, _I32P,
+                                     _I32P, _I32P]),
+    "mjpl_sweep_splines_dev": (C.c_int, [_VP, C.POINTER(SweepDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP,
+                                         _VP]),
+    "mjpl_time_sweep_dev": (C.c_int, [_VP, C.POINTER(SweepDesc), _VP, _VP, _I64P, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                      _VP, C.c_int32, C.POINTER(C.c_float)]),
     "mjpl_nearest_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "mjpl_nearest_range_dev": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_nearest_last_screen": (C.c_int32, [_VP]),
@@ -917,6 +923,59 @@ class Engine:
         self._ok(self.lib.mjpl_sweep_edges_dev(self.h, C.byref(desc), dQA, dQB, n, layout, dstatus, dt_hit, dclear_lb, dpair,
                                                dnodes, ddepth))
         del keep
+
+    # -- certified trajectories: no contact anywhere along the spline (include/mjpl_hip.h, mjpl_sweep_splines*)
+    def sweep_splines(self, W, wp_off, d_min=0.0, want_M=True, **params):
+        """Certified spline pieces -> (status, t_hit, clear_lb, pair, nodes, depth, M like W), the first six per PIECE:
+        the B paths packed in W [wp_off[B], nplan] (path b: rows wp_off[b] .. wp_off[b+1] - 1) have wp_off[B] - B
+        pieces, piece k of path b at index wp_off[b] - b + k.  The curve is the natural cubic spline topp_profile moves
+        along (M: its knot second derivatives, None with want_M False).  status SWEEP_FREE: no configuration of the piece
+        is in contact or nearer than d_min; SWEEP_HIT: the one at the local coordinate t_hit is; SWEEP_RANGE with pair
+        -2: the spline leaves lo / hi at t_hit; the rest as sweep_edges.  params: cap, max_depth, lo, hi."""
+        W = _f64(W)
+        if W.ndim != 2 or W.shape[1] != self.nplan:
+            raise ValueError(f"W must be [rows, {self.nplan}], got {W.shape}")
+        wp_off = np.ascontiguousarray(wp_off, dtype=np.int64)
+        B = len(wp_off) - 1
+        if B < 0 or wp_off[-1] != len(W):
+            raise ValueError(f"wp_off must end at the {len(W)} rows of W")
+        desc, keep = self.sweep_desc(d_min, **params)
+        n = max(int(wp_off[-1]) - B, 0)
+        M = np.zeros_like(W) if want_M else None
+        status, pair = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        nodes, depth = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        t_hit, clear_lb = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        self._ok(self.lib.mjpl_sweep_splines(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                             None if M is None else M.ctypes.data_as(_F64P), status.ctypes.data_as(_I32P),
+                                             t_hit.ctypes.data_as(_F64P), clear_lb.ctypes.data_as(_F64P),
+                                             pair.ctypes.data_as(_I32P), nodes.ctypes.data_as(_I32P),
+                                             depth.ctypes.data_as(_I32P)))
+        del keep
+        return status, t_hit, clear_lb, pair, nodes, depth, M
+
+    def sweep_splines_dev(self, dW, wp_off, d_min, dM, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth, **params):
+        """sweep_splines() on device pointers (wp_off, lo / hi stay host arrays; dM may be None).  Enqueued on the
+        engine's stream, which it synchronises on entry and once per round."""
+        wp_off = np.ascontiguousarray(wp_off, dtype=np.int64)
+        desc, keep = self.sweep_desc(d_min, **params)
+        self._ok(self.lib.mjpl_sweep_splines_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM,
+                                                 dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth))
+        del keep
+
+    def time_sweep_dev(self, dA, dB, wp_off, n, layout, d_min, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth, iters, **params):
+        """ms float32 [iters]: device-event times of `iters` sweep calls -- sweep_edges_dev(dA, dB, n, layout) with wp_off
+        None, else sweep_splines_dev(W = dA, wp_off, M = dB or None) on its len(wp_off) - 1 paths."""
+        desc, keep = self.sweep_desc(d_min, **params)
+        ms = np.zeros(iters, np.float32)
+        off = None
+        if wp_off is not None:
+            off = np.ascontiguousarray(wp_off, dtype=np.int64)
+            n = len(off) - 1
+        self._ok(self.lib.mjpl_time_sweep_dev(self.h, C.byref(desc), dA, dB, None if off is None else off.ctypes.data_as(_I64P),
+                                              n, layout, dstatus, dt_hit, dclear_lb, dpair, dnodes, ddepth, iters,
+                                              ms.ctypes.data_as(C.POINTER(C.c_float))))
+        del keep
+        return ms
 
     def check_edges_dev(self, dQA, dQB, n, step_dist, layout, dvalid, dfirst_bad=None, flags=0):
         self._ok(self.lib.mjpl_check_edges_dev(self.h, dQA, dQB, n, float(step_dist), layout, flags,

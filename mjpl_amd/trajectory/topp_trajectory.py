@@ -20,11 +20,20 @@ def sample_count(duration: float, dt: float) -> int:
 
 
 class HipToppTrajectoryGenerator(TrajectoryGenerator):
+    # every position of a trajectory lies on the natural cubic spline through the waypoints at uniform knots: the curve
+    # ``certified_splines`` decides (``generate_certified_trajectories`` asks for this declaration)
+    follows_natural_spline = True
+
     def __init__(self, dt: float, max_velocity, max_acceleration, min_velocity=None, min_acceleration=None,
-                 grid_per_segment: int = 8, engine: "_engine.Engine | None" = None, device: int = 0) -> None:
+                 grid_per_segment: int = 8, engine: "_engine.Engine | None" = None, device: int = 0,
+                 allow_repeated_waypoints: bool = False) -> None:
         """``min_velocity`` / ``min_acceleration`` default to the negated maxima.  ``grid_per_segment``: grid intervals
         per waypoint segment.  ``engine``: the Engine whose device and stream do the work (its model plays no part);
-        without one a small engine is made on ``device`` at the first call."""
+        without one a small engine is made on ``device`` at the first call.  ``allow_repeated_waypoints``: two equal
+        consecutive waypoints raise ValueError unless this is set.  The spline through them is well defined (it dwells
+        near the repeated waypoint and overshoots it), and the midpoint insertion of
+        ``generate_certified_trajectories`` makes such paths out of a path that has one; a path that does not move
+        at all still ends TOPP_STALLED and gives None."""
         if not dt > 0:
             raise ValueError("`dt` must be > 0.")
         if grid_per_segment < 2:
@@ -42,6 +51,7 @@ class HipToppTrajectoryGenerator(TrajectoryGenerator):
         self.grid = int(grid_per_segment)
         self.device = device
         self._engine = engine
+        self.allow_repeated_waypoints = bool(allow_repeated_waypoints)
 
     @property
     def engine(self) -> "_engine.Engine":
@@ -58,7 +68,7 @@ class HipToppTrajectoryGenerator(TrajectoryGenerator):
                 raise ValueError(f"path {k}: there must be at least two waypoints.")
             if W.shape[1] != len(self.vmax):
                 raise ValueError(f"path {k}: waypoints have {W.shape[1]} columns, the limits {len(self.vmax)}.")
-            if np.any(np.all(W[1:] == W[:-1], axis=1)):
+            if not self.allow_repeated_waypoints and np.any(np.all(W[1:] == W[:-1], axis=1)):
                 raise ValueError(f"path {k}: two consecutive waypoints are equal.")
             rows.append(W)
             off.append(off[-1] + len(W))

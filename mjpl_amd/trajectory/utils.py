@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .. import engine as _engine
 from ..constraint.constraint_interface import Constraint
 from ..constraint.utils import apply_constraints, obeys_constraints
 from .trajectory_interface import Trajectory, TrajectoryGenerator
@@ -103,10 +104,75 @@ def _add_intermediate_waypoint(waypoints: list[np.ndarray], timing: list[float],
         raise ValueError("`waypoints` and `timing` must be the same length.")
     for i in range(len(waypoints) - 1):
         if timing[i] <= timestamp <= timing[i + 1]:
-            mid = (np.asarray(waypoints[i]) + np.asarray(waypoints[i + 1])) / 2
-            mid = apply_constraints(mid, mid, list(constraints))
-            if mid is None:
-                return False
-            waypoints.insert(i + 1, mid)
-            return True
+            return _insert_midpoint(waypoints, i, constraints)
     return False
+
+
+def _insert_midpoint(waypoints: list[np.ndarray], i: int, constraints: list[Constraint] = ()) -> bool:
+    """Insert the constrained midpoint of segment ``i`` of ``waypoints``.  False, and nothing added, when the midpoint
+    cannot be made to obey the constraints."""
+    mid = (np.asarray(waypoints[i]) + np.asarray(waypoints[i + 1])) / 2
+    mid = apply_constraints(mid, mid, list(constraints))
+    if mid is None:
+        return False
+    waypoints.insert(i + 1, mid)
+    return True
+
+
+def generate_certified_trajectory(waypoints: list[np.ndarray], generator: TrajectoryGenerator,
+                                  constraints: list[Constraint], certifier, max_rounds: int = 16, **params):
+    """A trajectory through ``waypoints`` whose WHOLE curve is certified, with its certificate -> ``(Trajectory,
+    CertifiedPath)`` or None.  :func:`generate_certified_trajectories` for one path."""
+    return generate_certified_trajectories([waypoints], generator, constraints, certifier, max_rounds, **params)[0]
+
+
+def generate_certified_trajectories(paths: list[list[np.ndarray]], generator: TrajectoryGenerator,
+                                    constraints: list[Constraint], certifier, max_rounds: int = 16, **params) -> list:
+    """:func:`generate_constrained_trajectories` with a verdict on the curve between the samples.
+
+    ``generate_constrained_trajectory`` checks the positions ``dt`` apart and assumes the rest; the spline a trajectory
+    follows can leave the polyline the planner validated by a lot.  Here, once no sampled position of a path violates
+    ``constraints``, its spline goes to ``certifier.certified_splines`` (a ``CollisionConstraint`` or a
+    ``ClearanceConstraint``; ``params`` -- cap, max_depth, lo, hi -- are handed on), all such paths of a round in one
+    call.  A path whose spline is SWEEP_FREE is done: the result is ``(Trajectory, CertifiedPath)``.  Otherwise the
+    midpoint of the first piece that is not FREE is inserted between that piece's two waypoints, after
+    ``apply_constraints`` as in the sampled loop, and the path goes another round.  Midpoint insertion need not
+    converge, so ``max_rounds`` must be a finite count of generations; when it is used up the result is None, as it is
+    when the generator or the insertion fails or a waypoint is not finite.
+
+    The certificate is about the natural cubic spline through the waypoints at uniform knots, so ``generator`` must
+    declare that its trajectories follow it (``follows_natural_spline``, as ``HipToppTrajectoryGenerator`` does);
+    any other generator raises TypeError.  The caller's lists are not mutated."""
+    if not getattr(generator, "follows_natural_spline", False):
+        raise TypeError("the certificate is about the natural cubic spline through the waypoints: the generator must declare "
+                        "`follows_natural_spline = True`")
+    if max_rounds is None or isinstance(max_rounds, bool) or not np.isfinite(max_rounds):
+        raise ValueError("`max_rounds` must be finite: midpoint insertion need not converge")
+    work = [list(p) for p in paths]
+    result: list = [None] * len(work)
+    open_ids = list(range(len(work)))
+    rounds = 0
+    while open_ids and rounds < max_rounds:
+        rounds += 1
+        if hasattr(generator, "generate_trajectories"):
+            trajs = generator.generate_trajectories([work[k] for k in open_ids])
+        else:
+            trajs = [generator.generate_trajectory(work[k]) for k in open_ids]
+        alive = [(k, tr) for k, tr in zip(open_ids, trajs) if tr is not None]
+        firsts = _first_violations([tr.positions for _, tr in alive], constraints)
+        open_ids, clean = [], []
+        for (k, tr), i in zip(alive, firsts):
+            if i is None:
+                clean.append((k, tr))
+            elif _refine(work[k], tr, i, constraints):
+                open_ids.append(k)
+        certs = certifier.certified_splines([work[k] for k, _ in clean], **params) if clean else []
+        for (k, tr), cert in zip(clean, certs):
+            if cert.status == _engine.SWEEP_FREE:
+                result[k] = (tr, cert)
+            elif cert.status != _engine.SWEEP_NONFINITE:
+                first = int(np.flatnonzero(np.asarray(cert.piece_status) != _engine.SWEEP_FREE)[0])
+                if _insert_midpoint(work[k], first, constraints):
+                    open_ids.append(k)
+        open_ids.sort()
+    return result
