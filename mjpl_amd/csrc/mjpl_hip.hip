@@ -336,6 +336,36 @@ struct SpecLib {
   PatchFn patch = nullptr;
 };
 
+// The planner's knobs (options "rrt_<field>"; mjpl_rrt_create copies the engine's into the handle it makes).
+struct RrtTuning {
+  // The connect phase's nearest neighbours, early (round 5).  A lane's round does not depend on any other lane's (both trees
+  // are the round's snapshot), and the tail of the first extension is a handful of lanes taking a thousand sequential steps
+  // on an otherwise idle chip: once no more than `early_lanes` lanes are still extending, the lanes that are through get
+  // their nearest node of the OTHER tree on a second stream (what they reached is final: ln.C of a lane with act == 0);
+  // the second extension then looks up only the lanes that were still under way, and waits for the early answers.  The
+  // same queries against the same nodes: the same nodes.  `early_min_nodes`: from what size of the other tree on (tests
+  // set both thresholds low); `early_next`: the next round's look-up as well.
+  // (With the chains capped the last chunks are a millisecond and the look-ups two or three: rounds of 13.0 - 13.5 ms with
+  //  it at any threshold, 13.1 without (profiles/r06_rrt_early_ab.txt, one box): OFF by default from round 6 on -- one
+  //  stream, one scratch arena --, still an option and still tested.)
+  int early_nn = 0, early_lanes = 4096, early_next = 1;
+  int64_t early_min_nodes = 65536;
+  // projecting extensions: most steps a lane takes per chunk, and the candidate slots a chunk is sized for
+  // (round 4, with the chain as generated code a step is cheap enough for the chunk's fixed cost to show: 64 / 65 536 ->
+  //  65.2 ms per 131 072-lane round, 256 / 262 144 -> 62.6, 1 024 / 1 048 576 -> 59.8; the slots are bounded by the
+  //  candidate buffer, 4 L, all the same)
+  int proj_steps = 1024;
+  int64_t proj_slots = 1 << 20;
+  // ... and the shape of the generating launch (mjpl_rows.h; rows_shape), both there for A/B timing: lanes per row (0: by
+  // the number of active lanes; 1 / 4 / 8 / 16 / 64 forced), waves per launch (one per SIMD: the kernels' registers)
+  int proj_g = 0, proj_waves = 1024;
+  // rows of sixteen lanes that run a step ahead (mjpl_rows.h: k_rrt_gen_project_ahead), when no more than `ahead_lanes`
+  // lanes extend: one row per wave (measured: with four rows per wave, 1 536 lanes, 14.0 ms against 13.5 with eight lanes
+  // per row -- the statements of running ahead are paid by every row of the wave; one row per wave, 268 lanes x 1 024
+  // steps: 20.5 ms against 23.9).  ahead = 0: never
+  int ahead = 1, ahead_lanes = 1024;
+};
+
 }  // namespace
 
 struct mjpl_engine {
@@ -445,14 +475,7 @@ struct mjpl_engine {
   int pose_spec = 1;            // "pose_spec": 0 = projections and IK seeds on the interpreting kernels
   int pose_phase_steps = 0;     // "pose_phase_steps"
   int rrt_trace = 0;            // "rrt_trace": 1 = a planner round's phases on stderr, 2 = every extension chunk (synchronises)
-  // ... and the planner's (mjpl_rrt_create copies them into the handle it makes)
-  // (rrt_early_nn: the look-ups on a second stream beside the first extension's last chunks -- round 5's answer to tails of a
-  //  thousand steps.  With the chains capped the last chunks are a millisecond and the look-ups two or three: rounds of
-  //  13.0 - 13.5 ms with it at any threshold, 13.1 without (profiles/r06_rrt_early_ab.txt, one box): OFF by default from round 6
-  //  on -- one stream, one scratch arena --, still an option and still tested.)
-  int rrt_exact_counts = 1, rrt_early_nn = 0, rrt_early_lanes = 4096, rrt_early_next = 1, rrt_proj_steps = 1024, rrt_proj_g = 0,
-      rrt_ahead = 1, rrt_ahead_lanes = 1024, rrt_proj_waves = 1024;
-  int64_t rrt_early_min_nodes = 65536, rrt_proj_slots = 1 << 20;
+  RrtTuning rrt;                // "rrt_early_nn" ... "rrt_proj_waves"
   int nn_cells = 1;             // the cell-ordered scan for big trees (mjpl_nearest_cells.h); option "nn_cells"
   int64_t nn_cells_min = 131072; // ... from this many nodes on; option "nn_cells_min_nodes"
   int64_t nn_cells_sample = 32768; // ... with bounds from a strided sample of this many nodes ("nn_cells_sample"; measured on the planner's trees,
@@ -2168,18 +2191,17 @@ const EngineOption kEngineOptions[] = {
     MJPL_OPT_INT("pose_phase_steps", pose_phase_steps, 0, 1 << 20),
     // ---- the planner (read by mjpl_rrt_create)
     MJPL_OPT_INT("rrt_trace", rrt_trace, 0, 2),
-    MJPL_OPT_BOOL("rrt_exact_counts", rrt_exact_counts),
-    MJPL_OPT_BOOL("rrt_early_nn", rrt_early_nn),
-    MJPL_OPT_INT("rrt_early_lanes", rrt_early_lanes, 1, 1 << 30),
-    MJPL_OPT_INT("rrt_early_min_nodes", rrt_early_min_nodes, 1, 1ll << 40),
-    MJPL_OPT_BOOL("rrt_early_next", rrt_early_next),
-    MJPL_OPT_INT("rrt_proj_steps", rrt_proj_steps, 1, 1 << 30),
-    MJPL_OPT_INT("rrt_proj_slots", rrt_proj_slots, 1, 1ll << 40),
-    {"rrt_proj_g", [](mjpl_engine *e) { return (double)e->rrt_proj_g; },
-     [](mjpl_engine *e, double v) { const int g = (int)v; e->rrt_proj_g = (g == 1 || g == 4 || g == 8 || g == 16 || g == 64) ? g : 0; return true; }},
-    MJPL_OPT_BOOL("rrt_ahead", rrt_ahead),
-    MJPL_OPT_INT("rrt_ahead_lanes", rrt_ahead_lanes, 1, 1 << 30),
-    MJPL_OPT_INT("rrt_proj_waves", rrt_proj_waves, 1, 1 << 20),
+    MJPL_OPT_BOOL("rrt_early_nn", rrt.early_nn),
+    MJPL_OPT_INT("rrt_early_lanes", rrt.early_lanes, 1, 1 << 30),
+    MJPL_OPT_INT("rrt_early_min_nodes", rrt.early_min_nodes, 1, 1ll << 40),
+    MJPL_OPT_BOOL("rrt_early_next", rrt.early_next),
+    MJPL_OPT_INT("rrt_proj_steps", rrt.proj_steps, 1, 1 << 30),
+    MJPL_OPT_INT("rrt_proj_slots", rrt.proj_slots, 1, 1ll << 40),
+    {"rrt_proj_g", [](mjpl_engine *e) { return (double)e->rrt.proj_g; },
+     [](mjpl_engine *e, double v) { const int g = (int)v; e->rrt.proj_g = (g == 1 || g == 4 || g == 8 || g == 16 || g == 64) ? g : 0; return true; }},
+    MJPL_OPT_BOOL("rrt_ahead", rrt.ahead),
+    MJPL_OPT_INT("rrt_ahead_lanes", rrt.ahead_lanes, 1, 1 << 30),
+    MJPL_OPT_INT("rrt_proj_waves", rrt.proj_waves, 1, 1 << 20),
     // ---- nearest neighbour
     MJPL_OPT_BOOL("nn_cells", nn_cells),
     MJPL_OPT_BOOL("nn_home", nn_home),
@@ -3765,7 +3787,7 @@ int pose_check(const mjpl_pose *p, const void *a, int64_t n) {
 // a row gets as many lanes as that allows -- eight up to 8 192 rows, four up to 16 384 (the lanes split a third of a
 // Newton step's instructions) -- and every row starts with the launch: such batches are bound by their slowest row,
 // which must not wait for a free lane first.  Beyond that one lane per row, and a wave owns ceil(N / 1 024) >= 64 rows:
-// it refills as rows end.  MJPL_ROWS_G: force the lanes per row (A/B timing).
+// it refills as rows end.  Option "rows_g": force the lanes per row (A/B timing).
 struct RowsShape { int G; unsigned grid; int64_t per; };
 RowsShape rows_shape(int64_t N, int forced = 0) {  // (forced: option "rows_g" -- tests compare the three kernels on one batch)
   const int64_t max_waves = 1024;  // one per SIMD: what the row kernels' registers allow (mjpl_rows.h)

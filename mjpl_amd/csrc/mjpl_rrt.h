@@ -1,6 +1,5 @@
 // mjpl_rrt.h -- device-resident frontier bi-RRT and the RCCL exchange (SURVEY.md section 8e,
-// BASELINE configs[3]).  Included at the end of mjpl_hip.hip: same translation unit, so it uses the
-// engine's launch helpers directly.
+// BASELINE configs[3]).  Included at the end of mjpl_hip.hip: same translation unit.
 //
 // What it replaces, for L lanes at a time: RRT.plan_to_configs' sample / extend / connect loop
 // (reference src/mjpl/planning/rrt.py:190-235) with _constrained_extend's per-step accept / stop
@@ -50,8 +49,6 @@ struct RrtCarry {
 };
 
 // ----------------------------------------------------------------------------- kernels
-constexpr int kRingStride = 32;  // ints per slot of the pinned counter ring
-
 __global__ void __launch_bounds__(256)
 k_rrt_sample(int L, int nplan, uint64_t key, double pgoal, int grow, int ngoal, const double *__restrict__ lo,
              const double *__restrict__ hi, const double *__restrict__ qinit, const double *__restrict__ goalQ,
@@ -246,17 +243,10 @@ k_rrt_gen(int L, int nplan_arg, int S_arg, int max_steps, double eps, const doub
 
 // accept the leading valid candidates of every lane
 __global__ void __launch_bounds__(256)
-k_rrt_accept(int L, int nplan, RrtLanes ln, RrtCand cd, RrtAcc acc, int *__restrict__ ctr, int *__restrict__ host_slot, int seq,
-             int next_list, int max_steps, int second, const double *__restrict__ Tgt, RrtCarry cy) {
+k_rrt_accept(int L, int nplan, RrtLanes ln, RrtCand cd, RrtAcc acc, int *__restrict__ ctr, int next_list, int max_steps, int second,
+             const double *__restrict__ Tgt, RrtCarry cy) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  // The chunk's counts are closed (the generating kernel is through): leave them in the pinned block the host
-  // will look at two chunks from now (RC_SIZE ints and a sequence word written last) ...
-  if (host_slot && l < RC_SIZE) {
-    __hip_atomic_store(host_slot + l, ctr[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    if (l == 0) __hip_atomic_store(host_slot + 16, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  // ... and clear them for the next chunk instead of two fills
+  // the chunk's counts are closed (the generating kernel is through): clear them for the next chunk instead of two fills
   if (l == 0) { ctr[RC_EDGES] = 0; ctr[RC_ACTIVE] = 0; }
   // (every lane of the wave stays to the end: the accepted rows are copied by the whole wave)
   const bool live = l < L && ln.act[l] != 0;
@@ -588,6 +578,29 @@ Rccl *rccl() {
 
 constexpr int kNcclInt8 = 0;  // ncclInt8 / ncclChar
 
+// What exists only for the look-ups ahead of their round (RrtTuning: early_nn): a second stream, its events and scratch,
+// and the answers that wait there for the connect phase and for the next round.
+struct RrtEarly {
+  bool on = false;            // this round's first extension started the early look-up
+  hipStream_t side = nullptr;
+  hipEvent_t ev_tail = nullptr, ev_near = nullptr, ev_pre = nullptr;
+  double *d_RAe = nullptr;    // [nplan][L] what the lanes had reached when the early look-up started
+  int32_t *d_near_e = nullptr, *d_late_pos = nullptr, *d_late_near = nullptr;
+  uint8_t *d_early = nullptr; // the lane's answer is the early one
+  double *d_late_q = nullptr; // [nplan][early_lanes] the other lanes' queries, packed (padded with the first of them)
+  // ... and, behind that look-up on the same stream, the NEXT round's targets (counter-based draws: they depend on the seed,
+  // the rank and the round number only) against the nodes its growing tree holds NOW -- the tree this round's connect phase
+  // extends; what that adds is appended at the round's end, behind them, and is all the next round still has to scan
+  // (nearest_range: lower indices win ties, as in one scan).  pre_round: the round the draws are for (0: none).
+  int pre_round = 0;
+  int pre_n0 = 0;             // nodes of that tree covered by the early answers
+  double *d_Tn = nullptr;     // [nplan][L] the next round's targets
+  int32_t *d_goal_n = nullptr, *d_first_n = nullptr, *d_pre_idx = nullptr;
+  double *d_pre_d2 = nullptr;
+  // the look-ups on the second stream use their own scratch (the engine's may be in use by a look-up on the first)
+  NnScratch side_nn;
+};
+
 }  // namespace
 
 struct mjpl_rrt {
@@ -617,61 +630,14 @@ struct mjpl_rrt {
   double *d_pendQ[2] = {nullptr, nullptr};
   int32_t *d_pendpar[2] = {nullptr, nullptr};
   int pendcap = 0;
-  // projecting extensions: most steps a lane takes per chunk, and the candidate slots a chunk is sized for
-  // (S = min(proj_steps_max, proj_slots / active lanes); MJPL_RRT_PROJ_STEPS / MJPL_RRT_PROJ_SLOTS)
-  // (round 4, with the chain as generated code a step is cheap enough for the chunk's fixed cost to show: 64 / 65 536 ->
-  //  65.2 ms per 131 072-lane round, 256 / 262 144 -> 62.6, 1 024 / 1 048 576 -> 59.8; the slots are bounded by the
-  //  candidate buffer, 4 L, all the same)
-  int proj_steps_max = 1024;
-  int64_t proj_slots = 1 << 20;
-  // ... and the shape of the generating launch (mjpl_rows.h; mjpl_hip.hip: rows_shape): lanes per row, waves per launch
-  // (one per SIMD: the kernels' registers) -- MJPL_RRT_PROJ_G / MJPL_RRT_PROJ_WAVES for A/B timing
-  int proj_g = 0;            // 0: lanes per row by the number of active lanes (rows_shape); 1 / 4 / 8 / 16 forced
-  // rows of sixteen lanes that run a step ahead (mjpl_rows.h: k_rrt_gen_project_ahead), when no more lanes than this extend:
-  // one row per wave (measured: with four rows per wave, 1 536 lanes, 14.0 ms against 13.5 with eight lanes per row -- the
-  // statements of running ahead are paid by every row of the wave; one row per wave, 268 lanes x 1 024 steps: 20.5 ms
-  // against 23.9).  MJPL_RRT_AHEAD=0: never; MJPL_RRT_AHEAD_LANES
-  int ahead = 1, ahead_lanes = 1024;
-  int proj_waves_max = 1024;
-  // The connect phase's nearest neighbours, early (round 5).  A lane's round does not depend on any other lane's (both trees
-  // are the round's snapshot), and the tail of the first extension is a handful of lanes taking a thousand sequential steps
-  // on an otherwise idle chip: once no more than `early_lanes` lanes are still extending, the lanes that are through get
-  // their nearest node of the OTHER tree on a second stream (what they reached is final: ln.C of a lane with act == 0);
-  // the second extension then looks up only the lanes that were still under way, and waits for the early answers.  The
-  // same queries against the same nodes: the same nodes.  MJPL_RRT_EARLY_NN=0 turns it off; MJPL_RRT_EARLY_LANES /
-  // MJPL_RRT_EARLY_MIN_NODES move the thresholds (tests set them low).
-  int exact_counts = 1;  // a projecting extension reads every chunk's lane count before it sizes the chunk (MJPL_RRT_EXACT_COUNTS=0: two chunks late, from the pinned ring)
-  int early_nn = 1, early_lanes = 4096, early_next = 1;  // (early_next: the next round's look-up as well, MJPL_RRT_EARLY_NEXT=0: not)
-  int64_t early_min_nodes = 65536;
-  bool early_on = false;      // this round's first extension started the early look-up
-  hipStream_t side = nullptr;
-  hipEvent_t ev_tail = nullptr, ev_near = nullptr;
-  double *d_RAe = nullptr;    // [nplan][L] what the lanes had reached when the early look-up started
-  int32_t *d_near_e = nullptr, *d_late_pos = nullptr, *d_late_near = nullptr;
-  uint8_t *d_early = nullptr; // the lane's answer is the early one
-  double *d_late_q = nullptr; // [nplan][early_lanes] the other lanes' queries, packed (padded with the first of them)
-  // ... and, behind that look-up on the same stream, the NEXT round's targets (counter-based draws: they depend on the seed,
-  // the rank and the round number only) against the nodes its growing tree holds NOW -- the tree this round's connect phase
-  // extends; what that adds is appended at the round's end, behind them, and is all the next round still has to scan
-  // (nearest_range: lower indices win ties, as in one scan).  pre_round: the round the draws are for (0: none).
-  int pre_round = 0;
-  int pre_n0 = 0;             // nodes of that tree covered by the early answers
-  double *d_Tn = nullptr;     // [nplan][L] the next round's targets
-  int32_t *d_goal_n = nullptr, *d_first_n = nullptr, *d_pre_idx = nullptr;
-  double *d_pre_d2 = nullptr;
-  hipEvent_t ev_pre = nullptr;
-  // the look-ups on the second stream use their own scratch (the engine's may be in use by a look-up on the first)
-  NnScratch side_nn;
-  int *d_ctr = nullptr, *h_ctr = nullptr;
-  // projecting extensions read their chunk counters two chunks late (rrt_extend): a ring of pinned copies
-  int *h_ring = nullptr;      // 4 slots of kRingStride ints: RC_SIZE counters, then the sequence word
-  int ring_seq0 = 1;          // sequence number of chunk 0 of the extension under way (never repeats within the ring)
+  RrtTuning tune;              // the engine's knobs as they stood when the planner was made (early_nn: only with a pose)
+  RrtEarly early;
+  int *d_ctr = nullptr, *h_ctr = nullptr;  // the counter block (RC_*) and its pinned copy: read once per chunk
   // exchange
   int *d_heads = nullptr, *h_heads = nullptr;
-  char *d_gather = nullptr;
-  size_t gather_bytes = 0;
+  DevBuf<char> gather;         // every rank's slabs of a round, padded to the round's largest
   double *d_path = nullptr;
-  std::vector<void *> owned;
+  std::vector<void *> owned, pinned;  // device / pinned host allocations (rrt_alloc, rrt_alloc_pinned): freed by mjpl_rrt_destroy
   // result of the last successful round
   int conn_start = -1, conn_goal = -1;
   // rank identity when the caller moves the slabs itself (mjpl_rrt_set_world); else the engine's communicator
@@ -692,12 +658,23 @@ int rrt_alloc(mjpl_rrt *r, T **p, size_t count) {
   *p = (T *)v;
   return MJPL_OK;
 }
+template <class T>
+int rrt_alloc_pinned(mjpl_rrt *r, T **p, size_t count) {
+  HIP_TRY(hipHostMalloc((void **)p, count * sizeof(T)));
+  r->pinned.push_back(*p);
+  return MJPL_OK;
+}
 
 inline unsigned rgrid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// MJPL_RRT_TRACE=1: where a round's wall time goes (stderr; synchronises the stream at every mark)
+inline int rrt_launched(const char *stage) {  // (what a stage that launched kernels returns: a failed launch is named by it)
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? MJPL_OK : fail(MJPL_E_HIP, "rrt: a launch of %s failed: %s", stage, hipGetErrorString(err));
+}
+
+// option "rrt_trace": where a round's wall time goes (stderr; synchronises the stream at every mark)
 struct RrtTrace {
-  bool on, chunks;  // option "rrt_trace": 1 = the phases, 2 = a line per extension chunk as well (the stream is synchronised at every mark)
+  bool on, chunks;  // 1 = the phases, 2 = a line per extension chunk as well
   explicit RrtTrace(const mjpl_engine *e) : on(e->rrt_trace >= 1), chunks(e->rrt_trace >= 2) {}
   void chunk(hipStream_t st, int index, int active, int S, int G, unsigned grid) {
     if (!chunks) return;
@@ -727,9 +704,14 @@ struct RrtTrace {
   }
 };
 
-int rrt_read_ctr(mjpl_rrt *r) {
+// The counter block read (a 64-byte copy and a wait for it), its overflow bits turned into the capacity errors.  cand_fatal:
+// a lane refused candidate space is one -- with a projection every listed lane owns its slots; without, the lane waits.
+int rrt_read_counters(mjpl_rrt *r, bool cand_fatal) {
   HIP_TRY(hipMemcpyAsync(r->h_ctr, r->d_ctr, RC_SIZE * sizeof(int), hipMemcpyDeviceToHost, r->e->stream));
   HIP_TRY(hipStreamSynchronize(r->e->stream));
+  const int over = r->h_ctr[RC_OVERFLOW];
+  if (over & 2) return fail(MJPL_E_CAPACITY, "rrt: more new nodes in one extension than the pending slab holds");
+  if ((over & 1) && cand_fatal) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer overrun in a projecting extension");
   return MJPL_OK;
 }
 
@@ -741,245 +723,242 @@ int rrt_rank(const mjpl_rrt *r);
 // (Past mjpl_nearest_dev's argument checks, its return for M == 0 among them: both callers pass the planner's lanes,
 //  L >= 1, and a tree of at least one node.)
 int rrt_side_nearest(mjpl_rrt *r, const double *nodes, int64_t n, const double *queries, int64_t M, int32_t *idx, double *d2) {
-  return nearest_core(r->e, r->side_nn, {nodes, n, r->cap, queries, M, idx, d2, nullptr, r->side});
+  return nearest_core(r->e, r->early.side_nn, {nodes, n, r->cap, queries, M, idx, d2, nullptr, r->early.side});
 }
 
-// one extension of tree `t` towards the targets Tgt ([nplan][L]); `second`: the connect phase
-int rrt_extend(mjpl_rrt *r, int t, const double *Tgt, int second, int *nnew) {
-  mjpl_engine *e = r->e;
-  hipStream_t st = e->stream;
+// ----------------------------------------------------------------------------- the chunk policy: numbers in, numbers out
+// Without a projection the candidates do not depend on the verdicts.  Four steps per lane in the first chunk of a big
+// batch, doubling; a small batch -- a planner of a few hundred lanes -- starts with as many as 2^16 candidate slots allow,
+// up to 64: its chunks cost their launches' latency whatever they hold, and an extension of six chunks becomes one of two.
+inline int free_first_steps(int L, int cand_cap) {
+  const int l = std::max(1, L);
+  return (int)std::max<int64_t>(4, std::min<int64_t>(std::min<int64_t>(64, ((int64_t)1 << 16) / l), (int64_t)cand_cap / l));
+}
+// chunk sizes double: a chain of n steps costs O(log n) chunks and at most 2x its own checks
+inline int free_next_steps(int S, int active, int cand_cap) {
+  return S < 64 ? (int)std::max<int64_t>(1, std::min<int64_t>(2 * S, (int64_t)cand_cap / std::max(1, active))) : S;
+}
+// every waiting lane was refused space -- S is too large for the space left: one step per lane (0: it was one already)
+inline int free_retry_steps(int S) { return S == 1 ? 0 : 1; }
+// (lanes that were refused candidate space have reserved slots all the same: RC_EDGES may exceed the buffer)
+inline int free_chunk_rows(int edges, int cand_cap) { return std::min(edges, cand_cap); }
+
+// With a projection every active lane owns S slots of the chunk's candidates.  One step while the chunk's kernels are busy
+// with the lanes there are; more when they are not -- a chunk then costs the latency of its launches whatever it holds,
+// and S steps share it.  The speculation costs slots and nothing else: a lane that stops early stops generating.
+inline int proj_chunk_steps(const RrtTuning &tn, int active, int cand_cap, int max_steps, int steps_done) {
+  const int a = std::max(1, active);
+  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(tn.proj_steps, tn.proj_slots / a), (int64_t)cand_cap / a));
+  // the cap: a lane still extending has added every step of every chunk so far (any other outcome ended it)
+  return max_steps > 0 ? std::min(S, std::max(1, max_steps - steps_done)) : S;
+}
+inline int proj_chunk_rows(int S, int active, int cand_cap) { return (int)std::min<int64_t>((int64_t)S * active, cand_cap); }
+
+// The generating launch of a projecting chunk walks the chunk's packed list with waves that refill (mjpl_rows.h): one lane
+// per row while there are many, four or eight once all of them fit the chip at once (rows_shape) -- the tail of an
+// extension, which is most of its time.  Few rows: sixteen lanes each, the next step's first Newton pass beside this
+// step's closing evaluation (k_rrt_gen_project_ahead) -- G = 64 says sixteen lanes per row all the same, ONE row per wave.
+struct GenShape { int G; unsigned waves; };
+inline GenShape gen_shape(const RrtTuning &tn, int active, int G) {
+  const int64_t rows_per_wave = G == 64 ? 1 : 64 / G;
+  return {G, (unsigned)std::max<int64_t>(1, std::min<int64_t>(tn.proj_waves, (active + rows_per_wave - 1) / rows_per_wave))};
+}
+// ... the shape to try first, and the one for a library without the step-ahead kernels (G == 0: the first is none of theirs)
+struct GenPlan { GenShape planned, fallback; };
+inline GenPlan plan_gen(const RrtTuning &tn, int active, int rows_g) {
+  if (tn.proj_g > 0) return {gen_shape(tn, active, tn.proj_g), {0, 0u}};
+  const GenShape rows = gen_shape(tn, active, rows_shape(active, rows_g).G);
+  if (!tn.ahead || active > tn.ahead_lanes) return {rows, {0, 0u}};
+  return {gen_shape(tn, active, active <= tn.proj_waves ? 64 : 16), rows};
+}
+
+// ----------------------------------------------------------------------------- the stages of an extension
+// The look-ups that run beside the tail of the first extension (RrtTuning: early_nn), started once, when no more than
+// early_lanes lanes still extend: everything enqueued so far (the acceptance of the chunk before) decides which are through.
+int start_tail_lookups(mjpl_rrt *r, int t, int active) {
+  RrtEarly &ea = r->early;
+  const RrtTuning &tn = r->tune;
+  const bool first = t == (r->round - 1) % 2;  // (the tree that grows this round: the first extension)
+  if (!first || !tn.early_nn || ea.on || active > tn.early_lanes || r->n[1 - t] < tn.early_min_nodes) return MJPL_OK;
+  hipStream_t st = r->e->stream;
   const int L = r->L, nplan = r->nplan;
-  RrtTrace tr(e);
-  tr.mark(st, "(before the extension)");
-  int rc = MJPL_OK;
-  if (second && r->early_on) {
+  // (the snapshot of who is through, and of what they reached, is taken on the MAIN stream, between two chunks: on the
+  //  second stream it would read act / C while a later chunk's acceptance kernel writes them)
+  hipLaunchKernelGGL(k_rrt_early, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->ln, ea.d_early, ea.d_RAe);
+  HIP_TRY(hipEventRecord(ea.ev_tail, st));
+  HIP_TRY(hipStreamWaitEvent(ea.side, ea.ev_tail, 0));
+  MJPL_TRY(rrt_side_nearest(r, r->d_Q[1 - t], r->n[1 - t], ea.d_RAe, L, ea.d_near_e, nullptr));
+  HIP_TRY(hipEventRecord(ea.ev_near, ea.side));
+  if (tn.early_next) {
+    // the next round: its growing tree is 1 - t, its draws are keyed by the round number
+    RrtLanes lnn = r->ln;
+    lnn.T = ea.d_Tn; lnn.goal = ea.d_goal_n;
+    const int nf = std::max(r->ngoal, 1);
+    hipLaunchKernelGGL(k_rrt_first_init, dim3(rgrid(nf)), dim3(256), 0, ea.side, ea.d_first_n, nf);
+    hipLaunchKernelGGL(k_rrt_sample, dim3(rgrid(L)), dim3(256), 0, ea.side, L, nplan,
+                       rrt_key(r->seed, (uint64_t)rrt_rank(r), (uint64_t)(r->round + 1)), r->pgoal, 1 - t, r->ngoal, r->d_lo, r->d_hi,
+                       r->d_qinit, r->d_Q[1], r->cap, lnn, ea.d_first_n, r->carry[1 - t]);
+    MJPL_TRY(rrt_side_nearest(r, r->d_Q[1 - t], r->n[1 - t], ea.d_Tn, L, ea.d_pre_idx, ea.d_pre_d2));
+    HIP_TRY(hipEventRecord(ea.ev_pre, ea.side));
+    ea.pre_round = r->round + 1;
+    ea.pre_n0 = r->n[1 - t];
+  }
+  ea.on = true;
+  return rrt_launched("start_tail_lookups");
+}
+
+// One extension of tree `t` towards the targets Tgt ([nplan][L]); `second`: the connect phase.  Its stages: rrt_extend.
+struct Extension {
+  mjpl_rrt *r; mjpl_engine *e; hipStream_t st;
+  int L, nplan, t; const double *Tgt; int second;
+  RrtTrace tr;
+  int extend_lookup(), extend_open(), chunks_projecting(int *chunks), chunks_free(int *chunks), extend_close(int *nnew);
+  int launch_gen(int S), launch_gen_project(int list, int active, int S, GenShape *shape), validate_and_accept(int rows, int next_list);
+};
+
+// the lanes' nearest nodes of the tree, by one of three routes
+int Extension::extend_lookup() {
+  RrtEarly &ea = r->early;
+  if (second && ea.on) {
     // the lanes that were through when the first extension's tail began have their answers (or will have: ev_near);
     // the others -- early_lanes at most -- are looked up now
-    r->early_on = false;
-    const int room = r->early_lanes;
-    HIP_TRY(hipMemsetAsync(r->d_late_near, 0, sizeof(int), st));  // ([0] doubles as the list's counter until the look-up writes it)
-    hipLaunchKernelGGL(k_rrt_late_list, dim3(rgrid(L)), dim3(256), 0, st, L, r->d_early, r->d_late_pos, (int *)r->d_late_near);
-    hipLaunchKernelGGL(k_rrt_late_fill, dim3(rgrid(room)), dim3(256), 0, st, L, nplan, room, Tgt, r->d_late_q);
-    hipLaunchKernelGGL(k_rrt_late_queries, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, room, r->d_early, r->d_late_pos, Tgt, r->d_late_q,
+    ea.on = false;
+    const int room = r->tune.early_lanes;
+    HIP_TRY(hipMemsetAsync(ea.d_late_near, 0, sizeof(int), st));  // ([0] doubles as the list's counter until the look-up writes it)
+    hipLaunchKernelGGL(k_rrt_late_list, dim3(rgrid(L)), dim3(256), 0, st, L, ea.d_early, ea.d_late_pos, (int *)ea.d_late_near);
+    hipLaunchKernelGGL(k_rrt_late_fill, dim3(rgrid(room)), dim3(256), 0, st, L, nplan, room, Tgt, ea.d_late_q);
+    hipLaunchKernelGGL(k_rrt_late_queries, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, room, ea.d_early, ea.d_late_pos, Tgt, ea.d_late_q,
                        r->d_ctr);
-    HIP_TRY(hipStreamWaitEvent(st, r->ev_near, 0));  // (d_near_e: the early answers, written on the second stream)
-    rc = mjpl_nearest_dev(e, r->d_Q[t], r->n[t], r->cap, r->d_late_q, room, r->d_late_near, nullptr);
-    if (rc != MJPL_OK) return rc;
-    hipLaunchKernelGGL(k_rrt_near_merge, dim3(rgrid(L)), dim3(256), 0, st, L, room, r->d_early, r->d_late_pos, r->d_near_e, r->d_late_near,
+    HIP_TRY(hipStreamWaitEvent(st, ea.ev_near, 0));  // (d_near_e: the early answers, written on the second stream)
+    MJPL_TRY(mjpl_nearest_dev(e, r->d_Q[t], r->n[t], r->cap, ea.d_late_q, room, ea.d_late_near, nullptr));
+    hipLaunchKernelGGL(k_rrt_near_merge, dim3(rgrid(L)), dim3(256), 0, st, L, room, ea.d_early, ea.d_late_pos, ea.d_near_e, ea.d_late_near,
                        r->ln.near);
     tr.mark(st, "nearest neighbour (the lanes of the tail; the others were looked up early)", r->n[t]);
     tr.nn(e);
-  } else if (!second && r->pre_round == r->round && r->pre_n0 <= r->n[t]) {
+  } else if (!second && ea.pre_round == r->round && ea.pre_n0 <= r->n[t]) {
     // this round's targets were looked up in the tree's first pre_n0 nodes while the round before ran its tail
-    r->pre_round = 0;
-    HIP_TRY(hipStreamWaitEvent(st, r->ev_pre, 0));
-    rc = nearest_range(e, e->nn, st, r->d_Q[t], r->pre_n0, r->n[t], r->cap, Tgt, L, r->ln.near, nullptr, r->d_pre_idx, r->d_pre_d2);
-    if (rc != MJPL_OK) return rc;
-    tr.mark(st, "nearest neighbour (the nodes of the last round; the others were scanned early)", r->n[t] - r->pre_n0);
+    ea.pre_round = 0;
+    HIP_TRY(hipStreamWaitEvent(st, ea.ev_pre, 0));
+    MJPL_TRY(nearest_range(e, e->nn, st, r->d_Q[t], ea.pre_n0, r->n[t], r->cap, Tgt, L, r->ln.near, nullptr, ea.d_pre_idx, ea.d_pre_d2));
+    tr.mark(st, "nearest neighbour (the nodes of the last round; the others were scanned early)", r->n[t] - ea.pre_n0);
   } else {
-    rc = mjpl_nearest_dev(e, r->d_Q[t], r->n[t], r->cap, Tgt, L, r->ln.near, nullptr);
-    if (rc != MJPL_OK) return rc;
+    MJPL_TRY(mjpl_nearest_dev(e, r->d_Q[t], r->n[t], r->cap, Tgt, L, r->ln.near, nullptr));
     tr.mark(st, "nearest neighbour", r->n[t]);
     tr.nn(e);
   }
-  const bool projecting = r->pose != nullptr;
-  if (projecting) HIP_TRY(hipMemsetAsync(r->d_ctr + RC_LISTN, 0, 2 * sizeof(int), st));  // (both lists of the extension: empty)
+  return rrt_launched("extend_lookup");
+}
+
+// every lane at its nearest node, on or off; a projecting extension works from packed lists of its active lanes
+int Extension::extend_open() {
+  if (r->pose) HIP_TRY(hipMemsetAsync(r->d_ctr + RC_LISTN, 0, 2 * sizeof(int), st));  // (both lists of the extension: empty)
   hipLaunchKernelGGL(k_rrt_begin, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->d_Q[t], r->cap, r->ln, r->d_first, Tgt,
                      second, r->d_ctr, r->carry[second ? 1 - t : t],  // (the records of the tree that grows this round)
                      (const int32_t *)r->d_cf, r->d_coff);
-  if (projecting) hipLaunchKernelGGL(k_rrt_list_begin, dim3(rgrid(L)), dim3(256), 0, st, L, r->ln, r->d_ctr);
-  // (without a projection: four steps per lane in the first chunk of a big batch, doubling; a small batch -- a planner of
-  //  a few hundred lanes -- starts with as many as 2^16 candidate slots allow, up to 64: its chunks cost their launches'
-  //  latency whatever they hold, and an extension of six chunks becomes one of two)
-  int S = projecting ? 1 : (int)std::max<int64_t>(4, std::min<int64_t>(std::min<int64_t>(64, ((int64_t)1 << 16) / std::max(1, L)), (int64_t)r->cd.cap / std::max(1, L)));
-  // With a projecting constraint an extension is hundreds of chunks, the late ones with a handful of lanes:
-  // waiting for every chunk's counters before sizing its launches would leave the GPU idle while the host
-  // enqueues the next kernels.  Lanes only ever leave an extension, and every active lane owns S slots of the
-  // chunk's candidates, so the active count of two chunks ago bounds this chunk's: chunk i is sized by it -- the
-  // surplus rows are earlier chunks' candidates, validated again and read by nobody -- and the loop ends two
-  // chunks after the last lane has.  The counters come from a pinned ring k_rrt_accept writes (slot chunk % 4):
-  // no copy, no event, the host spins on a sequence word.
-  if (projecting && r->cd.cap < L) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer too small for one step per lane");
-  int chunks_done = 0;
-  // Sequence numbers of the pinned ring never repeat -- on ANY way out of this function: an extension that
-  // fails half-way has k_rrt_accept launches in flight that still write their slots, and the next extension
-  // on this planner must neither meet their numbers again nor find a stale slot that already carries the
-  // number it waits for.  A failing exit therefore also waits for the stream before the numbers move on.
-  struct RingGuard {
-    mjpl_rrt *r; const int *chunks; hipStream_t st; bool ok;
-    ~RingGuard() {
-      if (!ok) (void)hipStreamSynchronize(st);
-      r->ring_seq0 += *chunks + 8;
-    }
-  } ring_guard{r, &chunks_done, st, false};
-  // the look-ups that run beside the tail of the first extension (mjpl_rrt: early_nn), started once, when no more than
-  // early_lanes lanes are still extending: everything enqueued so far (the acceptance of the chunk before last) decides
-  // which lanes are through
-  auto start_tail_lookups = [&](int active) -> int {
-    if (second || !r->early_nn || r->early_on || active > r->early_lanes || r->n[1 - t] < r->early_min_nodes) return MJPL_OK;
-    // (the snapshot of who is through, and of what they reached, is taken on the MAIN stream, between two chunks: on the
-    //  second stream it would read act / C while a later chunk's acceptance kernel writes them)
-    hipLaunchKernelGGL(k_rrt_early, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->ln, r->d_early, r->d_RAe);
-    HIP_TRY(hipEventRecord(r->ev_tail, st));
-    HIP_TRY(hipStreamWaitEvent(r->side, r->ev_tail, 0));
-    int nrc = rrt_side_nearest(r, r->d_Q[1 - t], r->n[1 - t], r->d_RAe, L, r->d_near_e, nullptr);
-    if (nrc != MJPL_OK) return nrc;
-    HIP_TRY(hipEventRecord(r->ev_near, r->side));
-    if (r->early_next) {
-      // the next round: its growing tree is 1 - t, its draws are keyed by the round number
-      RrtLanes lnn = r->ln;
-      lnn.T = r->d_Tn; lnn.goal = r->d_goal_n;
-      const int nf = std::max(r->ngoal, 1);
-      hipLaunchKernelGGL(k_rrt_first_init, dim3(rgrid(nf)), dim3(256), 0, r->side, r->d_first_n, nf);
-      hipLaunchKernelGGL(k_rrt_sample, dim3(rgrid(L)), dim3(256), 0, r->side, L, nplan,
-                         rrt_key(r->seed, (uint64_t)rrt_rank(r), (uint64_t)(r->round + 1)), r->pgoal, 1 - t, r->ngoal, r->d_lo, r->d_hi,
-                         r->d_qinit, r->d_Q[1], r->cap, lnn, r->d_first_n, r->carry[1 - t]);
-      nrc = rrt_side_nearest(r, r->d_Q[1 - t], r->n[1 - t], r->d_Tn, L, r->d_pre_idx, r->d_pre_d2);
-      if (nrc != MJPL_OK) return nrc;
-      HIP_TRY(hipEventRecord(r->ev_pre, r->side));
-      r->pre_round = r->round + 1;
-      r->pre_n0 = r->n[1 - t];
-    }
-    r->early_on = true;
-    return MJPL_OK;
-  };
-  int active_bound = L;  // (projecting) no more lanes than this are active in the chunk about to be launched
-  int steps_done = 0;    // (projecting) steps per lane of the chunks launched so far
-  int trace_G = 0;
-  unsigned trace_grid = 0;
-  for (int chunk = 0;; chunk++) {
-    chunks_done = chunk + 1;
-    if (projecting) {
-      if (r->exact_counts) {
-        // Round 5: the chunk's list has been closed by the acceptance kernel before it (chunk 0: by k_rrt_list_begin); its
-        // length IS the number of active lanes.  Reading it costs a trip to the host with the chip idle (~30 us) and buys
-        // the right number of steps for the chunk: sized by the count of two chunks ago (below) an extension's first three
-        // chunks all took four steps and it needed eight to ten chunks where five or six do (profiles/README.md).
-        if ((rc = rrt_read_ctr(r)) != MJPL_OK) return rc;
-        if (r->h_ctr[RC_OVERFLOW] & 2) return fail(MJPL_E_CAPACITY, "rrt: more new nodes in one extension than the pending slab holds");
-        if (r->h_ctr[RC_OVERFLOW] & 1) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer overrun in a projecting extension");
-        if (r->h_ctr[RC_LISTN + (chunk & 1)] == 0) break;
-        active_bound = r->h_ctr[RC_LISTN + (chunk & 1)];
-        if (chunk >= 1 && (rc = start_tail_lookups(active_bound)) != MJPL_OK) return rc;
-      } else if (chunk >= 2) {
-        const int look = (chunk - 2) % 4;
-        volatile int *slot = r->h_ring + look * kRingStride;
-        const int want = r->ring_seq0 + chunk - 2;
-        for (long spins = 0; __atomic_load_n(slot + 16, __ATOMIC_ACQUIRE) != want; spins++) {
-          if (spins > 2000000000L) return fail(MJPL_E_HIP, "rrt: the counters of an extension chunk never arrived");
-          __builtin_ia32_pause();
-        }
-        for (int k = 0; k < RC_SIZE; k++) r->h_ctr[k] = slot[k];
-        if (r->h_ctr[RC_OVERFLOW] & 2) return fail(MJPL_E_CAPACITY, "rrt: more new nodes in one extension than the pending slab holds");
-        if (r->h_ctr[RC_OVERFLOW] & 1) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer overrun in a projecting extension");
-        if (r->h_ctr[RC_ACTIVE] == 0) break;
-        active_bound = r->h_ctr[RC_ACTIVE];
-        if ((rc = start_tail_lookups(active_bound)) != MJPL_OK) return rc;
-      }
-      // Steps per chunk: one while the chunk's kernels are busy with the lanes there are; more when they are
-      // not -- a chunk then costs the latency of its launches whatever it holds, and S steps share it.  The
-      // speculation costs slots (S per lane) and nothing else: a lane that stops early stops generating.
-      S = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(r->proj_steps_max, r->proj_slots / std::max(1, active_bound)),
-                                                      (int64_t)r->cd.cap / std::max(1, active_bound)));
-      // the cap: a lane still extending has added every step of every chunk so far (any other outcome ended it)
-      if (r->max_steps > 0) S = std::min(S, std::max(1, r->max_steps - steps_done));
-      {
-        // The chunk's rows are the packed list chunk & 1 (at most active_bound entries).  A model's library walks them
-        // with waves that refill (mjpl_rows.h): one lane per row while there are many, four or eight lanes per row once
-        // all of them fit the chip at once (rows_shape) -- the tail of an extension, which is most of its time.
-        const int par = chunk & 1;
-        const size_t plds = pose_lds(r->pose) + (size_t)kPoseBlock * sizeof(double) * (size_t)r->nq;
-        const int pk = pose_spec_index(r->pose);  // (the chain as straight-line code, if the engine's library has it)
-        int launched = -1;
-        KtScope kt_scope(e, 1);  // (option "kernel_timer": the generating kernel of every chunk)
-        trace_G = 1; trace_grid = (unsigned)((active_bound + kPoseBlock - 1) / kPoseBlock);
-        if (pk >= 0) {
-          const RowsShape rs = r->proj_g > 0 ? RowsShape{r->proj_g, 0u, 0} : rows_shape(active_bound, e->rows_g);
-          // (few rows: sixteen lanes each, the next step's first Newton pass beside this step's closing evaluation -- mjpl_rows.h,
-          //  k_rrt_gen_project_ahead; a library without that kernel refuses and the chunk falls back below)
-          const int G = (r->proj_g == 0 && r->ahead && active_bound <= r->ahead_lanes) ? (active_bound <= r->proj_waves_max ? 64 : 16) : rs.G;
-          const int64_t rows_per_wave = G == 64 ? 1 : 64 / G;  // (64: sixteen lanes per row all the same, ONE row per wave)
-          const unsigned rgridw = (unsigned)std::max<int64_t>(1, std::min<int64_t>(r->proj_waves_max, (active_bound + rows_per_wave - 1) / rows_per_wave));
-          // (a library refuses -- nothing launched, -1 -- when it was built for another number of planning joints)
-          trace_G = G; trace_grid = rgridw;
-          launched = e->spec->gen_project(pk, G, st, rgridw, L, nplan, S, r->eps, par, r->pose->d_pi, r->pose->d_pd, r->d_qidx, r->d_qbase,
-                                          r->d_isplan, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
-          if (launched == -1 && (G == 16 || G == 64) && r->proj_g == 0) {  // (no such kernel in this library: eight lanes per row)
-            const int64_t rpw = 64 / rs.G;
-            const unsigned gw = (unsigned)std::max<int64_t>(1, std::min<int64_t>(r->proj_waves_max, (active_bound + rpw - 1) / rpw));
-            trace_G = rs.G; trace_grid = gw;
-            launched = e->spec->gen_project(pk, rs.G, st, gw, L, nplan, S, r->eps, par, r->pose->d_pi, r->pose->d_pd, r->d_qidx, r->d_qbase,
-                                            r->d_isplan, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
-          }
-          if (launched != 0 && launched != -1) return fail(MJPL_E_HIP, "rrt: the generated extension kernel failed to launch");
-        }
-        if (launched != 0) {
-          const unsigned pgrid = (unsigned)((active_bound + kPoseBlock - 1) / kPoseBlock);
-          hipLaunchKernelGGL(k_rrt_gen_project, dim3(std::max(1u, pgrid)), dim3(kPoseBlock), plds, st, L, nplan, S, r->eps, par, r->pose->d_pi,
-                             r->pose->d_pd, r->d_qidx, r->d_qbase, r->d_isplan, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
-        }
-      }
-      if (!r->exact_counts && chunk < 2) {  // (the first two chunks: their own counts)
-        if ((rc = rrt_read_ctr(r)) != MJPL_OK) return rc;
-        if (r->h_ctr[RC_OVERFLOW] & 3) return fail(MJPL_E_CAPACITY, "rrt: buffer overrun in a projecting extension");
-        if (r->h_ctr[RC_ACTIVE] == 0) break;
-        active_bound = r->h_ctr[RC_ACTIVE];
-      }
-    } else {
-      {
-        auto gen = k_rrt_gen<0>;
-        switch (nplan) {  // (the usual planning sets: their rows in registers)
+  if (r->pose) hipLaunchKernelGGL(k_rrt_list_begin, dim3(rgrid(L)), dim3(256), 0, st, L, r->ln, r->d_ctr);
+  return rrt_launched("extend_open");
+}
+
+// the generating kernel of a chunk without a projection: S steps of every active lane
+int Extension::launch_gen(int S) {
+  auto gen = k_rrt_gen<0>;
+  switch (nplan) {  // (the usual planning sets: their rows in registers)
 #define MJPL_GEN_CASE(n) case n: gen = k_rrt_gen<n>; break;
-          MJPL_GEN_CASE(1) MJPL_GEN_CASE(2) MJPL_GEN_CASE(3) MJPL_GEN_CASE(4) MJPL_GEN_CASE(5) MJPL_GEN_CASE(6) MJPL_GEN_CASE(7)
-          MJPL_GEN_CASE(8) MJPL_GEN_CASE(9) MJPL_GEN_CASE(10) MJPL_GEN_CASE(12)
+    MJPL_GEN_CASE(1) MJPL_GEN_CASE(2) MJPL_GEN_CASE(3) MJPL_GEN_CASE(4) MJPL_GEN_CASE(5) MJPL_GEN_CASE(6) MJPL_GEN_CASE(7)
+    MJPL_GEN_CASE(8) MJPL_GEN_CASE(9) MJPL_GEN_CASE(10) MJPL_GEN_CASE(12)
 #undef MJPL_GEN_CASE
-          default: break;
-        }
-        hipLaunchKernelGGL(gen, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, S, r->max_steps, r->eps, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
-      }
-      if ((rc = rrt_read_ctr(r)) != MJPL_OK) return rc;
-      if (r->h_ctr[RC_OVERFLOW] & 2) return fail(MJPL_E_CAPACITY, "rrt: more new nodes in one extension than the pending slab holds");
-      if (r->h_ctr[RC_ACTIVE] == 0) {
-        if (r->h_ctr[RC_OVERFLOW] & 1) {  // every waiting lane was refused: S is too large for the space left
-          HIP_TRY(hipMemsetAsync(r->d_ctr + RC_OVERFLOW, 0, sizeof(int), st));
-          HIP_TRY(hipMemsetAsync(r->d_ctr + RC_EDGES, 0, sizeof(int), st));  // (k_rrt_accept clears it otherwise)
-          if (S == 1) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer too small for one step per lane");
-          S = 1;
-          continue;
-        }
-        break;
-      }
-      if (r->h_ctr[RC_OVERFLOW] & 1) HIP_TRY(hipMemsetAsync(r->d_ctr + RC_OVERFLOW, 0, sizeof(int), st));
-    }
-    // (lanes that were refused candidate space have reserved slots all the same: RC_EDGES may exceed
-    // the buffer, and only RC_ACTIVE says whether any lane emitted)
-    const int E = projecting ? (int)std::min<int64_t>((int64_t)S * active_bound, r->cd.cap) : std::min(r->h_ctr[RC_EDGES], r->cd.cap);
-    if (r->istep > 0)
-      rc = launch_edges(e, r->cd.A, r->cd.B, E, r->istep, MJPL_AOS, 0, r->cd.valid, nullptr, false);
-    else
-      rc = launch_configs(e, r->cd.B, E, MJPL_AOS, r->cd.valid, nullptr);
-    if (rc != MJPL_OK) return rc;
-    hipLaunchKernelGGL(k_rrt_accept, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->ln, r->cd, r->acc, r->d_ctr,
-                       projecting ? r->h_ring + (chunk % 4) * kRingStride : (int *)nullptr, r->ring_seq0 + chunk,
-                       projecting ? ((chunk + 1) & 1) : -1, r->max_steps, second, Tgt, r->carry[t]);
+    default: break;
+  }
+  hipLaunchKernelGGL(gen, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, S, r->max_steps, r->eps, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
+  return rrt_launched("launch_gen");
+}
+
+// ... and of a projecting chunk: S steps of the `active` lanes of packed list `list`, by the model's library in the planned
+// shape, in the fallback shape when the library answers -1 (no such kernel) for a step-ahead shape, else -- no library, or
+// one built for another number of planning joints: -1 again -- by the interpreting kernel.  *shape: what was launched.
+int Extension::launch_gen_project(int list, int active, int S, GenShape *shape) {
+  const int pk = pose_spec_index(r->pose);  // (the chain as straight-line code, if the engine's library has it)
+  KtScope kt_scope(e, 1);  // (option "kernel_timer": the generating kernel of every chunk)
+  int launched = -1;
+  if (pk >= 0) {
+    const GenPlan p = plan_gen(r->tune, active, e->rows_g);
+    auto gen = [&](GenShape s) {
+      *shape = s;
+      return e->spec->gen_project(pk, s.G, st, s.waves, L, nplan, S, r->eps, list, r->pose->d_pi, r->pose->d_pd, r->d_qidx, r->d_qbase,
+                                  r->d_isplan, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
+    };
+    launched = gen(p.planned);
+    if (launched == -1 && p.fallback.G) launched = gen(p.fallback);
+    if (launched != 0 && launched != -1) return fail(MJPL_E_HIP, "rrt: the generated extension kernel failed to launch");
+  }
+  if (launched != 0) {
+    *shape = {1, std::max(1u, (unsigned)((active + kPoseBlock - 1) / kPoseBlock))};
+    const size_t plds = pose_lds(r->pose) + (size_t)kPoseBlock * sizeof(double) * (size_t)r->nq;
+    hipLaunchKernelGGL(k_rrt_gen_project, dim3(shape->waves), dim3(kPoseBlock), plds, st, L, nplan, S, r->eps, list, r->pose->d_pi,
+                       r->pose->d_pd, r->d_qidx, r->d_qbase, r->d_isplan, r->d_lo, r->d_hi, Tgt, r->ln, r->cd, r->d_ctr);
+  }
+  return rrt_launched("launch_gen_project");
+}
+
+// the first `rows` candidates validated, the leading valid ones of every lane accepted (next_list: k_rrt_accept)
+int Extension::validate_and_accept(int rows, int next_list) {
+  if (r->istep > 0)
+    MJPL_TRY(launch_edges(e, r->cd.A, r->cd.B, rows, r->istep, MJPL_AOS, 0, r->cd.valid, nullptr, false));
+  else
+    MJPL_TRY(launch_configs(e, r->cd.B, rows, MJPL_AOS, r->cd.valid, nullptr));
+  hipLaunchKernelGGL(k_rrt_accept, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->ln, r->cd, r->acc, r->d_ctr, next_list, r->max_steps,
+                     second, Tgt, r->carry[t]);
+  return rrt_launched("validate_and_accept");
+}
+
+// The chunks of a projecting extension.  Chunk c reads packed list c & 1, closed by the acceptance kernel before it (chunk
+// 0: by k_rrt_list_begin); its length IS the number of active lanes.  Reading it costs a trip to the host with the chip
+// idle (~30 us) and buys the right number of steps for the chunk: 4 - 5 chunks per extension (profiles/README.md).
+int Extension::chunks_projecting(int *chunks) {
+  if (r->cd.cap < L) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer too small for one step per lane");
+  int steps_done = 0;  // steps per lane of the chunks launched so far
+  for (int chunk = 0;; chunk++) {
+    *chunks = chunk + 1;
+    MJPL_TRY(rrt_read_counters(r, true));
+    const int list = chunk & 1, active = r->h_ctr[RC_LISTN + list];
+    if (active == 0) return MJPL_OK;
+    if (chunk >= 1) MJPL_TRY(start_tail_lookups(r, t, active));
+    const int S = proj_chunk_steps(r->tune, active, r->cd.cap, r->max_steps, steps_done);
+    GenShape shape{};
+    MJPL_TRY(launch_gen_project(list, active, S, &shape));
+    MJPL_TRY(validate_and_accept(proj_chunk_rows(S, active, r->cd.cap), (chunk + 1) & 1));
     steps_done += S;
-    if (projecting) tr.chunk(st, chunk, active_bound, S, trace_G, trace_grid);
-    // chunk sizes double: a chain of n steps costs O(log n) chunks and at most 2x its own checks
-    if (!projecting && S < 64) {
-      const int64_t room = (int64_t)r->cd.cap / std::max(1, r->h_ctr[RC_ACTIVE]);
-      S = (int)std::max<int64_t>(1, std::min<int64_t>(2 * S, room));
+    tr.chunk(st, chunk, active, S, shape.G, shape.waves);
+  }
+}
+
+// ... and of one without a projection: only RC_ACTIVE says whether any lane emitted; RC_EDGES counts the rows they reserved
+int Extension::chunks_free(int *chunks) {
+  int S = free_first_steps(L, r->cd.cap);
+  for (int chunk = 0;; chunk++) {
+    *chunks = chunk + 1;
+    MJPL_TRY(launch_gen(S));
+    MJPL_TRY(rrt_read_counters(r, false));
+    const bool refused = (r->h_ctr[RC_OVERFLOW] & 1) != 0;  // (lanes that wait for the next chunk)
+    if (refused) HIP_TRY(hipMemsetAsync(r->d_ctr + RC_OVERFLOW, 0, sizeof(int), st));
+    if (r->h_ctr[RC_ACTIVE] == 0) {
+      if (!refused) return MJPL_OK;
+      HIP_TRY(hipMemsetAsync(r->d_ctr + RC_EDGES, 0, sizeof(int), st));  // (k_rrt_accept clears it otherwise)
+      if ((S = free_retry_steps(S)) == 0) return fail(MJPL_E_CAPACITY, "rrt: candidate buffer too small for one step per lane");
+      continue;
     }
+    MJPL_TRY(validate_and_accept(free_chunk_rows(r->h_ctr[RC_EDGES], r->cd.cap), -1));
+    S = free_next_steps(S, r->h_ctr[RC_ACTIVE], r->cd.cap);
   }
-  tr.mark(st, "extension chunks", chunks_done);
-  // node order of the extension: lanes ascending, levels ascending within a lane
-  {
-    const int nsb = (L + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(k_rrt_scan_sums, dim3(nsb), dim3(kScanBlock), 0, st, L, r->ln.cnt, r->d_scan);
-    hipLaunchKernelGGL(k_rrt_scan_blocks, dim3(1), dim3(kScanBlock), 0, st, nsb, r->d_scan, r->d_ctr + (t == (r->round - 1) % 2 ? RC_NEWA : RC_NEWB));
-    hipLaunchKernelGGL(k_rrt_scan_apply, dim3(nsb), dim3(kScanBlock), 0, st, L, r->ln.cnt, r->d_scan, r->ln.off);
-  }
-  if ((rc = rrt_read_ctr(r)) != MJPL_OK) return rc;
-  if (r->h_ctr[RC_OVERFLOW] & 2) return fail(MJPL_E_CAPACITY, "rrt: more new nodes in one extension than the pending slab holds");
+}
+
+// node order of the extension -- lanes ascending, levels ascending within a lane --, the new nodes placed in the pending slab
+int Extension::extend_close(int *nnew) {
+  const int nsb = (L + kScanBlock - 1) / kScanBlock;
+  hipLaunchKernelGGL(k_rrt_scan_sums, dim3(nsb), dim3(kScanBlock), 0, st, L, r->ln.cnt, r->d_scan);
+  hipLaunchKernelGGL(k_rrt_scan_blocks, dim3(1), dim3(kScanBlock), 0, st, nsb, r->d_scan, r->d_ctr + (t == (r->round - 1) % 2 ? RC_NEWA : RC_NEWB));
+  hipLaunchKernelGGL(k_rrt_scan_apply, dim3(nsb), dim3(kScanBlock), 0, st, L, r->ln.cnt, r->d_scan, r->ln.off);
+  MJPL_TRY(rrt_read_counters(r, false));
   {  // the validation launches of this extension never synchronised: a tail kernel that gave up waiting says so here
     int vstatus = 0;
     HIP_TRY(hipMemcpyAsync(&vstatus, e->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -994,10 +973,20 @@ int rrt_extend(mjpl_rrt *r, int t, const double *Tgt, int second, int *nnew) {
                        r->d_pendpar[t]);
   hipLaunchKernelGGL(k_rrt_finish, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, r->ln, second ? r->ln.refB : r->ln.refA,
                      second ? (double *)nullptr : r->ln.RA);
-  HIP_TRY(hipGetLastError());
+  MJPL_TRY(rrt_launched("extend_close"));
   tr.mark(st, "scan, place, finish", nacc);
-  ring_guard.ok = true;
   return MJPL_OK;
+}
+
+int rrt_extend(mjpl_rrt *r, int t, const double *Tgt, int second, int *nnew) {
+  Extension x{r, r->e, r->e->stream, r->L, r->nplan, t, Tgt, second, RrtTrace(r->e)};
+  x.tr.mark(x.st, "(before the extension)");
+  MJPL_TRY(x.extend_lookup());
+  MJPL_TRY(x.extend_open());
+  int chunks = 0;
+  MJPL_TRY(r->pose ? x.chunks_projecting(&chunks) : x.chunks_free(&chunks));
+  x.tr.mark(x.st, "extension chunks", chunks);
+  return x.extend_close(nnew);
 }
 
 }  // namespace
@@ -1062,16 +1051,12 @@ void mjpl_rrt_destroy(mjpl_rrt *r) {
   if (!r) return;
   (void)hipSetDevice(r->e->device);
   (void)hipStreamSynchronize(r->e->stream);
-  if (r->side) { (void)hipStreamSynchronize(r->side); (void)hipStreamDestroy(r->side); }
-  if (r->ev_tail) (void)hipEventDestroy(r->ev_tail);
-  if (r->ev_near) (void)hipEventDestroy(r->ev_near);
-  if (r->ev_pre) (void)hipEventDestroy(r->ev_pre);
+  RrtEarly &ea = r->early;
+  if (ea.side) { (void)hipStreamSynchronize(ea.side); (void)hipStreamDestroy(ea.side); }
+  for (hipEvent_t ev : {ea.ev_tail, ea.ev_near, ea.ev_pre})
+    if (ev) (void)hipEventDestroy(ev);
   for (void *p : r->owned) (void)hipFree(p);
-  if (r->h_ctr) (void)hipHostFree(r->h_ctr);
-  if (r->h_ring) (void)hipHostFree(r->h_ring);
-  if (r->h_heads) (void)hipHostFree(r->h_heads);
-  if (r->h_myhead) (void)hipHostFree(r->h_myhead);
-  if (r->d_gather) (void)hipFree(r->d_gather);
+  for (void *p : r->pinned) (void)hipHostFree(p);
   delete r;
 }
 
@@ -1127,29 +1112,24 @@ int mjpl_rrt_create(mjpl_engine *e, const mjpl_rrt_desc *d, mjpl_rrt **out) {
     for (int t = 0; t < 2; t++) {
       RA(r->carry[t].flag, L); RA(r->carry[t].T, (size_t)nplan * L); RA(r->carry[t].goal, L); RA(r->carry[t].node, L);
     }
-  // (the planner's switches: options of the engine -- "rrt_exact_counts", "rrt_early_nn", ... -- as they stand now)
-  r->exact_counts = e->rrt_exact_counts; r->early_nn = e->rrt_early_nn; r->early_lanes = e->rrt_early_lanes;
-  r->early_min_nodes = e->rrt_early_min_nodes; r->early_next = e->rrt_early_next;
-  if (!d->pose) r->early_nn = 0;  // (extensions without a projecting constraint have no such tail)
-  if (r->early_nn) {
-    RA(r->d_RAe, (size_t)nplan * L); RA(r->d_near_e, L); RA(r->d_late_pos, L); RA(r->d_early, L);
-    RA(r->d_late_near, std::max(r->early_lanes, 1)); RA(r->d_late_q, (size_t)nplan * r->early_lanes);
-    HIP_TRY(hipStreamCreateWithFlags(&r->side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&r->ev_tail, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&r->ev_near, hipEventDisableTiming));
-    if (r->early_next) {
-      RA(r->d_Tn, (size_t)nplan * L); RA(r->d_goal_n, L); RA(r->d_first_n, 1); RA(r->d_pre_idx, L); RA(r->d_pre_d2, L);
-      HIP_TRY(hipEventCreateWithFlags(&r->ev_pre, hipEventDisableTiming));
+  r->tune = e->rrt;  // (the engine's options "rrt_early_nn" ... "rrt_proj_waves" as they stand now)
+  if (!d->pose) r->tune.early_nn = 0;  // (extensions without a projecting constraint have no such tail)
+  if (r->tune.early_nn) {
+    RrtEarly &ea = r->early;
+    RA(ea.d_RAe, (size_t)nplan * L); RA(ea.d_near_e, L); RA(ea.d_late_pos, L); RA(ea.d_early, L);
+    RA(ea.d_late_near, std::max(r->tune.early_lanes, 1)); RA(ea.d_late_q, (size_t)nplan * r->tune.early_lanes);
+    HIP_TRY(hipStreamCreateWithFlags(&ea.side, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ea.ev_tail, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ea.ev_near, hipEventDisableTiming));
+    if (r->tune.early_next) {
+      RA(ea.d_Tn, (size_t)nplan * L); RA(ea.d_goal_n, L); RA(ea.d_first_n, 1); RA(ea.d_pre_idx, L); RA(ea.d_pre_d2, L);
+      HIP_TRY(hipEventCreateWithFlags(&ea.ev_pre, hipEventDisableTiming));
     }
   }
 #undef RA
-  HIP_TRY(hipHostMalloc((void **)&r->h_ctr, RC_SIZE * sizeof(int)));
-  HIP_TRY(hipHostMalloc((void **)&r->h_ring, 4 * kRingStride * sizeof(int)));
-  memset(r->h_ring, 0, 4 * kRingStride * sizeof(int));
-  r->proj_steps_max = e->rrt_proj_steps; r->proj_slots = e->rrt_proj_slots; r->proj_g = e->rrt_proj_g;
-  r->ahead = e->rrt_ahead; r->ahead_lanes = e->rrt_ahead_lanes; r->proj_waves_max = e->rrt_proj_waves;
-  HIP_TRY(hipHostMalloc((void **)&r->h_heads, 8 * 1024 * sizeof(int)));
-  HIP_TRY(hipHostMalloc((void **)&r->h_myhead, 8 * sizeof(int)));
+  if ((rc = rrt_alloc_pinned(r.get(), &r->h_ctr, RC_SIZE)) != MJPL_OK) return rc;
+  if ((rc = rrt_alloc_pinned(r.get(), &r->h_heads, 8 * 1024)) != MJPL_OK) return rc;
+  if ((rc = rrt_alloc_pinned(r.get(), &r->h_myhead, 8)) != MJPL_OK) return rc;
   std::vector<uint8_t> isplan(r->nq, 0);
   for (int c : e->qidx) isplan[c] = 1;
   HIP_TRY(hipMemcpy(r->d_lo, d->lo, nplan * sizeof(double), hipMemcpyHostToDevice));
@@ -1180,16 +1160,16 @@ int mjpl_rrt_reset(mjpl_rrt *r, const double *q_init, const double *q_goals, int
   HIP_TRY(hipMemcpy(r->d_parent[0], minus.data(), sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(r->d_parent[1], minus.data(), ngoal * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(r->d_qinit, q_init, nplan * sizeof(double), hipMemcpyHostToDevice));
-  if (r->side) HIP_TRY(hipStreamSynchronize(r->side));
+  if (r->early.side) HIP_TRY(hipStreamSynchronize(r->early.side));
   for (int t = 0; t < 2; t++)
     if (r->carry[t].flag) HIP_TRY(hipMemset(r->carry[t].flag, 0, (size_t)r->L));
   HIP_TRY(hipMemset(r->d_cf, 0x7f, (size_t)r->cap * sizeof(int32_t)));  // (a round that failed half-way leaves its claims)
-  r->pre_round = 0;
-  r->early_on = false;
+  r->early.pre_round = 0;
+  r->early.on = false;
   if (ngoal > r->first_cap) {
     int rc = rrt_alloc(r, &r->d_first, (size_t)ngoal);
     if (rc != MJPL_OK) return rc;
-    if (r->early_next && r->early_nn && (rc = rrt_alloc(r, &r->d_first_n, (size_t)ngoal)) != MJPL_OK) return rc;
+    if (r->tune.early_next && r->tune.early_nn && (rc = rrt_alloc(r, &r->early.d_first_n, (size_t)ngoal)) != MJPL_OK) return rc;
     r->first_cap = ngoal;
   }
   r->n[0] = 1;
@@ -1222,17 +1202,18 @@ int rrt_begin(mjpl_rrt *r, int32_t request_stop) {
   const int world = rrt_world(r), rank = rrt_rank(r);
   if (world > 1024) return fail(MJPL_E_CAPACITY, "rrt: world size %d not supported", world);  // (the same on every rank)
   r->round++;
-  r->early_on = false;
+  RrtEarly &ea = r->early;
+  ea.on = false;
   const int grow = (r->round - 1) % 2, other = 1 - grow;  // tree swap every round (rrt.py:234-235)
-  if (r->pre_round == r->round) {
+  if (ea.pre_round == r->round) {
     // the round before drew this round's targets (and looked them up in the nodes there were): its buffers become the round's
-    HIP_TRY(hipStreamWaitEvent(st, r->ev_pre, 0));
-    std::swap(r->ln.T, r->d_Tn);
-    std::swap(r->ln.goal, r->d_goal_n);
-    std::swap(r->d_first, r->d_first_n);
+    HIP_TRY(hipStreamWaitEvent(st, ea.ev_pre, 0));
+    std::swap(r->ln.T, ea.d_Tn);
+    std::swap(r->ln.goal, ea.d_goal_n);
+    std::swap(r->d_first, ea.d_first_n);
     hipLaunchKernelGGL(k_rrt_round_init, dim3(rgrid((int)RC_SIZE)), dim3(256), 0, st, r->d_ctr, r->d_first, 0);
   } else {
-    r->pre_round = 0;
+    ea.pre_round = 0;
     const int nf = std::max(r->ngoal, 1);
     hipLaunchKernelGGL(k_rrt_round_init, dim3(rgrid(std::max(nf, (int)RC_SIZE))), dim3(256), 0, st, r->d_ctr, r->d_first, nf);
     hipLaunchKernelGGL(k_rrt_sample, dim3(rgrid(L)), dim3(256), 0, st, L, nplan, rrt_key(r->seed, (uint64_t)rank, (uint64_t)r->round), r->pgoal,
@@ -1249,7 +1230,7 @@ int rrt_begin(mjpl_rrt *r, int32_t request_stop) {
   }
   r->local_err.clear();
   if (rc != MJPL_OK) {
-    r->pre_round = 0;
+    ea.pre_round = 0;
     r->local_err = g_err;
     const int h[8] = {0, 0, 0x7fffffff, 0, 0, request_stop ? 1 : 0, rc, 0};
     memcpy(r->h_myhead, h, sizeof(h));
@@ -1336,7 +1317,7 @@ int mjpl_rrt_set_world(mjpl_rrt *r, int32_t rank, int32_t world) {
   r->rank = rank;
   r->world = world;
   r->world_set = true;
-  r->pre_round = 0;  // (draws made ahead for the next round were keyed by the rank there was)
+  r->early.pre_round = 0;  // (draws made ahead for the next round were keyed by the rank there was)
   return MJPL_OK;
 }
 
@@ -1406,13 +1387,8 @@ int mjpl_rrt_round(mjpl_rrt *r, int32_t request_stop, mjpl_rrt_round_info *info)
     const size_t parb[2] = {(size_t)mx[0] * sizeof(int32_t), (size_t)mx[1] * sizeof(int32_t)};
     if (e->comm) {
       const size_t need = (size_t)world * (rowb[0] + parb[0] + rowb[1] + parb[1]);
-      if (need > r->gather_bytes) {
-        if (r->d_gather && hipFree(r->d_gather) != hipSuccess) return bail(fail(MJPL_E_HIP, "hipFree failed"));
-        r->d_gather = nullptr; r->gather_bytes = 0;
-        if (hipMalloc((void **)&r->d_gather, need) != hipSuccess) return bail(fail(MJPL_E_HIP, "rrt: no memory for the gathered slabs"));
-        r->gather_bytes = need;
-      }
-      char *at = r->d_gather;
+      if ((rc = r->gather.reserve(need)) != MJPL_OK) return bail(rc);
+      char *at = r->gather.p;
       for (int pass = 0; pass < 2; pass++) {
         const int t = pass == 0 ? grow : other;
         if (mx[pass] == 0) continue;

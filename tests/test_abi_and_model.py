@@ -300,6 +300,13 @@ def test_options_table_is_enumerable_without_a_device_and_documented():
         doc = f.read()
     missing = [n for n in names if f"`{n}`" not in doc]
     assert not missing, missing
+    # the planner's: the pinned counter ring went, and its option with it; every other one the table documents is
+    # still there and can be set
+    assert "rrt_exact_counts" not in names
+    documented = {n for line in doc.splitlines() if line.startswith("|") for n in re.findall(r"`(rrt_\w+)`", line)}
+    assert {"rrt_trace", "rrt_early_nn", "rrt_early_next", "rrt_early_lanes", "rrt_early_min_nodes", "rrt_ahead", "rrt_ahead_lanes",
+            "rrt_proj_g", "rrt_proj_steps", "rrt_proj_slots", "rrt_proj_waves"} <= documented
+    assert documented <= set(writable), sorted(documented - set(writable))
     sites = 0
     for fn in os.listdir(os.path.join(root, "mjpl_amd", "csrc")):
         if fn.endswith((".h", ".hip")):
