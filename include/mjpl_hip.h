@@ -431,7 +431,8 @@ int mjpl_push_out_dev(mjpl_engine *e, const mjpl_push_desc *desc, const double *
  * fewer than 2 waypoints or offsets that fall, a limit of the wrong sign, infinite or NaN, dt <= 0 or
  * NaN.  MJPL_E_CAPACITY: nq outside 1..16, a path of more than 2^24 grid points.  B = 0 (and a sample call
  * without samples) launches nothing.  All outputs are deterministic and depend on no option and no MJPL_*
- * variable.  The host forms synchronise.  The device forms synchronise the engine's stream once on entry
+ * variable: the option "topp_chunk_bytes" (the workspace of one chunk of paths, 512 MiB) changes the number
+ * of launches -- "topp_last_chunks" reads it back -- and no bit of any output.  The host forms synchronise.  The device forms synchronise the engine's stream once on entry
  * (before the offset tables of an earlier call are replaced) and return with their launches enqueued. */
 #define MJPL_TOPP_OK         0
 #define MJPL_TOPP_STALLED    1

@@ -46,6 +46,8 @@ using namespace mjpl;
 constexpr int kCtr = kCounterStride;  // ints between device counters: one 128-byte line each
 constexpr int kNumCtr = kNumCounters;
 constexpr size_t kFusedDbgWaves = 256 * 4 * 3 * 2;  // (wave slots of the chip, with room)
+// workspace of one chunk of paths of mjpl_topp_profile* (one path may exceed it): the default of the option "topp_chunk_bytes"
+constexpr size_t kToppChunkBytes = (size_t)512 << 20;
 
 thread_local std::string g_err;
 
@@ -551,6 +553,10 @@ struct mjpl_engine {
   std::vector<double> topp_lim_h, topp_cp_h;
   DevBuf<int64_t> d_topp_off;
   DevBuf<double> d_topp_lim, d_topp_cp, d_topp_ws;
+  // option "topp_chunk_bytes": the workspace of one chunk of paths (tests: chunk boundaries at small shapes; the number of
+  // launches changes, no bit of any output); read-only option "topp_last_chunks": chunks of the last mjpl_topp_profile*
+  int64_t topp_chunk_bytes = (int64_t)kToppChunkBytes;
+  int64_t topp_last_chunks = 0;
 };
 
 namespace {
@@ -2216,6 +2222,9 @@ const EngineOption kEngineOptions[] = {
     // (read-only, like the two below and mjpl_nearest_last_screen: the last look-up on the engine's own scratch -- none of the
     //  planner's on its second stream -- took the cell-ordered scan)
     {"nn_last_cells", [](mjpl_engine *e) { return e->nn.last.cells ? 1.0 : 0.0; }, nullptr},
+    // ---- trajectories (launch_topp_profile; read at the next call: more or fewer launches, the same bits)
+    MJPL_OPT_INT("topp_chunk_bytes", topp_chunk_bytes, 1, 1ll << 40),
+    {"topp_last_chunks", [](mjpl_engine *e) { return (double)e->topp_last_chunks; }, nullptr},
     {"kernel_timer", [](mjpl_engine *e) { return (double)e->kt_mode; },
      [](mjpl_engine *e, double v) {
        if (!(v >= 0 && v <= 3)) return false;
@@ -2892,8 +2901,6 @@ int launch_push(mjpl_engine *e, const mjpl_push_desc &d, const double *dQ, int64
 // ---- time-optimal path parameterisation (mjpl_topp.h)
 namespace {
 
-constexpr size_t kToppChunkBytes = (size_t)512 << 20;  // workspace of one chunk of paths (one path may exceed it)
-
 // first grid point of path b (the host's topp_g_off)
 int64_t topp_g_off_h(const int64_t *wp_off, int G, int64_t b) { return (int64_t)G * (wp_off[b] - b) + b; }
 
@@ -2963,11 +2970,13 @@ int topp_cp_table(mjpl_engine *e, const int64_t *wp_off, int64_t B) {
 }
 
 // mjpl_topp_profile* on device batches (wp_off on the host): the spline of every path in one launch, then per chunk of
-// paths whose workspace fits kToppChunkBytes the two grid kernels and the sweeps.
+// paths whose workspace fits the option "topp_chunk_bytes" (always at least one path) the two grid kernels and the sweeps.
 int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
                         double *dx, double *du, double *dt, int32_t *dstatus) {
+  e->topp_last_chunks = 0;
   MJPL_TRY(topp_upload(e, d, wp_off, nullptr, B));
   const hipStream_t st = e->stream;
+  const size_t chunk_bytes = (size_t)e->topp_chunk_bytes;
   MJPL_TRY(topp_cp_table(e, wp_off, B));
   ToppBatch a = {};
   a.W = dW; a.wp_off = e->d_topp_off.p; a.B = (int)B; a.d = d.nq; a.G = d.grid;
@@ -2979,7 +2988,7 @@ int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *d
   for (int64_t b0 = 0; b0 < B;) {
     const int64_t g0 = topp_g_off_h(wp_off, d.grid, b0);
     int64_t b1 = b0 + 1;
-    while (b1 < B && (size_t)(topp_g_off_h(wp_off, d.grid, b1 + 1) - g0) * per_pt <= kToppChunkBytes) b1++;
+    while (b1 < B && (size_t)(topp_g_off_h(wp_off, d.grid, b1 + 1) - g0) * per_pt <= chunk_bytes) b1++;
     const int64_t pts = topp_g_off_h(wp_off, d.grid, b1) - g0;
     MJPL_TRY(e->d_topp_ws.reserve((size_t)pts * (5 * rows + 1)));
     const size_t span = (size_t)pts * rows;
@@ -2993,6 +3002,7 @@ int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *d
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_topp_sweep, dim3((unsigned)((b1 - b0 + kToppSweepWaves - 1) / kToppSweepWaves)), dim3(64 * kToppSweepWaves), 0, st, a);
     HIP_TRY(hipGetLastError());
+    e->topp_last_chunks++;
     b0 = b1;
   }
   return MJPL_OK;
@@ -3476,6 +3486,7 @@ int mjpl_push_out(mjpl_engine *e, const mjpl_push_desc *d, const double *Q, int6
 int mjpl_topp_profile_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
                           double *dx, double *du, double *dt, int32_t *dstatus) {
   int rc = check_topp_args(e, d, dW, wp_off, B, {dM, dx, du, dt, dstatus});
+  if (rc == MJPL_OK && B == 0) e->topp_last_chunks = 0;
   if (rc != MJPL_OK || B == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
   return launch_topp_profile(e, *d, dW, wp_off, B, dM, dx, du, dt, dstatus);
@@ -3484,6 +3495,7 @@ int mjpl_topp_profile_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double 
 int mjpl_topp_profile(mjpl_engine *e, const mjpl_topp_desc *d, const double *W, const int64_t *wp_off, int64_t B, double *M,
                       double *x, double *u, double *t, int32_t *status) {
   int rc = check_topp_args(e, d, W, wp_off, B, {M, x, u, t, status});
+  if (rc == MJPL_OK && B == 0) e->topp_last_chunks = 0;
   if (rc != MJPL_OK || B == 0) return rc;
   const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
   const HostOut outs[] = {{M, wb}, {x, gb}, {u, gb}, {t, gb}, {status, (size_t)B * sizeof(int32_t)}};

@@ -1,8 +1,10 @@
-"""The NumPy statement of the trajectory kernels (tests/trajectory_reference.py) against closed forms, scipy and its own
-constraints, and the host-side trajectory helpers (mjpl_amd/trajectory/utils.py).  No GPU."""
+"""The NumPy statement of the trajectory kernels (tests/trajectory_reference.py) against closed forms, scipy, its own
+constraints and a linear-programming reference that shares no code with it (tests/trajectory_lp_reference.py), and the
+host-side trajectory helpers (mjpl_amd/trajectory/utils.py).  No GPU."""
 import numpy as np
 import pytest
 
+import trajectory_lp_reference as LP
 import trajectory_reference as R
 from mjpl_amd.constraint import Constraint
 from mjpl_amd.trajectory import Trajectory, TrajectoryGenerator, generate_constrained_trajectories, generate_constrained_trajectory
@@ -11,6 +13,9 @@ from mjpl_amd.trajectory.utils import _add_intermediate_waypoint, _waypoint_timi
 
 CASES = R.parity_cases()
 IDS = [c[0] for c in CASES]
+EDGES = R.edge_cases()
+EDGE_IDS = [c[0] for c in EDGES]
+TOL = 1e-9  # relative to an array's largest magnitude: the project's bound for NumPy statements
 
 
 @pytest.mark.parametrize("n", [2, 3, 5, 17, 64])
@@ -35,12 +40,21 @@ def test_closed_forms(vmax, G, T):
     assert abs(p["t"][-1] - T) <= 1e-12
 
 
-@pytest.mark.parametrize("k", range(len(CASES)), ids=IDS)
-def test_statement_keeps_the_limits(k):
-    _, W, vmin, vmax, amin, amax = CASES[k]
-    p = R.parity_profile(k)
+def every_case():
+    """(name, W, limits, G, the shared profile) of the parity cases at PARITY_GRID and of the edge cases at their own."""
+    for k, (name, W, *lim) in enumerate(CASES):
+        yield pytest.param(W, lim, R.PARITY_GRID, lambda dtype=np.float64, k=k: R.parity_profile(k, dtype), id=name)
+    for k, (name, W, *lim, G) in enumerate(EDGES):
+        yield pytest.param(W, lim, G, lambda dtype=np.float64, k=k: R.edge_profile(k, dtype), id=name)
+
+
+@pytest.mark.parametrize("W, lim, G, shared", every_case())
+def test_statement_keeps_the_limits(W, lim, G, shared):
+    vmin, vmax, amin, amax = lim
+    p = shared()
     x, u, a, b = p["x"], p["u"], p["a"], p["b"]
     N = len(x) - 1
+    assert N == (len(W) - 1) * G
     assert p["status"] == R.OK
     assert x[0] == 0 and x[N] == 0
     assert np.abs(x[:-1] + (2.0 * (1.0 / N)) * u[:-1] - x[1:]).max() <= 4e-16 * x.max()  # x and u agree
@@ -54,19 +68,78 @@ def test_statement_keeps_the_limits(k):
     assert np.abs(vel[-1]).max() <= 1e-12
 
 
-@pytest.mark.parametrize("k", range(len(CASES)), ids=IDS)
-def test_conditioning_guard(k):
-    """A parity case must be one whose numbers rounding cannot move: float64 and longdouble agree to 1e-11 and no
-    interior x comes near 0 (where T depends on the square root of a rounding-level number)."""
-    p = R.parity_profile(k)
+@pytest.mark.parametrize("W, lim, G, shared", every_case())
+def test_conditioning_guard(W, lim, G, shared):
+    """A parity or edge case must be one whose numbers rounding cannot move: float64 and longdouble agree to 1e-11 and
+    no interior x comes near 0 (where T depends on the square root of a rounding-level number)."""
+    p = shared()
     x, N = p["x"], len(p["x"]) - 1
     assert x[1:N].min() >= 1e-6 * x.max()
     if np.finfo(np.longdouble).eps >= np.finfo(np.float64).eps:
         pytest.skip("np.longdouble is no wider than float64 on this machine")
-    _, W, vmin, vmax, amin, amax = CASES[k]
-    pl = R.profile(W, vmin, vmax, amin, amax, R.PARITY_GRID, np.longdouble)
+    pl = shared(np.longdouble)
     assert abs(float(pl["t"][-1]) - p["t"][-1]) <= 1e-11 * p["t"][-1]
     assert np.abs(pl["x"].astype(np.float64) - x).max() <= 1e-11 * x.max()
+
+
+def test_edge_cases_are_what_their_names_say():
+    """The block edges of the forward sweep, the row without u and the dead rows are really in the inputs."""
+    p = {name: R.edge_profile(k) for k, name in enumerate(EDGE_IDS)}
+    for name, N in (("N63", 63), ("N64", 64), ("N65", 65), ("N129", 129)):
+        assert len(p[name]["x"]) - 1 == N, name
+    assert {(len(p[name]["x"]) - 1) % 64 for name in ("N63", "N64", "N65", "N129")} == {63, 0, 1}
+    assert any(G & (G - 1) for *_, G in EDGES)  # a grid that is no power of two
+    for name in ("reversal-1d", "reversal-2d"):  # q' = 0 with q'' != 0 at a grid point: a row without u
+        a, b = p[name]["a"], p[name]["b"]
+        assert np.count_nonzero((a == 0) & (b != 0)) == 1, name
+        assert a[8, 0] == 0 and b[8, 0] == -12
+    W = dict((c[0], c[1]) for c in EDGES)
+    still = np.all(W["d16-still-0-15"] == W["d16-still-0-15"][0], axis=0)
+    assert np.array_equal(np.flatnonzero(still), [0, 15])
+    assert np.array_equal(np.flatnonzero(~np.all(W["d16-one-moving"] == W["d16-one-moving"][0], axis=0)), [0])
+    assert np.array_equal(W["repeat"][1], W["repeat"][2])
+
+
+LP_PARITY = ("d1-n3", "d3-n17", "d4-n17", "d7-n17", "d16-n3", "asymmetric", "still-column")
+
+
+def lp_cases():
+    for k, (name, W, *lim, G) in enumerate(EDGES):
+        for g in sorted({G, 5}):
+            yield pytest.param(W, lim, g, (lambda k=k: R.edge_profile(k)) if g == G else None, id=f"{name}-G{g}")
+    for name in LP_PARITY:
+        k = IDS.index(name)
+        _, W, *lim = CASES[k]
+        for g in (5, R.PARITY_GRID):
+            yield pytest.param(W, lim, g, (lambda k=k: R.parity_profile(k)) if g == R.PARITY_GRID else None, id=f"{name}-G{g}")
+
+
+@pytest.mark.parametrize("W, lim, G, shared", lp_cases())
+def test_statement_matches_the_lp(W, lim, G, shared):
+    """K and x of the statement's closed form (header step 5: "the least intersection of a lower with an upper line")
+    against two linear programmes per grid point over the constraints of step 4 written as inequalities
+    (trajectory_lp_reference.py): the profile is the time-optimal one, not merely a feasible one.  Every edge case and
+    seven parity cases, at the case's grid and at 5.  Largest differences measured, relative to the array's largest
+    magnitude: K 7.8e-15 (N129 at G = 3), x 3.4e-12 (d7-n17 at G = 8; set by the solver's tolerance: the next largest
+    is 2.8e-13, d7-n17 at G = 5, and every other case is below 6e-14).  The bound is TOL = 1e-9."""
+    p = shared() if shared else R.profile(W, *lim, G)
+    assert p["status"] == R.OK
+    K, x = LP.lp_profile(W, lim, G)
+    for name, got, want in (("K", p["K"], K), ("x", p["x"], x)):
+        scale = np.abs(want).max()
+        err = np.abs(got - want).max()
+        print(f"{name}: the statement differs from the LP by {err / scale:.3e} of {scale:.3e}")
+        assert err <= TOL * scale, name
+
+
+def test_stalled_input():
+    """A path so large that every K underflows: STALLED, x all zero, the duration infinite, M finite."""
+    W, *lim, G = R.stalled_case()
+    p = R.profile(W, *lim, G)
+    assert p["status"] == R.STALLED
+    assert np.all(p["x"] == 0) and np.all(p["u"] == 0)
+    assert p["t"][0] == 0 and p["t"][-1] == np.inf
+    assert np.all(np.isfinite(p["M"])) and np.abs(p["M"]).max() > 1e170
 
 
 def test_sample_count_rule():

@@ -218,3 +218,48 @@ def parity_profile(k, dtype=np.float64):
         _, W, vmin, vmax, amin, amax = parity_cases()[k]
         _profiles[(k, dtype)] = profile(W, vmin, vmax, amin, amax, PARITY_GRID, dtype)
     return _profiles[(k, dtype)]
+
+
+EDGE_SHAPES = (  # (name, d, n, G): N = (n-1) G
+    ("N63", 7, 10, 7), ("N64", 7, 9, 8), ("N65", 7, 14, 5), ("N129", 16, 44, 3), ("G2", 4, 17, 2), ("G64", 3, 5, 64),
+    ("d16-still-0-15", 16, 17, 8), ("d16-one-moving", 16, 17, 8))
+
+
+def edge_cases():
+    """[(name, W, vmin, vmax, amin, amax, G)]: what parity_cases() leaves out.  N % 64 in {63, 0, 1} around the forward
+    sweep's blocks of 64 (N63, N64, N65, N129), grids that are no power of two (7, 5, 3: i / G is not exact) and the
+    ends of the range tried (2, 64), still columns at d = 16 (rows 0, 15, 16 and 31 dead; one live column) -- random
+    walks drawn from default_rng(23) in this order -- and three fixed paths with v = +-1, a = +-2 at G = 8: a column
+    that reverses (q' = 0 exactly at the middle knot, q'' = -12 there: a row without u), the same beside a column that
+    does not, and a repeated waypoint.  test_trajectory_host.py guards their conditioning like the parity cases'."""
+    rng = np.random.default_rng(23)
+    cases = []
+    for name, d, n, G in EDGE_SHAPES:
+        W, vmin, vmax, amin, amax = random_case(rng, d, n, walk=True)
+        if name == "d16-still-0-15":
+            W[:, [0, 15]] = W[0, [0, 15]]
+        if name == "d16-one-moving":
+            W[:, 1:] = W[0, 1:]
+        cases.append((name, W, vmin, vmax, amin, amax, G))
+    for name, W in (("reversal-1d", [[0.0], [1.0], [0.0]]), ("reversal-2d", [[0.0, 0.0], [1.0, 0.5], [0.0, 1.0]]),
+                    ("repeat", [[0.0], [0.8], [0.8], [0.0]])):
+        W = np.array(W)
+        one = np.ones(W.shape[1])
+        cases.append((name, W, -one, one, -2 * one, 2 * one, PARITY_GRID))
+    return cases
+
+
+def stalled_case():
+    """(W, vmin, vmax, amin, amax, G) of a path the statement gives STALLED: at this scale every K underflows to 0, so x
+    is all zero and t is inf from the first interval on (at 1e160 x would be subnormal instead, which no test wants)."""
+    W = np.array([[0.0], [1.0], [0.3]]) * 1e170
+    one = np.ones(1)
+    return W, -one, one, -2 * one, 2 * one, PARITY_GRID
+
+
+def edge_profile(k, dtype=np.float64):
+    """profile() of edge case k at its own grid, computed once per process and shared (do not write into it)."""
+    if ("edge", k, dtype) not in _profiles:
+        _, W, vmin, vmax, amin, amax, G = edge_cases()[k]
+        _profiles[("edge", k, dtype)] = profile(W, vmin, vmax, amin, amax, G, dtype)
+    return _profiles[("edge", k, dtype)]
