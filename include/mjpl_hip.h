@@ -452,6 +452,69 @@ int mjpl_topp_sample_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const doubl
                          int64_t B, const double *dM, const double *dx, const double *du, const double *dt_grid,
                          double dt, const int64_t *samp_off, double *dpos, double *dvel, double *dacc);
 
+/* ---- trajectories: jerk-limited parameterisation of a batch of paths -----------------------
+ * The same paths, packing, spline and engine as mjpl_topp_* above, under per-column limits on velocity,
+ * acceleration AND jerk (mjpl_jerk_desc: HOST arrays of nq magnitudes > 0, in both forms of the calls;
+ * grid >= 1 intervals per waypoint segment, 2 is a good default).  The motion passes through the waypoints
+ * without stopping; it is not time-optimal (DESIGN.md section 5.14 says by how much).  Every column's
+ * velocity, acceleration and jerk stay within their limits at every instant, not only at grid points.
+ *
+ * Per path (tests/jerk_reference.py states every operation; DESIGN.md section 5.14 proves the guarantee):
+ *   1. M as mjpl_topp_profile's, bit for bit.  A grid of N = (n-1) * grid intervals of width D = 1/N; the
+ *      grid points are the junctions.
+ *   2. Interval i, column j: p1 = max |q'|, p2 = max |q''|, p3 = |q'''| over the interval, exactly (q' at both
+ *      ends and at its vertex if that lies inside, q'' at both ends, q''' is constant).
+ *   3. The interval's limits on sdot, |sddot|, |sdddot| (a term with a zero denominator is +inf):
+ *        V_i = min_j min(v_j / p1, sqrt(a_j / (2 p2)), cbrt(j_j / (3 p3)))
+ *        A_i = min_j min((a_j - p2 V_i^2) / p1, j_j / (9 p2 V_i))
+ *        J_i = min_j (j_j - p3 V_i^3 - 3 p2 V_i A_i) / p1.
+ *   4. A ramp changes the speed by dv with sddot = 0 at both ends in T(dv) = dv/A + A/J if dv >= A^2/J, else
+ *      2 sqrt(dv/J), over the length (v0 + v1)/2 T(dv).
+ *   5. Junction speeds v_i (sddot = 0 there): v_0 = v_N = 0, v_i <= min(V_{i-1}, V_i); backward, v_i is no
+ *      faster than a ramp down to v_{i+1} within D allows; forward, v_{i+1} no faster than a ramp up from v_i.
+ *      The largest such speed is found by a section search: ten rounds of 64 candidates, always feasible.
+ *   6. Interval i: ramp from v_i up to the peak vp_i (the largest <= V_i whose two ramps fit D, by the same
+ *      search), cruise for tc_i = (D - their length) / vp_i, ramp down to v_{i+1}: seven phases of constant
+ *      sdddot (J, 0, -J, 0, -J, 0, J), some of zero length.
+ *   7. t_0 = 0, t_{i+1} = t_i + ((T_up + tc_i) + T_down).
+ * Outputs: M like W; v, vp, tc, t packed at g_off[b] = grid (wp_off[b] - b) + b with N_b + 1 entries per
+ * path (vp's and tc's last entry 0, t's last entry the duration); lim with N_b + 1 rows (V, A, J) per path
+ * at 3 g_off[b], the last row 0.  status[b], numerically mjpl_topp_profile's:
+ *   MJPL_TOPP_OK         otherwise.
+ *   MJPL_TOPP_STALLED    some V_i is +inf: nothing moves on that interval.  v and vp are 0, tc and t +inf
+ *                        (t_0 = 0).
+ *   MJPL_TOPP_NONFINITE  a waypoint of the path holds NaN / inf, or a result is not finite: its M, lim, v, vp,
+ *                        tc, t are NaN.  Other paths of the batch are not affected.
+ *
+ * mjpl_jerk_sample evaluates the motion at mjpl_topp_sample's times and counts.  In the interval
+ * t_i <= t_k, tau = t_k - t_i, the phases are walked from (s, sdot, sddot) = (0, v_i, 0) to the one that
+ * holds tau; at or past t_{i+1} - t_i the state is (D, v_{i+1}, 0).  Then pos = q(s), vel = q'(s) sdot,
+ * acc = q''(s) sdot^2 + q'(s) sddot: the last sample is the last waypoint, at rest.  Sampling a path that is
+ * not OK gives meaningless rows, never a fault.
+ *
+ * wp_off and samp_off are HOST arrays in both forms.  MJPL_E_ARG: a NULL pointer, grid < 1, a path with
+ * fewer than 2 waypoints or offsets that fall, a limit that is not > 0, infinite or NaN, dt <= 0 or NaN.
+ * MJPL_E_CAPACITY: nq outside 1..16, a path of more than 2^24 grid points.  B = 0 (and a sample call without
+ * samples) launches nothing.  All outputs are deterministic and depend on no option and no MJPL_* variable;
+ * there is no workspace.  The host forms synchronise.  The device forms synchronise the engine's stream
+ * once on entry and return with their launches enqueued. */
+typedef struct {
+  int32_t nq, grid;
+  const double *vlim, *alim, *jlim; /* host, [nq], both forms */
+} mjpl_jerk_desc;
+int mjpl_jerk_profile(mjpl_engine *e, const mjpl_jerk_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                      double *M, double *lim, double *v, double *vp, double *tc, double *t, int32_t *status);
+int mjpl_jerk_profile_dev(mjpl_engine *e, const mjpl_jerk_desc *desc, const double *dW, const int64_t *wp_off,
+                          int64_t B, double *dM, double *dlim, double *dv, double *dvp, double *dtc, double *dt,
+                          int32_t *dstatus);
+int mjpl_jerk_sample(mjpl_engine *e, const mjpl_jerk_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                     const double *M, const double *lim, const double *v, const double *vp, const double *tc,
+                     const double *t, double dt, const int64_t *samp_off, double *pos, double *vel, double *acc);
+int mjpl_jerk_sample_dev(mjpl_engine *e, const mjpl_jerk_desc *desc, const double *dW, const int64_t *wp_off,
+                         int64_t B, const double *dM, const double *dlim, const double *dv, const double *dvp,
+                         const double *dtc, const double *dt_grid, double dt, const int64_t *samp_off, double *dpos,
+                         double *dvel, double *dacc);
+
 /* ---- certified edge checks: no contact anywhere along an edge ------------------------------
  * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
  * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md
@@ -681,6 +744,11 @@ int mjpl_time_configs_dev(mjpl_engine *e, const double *dQ, int64_t N, int32_t l
 int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *desc, const double *dW, const int64_t *wp_off, int64_t B,
                        double *dM, double *dx, double *du, double *dt_grid, int32_t *dstatus, double dt,
                        const int64_t *samp_off, double *dpos, double *dvel, double *dacc, int32_t iters,
+                       float *ms_profile, float *ms_sample);
+/* The same for mjpl_jerk_profile_dev and mjpl_jerk_sample_dev. */
+int mjpl_time_jerk_dev(mjpl_engine *e, const mjpl_jerk_desc *desc, const double *dW, const int64_t *wp_off, int64_t B,
+                       double *dM, double *dlim, double *dv, double *dvp, double *dtc, double *dt_grid, int32_t *dstatus,
+                       double dt, const int64_t *samp_off, double *dpos, double *dvel, double *dacc, int32_t iters,
                        float *ms_profile, float *ms_sample);
 /* iters times one sweep call between two events: with wp_off NULL mjpl_sweep_edges_dev(dA, dB, n edges, layout), else
  * mjpl_sweep_splines_dev(W = dA, wp_off, n paths, M = dB, which may be NULL); ms[k] = what call k took on the

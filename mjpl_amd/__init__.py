@@ -9,8 +9,8 @@ from .lie import SE3, SO3
 from .model import Model, ModelBuilder, load_mjcf, parse_mjcf
 from .planning import (RRT, DeviceBiRRT, EdgeValidator, HipEdgeValidator, Node, ParallelBiRRT, Tree,
                        cartesian_plan, path_length, smooth_path)
-from .trajectory import (HipToppTrajectoryGenerator, Trajectory, TrajectoryGenerator, generate_certified_trajectories,
-                         generate_certified_trajectory, generate_constrained_trajectories, generate_constrained_trajectory)
+from .trajectory import (HipJerkTrajectoryGenerator, HipToppTrajectoryGenerator, Trajectory, TrajectoryGenerator,
+                         generate_certified_trajectories, generate_certified_trajectory, generate_constrained_trajectories, generate_constrained_trajectory)
 from .utils import all_joints, qpos_idx, qvel_idx, random_config, site_pose
 
 
@@ -24,7 +24,7 @@ __all__ = (
     "SE3", "SO3", "site_pose", "HipIKSolver", "IKSolver", "cartesian_plan",
     "apply_constraints", "obeys_constraints", "Model", "ModelBuilder", "load_mjcf", "parse_mjcf",
     "RRT", "Node", "Tree", "path_length", "smooth_path", "ParallelBiRRT", "DeviceBiRRT", "EdgeValidator", "HipEdgeValidator",
-    "Trajectory", "TrajectoryGenerator", "HipToppTrajectoryGenerator", "generate_constrained_trajectory",
+    "Trajectory", "TrajectoryGenerator", "HipToppTrajectoryGenerator", "HipJerkTrajectoryGenerator", "generate_constrained_trajectory",
     "generate_constrained_trajectories", "generate_certified_trajectory", "generate_certified_trajectories",
     "all_joints", "qpos_idx", "qvel_idx", "random_config", "comm_unique_id",
 )

@@ -38,6 +38,7 @@
 #include "mjpl_push.h"
 #include "mjpl_sweep.h"
 #include "mjpl_topp.h"
+#include "mjpl_jerk.h"
 
 namespace {
 
@@ -2904,13 +2905,35 @@ namespace {
 // first grid point of path b (the host's topp_g_off)
 int64_t topp_g_off_h(const int64_t *wp_off, int G, int64_t b) { return (int64_t)G * (wp_off[b] - b) + b; }
 
+// Argument checks of a batch of paths, shared by mjpl_topp_* and mjpl_jerk_*: the engine, the batch size and the columns ...
+int check_path_dims(const mjpl_engine *e, const void *desc, int64_t B, int nq) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (!desc) return fail(MJPL_E_ARG, "mjpl_topp: NULL descriptor");
+  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_topp: batch size %lld out of range", (long long)B);
+  if (nq < 1 || nq > kToppMaxCols) return fail(MJPL_E_CAPACITY, "mjpl_topp: %d columns (1..%d supported)", nq, kToppMaxCols);
+  return MJPL_OK;
+}
+
+// ... and the offsets and non-null batches
+int check_path_batches(int grid, const void *W, const int64_t *wp_off, int64_t B, std::initializer_list<const void *> bufs) {
+  if (B == 0) return MJPL_OK;
+  if (!wp_off) return fail(MJPL_E_ARG, "mjpl_topp: NULL offsets");
+  if (wp_off[0] != 0) return fail(MJPL_E_ARG, "wp_off[0] must be 0, got %lld", (long long)wp_off[0]);
+  for (int64_t b = 0; b < B; b++) {
+    const int64_t n = wp_off[b + 1] - wp_off[b];
+    if (n < 2) return fail(MJPL_E_ARG, "path %lld has %lld waypoints (offsets must rise by at least 2)", (long long)b, (long long)n);
+    if (n > (1 << 24) / grid) return fail(MJPL_E_CAPACITY, "path %lld: %lld waypoints at grid %d exceed 2^24 grid points", (long long)b, (long long)n, grid);
+  }
+  if (!W) return fail(MJPL_E_ARG, "NULL batch pointer");
+  for (const void *o : bufs)
+    if (!o) return fail(MJPL_E_ARG, "NULL batch pointer");
+  return MJPL_OK;
+}
+
 // Argument checks shared by mjpl_topp_profile* and mjpl_topp_sample*: the descriptor, the offsets, non-null batches.
 int check_topp_args(const mjpl_engine *e, const mjpl_topp_desc *d, const void *W, const int64_t *wp_off, int64_t B,
                     std::initializer_list<const void *> bufs) {
-  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
-  if (!d) return fail(MJPL_E_ARG, "mjpl_topp: NULL descriptor");
-  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_topp: batch size %lld out of range", (long long)B);
-  if (d->nq < 1 || d->nq > kToppMaxCols) return fail(MJPL_E_CAPACITY, "mjpl_topp: %d columns (1..%d supported)", d->nq, kToppMaxCols);
+  MJPL_TRY(check_path_dims(e, d, B, d ? d->nq : 0));
   if (d->grid < 2 || d->grid > (1 << 16)) return fail(MJPL_E_ARG, "grid must be 2..65536 intervals per segment, got %d", d->grid);
   if (!d->vmin || !d->vmax || !d->amin || !d->amax) return fail(MJPL_E_ARG, "mjpl_topp: NULL limit array");
   for (int j = 0; j < d->nq; j++) {
@@ -2919,39 +2942,24 @@ int check_topp_args(const mjpl_engine *e, const mjpl_topp_desc *d, const void *W
     if (!(d->amin[j] < 0 && d->amax[j] > 0 && d->amin[j] > -INFINITY && d->amax[j] < INFINITY))
       return fail(MJPL_E_ARG, "acceleration limits of column %d: [%g, %g] (finite amin < 0 < amax wanted, NaN is refused)", j, d->amin[j], d->amax[j]);
   }
-  if (B == 0) return MJPL_OK;
-  if (!wp_off) return fail(MJPL_E_ARG, "mjpl_topp: NULL offsets");
-  if (wp_off[0] != 0) return fail(MJPL_E_ARG, "wp_off[0] must be 0, got %lld", (long long)wp_off[0]);
-  for (int64_t b = 0; b < B; b++) {
-    const int64_t n = wp_off[b + 1] - wp_off[b];
-    if (n < 2) return fail(MJPL_E_ARG, "path %lld has %lld waypoints (offsets must rise by at least 2)", (long long)b, (long long)n);
-    if (n > (1 << 24) / d->grid) return fail(MJPL_E_CAPACITY, "path %lld: %lld waypoints at grid %d exceed 2^24 grid points", (long long)b, (long long)n, d->grid);
-  }
-  if (!W) return fail(MJPL_E_ARG, "NULL batch pointer");
-  for (const void *o : bufs)
-    if (!o) return fail(MJPL_E_ARG, "NULL batch pointer");
-  return MJPL_OK;
+  return check_path_batches(d->grid, W, wp_off, B, bufs);
 }
 
 // The call's tables on the device: [wp_off | samp_off] and the limits.  The stream is drained first: an earlier call's
 // launches read the same buffers.
-int topp_upload(mjpl_engine *e, const mjpl_topp_desc &d, const int64_t *wp_off, const int64_t *samp_off, int64_t B) {
+int topp_upload(mjpl_engine *e, int nq, std::initializer_list<const double *> lims, const int64_t *wp_off, const int64_t *samp_off,
+                int64_t B) {
   HIP_TRY(hipStreamSynchronize(e->stream));
-  const size_t nb = (size_t)B + 1, nd = d.nq;
+  const size_t nb = (size_t)B + 1, nd = nq;
   e->topp_off_h.assign(2 * nb, 0);
   std::copy(wp_off, wp_off + nb, e->topp_off_h.begin());
   if (samp_off) std::copy(samp_off, samp_off + nb, e->topp_off_h.begin() + nb);
-  e->topp_lim_h.resize(4 * nd);
-  for (size_t j = 0; j < nd; j++) {
-    e->topp_lim_h[j] = d.vmin[j];
-    e->topp_lim_h[nd + j] = d.vmax[j];
-    e->topp_lim_h[2 * nd + j] = d.amin[j];
-    e->topp_lim_h[3 * nd + j] = d.amax[j];
-  }
+  e->topp_lim_h.clear();
+  for (const double *l : lims) e->topp_lim_h.insert(e->topp_lim_h.end(), l, l + nd);  // (at most four arrays)
   MJPL_TRY(e->d_topp_off.reserve(2 * nb, 1024));
   MJPL_TRY(e->d_topp_lim.reserve(4 * kToppMaxCols));
   HIP_TRY(hipMemcpyAsync(e->d_topp_off.p, e->topp_off_h.data(), 2 * nb * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_topp_lim.p, e->topp_lim_h.data(), 4 * nd * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_topp_lim.p, e->topp_lim_h.data(), e->topp_lim_h.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
   return MJPL_OK;
 }
 
@@ -2974,7 +2982,7 @@ int topp_cp_table(mjpl_engine *e, const int64_t *wp_off, int64_t B) {
 int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
                         double *dx, double *du, double *dt, int32_t *dstatus) {
   e->topp_last_chunks = 0;
-  MJPL_TRY(topp_upload(e, d, wp_off, nullptr, B));
+  MJPL_TRY(topp_upload(e, d.nq, {d.vmin, d.vmax, d.amin, d.amax}, wp_off, nullptr, B));
   const hipStream_t st = e->stream;
   const size_t chunk_bytes = (size_t)e->topp_chunk_bytes;
   MJPL_TRY(topp_cp_table(e, wp_off, B));
@@ -3008,7 +3016,7 @@ int launch_topp_profile(mjpl_engine *e, const mjpl_topp_desc &d, const double *d
   return MJPL_OK;
 }
 
-int check_topp_sample_args(const mjpl_topp_desc *d, const int64_t *wp_off, int64_t B, double dt, const int64_t *samp_off) {
+int check_topp_sample_args(const int64_t *wp_off, int64_t B, double dt, const int64_t *samp_off) {
   if (!(dt > 0) || !(dt < INFINITY)) return fail(MJPL_E_ARG, "dt must be > 0 and finite (NaN is refused), got %g", dt);
   if (B == 0) return MJPL_OK;
   if (!samp_off) return fail(MJPL_E_ARG, "mjpl_topp_sample: NULL offsets");
@@ -3021,13 +3029,67 @@ int check_topp_sample_args(const mjpl_topp_desc *d, const int64_t *wp_off, int64
 int launch_topp_sample(mjpl_engine *e, const mjpl_topp_desc &d, const double *dW, const int64_t *wp_off, int64_t B,
                        const double *dM, const double *dx, const double *du, const double *dt_grid, double dt,
                        const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
-  MJPL_TRY(topp_upload(e, d, wp_off, samp_off, B));
+  MJPL_TRY(topp_upload(e, d.nq, {d.vmin, d.vmax, d.amin, d.amax}, wp_off, samp_off, B));
   ToppSamples a = {};
   a.W = dW; a.M = dM; a.x = dx; a.u = du; a.t = dt_grid;
   a.wp_off = e->d_topp_off.p; a.samp_off = e->d_topp_off.p + (B + 1);
   a.B = (int)B; a.d = d.nq; a.G = d.grid; a.dt = dt;
   a.pos = dpos; a.vel = dvel; a.acc = dacc;
   hipLaunchKernelGGL(k_topp_sample, dim3((unsigned)((samp_off[B] + 255) / 256)), dim3(256), 0, e->stream, a);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+// ---- jerk-limited path parameterisation (mjpl_jerk.h); offsets, limits and the spline go the way of mjpl_topp_*
+// Argument checks shared by mjpl_jerk_profile* and mjpl_jerk_sample*
+int check_jerk_args(const mjpl_engine *e, const mjpl_jerk_desc *d, const void *W, const int64_t *wp_off, int64_t B,
+                    std::initializer_list<const void *> bufs) {
+  MJPL_TRY(check_path_dims(e, d, B, d ? d->nq : 0));
+  if (d->grid < 1 || d->grid > (1 << 16)) return fail(MJPL_E_ARG, "grid must be 1..65536 intervals per segment, got %d", d->grid);
+  if (!d->vlim || !d->alim || !d->jlim) return fail(MJPL_E_ARG, "mjpl_jerk: NULL limit array");
+  for (int j = 0; j < d->nq; j++)
+    if (!(d->vlim[j] > 0 && d->vlim[j] < INFINITY && d->alim[j] > 0 && d->alim[j] < INFINITY && d->jlim[j] > 0 && d->jlim[j] < INFINITY))
+      return fail(MJPL_E_ARG, "limits of column %d: velocity %g, acceleration %g, jerk %g (finite magnitudes > 0 wanted, NaN is refused)", j,
+                  d->vlim[j], d->alim[j], d->jlim[j]);
+  return check_path_batches(d->grid, W, wp_off, B, bufs);
+}
+
+// mjpl_jerk_profile* on device batches (wp_off on the host): five launches for the whole batch, no workspace
+int launch_jerk_profile(mjpl_engine *e, const mjpl_jerk_desc &d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                        double *dlim, double *dv, double *dvp, double *dtc, double *dt, int32_t *dstatus) {
+  MJPL_TRY(topp_upload(e, d.nq, {d.vlim, d.alim, d.jlim}, wp_off, nullptr, B));
+  const hipStream_t st = e->stream;
+  MJPL_TRY(topp_cp_table(e, wp_off, B));
+  ToppBatch s = {};
+  s.W = dW; s.wp_off = e->d_topp_off.p; s.B = (int)B; s.d = d.nq; s.cp = e->d_topp_cp.p; s.M = dM;
+  hipLaunchKernelGGL(k_topp_spline, dim3((unsigned)((B * d.nq + 255) / 256)), dim3(256), 0, st, s);
+  HIP_TRY(hipGetLastError());
+  JerkBatch a = {};
+  a.W = dW; a.wp_off = e->d_topp_off.p; a.B = (int)B; a.d = d.nq; a.G = d.grid;
+  a.lim = e->d_topp_lim.p; a.M = dM; a.pts = topp_g_off_h(wp_off, d.grid, B);
+  a.L = dlim; a.v = dv; a.vp = dvp; a.tc = dtc; a.t = dt; a.status = dstatus;
+  const dim3 per_path((unsigned)((B + kJerkSweepWaves - 1) / kJerkSweepWaves)), waves(64 * kJerkSweepWaves);
+  hipLaunchKernelGGL(k_jerk_bounds, dim3((unsigned)((a.pts * 16 + 255) / 256)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_jerk_sweep, per_path, waves, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_jerk_intervals, dim3((unsigned)((a.pts + kJerkSweepWaves - 1) / kJerkSweepWaves)), waves, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_jerk_times, per_path, waves, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+int launch_jerk_sample(mjpl_engine *e, const mjpl_jerk_desc &d, const double *dW, const int64_t *wp_off, int64_t B, const double *dM,
+                       const double *dlim, const double *dv, const double *dvp, const double *dtc, const double *dt_grid, double dt,
+                       const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
+  MJPL_TRY(topp_upload(e, d.nq, {d.vlim, d.alim, d.jlim}, wp_off, samp_off, B));
+  JerkSamples a = {};
+  a.W = dW; a.M = dM; a.L = dlim; a.v = dv; a.vp = dvp; a.tc = dtc; a.t = dt_grid;
+  a.wp_off = e->d_topp_off.p; a.samp_off = e->d_topp_off.p + (B + 1);
+  a.B = (int)B; a.d = d.nq; a.G = d.grid; a.dt = dt;
+  a.pos = dpos; a.vel = dvel; a.acc = dacc;
+  hipLaunchKernelGGL(k_jerk_sample, dim3((unsigned)((samp_off[B] + 255) / 256)), dim3(256), 0, e->stream, a);
   HIP_TRY(hipGetLastError());
   return MJPL_OK;
 }
@@ -3509,7 +3571,7 @@ int mjpl_topp_sample_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *
                          const double *dM, const double *dx, const double *du, const double *dt_grid, double dt,
                          const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
   int rc = check_topp_args(e, d, dW, wp_off, B, {dM, dx, du, dt_grid});
-  if (rc == MJPL_OK) rc = check_topp_sample_args(d, wp_off, B, dt, samp_off);
+  if (rc == MJPL_OK) rc = check_topp_sample_args(wp_off, B, dt, samp_off);
   if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
   if (!dpos || !dvel || !dacc) return fail(MJPL_E_ARG, "NULL output pointer");
   HIP_TRY(hipSetDevice(e->device));
@@ -3520,7 +3582,7 @@ int mjpl_topp_sample(mjpl_engine *e, const mjpl_topp_desc *d, const double *W, c
                      const double *x, const double *u, const double *t, double dt, const int64_t *samp_off, double *pos,
                      double *vel, double *acc) {
   int rc = check_topp_args(e, d, W, wp_off, B, {M, x, u, t});
-  if (rc == MJPL_OK) rc = check_topp_sample_args(d, wp_off, B, dt, samp_off);
+  if (rc == MJPL_OK) rc = check_topp_sample_args(wp_off, B, dt, samp_off);
   if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
   if (!pos || !vel || !acc) return fail(MJPL_E_ARG, "NULL output pointer");
   const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
@@ -3529,6 +3591,56 @@ int mjpl_topp_sample(mjpl_engine *e, const mjpl_topp_desc *d, const double *W, c
     return launch_topp_sample(e, *d, (const double *)in[0], wp_off, B, (const double *)in[1], (const double *)in[2],
                               (const double *)in[3], (const double *)in[4], dt, samp_off, (double *)out[0], (double *)out[1],
                               (double *)out[2]);
+  });
+}
+
+// ---- jerk-limited path parameterisation (mjpl_jerk.h)
+
+int mjpl_jerk_profile_dev(mjpl_engine *e, const mjpl_jerk_desc *d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                          double *dlim, double *dv, double *dvp, double *dtc, double *dt, int32_t *dstatus) {
+  int rc = check_jerk_args(e, d, dW, wp_off, B, {dM, dlim, dv, dvp, dtc, dt, dstatus});
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_jerk_profile(e, *d, dW, wp_off, B, dM, dlim, dv, dvp, dtc, dt, dstatus);
+}
+
+int mjpl_jerk_profile(mjpl_engine *e, const mjpl_jerk_desc *d, const double *W, const int64_t *wp_off, int64_t B, double *M,
+                      double *lim, double *v, double *vp, double *tc, double *t, int32_t *status) {
+  int rc = check_jerk_args(e, d, W, wp_off, B, {M, lim, v, vp, tc, t, status});
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
+  const HostOut outs[] = {{M, wb}, {lim, 3 * gb}, {v, gb}, {vp, gb}, {tc, gb}, {t, gb}, {status, (size_t)B * sizeof(int32_t)}};
+  return staged(e, false, {{W, wb}}, outs, [&](void **in, void **out) {
+    return launch_jerk_profile(e, *d, (const double *)in[0], wp_off, B, (double *)out[0], (double *)out[1], (double *)out[2],
+                               (double *)out[3], (double *)out[4], (double *)out[5], (int32_t *)out[6]);
+  });
+}
+
+int mjpl_jerk_sample_dev(mjpl_engine *e, const mjpl_jerk_desc *d, const double *dW, const int64_t *wp_off, int64_t B,
+                         const double *dM, const double *dlim, const double *dv, const double *dvp, const double *dtc,
+                         const double *dt_grid, double dt, const int64_t *samp_off, double *dpos, double *dvel, double *dacc) {
+  int rc = check_jerk_args(e, d, dW, wp_off, B, {dM, dlim, dv, dvp, dtc, dt_grid});
+  if (rc == MJPL_OK) rc = check_topp_sample_args(wp_off, B, dt, samp_off);
+  if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
+  if (!dpos || !dvel || !dacc) return fail(MJPL_E_ARG, "NULL output pointer");
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_jerk_sample(e, *d, dW, wp_off, B, dM, dlim, dv, dvp, dtc, dt_grid, dt, samp_off, dpos, dvel, dacc);
+}
+
+int mjpl_jerk_sample(mjpl_engine *e, const mjpl_jerk_desc *d, const double *W, const int64_t *wp_off, int64_t B, const double *M,
+                     const double *lim, const double *v, const double *vp, const double *tc, const double *t, double dt,
+                     const int64_t *samp_off, double *pos, double *vel, double *acc) {
+  int rc = check_jerk_args(e, d, W, wp_off, B, {M, lim, v, vp, tc, t});
+  if (rc == MJPL_OK) rc = check_topp_sample_args(wp_off, B, dt, samp_off);
+  if (rc != MJPL_OK || B == 0 || samp_off[B] == 0) return rc;
+  if (!pos || !vel || !acc) return fail(MJPL_E_ARG, "NULL output pointer");
+  const size_t db = sizeof(double), wb = (size_t)wp_off[B] * d->nq * db, gb = (size_t)topp_g_off_h(wp_off, d->grid, B) * db;
+  const size_t sb = (size_t)samp_off[B] * d->nq * db;
+  return staged(e, false, {{W, wb}, {M, wb}, {lim, 3 * gb}, {v, gb}, {vp, gb}, {tc, gb}, {t, gb}}, {{pos, sb}, {vel, sb}, {acc, sb}},
+                [&](void **in, void **out) {
+    return launch_jerk_sample(e, *d, (const double *)in[0], wp_off, B, (const double *)in[1], (const double *)in[2],
+                              (const double *)in[3], (const double *)in[4], (const double *)in[5], (const double *)in[6], dt,
+                              samp_off, (double *)out[0], (double *)out[1], (double *)out[2]);
   });
 }
 
@@ -3740,6 +3852,31 @@ int mjpl_time_topp_dev(mjpl_engine *e, const mjpl_topp_desc *d, const double *dW
     rc = mjpl_topp_profile_dev(e, d, dW, wp_off, B, dM, dx, du, dt_grid, dstatus);
     HIP_TRY(hipEventRecord(ev[3 * k + 1], e->stream));
     if (rc == MJPL_OK) rc = mjpl_topp_sample_dev(e, d, dW, wp_off, B, dM, dx, du, dt_grid, dt, samp_off, dpos, dvel, dacc);
+    HIP_TRY(hipEventRecord(ev[3 * k + 2], e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) {
+    HIP_TRY(hipEventElapsedTime(&ms_profile[k], ev[3 * k], ev[3 * k + 1]));
+    HIP_TRY(hipEventElapsedTime(&ms_sample[k], ev[3 * k + 1], ev[3 * k + 2]));
+  }
+  for (auto &x : ev) (void)hipEventDestroy(x);
+  return rc;
+}
+
+int mjpl_time_jerk_dev(mjpl_engine *e, const mjpl_jerk_desc *d, const double *dW, const int64_t *wp_off, int64_t B, double *dM,
+                       double *dlim, double *dv, double *dvp, double *dtc, double *dt_grid, int32_t *dstatus, double dt,
+                       const int64_t *samp_off, double *dpos, double *dvel, double *dacc, int32_t iters, float *ms_profile,
+                       float *ms_sample) {
+  if (!e || iters < 0 || (iters > 0 && (!ms_profile || !ms_sample))) return fail(MJPL_E_ARG, "mjpl_time_jerk_dev: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<hipEvent_t> ev(3 * (size_t)iters);
+  for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+  int rc = MJPL_OK;
+  for (int k = 0; k < iters && rc == MJPL_OK; k++) {
+    HIP_TRY(hipEventRecord(ev[3 * k], e->stream));
+    rc = mjpl_jerk_profile_dev(e, d, dW, wp_off, B, dM, dlim, dv, dvp, dtc, dt_grid, dstatus);
+    HIP_TRY(hipEventRecord(ev[3 * k + 1], e->stream));
+    if (rc == MJPL_OK) rc = mjpl_jerk_sample_dev(e, d, dW, wp_off, B, dM, dlim, dv, dvp, dtc, dt_grid, dt, samp_off, dpos, dvel, dacc);
     HIP_TRY(hipEventRecord(ev[3 * k + 2], e->stream));
   }
   HIP_TRY(hipStreamSynchronize(e->stream));

@@ -102,6 +102,10 @@ class ToppDesc(C.Structure):
     _fields_ = [("nq", C.c_int32), ("grid", C.c_int32), ("vmin", _F64P), ("vmax", _F64P), ("amin", _F64P), ("amax", _F64P)]
 
 
+class JerkDesc(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("grid", C.c_int32), ("vlim", _F64P), ("alim", _F64P), ("jlim", _F64P)]
+
+
 class SweepDesc(C.Structure):
     _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
 
@@ -166,6 +170,13 @@ ABI = {
                                    _I64P, _F64P, _F64P, _F64P]),
     "mjpl_topp_sample_dev": (C.c_int, [_VP, C.POINTER(ToppDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, C.c_double,
                                        _I64P, _VP, _VP, _VP]),
+    "mjpl_jerk_profile": (C.c_int, [_VP, C.POINTER(JerkDesc), _F64P, _I64P, C.c_int64, _F64P, _F64P, _F64P, _F64P, _F64P, _F64P,
+                                    _I32P]),
+    "mjpl_jerk_profile_dev": (C.c_int, [_VP, C.POINTER(JerkDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_jerk_sample": (C.c_int, [_VP, C.POINTER(JerkDesc), _F64P, _I64P, C.c_int64, _F64P, _F64P, _F64P, _F64P, _F64P, _F64P,
+                                   C.c_double, _I64P, _F64P, _F64P, _F64P]),
+    "mjpl_jerk_sample_dev": (C.c_int, [_VP, C.POINTER(JerkDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_double,
+                                       _I64P, _VP, _VP, _VP]),
     "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
                                     C.c_int64]),
     "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
@@ -198,6 +209,8 @@ ABI = {
                                         C.POINTER(C.c_float)]),
     "mjpl_time_topp_dev": (C.c_int, [_VP, C.POINTER(ToppDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_double, _I64P,
                                      _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mjpl_time_jerk_dev": (C.c_int, [_VP, C.POINTER(JerkDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_double,
+                                     _I64P, _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mjpl_pose_create": (C.c_int, [_VP, C.POINTER(PoseDesc), C.POINTER(_VP)]),
     "mjpl_pose_destroy": (None, [_VP]),
     "mjpl_pose_spec_loaded": (C.c_int, [_VP]),
@@ -844,6 +857,98 @@ class Engine:
         self._ok(self.lib.mjpl_topp_sample_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dx,
                                                du, dt_grid, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc))
         del keep
+
+    # -- trajectories: jerk-limited parameterisation of a batch of paths (include/mjpl_hip.h, mjpl_jerk_*)
+    @staticmethod
+    def jerk_desc(nq, grid, vlim, alim, jlim):
+        """The mjpl_jerk_desc of a call and the arrays it points into (keep both alive for the call)."""
+        keep = []
+        for v in (vlim, alim, jlim):
+            v = _f64(v)
+            if v.shape != (nq,):
+                raise ValueError(f"limits must have {nq} entries, got {v.shape}")
+            keep.append(v)
+        return JerkDesc(int(nq), int(grid), *(v.ctypes.data_as(_F64P) for v in keep)), keep
+
+    def jerk_profile(self, W, wp_off, vlim, alim, jlim, grid=2):
+        """(M like W, lim float64 [g_off[B], 3], v, vp, tc, t float64 [g_off[B]], status int32 [B]) of the B paths packed
+        in W as for topp_profile(): knot second derivatives, the limits (V, A, J) of every grid interval, the path speed
+        at the junctions, the peak speed and the cruise time of every interval, the time of every grid point (last
+        entry of a path: its duration); status TOPP_OK / TOPP_STALLED / TOPP_NONFINITE.  Path b's entries start at
+        topp_offsets(wp_off, grid)[1][b]."""
+        W = _f64(W)
+        if W.ndim != 2:
+            raise ValueError(f"W must be [rows, nq], got {W.shape}")
+        wp_off, g_off = self.topp_offsets(wp_off, grid)
+        B = len(wp_off) - 1
+        if B >= 0 and len(wp_off) and wp_off[-1] != len(W):
+            raise ValueError(f"wp_off ends at {wp_off[-1]}, W has {len(W)} rows")
+        desc, keep = self.jerk_desc(W.shape[1], grid, vlim, alim, jlim)
+        ng = max(int(g_off[-1]), 0) if B > 0 else 0
+        M = np.zeros_like(W)
+        lim = np.zeros((ng, 3), np.float64)
+        v, vp, tc, t = (np.zeros(ng, np.float64) for _ in range(4))
+        status = np.zeros(max(B, 0), np.int32)
+        self._ok(self.lib.mjpl_jerk_profile(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                            *(a.ctypes.data_as(_F64P) for a in (M, lim, v, vp, tc, t)),
+                                            status.ctypes.data_as(_I32P)))
+        del keep
+        return M, lim, v, vp, tc, t, status
+
+    def jerk_profile_dev(self, dW, wp_off, nq, vlim, alim, jlim, grid, dM, dlim, dv, dvp, dtc, dt, dstatus):
+        """jerk_profile() on device pointers (wp_off and the limits stay host arrays)."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        desc, keep = self.jerk_desc(nq, grid, vlim, alim, jlim)
+        self._ok(self.lib.mjpl_jerk_profile_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dlim,
+                                                dv, dvp, dtc, dt, dstatus))
+        del keep
+
+    def jerk_sample(self, W, wp_off, M, lim, v, vp, tc, t, dt, samp_off, vlim, alim, jlim, grid=2):
+        """(pos, vel, acc float64 [samp_off[B], nq]): path b sampled at min(k dt, duration), k = 1 .. samp_off[b+1] -
+        samp_off[b], from the outputs of jerk_profile()."""
+        W, M, lim = _f64(W), _f64(M), _f64(lim)
+        v, vp, tc, t = _f64(v), _f64(vp), _f64(tc), _f64(t)
+        wp_off, g_off = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        B = len(wp_off) - 1
+        if len(samp_off) != len(wp_off):
+            raise ValueError("samp_off and wp_off must have the same length")
+        ng = max(int(g_off[-1]), 0)
+        if (W.ndim != 2 or M.shape != W.shape or wp_off[-1] != len(W) or lim.shape != (ng, 3)
+                or not (len(v) == len(vp) == len(tc) == len(t) == ng)):
+            raise ValueError("W, M, lim, v, vp, tc, t do not have the sizes wp_off gives them")
+        desc, keep = self.jerk_desc(W.shape[1], grid, vlim, alim, jlim)
+        ns = max(int(samp_off[-1]), 0)
+        pos, vel, acc = (np.zeros((ns, W.shape[1]), np.float64) for _ in range(3))
+        self._ok(self.lib.mjpl_jerk_sample(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                           *(a.ctypes.data_as(_F64P) for a in (M, lim, v, vp, tc, t)), float(dt),
+                                           samp_off.ctypes.data_as(_I64P), pos.ctypes.data_as(_F64P), vel.ctypes.data_as(_F64P),
+                                           acc.ctypes.data_as(_F64P)))
+        del keep
+        return pos, vel, acc
+
+    def jerk_sample_dev(self, dW, wp_off, nq, dM, dlim, dv, dvp, dtc, dt_grid, dt, samp_off, vlim, alim, jlim, grid, dpos, dvel,
+                        dacc):
+        """jerk_sample() on device pointers (wp_off, samp_off and the limits stay host arrays)."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        desc, keep = self.jerk_desc(nq, grid, vlim, alim, jlim)
+        self._ok(self.lib.mjpl_jerk_sample_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dlim,
+                                               dv, dvp, dtc, dt_grid, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc))
+        del keep
+
+    def time_jerk_dev(self, dW, wp_off, nq, dM, dlim, dv, dvp, dtc, dt_grid, dstatus, dt, samp_off, vlim, alim, jlim, grid, dpos,
+                      dvel, dacc, iters):
+        """(ms_profile, ms_sample) float32 [iters]: device-event times of `iters` jerk_profile_dev + jerk_sample_dev calls."""
+        wp_off, _ = self.topp_offsets(wp_off, grid)
+        samp_off = np.ascontiguousarray(samp_off, dtype=np.int64)
+        desc, keep = self.jerk_desc(nq, grid, vlim, alim, jlim)
+        mp, ms = np.zeros(iters, np.float32), np.zeros(iters, np.float32)
+        self._ok(self.lib.mjpl_time_jerk_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dlim, dv,
+                                             dvp, dtc, dt_grid, dstatus, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc,
+                                             iters, mp.ctypes.data_as(C.POINTER(C.c_float)), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        del keep
+        return mp, ms
 
     # -- certified edge checks: no contact anywhere along an edge (include/mjpl_hip.h, mjpl_sweep_*)
     def sweep_levers(self, lo=None, hi=None) -> np.ndarray:
