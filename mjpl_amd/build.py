@@ -39,6 +39,16 @@ def hipcc_flags() -> list[str]:
     return [*_BASE_FLAGS, f"-DMJPL_SRC_STAMP=0x{src_stamp():016x}ull"]
 
 
+# Specialisations laid over mjpl_device.h by a forced include, on both sides (this library and the per-model ones).
+# NOT a stamped header: it changes no layout, table or value -- a library built without it is slower, not wrong, so
+# the stamp and the program hashes stay what they are (tests/test_gpu_overlay.py compares the two builds).
+OVERLAY_HEADER = os.path.join(CSRC, "mjpl_overlay.h")
+
+
+def overlay_flags() -> list[str]:
+    return ["-include", OVERLAY_HEADER]
+
+
 def _stale(target: str) -> bool:
     if not os.path.exists(target):
         return True
@@ -60,7 +70,7 @@ def build_hip(force: bool = False, lds_tables: bool = False, verbose: bool = Fal
     target = LIB_LDS_PATH if lds_tables else LIB_PATH
     if force or _stale(target):
         tmp = f"{target}.tmp{os.getpid()}"  # (complete under its final name or not at all)
-        cmd = [hipcc(), *hipcc_flags(), "-o", tmp, os.path.join(CSRC, "mjpl_hip.hip")]
+        cmd = [hipcc(), *hipcc_flags(), *overlay_flags(), "-o", tmp, os.path.join(CSRC, "mjpl_hip.hip")]
         if lds_tables:
             cmd.insert(1, "-DMJPL_TABLES_LDS=1")
         if verbose:
