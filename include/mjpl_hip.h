@@ -515,6 +515,60 @@ int mjpl_jerk_sample_dev(mjpl_engine *e, const mjpl_jerk_desc *desc, const doubl
                          const double *dtc, const double *dt_grid, double dt, const int64_t *samp_off, double *dpos,
                          double *dvel, double *dacc);
 
+/* ---- path shortcutting: many paths in lockstep, one edge launch per round ---------------------
+ * The B paths are packed as for mjpl_topp_*: rows W[wp_off[b] .. wp_off[b+1] - 1], each of as many columns
+ * as the engine's planning set (mjpl_set_planning; the full nq by default).  mjpl_shortcut_paths removes
+ * waypoints: wherever the straight edge between two waypoints of a path passes mjpl_check_edges and is
+ * shorter than the stretch between them.  Every number and decision below is stated in NumPy by
+ * tests/shortcut_reference.py; the kernels (mjpl_amd/csrc/mjpl_shortcut.h) match it bit for bit.
+ *
+ * d(a, b) = sqrt(sum_c (W[b][c] - W[a][c])^2), the columns added in order from 0.0, one IEEE rounding per
+ * operation.  A path's live list starts as all its rows.  A path with a NaN or inf anywhere gets status
+ * NONFINITE and is left alone (keep all 1, n_out its row count, length NaN, proposed = accepted = 0).
+ * For round r = 0 .. rounds - 1, for every path b (its index in the call) not yet retired, of m live waypoints:
+ *   1. m <= 2: status CONVERGED, retired.
+ *   2. L[0] = 0, L[k] = L[k-1] + d(live[k-1], live[k]), added in index order.
+ *   3. npairs = (m-1)(m-2)/2; the round is exhaustive iff npairs <= candidates.  Candidate l < candidates is,
+ *      in an exhaustive round, the l-th pair (i, j), j >= i + 2, in lexicographic order (none for l >= npairs);
+ *      otherwise z = sm(sm(sm(seed) ^ b) ^ (64 r + l)), sm = splitmix64's step (x += 0x9E3779B97F4A7C15;
+ *      x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^= x >> 31; mod 2^64),
+ *      i = ((z & 0xffffffff) (m-2)) >> 32, j = i + 2 + (((z >> 32) (m-2-i)) >> 32).  Its saving is
+ *      s = (L[j] - L[i]) - d(live[i], live[j]); it is PROPOSED iff s > min_saving.
+ *   4. The verdict of a proposed candidate is mjpl_check_edges(QA = W[live[i]], QB = W[live[j]], step_dist,
+ *      flags = 0) -- every proposal of every path in ONE launch of the edge pipeline per round; an edge the
+ *      edge kernels refuse (first_bad = -2) counts as invalid, and no MJPL_E_NONFINITE is reported for it.
+ *   5. An exhaustive round without a valid proposal: status CONVERGED, retired -- at the sampled verdict no
+ *      single shortcut of the path is both valid and shorter.
+ *   6. The valid proposals, by (s descending, l ascending): one is accepted iff it is compatible with every
+ *      one accepted before it ((i, j) and (i', j') are compatible iff j <= i' or j' <= i); live[i+1 .. j-1]
+ *      of every accepted one leave the list.  Comparisons only.
+ * Paths not retired after the last round get status ROUNDS.  keep [wp_off[B]]: 1 = the row survives (the
+ * first and last row of a path always do); n_out [B] the survivors; length [B] is L over the final live
+ * list; proposed [B] the edges validated, accepted [B] the shortcuts taken.  length, proposed and accepted
+ * may be NULL.  The state after `rounds` = R equals the state of a longer run after R rounds.
+ *
+ * MJPL_E_ARG: a NULL pointer, step_dist <= 0 or NaN, rounds < 1, candidates outside 1..64, min_saving
+ * negative or NaN, a path of fewer than 2 rows (offsets that fall included); MJPL_E_CAPACITY: a path of more
+ * than 65 536 rows.  B = 0 launches nothing.  The option "shortcut_chunk_bytes" (the workspace of one chunk
+ * of paths, 256 MiB) changes the number of launches -- "shortcut_last_chunks" reads it back -- and no bit of
+ * any output.  Both forms synchronise the engine's stream once per round (the round's edge count comes
+ * back to the host); wp_off is a host array in both.  The edge pipeline's status word (mjpl_take_status)
+ * is cleared by the call. */
+#define MJPL_SHORTCUT_CONVERGED 0
+#define MJPL_SHORTCUT_ROUNDS    1
+#define MJPL_SHORTCUT_NONFINITE 2
+typedef struct {
+  double step_dist, min_saving;
+  uint64_t seed;
+  int32_t rounds, candidates;
+} mjpl_shortcut_desc;
+int mjpl_shortcut_paths(mjpl_engine *e, const mjpl_shortcut_desc *desc, const double *W, const int64_t *wp_off, int64_t B,
+                        uint8_t *keep, int32_t *n_out, double *length, int32_t *status, int32_t *proposed,
+                        int32_t *accepted);
+int mjpl_shortcut_paths_dev(mjpl_engine *e, const mjpl_shortcut_desc *desc, const double *dW, const int64_t *wp_off,
+                            int64_t B, uint8_t *dkeep, int32_t *dn_out, double *dlength, int32_t *dstatus,
+                            int32_t *dproposed, int32_t *daccepted);
+
 /* ---- certified edge checks: no contact anywhere along an edge ------------------------------
  * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
  * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md

@@ -39,6 +39,9 @@
 #include "mjpl_sweep.h"
 #include "mjpl_topp.h"
 #include "mjpl_jerk.h"
+#include "mjpl_shortcut.h"
+
+#include <rocprim/device/device_scan.hpp>
 
 namespace {
 
@@ -49,6 +52,8 @@ constexpr int kNumCtr = kNumCounters;
 constexpr size_t kFusedDbgWaves = 256 * 4 * 3 * 2;  // (wave slots of the chip, with room)
 // workspace of one chunk of paths of mjpl_topp_profile* (one path may exceed it): the default of the option "topp_chunk_bytes"
 constexpr size_t kToppChunkBytes = (size_t)512 << 20;
+// workspace of one chunk of paths of mjpl_shortcut_paths* (one path may exceed it): the default of the option "shortcut_chunk_bytes"
+constexpr size_t kShortcutChunkBytes = (size_t)256 << 20;
 
 thread_local std::string g_err;
 
@@ -558,6 +563,18 @@ struct mjpl_engine {
   // launches changes, no bit of any output); read-only option "topp_last_chunks": chunks of the last mjpl_topp_profile*
   int64_t topp_chunk_bytes = (int64_t)kToppChunkBytes;
   int64_t topp_last_chunks = 0;
+  // mjpl_shortcut_paths* (mjpl_shortcut.h): the call's offsets on the device, and per chunk of paths the live lists, arc
+  // lengths, candidates, the round's edge batch with its verdicts, the round's header and rocPRIM's scan space.
+  DevBuf<int64_t> d_sc_off;
+  DevBuf<double> d_sc_f64;
+  DevBuf<int> d_sc_i32;
+  DevBuf<unsigned long long> d_sc_head;
+  DevBuf<char> d_sc_tmp;
+  // option "shortcut_chunk_bytes": the workspace of one chunk of paths (more or fewer launches, no bit of any output);
+  // read-only: "shortcut_last_chunks", and what the last call validated and -- with "kernel_timer" & 1 -- spent per phase
+  int64_t shortcut_chunk_bytes = (int64_t)kShortcutChunkBytes;
+  int64_t shortcut_last_chunks = 0, shortcut_last_rounds = 0, shortcut_last_edges = 0;
+  double shortcut_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
 };
 
 namespace {
@@ -2226,6 +2243,14 @@ const EngineOption kEngineOptions[] = {
     // ---- trajectories (launch_topp_profile; read at the next call: more or fewer launches, the same bits)
     MJPL_OPT_INT("topp_chunk_bytes", topp_chunk_bytes, 1, 1ll << 40),
     {"topp_last_chunks", [](mjpl_engine *e) { return (double)e->topp_last_chunks; }, nullptr},
+    // ---- path shortcutting (launch_shortcut; the chunk size is read at the next call: more or fewer launches, the same bits)
+    MJPL_OPT_INT("shortcut_chunk_bytes", shortcut_chunk_bytes, 1, 1ll << 40),
+    {"shortcut_last_chunks", [](mjpl_engine *e) { return (double)e->shortcut_last_chunks; }, nullptr},
+    {"shortcut_last_rounds", [](mjpl_engine *e) { return (double)e->shortcut_last_rounds; }, nullptr},
+    {"shortcut_last_edges", [](mjpl_engine *e) { return (double)e->shortcut_last_edges; }, nullptr},
+    {"shortcut_last_propose_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[0]; }, nullptr},
+    {"shortcut_last_validate_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[1]; }, nullptr},
+    {"shortcut_last_commit_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[2]; }, nullptr},
     {"kernel_timer", [](mjpl_engine *e) { return (double)e->kt_mode; },
      [](mjpl_engine *e, double v) {
        if (!(v >= 0 && v <= 3)) return false;
@@ -3094,6 +3119,153 @@ int launch_jerk_sample(mjpl_engine *e, const mjpl_jerk_desc &d, const double *dW
   return MJPL_OK;
 }
 
+// ---- path shortcutting (mjpl_shortcut.h)
+int check_shortcut_args(const mjpl_engine *e, const mjpl_shortcut_desc *d, const void *W, const int64_t *wp_off, int64_t B,
+                        const void *keep, const void *n_out, const void *status) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (!d) return fail(MJPL_E_ARG, "mjpl_shortcut: NULL descriptor");
+  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_shortcut: batch size %lld out of range", (long long)B);
+  if (!(d->step_dist > 0.0)) return fail(MJPL_E_ARG, "`step_dist` must be > 0, got %g", d->step_dist);
+  if (!(d->min_saving >= 0.0)) return fail(MJPL_E_ARG, "`min_saving` must be >= 0, got %g", d->min_saving);
+  if (d->rounds < 1) return fail(MJPL_E_ARG, "`rounds` must be >= 1, got %d", d->rounds);
+  if (d->candidates < 1 || d->candidates > kShortcutLanes)
+    return fail(MJPL_E_ARG, "`candidates` must be 1..%d, got %d", kShortcutLanes, d->candidates);
+  if (B == 0) return MJPL_OK;
+  if (!wp_off) return fail(MJPL_E_ARG, "mjpl_shortcut: NULL offsets");
+  if (wp_off[0] != 0) return fail(MJPL_E_ARG, "wp_off[0] must be 0, got %lld", (long long)wp_off[0]);
+  for (int64_t b = 0; b < B; b++) {
+    const int64_t n = wp_off[b + 1] - wp_off[b];
+    if (n < 2) return fail(MJPL_E_ARG, "path %lld has %lld waypoints (offsets must rise by at least 2)", (long long)b, (long long)n);
+    if (n > kShortcutMaxRows) return fail(MJPL_E_CAPACITY, "path %lld: %lld waypoints (at most %d supported)", (long long)b, (long long)n, kShortcutMaxRows);
+  }
+  if (!W || !keep || !n_out || !status) return fail(MJPL_E_ARG, "NULL batch pointer");
+  return MJPL_OK;
+}
+
+// option "kernel_timer" & 1 around one phase of mjpl_shortcut_paths*: where its pair of events sits, for the sums of the call
+struct ShortcutPhase {
+  mjpl_engine *e;
+  std::vector<std::pair<int, int>> &log;
+  int phase, at;
+  ShortcutPhase(mjpl_engine *e_, std::vector<std::pair<int, int>> &log_, int phase_) : e(e_), log(log_), phase(phase_), at(e_->kt_used[0]) {
+    kt_mark(e, 1, e->stream);
+  }
+  ~ShortcutPhase() {
+    kt_mark(e, 1, e->stream);
+    if (e->kt_used[0] == at + 2) log.emplace_back(phase, at);
+  }
+};
+
+// mjpl_shortcut_paths* on device batches (wp_off on the host).  Per chunk of paths whose workspace fits the option
+// "shortcut_chunk_bytes" (always at least one path): k_shortcut_init, then per round propose -> one small copy and one
+// synchronisation (the round's header) -> scan, gather, ONE launch_edges -> commit, then k_shortcut_finish.  A round
+// that proposed nothing launches no validation; a chunk whose paths are all retired ends its rounds.
+int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *dW, const int64_t *wp_off, int64_t B, uint8_t *dkeep,
+                    int32_t *dn_out, double *dlength, int32_t *dstatus, int32_t *dproposed, int32_t *daccepted) {
+  e->shortcut_last_chunks = e->shortcut_last_rounds = e->shortcut_last_edges = 0;
+  e->shortcut_last_ms[0] = e->shortcut_last_ms[1] = e->shortcut_last_ms[2] = 0.0;
+  const hipStream_t st = e->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
+  MJPL_TRY(e->d_sc_off.reserve((size_t)B + 1, 1024));
+  MJPL_TRY(e->d_sc_head.reserve(4));
+  HIP_TRY(hipMemcpyAsync(e->d_sc_off.p, wp_off, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  const size_t np = e->qidx.size(), K = (size_t)d.candidates, L64 = kShortcutLanes;
+  // what one path adds to a chunk: K edges (two rows and a verdict each), its candidates, its rows' live list and arc lengths
+  const size_t per_path = K * (2 * np * sizeof(double) + 1) + L64 * (3 * sizeof(int) + sizeof(double)) + 6 * sizeof(int);
+  const size_t per_row = sizeof(int) + sizeof(double), chunk_bytes = (size_t)e->shortcut_chunk_bytes;
+  std::vector<std::pair<int, int>> phases;
+  ShortcutBatch a = {};
+  a.W = dW; a.wp_off = e->d_sc_off.p; a.d = (int)np; a.K = d.candidates;
+  a.min_saving = d.min_saving;
+  {
+    unsigned long long x = d.seed + 0x9E3779B97F4A7C15ull;  // splitmix64's step (shortcut_mix, mjpl_shortcut.h)
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    a.seed_mixed = x ^ (x >> 31);
+  }
+  a.head = e->d_sc_head.p;
+  a.keep = dkeep; a.n_out = dn_out; a.length = dlength; a.status = dstatus; a.proposed = dproposed; a.accepted = daccepted;
+  for (int64_t b0 = 0; b0 < B;) {
+    int64_t b1 = b0 + 1;
+    size_t bytes = per_path + (size_t)(wp_off[b1] - wp_off[b0]) * per_row;
+    while (b1 < B) {
+      const size_t more = per_path + (size_t)(wp_off[b1 + 1] - wp_off[b1]) * per_row;
+      if (bytes + more > chunk_bytes || (size_t)(b1 - b0 + 1) * K > ((size_t)1 << 30)) break;  // (edge offsets are ints)
+      bytes += more;
+      b1++;
+    }
+    const size_t nb = (size_t)(b1 - b0), rows = (size_t)(wp_off[b1] - wp_off[b0]), emax = nb * K;
+    // (the edge batch starts on a 256-byte boundary, as the staged batches of mjpl_check_edges do)
+    const size_t qa_at = (rows + nb * L64 + 31) / 32 * 32, qb_at = (qa_at + emax * np + 31) / 32 * 32;
+    MJPL_TRY(e->d_sc_f64.reserve(qb_at + emax * np));
+    MJPL_TRY(e->d_sc_i32.reserve(rows + 4 * nb + 2 * (nb + 1) + 3 * nb * L64 + (emax + 3) / 4));
+    size_t tmp_bytes = 0;
+    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
+    MJPL_TRY(e->d_sc_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    a.b0 = (int)b0; a.nb = (int)nb; a.row0 = wp_off[b0];
+    a.L = e->d_sc_f64.p; a.cs = a.L + rows; a.QA = a.L + qa_at; a.QB = a.L + qb_at;
+    a.live = e->d_sc_i32.p; a.m = a.live + rows; a.state = a.m + nb; a.nprop = a.state + nb; a.nacc = a.nprop + nb;
+    a.cnt = a.nacc + nb; a.off = a.cnt + (nb + 1); a.ci = a.off + (nb + 1); a.cj = a.ci + nb * L64; a.crank = a.cj + nb * L64;
+    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.crank + nb * L64);
+    a.valid = dvalid;
+    const dim3 grid((unsigned)((nb + kShortcutWaves - 1) / kShortcutWaves)), block(64 * kShortcutWaves);
+    hipLaunchKernelGGL(k_shortcut_init, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    for (int r = 0; r < d.rounds; r++) {
+      a.round = r;
+      unsigned long long head[3] = {0, 0, 0};
+      {
+        ShortcutPhase ph(e, phases, 0);
+        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
+        hipLaunchKernelGGL(k_shortcut_propose, grid, block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (head[2] == 0) break;  // every path of the chunk is retired
+      e->shortcut_last_rounds++;
+      const int64_t E = (int64_t)head[1];
+      a.have_verdicts = E > 0 ? 1 : 0;
+      if (E > 0) {
+        {
+          ShortcutPhase ph(e, phases, 0);
+          if (rocprim::exclusive_scan(e->d_sc_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+            return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+          hipLaunchKernelGGL(k_shortcut_gather, grid, block, 0, st, a);
+          HIP_TRY(hipGetLastError());
+        }
+        double longest;
+        memcpy(&longest, &head[0], sizeof(double));
+        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
+        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
+        ShortcutPhase ph(e, phases, 1);
+        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
+        e->shortcut_last_edges += E;
+      }
+      ShortcutPhase ph(e, phases, 2);
+      hipLaunchKernelGGL(k_shortcut_commit, grid, block, 0, st, a);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(dkeep + wp_off[b0], 0, rows, st));
+    hipLaunchKernelGGL(k_shortcut_finish, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    e->shortcut_last_chunks++;
+    b0 = b1;
+  }
+  // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
+  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
+  if (!phases.empty()) {
+    HIP_TRY(hipStreamSynchronize(st));
+    for (const auto &ph : phases) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph.second], e->kt_ev[0][(size_t)ph.second + 1]));
+      e->shortcut_last_ms[ph.first] += ms;
+    }
+  }
+  return MJPL_OK;
+}
+
 }  // namespace
 
 // ---- certified edge checks (mjpl_sweep.h)
@@ -3641,6 +3813,32 @@ int mjpl_jerk_sample(mjpl_engine *e, const mjpl_jerk_desc *d, const double *W, c
     return launch_jerk_sample(e, *d, (const double *)in[0], wp_off, B, (const double *)in[1], (const double *)in[2],
                               (const double *)in[3], (const double *)in[4], (const double *)in[5], (const double *)in[6], dt,
                               samp_off, (double *)out[0], (double *)out[1], (double *)out[2]);
+  });
+}
+
+// ---- path shortcutting (mjpl_shortcut.h)
+
+int mjpl_shortcut_paths_dev(mjpl_engine *e, const mjpl_shortcut_desc *d, const double *dW, const int64_t *wp_off, int64_t B,
+                            uint8_t *dkeep, int32_t *dn_out, double *dlength, int32_t *dstatus, int32_t *dproposed,
+                            int32_t *daccepted) {
+  int rc = check_shortcut_args(e, d, dW, wp_off, B, dkeep, dn_out, dstatus);
+  if (rc == MJPL_OK && B == 0) e->shortcut_last_chunks = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_shortcut(e, *d, dW, wp_off, B, dkeep, dn_out, dlength, dstatus, dproposed, daccepted);
+}
+
+int mjpl_shortcut_paths(mjpl_engine *e, const mjpl_shortcut_desc *d, const double *W, const int64_t *wp_off, int64_t B, uint8_t *keep,
+                        int32_t *n_out, double *length, int32_t *status, int32_t *proposed, int32_t *accepted) {
+  int rc = check_shortcut_args(e, d, W, wp_off, B, keep, n_out, status);
+  if (rc == MJPL_OK && B == 0) e->shortcut_last_chunks = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t wb = (size_t)wp_off[B] * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
+  const HostOut outs[] = {{keep, (size_t)wp_off[B]}, {n_out, ib}, {length, (size_t)B * sizeof(double)}, {status, ib}, {proposed, ib},
+                          {accepted, ib}};
+  return staged(e, false, {{W, wb}}, outs, [&](void **in, void **out) {
+    return launch_shortcut(e, *d, (const double *)in[0], wp_off, B, (uint8_t *)out[0], (int32_t *)out[1], (double *)out[2],
+                           (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
   });
 }
 

@@ -24,6 +24,8 @@ PUSH_OK, PUSH_STUCK, PUSH_DEGENERATE, PUSH_NONFINITE = 0, 1, 2, 3
 SWEEP_FREE, SWEEP_HIT, SWEEP_UNDECIDED, SWEEP_NONFINITE, SWEEP_RANGE = 0, 1, 2, 3, 4
 # mjpl_topp_profile* status values (include/mjpl_hip.h: MJPL_TOPP_*)
 TOPP_OK, TOPP_STALLED, TOPP_NONFINITE = 0, 1, 2
+# mjpl_shortcut_paths* status values (include/mjpl_hip.h: MJPL_SHORTCUT_*)
+SHORTCUT_CONVERGED, SHORTCUT_ROUNDS, SHORTCUT_NONFINITE = 0, 1, 2
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -106,6 +108,11 @@ class JerkDesc(C.Structure):
     _fields_ = [("nq", C.c_int32), ("grid", C.c_int32), ("vlim", _F64P), ("alim", _F64P), ("jlim", _F64P)]
 
 
+class ShortcutDesc(C.Structure):
+    _fields_ = [("step_dist", C.c_double), ("min_saving", C.c_double), ("seed", C.c_uint64), ("rounds", C.c_int32),
+                ("candidates", C.c_int32)]
+
+
 class SweepDesc(C.Structure):
     _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
 
@@ -177,6 +184,9 @@ ABI = {
                                    C.c_double, _I64P, _F64P, _F64P, _F64P]),
     "mjpl_jerk_sample_dev": (C.c_int, [_VP, C.POINTER(JerkDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_double,
                                        _I64P, _VP, _VP, _VP]),
+    "mjpl_shortcut_paths": (C.c_int, [_VP, C.POINTER(ShortcutDesc), _F64P, _I64P, C.c_int64, _U8P, _I32P, _F64P, _I32P, _I32P,
+                                      _I32P]),
+    "mjpl_shortcut_paths_dev": (C.c_int, [_VP, C.POINTER(ShortcutDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
                                     C.c_int64]),
     "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
@@ -857,6 +867,52 @@ class Engine:
         self._ok(self.lib.mjpl_topp_sample_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dM, dx,
                                                du, dt_grid, float(dt), samp_off.ctypes.data_as(_I64P), dpos, dvel, dacc))
         del keep
+
+    # -- path shortcutting: a batch of paths in lockstep (include/mjpl_hip.h, mjpl_shortcut_paths*)
+    @staticmethod
+    def shortcut_desc(step_dist, rounds=16, candidates=64, seed=0, min_saving=0.0):
+        """The mjpl_shortcut_desc of a call; ValueError for what the library would refuse as MJPL_E_ARG."""
+        step_dist, min_saving, rounds, candidates = float(step_dist), float(min_saving), int(rounds), int(candidates)
+        if not step_dist > 0.0:
+            raise ValueError(f"step_dist must be > 0, got {step_dist}")
+        if not min_saving >= 0.0:
+            raise ValueError(f"min_saving must be >= 0, got {min_saving}")
+        if rounds < 1 or rounds > 2**31 - 1:
+            raise ValueError(f"rounds must be >= 1, got {rounds}")
+        if not 1 <= candidates <= 64:
+            raise ValueError(f"candidates must be 1..64, got {candidates}")
+        return ShortcutDesc(step_dist, min_saving, int(seed) & (2**64 - 1), rounds, candidates)
+
+    def shortcut_paths(self, W, wp_off, step_dist, rounds=16, candidates=64, seed=0, min_saving=0.0):
+        """(keep uint8 [rows], n_out int32 [B], length float64 [B], status int32 [B], proposed int32 [B], accepted int32 [B])
+        of the B paths packed in W [wp_off[B], nplan] (path b: rows wp_off[b] .. wp_off[b+1] - 1), shortcut in lockstep:
+        per round up to `candidates` shortcuts per path, all validated by one edge launch at step_dist, the valid ones
+        committed greedily by saving (include/mjpl_hip.h states the algorithm).  keep marks the surviving rows; status
+        SHORTCUT_CONVERGED / SHORTCUT_ROUNDS / SHORTCUT_NONFINITE."""
+        W = _f64(W)
+        if W.ndim != 2 or W.shape[1] != self.nplan:
+            raise ValueError(f"W must be [rows, nplan] with nplan={self.nplan}, got {W.shape}")
+        wp_off = np.ascontiguousarray(wp_off, dtype=np.int64)
+        B = len(wp_off) - 1
+        if B < 0 or wp_off[-1] != len(W):
+            raise ValueError(f"wp_off must end at W's {len(W)} rows")
+        desc = self.shortcut_desc(step_dist, rounds, candidates, seed, min_saving)
+        keep = np.zeros(len(W), np.uint8)
+        n_out, status, proposed, accepted = (np.zeros(B, np.int32) for _ in range(4))
+        length = np.zeros(B, np.float64)
+        self._ok(self.lib.mjpl_shortcut_paths(self.h, C.byref(desc), W.ctypes.data_as(_F64P), wp_off.ctypes.data_as(_I64P), B,
+                                              keep.ctypes.data_as(_U8P), n_out.ctypes.data_as(_I32P), length.ctypes.data_as(_F64P),
+                                              status.ctypes.data_as(_I32P), proposed.ctypes.data_as(_I32P),
+                                              accepted.ctypes.data_as(_I32P)))
+        return keep, n_out, length, status, proposed, accepted
+
+    def shortcut_paths_dev(self, dW, wp_off, step_dist, dkeep, dn_out, dlength, dstatus, dproposed=None, daccepted=None, rounds=16,
+                           candidates=64, seed=0, min_saving=0.0):
+        """shortcut_paths() on device pointers (wp_off stays a host array; dlength, dproposed, daccepted may be None)."""
+        wp_off = np.ascontiguousarray(wp_off, dtype=np.int64)
+        desc = self.shortcut_desc(step_dist, rounds, candidates, seed, min_saving)
+        self._ok(self.lib.mjpl_shortcut_paths_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dkeep,
+                                                  dn_out, dlength, dstatus, dproposed, daccepted))
 
     # -- trajectories: jerk-limited parameterisation of a batch of paths (include/mjpl_hip.h, mjpl_jerk_*)
     @staticmethod

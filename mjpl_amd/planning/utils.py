@@ -165,3 +165,58 @@ def smooth_path(waypoints: list[np.ndarray], constraints: list[Constraint],
                 chain.reverse()
                 path = path[:i] + chain[:-1] + path[j:]
     return path
+
+
+def smooth_paths(paths: list[list[np.ndarray]], collision, step_dist: float, *, rounds: int = 16, candidates: int = 64,
+                 seed: int = 0, min_saving: float = 0.0, return_info: bool = False):
+    """Shortcut many paths at once on the GPU: the batched counterpart of ``smooth_path(..., sparse=True)``.
+
+    The paths advance in lockstep.  Every round each path proposes up to ``candidates`` (1..64) shortcuts between
+    waypoints it still holds -- all pairs once they are few enough, seeded random pairs otherwise --, the proposals of
+    ALL paths that would shorten their path by more than ``min_saving`` are validated by one edge launch of
+    ``collision`` (a :class:`mjpl_amd.CollisionConstraint`; end point and interior waypoints ``step_dist`` apart), and
+    each path takes its valid ones greedily, largest saving first, skipping any that overlaps one already taken.  A path
+    is done when no single shortcut is both valid and shorter, or after ``rounds`` rounds.  ``include/mjpl_hip.h``
+    (``mjpl_shortcut_paths``) states the algorithm; the result depends on ``seed``, never on how the batch is chunked.
+
+    Returns a list of waypoint lists: a subset of each path's own full-``nq`` arrays (sparse output, first and last
+    waypoint always kept).  With ``return_info`` also a list of dicts, one per path: ``status`` ("converged", "rounds"
+    or "nonfinite": a path holding NaN / inf comes back whole), ``length``, ``proposed`` (edges validated) and
+    ``accepted`` (shortcuts taken).
+
+    Only the collision constraint is consulted.  A straight segment between two configurations inside the joint box
+    stays inside it, so a ``JointLimitConstraint`` the waypoints obey needs no check.  Constraints that project
+    (``PoseConstraint``) and dense output (``sparse=False``) remain with :func:`smooth_path`.
+
+    Raises ``ValueError`` for an empty path, a path of fewer than 2 waypoints, a waypoint that is not a full-``nq``
+    configuration, or a bad parameter.
+    """
+    from .. import engine as _engine
+    nq = collision.model.nq
+    desc = _engine.Engine.shortcut_desc(step_dist, rounds, candidates, seed, min_saving)  # (ValueError for a bad parameter)
+    del desc
+    paths = list(paths)
+    rows, wp_off = [], [0]
+    for b, path in enumerate(paths):
+        if path is None or len(path) == 0:
+            raise ValueError(f"path {b} is empty")
+        if len(path) < 2:
+            raise ValueError(f"path {b} has {len(path)} waypoint: at least 2 are needed")
+        P = np.asarray(path, dtype=np.float64)
+        if P.ndim != 2 or P.shape[1] != nq:
+            raise ValueError(f"path {b}: waypoints must be full configurations of {nq} entries, got {P.shape}")
+        rows.append(P)
+        wp_off.append(wp_off[-1] + len(P))
+    if not paths:
+        return ([], []) if return_info else []
+    collision._ensure_full()
+    keep, _, length, status, proposed, accepted = collision.engine.shortcut_paths(
+        np.concatenate(rows), np.asarray(wp_off, dtype=np.int64), step_dist, rounds=rounds, candidates=candidates, seed=seed,
+        min_saving=min_saving)
+    out = [[q for q, k in zip(path, keep[wp_off[b]:wp_off[b + 1]]) if k] for b, path in enumerate(paths)]
+    if not return_info:
+        return out
+    names = {_engine.SHORTCUT_CONVERGED: "converged", _engine.SHORTCUT_ROUNDS: "rounds", _engine.SHORTCUT_NONFINITE: "nonfinite"}
+    info = [dict(status=names[int(status[b])], length=float(length[b]), proposed=int(proposed[b]), accepted=int(accepted[b]))
+            for b in range(len(paths))]
+    return out, info
