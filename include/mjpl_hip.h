@@ -569,6 +569,70 @@ int mjpl_shortcut_paths_dev(mjpl_engine *e, const mjpl_shortcut_desc *desc, cons
                             int64_t B, uint8_t *dkeep, int32_t *dn_out, double *dlength, int32_t *dstatus,
                             int32_t *dproposed, int32_t *daccepted);
 
+/* ---- planning: many start/goal pairs in lockstep, one edge launch per round --------------------
+ * A bidirectional RRT over B independent problems that all take their rounds together: the planner for many
+ * mostly easy queries (mjpl_rrt_* stays the one for a single hard query).  QI, QG [B][nplan] are the ends, over
+ * the engine's planning columns (mjpl_set_planning; the full nq by default); lo, hi [nplan] the sampling box,
+ * HOST arrays in both forms.  Every number and decision below is stated in NumPy by tests/plan_reference.py;
+ * the kernels (mjpl_amd/csrc/mjpl_plan.h) match it bit for bit.
+ *
+ * d2(a, t) = sum_c (t[c] - a[c])^2, the columns added in order from 0.0, one IEEE rounding per operation.
+ * step(a, t): m = sqrt(d2(a, t)); t itself if m <= epsilon, otherwise column c is
+ * a[c] + ((t[c] - a[c]) / m) * epsilon.  nearest(T, t) is the lowest index k that minimises d2(T[k], t).
+ * sm is splitmix64's step (see mjpl_shortcut_paths).
+ *
+ * Ends.  1. A problem with a NaN or inf in either end gets status NONFINITE.  2. One configuration launch
+ * (mjpl_check_configs) validates all remaining ends; a problem with an invalid end gets INVALID_END.  3. One
+ * edge launch validates the direct edges QA = QI[b], QB = QG[b]; a valid one gives SOLVED, the path
+ * [QI[b], QG[b]] and rounds_used = 0.  4. Otherwise T0 = {QI[b]}, T1 = {QG[b]}, both of parent -1, gained = 0.
+ *
+ * Round r = 0 .. rounds - 1, for every live problem b (its index in the call):
+ *   1. Tree g = r & 1 grows, o = 1 - g is the other; n_g, n_o are their sizes at the start of the round.
+ *   2. n_g >= nodes: status NODES, rounds_used = r, retired.
+ *   3. The connect candidate exists only if gained > 0: for each p among the last `gained` nodes of T_o (those
+ *      it gained in round r - 1), n = nearest(T_g, T_o[p]); the pair of the least d2 wins, ties to the lowest
+ *      p; the connect edge is QA = T_o[p], QB = T_g[n].
+ *   4. Extension candidates l < min(candidates, nodes - n_g): z = sm(sm(sm(seed) ^ b) ^ (64 r + l)); for
+ *      c = 0 .. nplan - 1: u = (z >> 11) * 2^-53, t[c] = lo[c] + u * (hi[c] - lo[c]), z = sm(z);
+ *      k = nearest(T_g, t), q = step(T_g[k], t); the extension edge is QA = T_g[k], QB = q.
+ *   5. ONE launch of the edge pipeline validates every edge of every problem (per problem: the connect edge,
+ *      then the extensions in order of l), at step_dist, flags 0: the verdicts of mjpl_check_edges on the
+ *      same rows.  An edge the edge kernels refuse counts as invalid, and no MJPL_E_NONFINITE is reported.
+ *   6. A valid connect edge: SOLVED, rounds_used = r + 1, this round's extensions dropped; the path is T0 from
+ *      its root to its junction node, then T1 from its junction node to its root, nothing de-duplicated.
+ *      Otherwise the valid extensions are appended to T_g in order of l with parent k, and gained = their count.
+ * Problems live after the last round get ROUNDS, rounds_used = rounds.  A tree's depth is at most the number
+ * of rounds it grew in, so a path has at most rounds + 2 rows.
+ *
+ * P [B][rounds + 2][nplan]: rows 0 .. n_out - 1 are the path of a SOLVED problem (first and last row bit-equal
+ * to the ends), every other row is zero; n_out [B] (0 unless SOLVED); status [B]; and, each may be NULL,
+ * rounds_used [B], edges [B] (edges validated for the problem, the direct one included), tree_nodes [B][2]
+ * (the sizes of T0 and T1; 0 0 for a problem that never reached step 4).  The state after `rounds` = R
+ * equals the state of a longer run after R rounds.
+ *
+ * MJPL_E_ARG: a NULL required pointer, epsilon or step_dist <= 0 or NaN, rounds outside 1..4096, candidates
+ * outside 1..64, nodes outside 2..65536, a non-finite lo or hi (or width hi - lo), lo[c] > hi[c], B < 0.
+ * B = 0 launches nothing.  The option "plan_chunk_bytes" (the workspace of one chunk of problems, 256 MiB)
+ * changes the number of launches -- "plan_last_chunks" reads it back -- and no bit of any output.  Both
+ * forms synchronise the engine's stream once per round (the round's edge count comes back to the host).
+ * The edge pipeline's status word (mjpl_take_status) is cleared by the call. */
+#define MJPL_PLAN_SOLVED      0
+#define MJPL_PLAN_ROUNDS      1
+#define MJPL_PLAN_NONFINITE   2
+#define MJPL_PLAN_INVALID_END 3
+#define MJPL_PLAN_NODES       4
+typedef struct {
+  double epsilon, step_dist;
+  uint64_t seed;
+  int32_t rounds, candidates, nodes, reserved;
+} mjpl_plan_desc;
+int mjpl_plan_paths(mjpl_engine *e, const mjpl_plan_desc *desc, const double *QI, const double *QG, int64_t B,
+                    const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status,
+                    int32_t *rounds_used, int32_t *edges, int32_t *tree_nodes);
+int mjpl_plan_paths_dev(mjpl_engine *e, const mjpl_plan_desc *desc, const double *dQI, const double *dQG, int64_t B,
+                        const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
+                        int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes);
+
 /* ---- certified edge checks: no contact anywhere along an edge ------------------------------
  * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
  * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md

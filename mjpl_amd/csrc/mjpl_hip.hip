@@ -40,6 +40,7 @@
 #include "mjpl_topp.h"
 #include "mjpl_jerk.h"
 #include "mjpl_shortcut.h"
+#include "mjpl_plan.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -54,6 +55,8 @@ constexpr size_t kFusedDbgWaves = 256 * 4 * 3 * 2;  // (wave slots of the chip, 
 constexpr size_t kToppChunkBytes = (size_t)512 << 20;
 // workspace of one chunk of paths of mjpl_shortcut_paths* (one path may exceed it): the default of the option "shortcut_chunk_bytes"
 constexpr size_t kShortcutChunkBytes = (size_t)256 << 20;
+// workspace of one chunk of problems of mjpl_plan_paths* (one problem may exceed it): the default of the option "plan_chunk_bytes"
+constexpr size_t kPlanChunkBytes = (size_t)256 << 20;
 
 thread_local std::string g_err;
 
@@ -575,6 +578,18 @@ struct mjpl_engine {
   int64_t shortcut_chunk_bytes = (int64_t)kShortcutChunkBytes;
   int64_t shortcut_last_chunks = 0, shortcut_last_rounds = 0, shortcut_last_edges = 0;
   double shortcut_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
+  // mjpl_plan_paths* (mjpl_plan.h): the sampling box, and per chunk of problems the trees with their parents, the
+  // round's targets, the ends' batch, the round's edge batch with its verdicts, the round's header and rocPRIM's scan space.
+  DevBuf<double> d_pl_box;
+  DevBuf<double> d_pl_f64;
+  DevBuf<int> d_pl_i32;
+  DevBuf<unsigned long long> d_pl_head;
+  DevBuf<char> d_pl_tmp;
+  // option "plan_chunk_bytes": the workspace of one chunk of problems (more or fewer launches, no bit of any output);
+  // read-only: "plan_last_chunks", and what the last call validated and -- with "kernel_timer" & 1 -- spent per phase
+  int64_t plan_chunk_bytes = (int64_t)kPlanChunkBytes;
+  int64_t plan_last_chunks = 0, plan_last_rounds = 0, plan_last_edges = 0;
+  double plan_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
 };
 
 namespace {
@@ -2251,6 +2266,14 @@ const EngineOption kEngineOptions[] = {
     {"shortcut_last_propose_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[0]; }, nullptr},
     {"shortcut_last_validate_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[1]; }, nullptr},
     {"shortcut_last_commit_ms", [](mjpl_engine *e) { return e->shortcut_last_ms[2]; }, nullptr},
+    // ---- planning in lockstep (launch_plan; the chunk size is read at the next call: more or fewer launches, the same bits)
+    MJPL_OPT_INT("plan_chunk_bytes", plan_chunk_bytes, 1, 1ll << 40),
+    {"plan_last_chunks", [](mjpl_engine *e) { return (double)e->plan_last_chunks; }, nullptr},
+    {"plan_last_rounds", [](mjpl_engine *e) { return (double)e->plan_last_rounds; }, nullptr},
+    {"plan_last_edges", [](mjpl_engine *e) { return (double)e->plan_last_edges; }, nullptr},
+    {"plan_last_propose_ms", [](mjpl_engine *e) { return e->plan_last_ms[0]; }, nullptr},
+    {"plan_last_validate_ms", [](mjpl_engine *e) { return e->plan_last_ms[1]; }, nullptr},
+    {"plan_last_commit_ms", [](mjpl_engine *e) { return e->plan_last_ms[2]; }, nullptr},
     {"kernel_timer", [](mjpl_engine *e) { return (double)e->kt_mode; },
      [](mjpl_engine *e, double v) {
        if (!(v >= 0 && v <= 3)) return false;
@@ -3142,7 +3165,8 @@ int check_shortcut_args(const mjpl_engine *e, const mjpl_shortcut_desc *d, const
   return MJPL_OK;
 }
 
-// option "kernel_timer" & 1 around one phase of mjpl_shortcut_paths*: where its pair of events sits, for the sums of the call
+// option "kernel_timer" & 1 around one phase of mjpl_shortcut_paths* or mjpl_plan_paths*: where its pair of events sits, for
+// the sums of the call
 struct ShortcutPhase {
   mjpl_engine *e;
   std::vector<std::pair<int, int>> &log;
@@ -3155,6 +3179,18 @@ struct ShortcutPhase {
     if (e->kt_used[0] == at + 2) log.emplace_back(phase, at);
   }
 };
+
+// ... and the sums: device time per phase (propose with scan and gather, validate, commit)
+int phase_sums(mjpl_engine *e, const std::vector<std::pair<int, int>> &phases, double (&sums)[3]) {
+  if (phases.empty()) return MJPL_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (const auto &ph : phases) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph.second], e->kt_ev[0][(size_t)ph.second + 1]));
+    sums[ph.first] += ms;
+  }
+  return MJPL_OK;
+}
 
 // mjpl_shortcut_paths* on device batches (wp_off on the host).  Per chunk of paths whose workspace fits the option
 // "shortcut_chunk_bytes" (always at least one path): k_shortcut_init, then per round propose -> one small copy and one
@@ -3177,12 +3213,7 @@ int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *d
   ShortcutBatch a = {};
   a.W = dW; a.wp_off = e->d_sc_off.p; a.d = (int)np; a.K = d.candidates;
   a.min_saving = d.min_saving;
-  {
-    unsigned long long x = d.seed + 0x9E3779B97F4A7C15ull;  // splitmix64's step (shortcut_mix, mjpl_shortcut.h)
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    a.seed_mixed = x ^ (x >> 31);
-  }
+  a.seed_mixed = shortcut_mix(d.seed);
   a.head = e->d_sc_head.p;
   a.keep = dkeep; a.n_out = dn_out; a.length = dlength; a.status = dstatus; a.proposed = dproposed; a.accepted = daccepted;
   for (int64_t b0 = 0; b0 < B;) {
@@ -3255,15 +3286,128 @@ int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *d
   }
   // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
   HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
-  if (!phases.empty()) {
-    HIP_TRY(hipStreamSynchronize(st));
-    for (const auto &ph : phases) {
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph.second], e->kt_ev[0][(size_t)ph.second + 1]));
-      e->shortcut_last_ms[ph.first] += ms;
-    }
+  return phase_sums(e, phases, e->shortcut_last_ms);
+}
+
+// ---- planning in lockstep (mjpl_plan.h)
+int check_plan_args(const mjpl_engine *e, const mjpl_plan_desc *d, const void *QI, const void *QG, int64_t B, const double *lo,
+                    const double *hi, const void *P, const void *n_out, const void *status) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (!d) return fail(MJPL_E_ARG, "mjpl_plan: NULL descriptor");
+  if (B < 0 || B > INT32_MAX) return fail(MJPL_E_ARG, "mjpl_plan: batch size %lld out of range", (long long)B);
+  if (!(d->epsilon > 0.0)) return fail(MJPL_E_ARG, "`epsilon` must be > 0, got %g", d->epsilon);
+  if (!(d->step_dist > 0.0)) return fail(MJPL_E_ARG, "`step_dist` must be > 0, got %g", d->step_dist);
+  if (d->rounds < 1 || d->rounds > 4096) return fail(MJPL_E_ARG, "`rounds` must be 1..4096, got %d", d->rounds);
+  if (d->candidates < 1 || d->candidates > kPlanLanes)
+    return fail(MJPL_E_ARG, "`candidates` must be 1..%d, got %d", kPlanLanes, d->candidates);
+  if (d->nodes < 2 || d->nodes > 65536) return fail(MJPL_E_ARG, "`nodes` must be 2..65536, got %d", d->nodes);
+  if (!lo || !hi) return fail(MJPL_E_ARG, "mjpl_plan: NULL sampling box");
+  for (size_t c = 0; c < e->qidx.size(); c++) {
+    if (!std::isfinite(lo[c]) || !std::isfinite(hi[c]) || !std::isfinite(hi[c] - lo[c]))
+      return fail(MJPL_E_ARG, "sampling box column %zu is not finite: [%g, %g]", c, lo[c], hi[c]);
+    if (lo[c] > hi[c]) return fail(MJPL_E_ARG, "sampling box column %zu: lo %g > hi %g", c, lo[c], hi[c]);
   }
+  if (B == 0) return MJPL_OK;
+  if (!QI || !QG || !P || !n_out || !status) return fail(MJPL_E_ARG, "NULL batch pointer");
   return MJPL_OK;
+}
+
+// mjpl_plan_paths* on device batches (lo, hi on the host).  Per chunk of problems whose workspace fits the option
+// "plan_chunk_bytes" (always at least one problem): k_plan_init, ONE launch_configs on the ends, then per round -- the
+// direct edges are round -1 -- propose -> one small copy and one synchronisation (the round's header) -> scan, gather,
+// ONE launch_edges -> commit, then k_plan_finish.  A chunk whose problems are all retired ends its rounds.
+int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, const double *dQG, int64_t B, const double *lo,
+                const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
+                int32_t *dtree_nodes) {
+  e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = 0.0;
+  const hipStream_t st = e->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
+  const size_t np = e->qidx.size(), K = (size_t)d.candidates, N = (size_t)d.nodes, L64 = kPlanLanes;
+  MJPL_TRY(e->d_pl_box.reserve(2 * np, 64));
+  MJPL_TRY(e->d_pl_head.reserve(4));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_box.p, lo, np * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_box.p + np, hi, np * sizeof(double), hipMemcpyHostToDevice, st));
+  const size_t prows = (size_t)d.rounds + 2;
+  HIP_TRY(hipMemsetAsync(dP, 0, (size_t)B * prows * np * sizeof(double), st));
+  // what one problem adds to a chunk: two trees with their parents, K + 1 edges (two rows and a verdict each), the
+  // round's targets and the nodes they step from, its two ends, its counters
+  const size_t per_problem = 2 * N * (np * sizeof(double) + sizeof(int)) + (K + 1) * (2 * np * sizeof(double) + 1) +
+                             L64 * (np * sizeof(double) + sizeof(int)) + 2 * np * sizeof(double) + 16 * sizeof(int);
+  const size_t fit = std::max<size_t>((size_t)e->plan_chunk_bytes / per_problem, 1);
+  const size_t chunk = std::min(fit, ((size_t)1 << 30) / (K + 1));  // (edge offsets are ints)
+  std::vector<std::pair<int, int>> phases;
+  PlanBatch a = {};
+  a.QI = dQI; a.QG = dQG; a.box = e->d_pl_box.p;
+  a.d = (int)np; a.K = d.candidates; a.N = d.nodes; a.R = d.rounds;
+  a.epsilon = d.epsilon;
+  a.seed_mixed = shortcut_mix(d.seed);
+  a.head = e->d_pl_head.p;
+  a.P = dP; a.n_out = dn_out; a.status = dstatus; a.rounds_used = drounds_used; a.edges = dedges; a.tree_nodes = dtree_nodes;
+  for (int64_t b0 = 0; b0 < B; b0 += (int64_t)chunk) {
+    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * (K + 1);
+    // (the configuration and edge batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do)
+    const size_t ct_at = nb * 2 * N * np, cfg_at = (ct_at + nb * np * L64 + 31) / 32 * 32, qa_at = (cfg_at + 2 * nb * np + 31) / 32 * 32,
+                 qb_at = (qa_at + emax * np + 31) / 32 * 32;
+    MJPL_TRY(e->d_pl_f64.reserve(qb_at + emax * np));
+    const size_t ints = nb * 2 * N + nb * L64 + 2 * nb + 4 * nb + 3 * nb + 2 * nb + 2 * (nb + 1);
+    MJPL_TRY(e->d_pl_i32.reserve(ints + (std::max(emax, 2 * nb) + 3) / 4));
+    size_t tmp_bytes = 0;
+    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
+    MJPL_TRY(e->d_pl_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    a.b0 = (int)b0; a.nb = (int)nb;
+    a.T = e->d_pl_f64.p; a.ct = a.T + ct_at; a.cfg = a.T + cfg_at; a.QA = a.T + qa_at; a.QB = a.T + qb_at;
+    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.n = a.ck + nb * L64; a.state = a.n + 2 * nb; a.gained = a.state + nb;
+    a.rused = a.gained + nb; a.nedges = a.rused + nb; a.conn = a.nedges + nb; a.jn = a.conn + 3 * nb; a.cnt = a.jn + 2 * nb;
+    a.off = a.cnt + (nb + 1);
+    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.off + (nb + 1));  // the ends' verdicts first, every round's after
+    a.cvalid = dvalid; a.valid = dvalid;
+    const dim3 grid((unsigned)((nb + kPlanWaves - 1) / kPlanWaves)), block(64 * kPlanWaves);
+    hipLaunchKernelGGL(k_plan_init, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, dvalid, nullptr));
+    for (int r = -1; r < d.rounds; r++) {
+      a.round = r;
+      unsigned long long head[3] = {0, 0, 0};
+      {
+        ShortcutPhase ph(e, phases, 0);
+        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
+        hipLaunchKernelGGL(k_plan_propose, grid, block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (head[2] == 0) break;  // every problem of the chunk is retired
+      if (r >= 0) e->plan_last_rounds++;
+      const int64_t E = (int64_t)head[1];  // (a problem at work has at least one edge)
+      {
+        ShortcutPhase ph(e, phases, 0);
+        if (rocprim::exclusive_scan(e->d_pl_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+          return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+        hipLaunchKernelGGL(k_plan_gather, grid, block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+      {
+        double longest;
+        memcpy(&longest, &head[0], sizeof(double));
+        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
+        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
+        ShortcutPhase ph(e, phases, 1);
+        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
+        e->plan_last_edges += E;
+      }
+      ShortcutPhase ph(e, phases, 2);
+      hipLaunchKernelGGL(k_plan_commit, grid, block, 0, st, a);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_plan_finish, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    e->plan_last_chunks++;
+  }
+  // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
+  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
+  return phase_sums(e, phases, e->plan_last_ms);
 }
 
 }  // namespace
@@ -3839,6 +3983,32 @@ int mjpl_shortcut_paths(mjpl_engine *e, const mjpl_shortcut_desc *d, const doubl
   return staged(e, false, {{W, wb}}, outs, [&](void **in, void **out) {
     return launch_shortcut(e, *d, (const double *)in[0], wp_off, B, (uint8_t *)out[0], (int32_t *)out[1], (double *)out[2],
                            (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
+  });
+}
+
+// ---- planning in lockstep (mjpl_plan.h)
+
+int mjpl_plan_paths_dev(mjpl_engine *e, const mjpl_plan_desc *d, const double *dQI, const double *dQG, int64_t B, const double *lo,
+                        const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
+                        int32_t *dtree_nodes) {
+  int rc = check_plan_args(e, d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
+  if (rc == MJPL_OK && B == 0) e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_plan(e, *d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
+}
+
+int mjpl_plan_paths(mjpl_engine *e, const mjpl_plan_desc *d, const double *QI, const double *QG, int64_t B, const double *lo,
+                    const double *hi, double *P, int32_t *n_out, int32_t *status, int32_t *rounds_used, int32_t *edges,
+                    int32_t *tree_nodes) {
+  int rc = check_plan_args(e, d, QI, QG, B, lo, hi, P, n_out, status);
+  if (rc == MJPL_OK && B == 0) e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t qb = (size_t)B * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
+  const HostOut outs[] = {{P, qb * ((size_t)d->rounds + 2)}, {n_out, ib}, {status, ib}, {rounds_used, ib}, {edges, ib}, {tree_nodes, 2 * ib}};
+  return staged(e, false, {{QI, qb}, {QG, qb}}, outs, [&](void **in, void **out) {
+    return launch_plan(e, *d, (const double *)in[0], (const double *)in[1], B, lo, hi, (double *)out[0], (int32_t *)out[1],
+                       (int32_t *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
   });
 }
 

@@ -63,7 +63,7 @@ struct ShortcutBatch {
   double *length;
 };
 
-__device__ __forceinline__ unsigned long long shortcut_mix(unsigned long long x) {  // splitmix64's step
+__host__ __device__ __forceinline__ unsigned long long shortcut_mix(unsigned long long x) {  // splitmix64's step
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;

@@ -26,6 +26,8 @@ SWEEP_FREE, SWEEP_HIT, SWEEP_UNDECIDED, SWEEP_NONFINITE, SWEEP_RANGE = 0, 1, 2, 
 TOPP_OK, TOPP_STALLED, TOPP_NONFINITE = 0, 1, 2
 # mjpl_shortcut_paths* status values (include/mjpl_hip.h: MJPL_SHORTCUT_*)
 SHORTCUT_CONVERGED, SHORTCUT_ROUNDS, SHORTCUT_NONFINITE = 0, 1, 2
+# mjpl_plan_paths* status values (include/mjpl_hip.h: MJPL_PLAN_*)
+PLAN_SOLVED, PLAN_ROUNDS, PLAN_NONFINITE, PLAN_INVALID_END, PLAN_NODES = 0, 1, 2, 3, 4
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -113,6 +115,11 @@ class ShortcutDesc(C.Structure):
                 ("candidates", C.c_int32)]
 
 
+class PlanDesc(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("step_dist", C.c_double), ("seed", C.c_uint64), ("rounds", C.c_int32),
+                ("candidates", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SweepDesc(C.Structure):
     _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
 
@@ -187,6 +194,9 @@ ABI = {
     "mjpl_shortcut_paths": (C.c_int, [_VP, C.POINTER(ShortcutDesc), _F64P, _I64P, C.c_int64, _U8P, _I32P, _F64P, _I32P, _I32P,
                                       _I32P]),
     "mjpl_shortcut_paths_dev": (C.c_int, [_VP, C.POINTER(ShortcutDesc), _VP, _I64P, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_plan_paths": (C.c_int, [_VP, C.POINTER(PlanDesc), _F64P, _F64P, C.c_int64, _F64P, _F64P, _F64P, _I32P, _I32P, _I32P, _I32P,
+                                  _I32P]),
+    "mjpl_plan_paths_dev": (C.c_int, [_VP, C.POINTER(PlanDesc), _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
                                     C.c_int64]),
     "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
@@ -913,6 +923,64 @@ class Engine:
         desc = self.shortcut_desc(step_dist, rounds, candidates, seed, min_saving)
         self._ok(self.lib.mjpl_shortcut_paths_dev(self.h, C.byref(desc), dW, wp_off.ctypes.data_as(_I64P), len(wp_off) - 1, dkeep,
                                                   dn_out, dlength, dstatus, dproposed, daccepted))
+
+    # -- planning: a batch of start/goal pairs in lockstep (include/mjpl_hip.h, mjpl_plan_paths*)
+    @staticmethod
+    def plan_desc(step_dist, epsilon, rounds=32, candidates=16, nodes=1024, seed=0):
+        """The mjpl_plan_desc of a call; ValueError for what the library would refuse as MJPL_E_ARG."""
+        step_dist, epsilon, rounds, candidates, nodes = float(step_dist), float(epsilon), int(rounds), int(candidates), int(nodes)
+        if not step_dist > 0.0:
+            raise ValueError(f"step_dist must be > 0, got {step_dist}")
+        if not epsilon > 0.0:
+            raise ValueError(f"epsilon must be > 0, got {epsilon}")
+        if not 1 <= rounds <= 4096:
+            raise ValueError(f"rounds must be 1..4096, got {rounds}")
+        if not 1 <= candidates <= 64:
+            raise ValueError(f"candidates must be 1..64, got {candidates}")
+        if not 2 <= nodes <= 65536:
+            raise ValueError(f"nodes must be 2..65536, got {nodes}")
+        return PlanDesc(epsilon, step_dist, int(seed) & (2**64 - 1), rounds, candidates, nodes, 0)
+
+    def _plan_box(self, lo, hi):
+        lo, hi = _f64(lo), _f64(hi)
+        if lo.shape != (self.nplan,) or hi.shape != (self.nplan,):
+            raise ValueError(f"lo and hi must be [nplan] with nplan={self.nplan}, got {lo.shape} and {hi.shape}")
+        with np.errstate(over="ignore", invalid="ignore"):
+            if not (np.isfinite(lo).all() and np.isfinite(hi).all() and np.isfinite(hi - lo).all()):
+                raise ValueError("lo and hi must be finite (and so must hi - lo)")
+        if (lo > hi).any():
+            raise ValueError("lo must not exceed hi")
+        return lo, hi
+
+    def plan_paths(self, QI, QG, lo, hi, step_dist, epsilon, rounds=32, candidates=16, nodes=1024, seed=0):
+        """(P float64 [B, rounds + 2, nplan], n_out, status, rounds_used, edges int32 [B], tree_nodes int32 [B, 2]) of the
+        B problems QI[b] -> QG[b] ([B, nplan] each), planned in lockstep by a bidirectional RRT that samples the box
+        [lo, hi]: per round one connect edge and up to `candidates` extensions of at most `epsilon` per problem, all
+        validated by one edge launch at step_dist (include/mjpl_hip.h states the algorithm).  Rows 0 .. n_out[b] - 1 of
+        P[b] are the path of a problem whose status is PLAN_SOLVED; the other statuses are PLAN_ROUNDS, PLAN_NONFINITE,
+        PLAN_INVALID_END and PLAN_NODES."""
+        QI, QG = _f64(QI), _f64(QG)
+        if QI.ndim != 2 or QI.shape[1] != self.nplan or QG.shape != QI.shape:
+            raise ValueError(f"QI and QG must both be [B, nplan] with nplan={self.nplan}, got {QI.shape} and {QG.shape}")
+        lo, hi = self._plan_box(lo, hi)
+        desc = self.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)
+        B = len(QI)
+        P = np.zeros((B, desc.rounds + 2, self.nplan), np.float64)
+        n_out, status, rounds_used, edges = (np.zeros(B, np.int32) for _ in range(4))
+        tree_nodes = np.zeros((B, 2), np.int32)
+        self._ok(self.lib.mjpl_plan_paths(self.h, C.byref(desc), QI.ctypes.data_as(_F64P), QG.ctypes.data_as(_F64P), B,
+                                          lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P), P.ctypes.data_as(_F64P),
+                                          n_out.ctypes.data_as(_I32P), status.ctypes.data_as(_I32P), rounds_used.ctypes.data_as(_I32P),
+                                          edges.ctypes.data_as(_I32P), tree_nodes.ctypes.data_as(_I32P)))
+        return P, n_out, status, rounds_used, edges, tree_nodes
+
+    def plan_paths_dev(self, dQI, dQG, B, lo, hi, step_dist, epsilon, dP, dn_out, dstatus, drounds_used=None, dedges=None,
+                       dtree_nodes=None, rounds=32, candidates=16, nodes=1024, seed=0):
+        """plan_paths() on device pointers (lo and hi stay host arrays; drounds_used, dedges, dtree_nodes may be None)."""
+        lo, hi = self._plan_box(lo, hi)
+        desc = self.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)
+        self._ok(self.lib.mjpl_plan_paths_dev(self.h, C.byref(desc), dQI, dQG, int(B), lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P),
+                                              dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes))
 
     # -- trajectories: jerk-limited parameterisation of a batch of paths (include/mjpl_hip.h, mjpl_jerk_*)
     @staticmethod

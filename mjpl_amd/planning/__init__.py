@@ -14,6 +14,7 @@ Node, Tree = _tree.Node, _tree.Tree
 cartesian_plan = _cart.cartesian_plan
 smooth_path, path_length = _utils.smooth_path, _utils.path_length
 smooth_paths = _utils.smooth_paths
+plan_paths = _utils.plan_paths
 
 __all__ = ["RRT", "DeviceBiRRT", "ParallelBiRRT", "EdgeValidator", "HipEdgeValidator", "Node", "Tree", "cartesian_plan",
-           "smooth_path", "smooth_paths", "path_length"]
+           "smooth_path", "smooth_paths", "plan_paths", "path_length"]

@@ -220,3 +220,69 @@ def smooth_paths(paths: list[list[np.ndarray]], collision, step_dist: float, *, 
     info = [dict(status=names[int(status[b])], length=float(length[b]), proposed=int(proposed[b]), accepted=int(accepted[b]))
             for b in range(len(paths))]
     return out, info
+
+
+def plan_paths(q_inits, q_goals, collision, step_dist: float, *, epsilon: float, rounds: int = 32, candidates: int = 16,
+               nodes: int = 1024, seed: int = 0, lo=None, hi=None, return_info: bool = False):
+    """Plan many start/goal pairs at once on the GPU: a bidirectional RRT whose problems take their rounds in lockstep.
+
+    This is the planner for many independent, mostly easy queries -- pick/place pairs, the edges of a roadmap, a set of
+    IK goals to rank; :class:`DeviceBiRRT` stays the one for a single hard query.  A pair whose straight edge is valid
+    is solved at once.  Otherwise each problem grows a tree from either end, alternately: every round it proposes up to
+    ``candidates`` (1..64) extensions of at most ``epsilon`` towards seeded uniform samples of the box ``[lo, hi]``, and
+    one edge that would join the trees where the other tree grew last; the edges of ALL problems are validated by one
+    edge launch of ``collision`` (a :class:`mjpl_amd.CollisionConstraint`; waypoints ``step_dist`` apart), and each
+    problem takes the join if it is valid, its valid extensions otherwise.  A tree holds at most ``nodes`` (2..65536)
+    configurations.  ``include/mjpl_hip.h`` (``mjpl_plan_paths``) states the algorithm; the result depends on ``seed``
+    and on a problem's index in the call, never on how the batch is chunked.
+
+    ``q_inits`` and ``q_goals`` are full-``nq`` configurations.  ``lo`` and ``hi`` default to the model's joint ranges;
+    a joint with ``lo == hi`` stays put (both ends must hold it there).
+
+    Returns, per problem, the path as a list of ``nq`` arrays -- the first and last are the caller's own objects -- or
+    ``None`` for a problem that was not solved.  With ``return_info`` also a list of dicts, one per problem: ``status``
+    ("solved", "rounds", "nonfinite", "invalid_end" or "nodes"), ``rounds_used``, ``edges`` (edges validated, the
+    direct one included) and ``nodes`` (the sizes of the two trees).  The paths are unsmoothed; :func:`smooth_paths`
+    takes them as they are (drop the ``None`` entries first).
+
+    Raises ``ValueError`` for lists of different lengths, a configuration that is not a full-``nq`` one, a finite end
+    outside ``[lo, hi]``, or a bad parameter.
+    """
+    from .. import engine as _engine
+    model = collision.model
+    nq = model.nq
+    _engine.Engine.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)  # (ValueError for a bad parameter)
+    q_inits, q_goals = list(q_inits), list(q_goals)
+    if len(q_inits) != len(q_goals):
+        raise ValueError(f"{len(q_inits)} q_inits but {len(q_goals)} q_goals")
+    lo = np.asarray(model.jnt_range[:, 0] if lo is None else lo, dtype=np.float64)
+    hi = np.asarray(model.jnt_range[:, 1] if hi is None else hi, dtype=np.float64)
+    if lo.shape != (nq,) or hi.shape != (nq,):
+        raise ValueError(f"lo and hi must have {nq} entries, got {lo.shape} and {hi.shape}")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (lo > hi).any():
+        raise ValueError("lo and hi must be finite, with lo <= hi")
+    if not q_inits:
+        return ([], []) if return_info else []
+    QI, QG = np.asarray(q_inits, dtype=np.float64), np.asarray(q_goals, dtype=np.float64)
+    if QI.shape != (len(q_inits), nq) or QG.shape != QI.shape:
+        raise ValueError(f"q_inits and q_goals must be full configurations of {nq} entries, got {QI.shape} and {QG.shape}")
+    for name, Q in (("q_inits", QI), ("q_goals", QG)):
+        out = np.flatnonzero(((Q < lo) | (Q > hi)).any(axis=1))  # (NaN compares false: the library reports it)
+        if len(out):
+            raise ValueError(f"{name}[{out[0]}] lies outside [lo, hi]")
+    collision._ensure_full()
+    P, n_out, status, rounds_used, edges, tree_nodes = collision.engine.plan_paths(
+        QI, QG, lo, hi, step_dist, epsilon, rounds=rounds, candidates=candidates, nodes=nodes, seed=seed)
+    paths = []
+    for b in range(len(q_inits)):
+        if status[b] != _engine.PLAN_SOLVED:
+            paths.append(None)
+            continue
+        paths.append([q_inits[b]] + [P[b, k].copy() for k in range(1, n_out[b] - 1)] + [q_goals[b]])
+    if not return_info:
+        return paths
+    names = {_engine.PLAN_SOLVED: "solved", _engine.PLAN_ROUNDS: "rounds", _engine.PLAN_NONFINITE: "nonfinite",
+             _engine.PLAN_INVALID_END: "invalid_end", _engine.PLAN_NODES: "nodes"}
+    info = [dict(status=names[int(status[b])], rounds_used=int(rounds_used[b]), edges=int(edges[b]),
+                 nodes=(int(tree_nodes[b, 0]), int(tree_nodes[b, 1]))) for b in range(len(q_inits))]
+    return paths, info
