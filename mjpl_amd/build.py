@@ -49,6 +49,19 @@ def overlay_flags() -> list[str]:
     return ["-include", OVERLAY_HEADER]
 
 
+# Code generation options of the kernel compile lines, on both sides like the overlay and for the same reason NOT in
+# hipcc_flags() (the stamp's line) or in the sources: no text, layout or value changes, so stamp and program hashes stay.
+# -structurizecfg-skip-uniform-regions: a branch every lane of a wave takes alike (the wave-uniform `switch (g)` statements
+# of a generated Spec::run's stage loop) stays a scalar branch instead of being linearised into flow blocks with flag
+# registers -- whose phis kept the eight-wide slot file in two places, 48 .. 72 v_mov_b64 per stage iteration (DESIGN.md
+# 5.1).  Off by default in the AMDGPU pipeline: tests/test_gpu_uniform_regions.py compares a build without it bit for bit.
+UNIFORM_REGIONS_FLAGS = ("-mllvm", "-structurizecfg-skip-uniform-regions")
+
+
+def codegen_flags(uniform_regions: bool = True) -> list[str]:
+    return list(UNIFORM_REGIONS_FLAGS) if uniform_regions else []
+
+
 def _stale(target: str) -> bool:
     if not os.path.exists(target):
         return True
@@ -70,7 +83,7 @@ def build_hip(force: bool = False, lds_tables: bool = False, verbose: bool = Fal
     target = LIB_LDS_PATH if lds_tables else LIB_PATH
     if force or _stale(target):
         tmp = f"{target}.tmp{os.getpid()}"  # (complete under its final name or not at all)
-        cmd = [hipcc(), *hipcc_flags(), *overlay_flags(), "-o", tmp, os.path.join(CSRC, "mjpl_hip.hip")]
+        cmd = [hipcc(), *hipcc_flags(), *overlay_flags(), *codegen_flags(), "-o", tmp, os.path.join(CSRC, "mjpl_hip.hip")]
         if lds_tables:
             cmd.insert(1, "-DMJPL_TABLES_LDS=1")
         if verbose:

@@ -46,6 +46,9 @@ from .program import (B_BODYID, B_DOFF, B_NGEOM, B_NJNT, B_PARENT, B_SAVE, B_SIZ
                       P_FIRST, PARENT_CUR, PARENT_STATIC, SLOT_NONE, WN_LEN, WN_ZAXIS, Geom, decode)
 
 SPEC_DIR = os.path.join(_build.CSRC, "spec")
+# under SPEC_DIR: a few libraries once more WITHOUT build.codegen_flags' option (build(uniform_regions=False)), compiled by
+# __graft_entry__.build() and compared bit for bit by tests/test_gpu_uniform_regions.py
+STRUCTURIZED_SUBDIR = "structurized"
 
 
 class ProgramInfo(C.Structure):
@@ -1466,7 +1469,7 @@ def library_source(model, allowed_collision_bodies=(), qidx=None, qpos_base=None
 
 def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, force: bool = False,
           keep_source: bool = True, extra_flags=(), output: str | None = None, generic: bool = False, prune_contacts: int = 1,
-          overlay: bool = True) -> str | None:
+          overlay: bool = True, uniform_regions: bool = True) -> str | None:
     """Generate and compile the specialised library of (model, planning set, tolerance).  Returns the
     path of the library, or None if the model cannot be specialised (immediate interpreter).
     generic: the ROBOT's scene-generic library instead (named by the robot hash): built from any scene that
@@ -1474,7 +1477,9 @@ def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_
     prune_contacts: the engine option of that name the library is for (0: the program without its never-touch set, which
     an engine with the option off looks for -- A/B measurements).
     overlay: False leaves mjpl_overlay.h (build.overlay_flags) off the compiler's line: the same text, the same hash, the
-    same values from the plain templates of mjpl_device.h -- the comparison build of tests/test_gpu_overlay.py."""
+    same values from the plain templates of mjpl_device.h -- the comparison build of tests/test_gpu_overlay.py.
+    uniform_regions: False leaves build.codegen_flags' option off the line in the same way: the compiler's default control
+    flow, the same values -- the comparison build of tests/test_gpu_uniform_regions.py."""
     made = library_source(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, generic, prune_contacts)
     if made is None:
         return None
@@ -1484,10 +1489,10 @@ def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_
     deps = [os.path.join(_build.CSRC, f) for f in _build.STAMPED_HEADERS] + [_build.OVERLAY_HEADER] + list(GENERATOR_SOURCES)
     if not force and os.path.exists(target) and all(os.path.getmtime(d) <= os.path.getmtime(target) for d in deps):
         return target
-    return _compile(src, os.path.join(SPEC_DIR, f"spec{'g' if generic else ''}_{key:016x}.hip"), target, keep_source, extra_flags, overlay)
+    return _compile(src, os.path.join(SPEC_DIR, f"spec{'g' if generic else ''}_{key:016x}.hip"), target, keep_source, extra_flags, overlay, uniform_regions)
 
 
-def _compile(src: str, src_path: str, target: str, keep_source: bool, extra_flags, overlay: bool = True) -> str:
+def _compile(src: str, src_path: str, target: str, keep_source: bool, extra_flags, overlay: bool = True, uniform_regions: bool = True) -> str:
     """The compile half of build(): `src` through hipcc into `target`; with keep_source the text stays as `src_path`."""
     # Source and library appear under their final names complete or not at all (os.replace): an engine created
     # while a rebuild is running finds the old library or the new one, never half a file -- a failed dlopen would
@@ -1501,7 +1506,7 @@ def _compile(src: str, src_path: str, target: str, keep_source: bool, extra_flag
     # code into v_pk_* instructions -- which issue no faster than the two instructions they replace -- at the
     # price of ~700 v_mov to assemble the pairs and of spilled registers: 0.279 -> 0.259 ms per step
     cmd = [_build.hipcc(), *_build.hipcc_flags(), "-fno-slp-vectorize", "-Wno-unused-variable", "-Wno-unused-but-set-variable", f"-I{_build.CSRC}",
-           *(_build.overlay_flags() if overlay else ()), *extra_flags, "-o", lib_tmp, src_tmp]
+           *(_build.overlay_flags() if overlay else ()), *_build.codegen_flags(uniform_regions), *extra_flags, "-o", lib_tmp, src_tmp]
     try:
         subprocess.run(cmd, check=True)
         os.replace(lib_tmp, target)
