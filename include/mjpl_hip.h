@@ -633,6 +633,91 @@ int mjpl_plan_paths_dev(mjpl_engine *e, const mjpl_plan_desc *desc, const double
                         const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
                         int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes);
 
+/* ---- roadmap planning: validate a scene's edges once, answer many queries ------------------------
+ * mjpl_plan_paths keeps nothing between calls: every call validates its edges again in the same static scene.
+ * These two calls are the multi-query form (a probabilistic roadmap).  mjpl_roadmap_build turns N configurations
+ * into a graph of validated edges, written into the CALLER's arrays; mjpl_roadmap_query reads those arrays and
+ * answers B start/goal pairs with one configuration launch, ONE edge launch and a shortest-path search.  The
+ * engine keeps no roadmap: a graph is valid for the scene and planning columns it was built with, and it is the
+ * caller who keeps them together.  Every number and decision below is stated in NumPy by
+ * tests/roadmap_reference.py; the kernels (mjpl_amd/csrc/mjpl_roadmap.h) match it bit for bit.
+ *
+ * d2(a, t) = sum_c (t[c] - a[c])^2, the columns added in order from 0.0, one IEEE rounding per operation (as for
+ * mjpl_plan_paths); d2(a, t) and d2(t, a) are the same bits.  r2 = radius * radius; lo2 = r2 * 2^-40 (exact).
+ *
+ * mjpl_roadmap_build.  Q [N][nplan] over the engine's planning columns.  Outputs node_valid [N], row_off [N + 1],
+ * adj [2 N k], w [2 N k].
+ *   1. Nodes.  A row with a NaN or inf is invalid; one configuration launch (mjpl_check_configs; zeros stand in for
+ *      such a row) gives the validity of every other row.
+ *   2. Neighbours.  For each valid i, knn(i) is the first k by ascending (d2, j) of the valid j != i with
+ *      lo2 <= d2(Q[i], Q[j]) <= r2: ties go to the lowest index.  The lower bound keeps coincident and
+ *      near-coincident nodes apart: every weight is at least 2^-20 radius, so with N <= 2^20 every path length
+ *      L <= 2^21 radius has fl(L + w) > L, on which step 4 of the query relies.
+ *   3. Candidate edges: the pairs i < j with j in knn(i) or i in knn(j), each once, in ascending (i, j); the edge
+ *      is QA = Q[i], QB = Q[j].  The edge pipeline validates them at step_dist, flags 0 (the verdicts of
+ *      mjpl_check_edges on the same rows; an edge the edge kernels refuse counts as invalid, and no
+ *      MJPL_E_NONFINITE is reported), in as many launches as the option "roadmap_chunk_bytes" asks for.
+ *   4. Graph: a symmetric CSR adjacency.  Entries row_off[v] .. row_off[v + 1] - 1 of adj hold the other endpoint of
+ *      each valid edge at v, ascending by node index; w holds sqrt(d2) of the edge (the same bits in both rows).
+ *      Entries at and past row_off[N] are adj = -1, w = 0.
+ * MJPL_E_ARG: a NULL required pointer, radius or step_dist <= 0, NaN or inf, k outside 1..32, N outside 0..2^20.
+ * N = 0 launches nothing and writes nothing (the empty graph is row_off[0] = 0).
+ *
+ * mjpl_roadmap_query.  The graph arrays as built, and QI, QG [B][nplan].  Outputs P [B][max_rows][nplan] (zeroed by
+ * the call; rows 0 .. n_out - 1 are the path), n_out [B], status [B] and cost [B] (may be NULL; 0.0 unless SOLVED).
+ *   1. Ends.  A NaN or inf in either end: NONFINITE.  Otherwise one configuration launch over all ends; an invalid
+ *      end: INVALID_END.
+ *   2. Attachments of an end x: the first `connections` by ascending (d2(Q[v], x), v) of the valid nodes v with
+ *      d2 <= r2 (no lower bound).
+ *   3. ONE edge launch covers every problem; per problem, in order: the direct edge QI -> QG, the start attachments
+ *      QI -> Q[v] in rank order, the goal attachments Q[v] -> QG in rank order.  A valid direct edge: SOLVED, the
+ *      path [QI, QG], cost = sqrt(d2(QI, QG)).
+ *   4. Search.  init[v] = sqrt(d2) for the valid start attachments, +inf elsewhere; dist is the least fixed point of
+ *      dist[v] = min(init[v], min over u in adj(v) of fl(dist[u] + w(u, v))).  Rounded addition is monotone and the
+ *      weights are positive, so that fixed point is unique and is what Dijkstra's algorithm computes; the kernel
+ *      relaxes in sweeps until one changes nothing, at most N of them.  Goal choice: among the valid goal
+ *      attachments, rank j at node g_j, the least fl(dist[g_j] + sqrt(d2(Q[g_j], QG))), ties to the lowest rank;
+ *      none finite: NO_PATH.  Walk back from the chosen node: at v stop if init[v] == dist[v], otherwise go to the
+ *      lowest-index u in adj(v) with fl(dist[u] + w(u, v)) == dist[v]; dist strictly decreases (the lo2 rule), so
+ *      the walk ends.  The path is QI, the nodes in travel order, QG, and cost the chosen total: the left-to-right
+ *      sum of its segments.  A path of more than max_rows rows: LONG, n_out = 0.
+ * MJPL_E_ARG: a NULL required pointer, connections outside 1..32, max_rows < 2, B < 0 (or above 2^24), N outside
+ * 0..2^20, radius or step_dist <= 0, NaN or inf.  row_off, adj and w are not checked: they must be a build's.
+ * B = 0 launches nothing.
+ *
+ * Options: "roadmap_chunk_bytes" (256 MiB: the edge batch of one launch of a build, and the distance workspace of
+ * one search launch of a query whose graph does not fit in LDS) and "roadmap_lds_nodes" (the largest N whose
+ * distances a query keeps in LDS) change launches and no bit of any output.  Read-only, of the last call:
+ * "roadmap_last_edges" (build: candidate edges; query: edges validated), "roadmap_last_chunks" (build: edge
+ * launches; query: search launches), "roadmap_last_sweeps" (query: relaxation sweeps summed over the problems that
+ * searched; build: 0).  Both calls synchronise the engine's stream (the edge count comes back to the host) and
+ * clear the edge pipeline's status word (mjpl_take_status). */
+#define MJPL_ROADMAP_SOLVED      0
+#define MJPL_ROADMAP_NO_PATH     1
+#define MJPL_ROADMAP_NONFINITE   2
+#define MJPL_ROADMAP_INVALID_END 3
+#define MJPL_ROADMAP_LONG        4
+typedef struct {
+  double radius, step_dist;
+  int32_t k, reserved;
+} mjpl_roadmap_desc;
+typedef struct {
+  double radius, step_dist;
+  int32_t connections, max_rows;
+} mjpl_roadmap_query_desc;
+int mjpl_roadmap_build(mjpl_engine *e, const mjpl_roadmap_desc *desc, const double *Q, int64_t N, uint8_t *node_valid,
+                       int32_t *row_off, int32_t *adj, double *w);
+int mjpl_roadmap_build_dev(mjpl_engine *e, const mjpl_roadmap_desc *desc, const double *dQ, int64_t N, uint8_t *dnode_valid,
+                           int32_t *drow_off, int32_t *dadj, double *dw);
+int mjpl_roadmap_query(mjpl_engine *e, const mjpl_roadmap_query_desc *desc, const double *Q, int64_t N,
+                       const uint8_t *node_valid, const int32_t *row_off, const int32_t *adj, const double *w,
+                       const double *QI, const double *QG, int64_t B, double *P, int32_t *n_out, int32_t *status,
+                       double *cost);
+int mjpl_roadmap_query_dev(mjpl_engine *e, const mjpl_roadmap_query_desc *desc, const double *dQ, int64_t N,
+                           const uint8_t *dnode_valid, const int32_t *drow_off, const int32_t *dadj, const double *dw,
+                           const double *dQI, const double *dQG, int64_t B, double *dP, int32_t *dn_out,
+                           int32_t *dstatus, double *dcost);
+
 /* ---- certified edge checks: no contact anywhere along an edge ------------------------------
  * mjpl_check_edges tests waypoints step_dist apart and nothing between them.  The calls below decide the
  * whole segment q(t) = QA + t (QB - QA), t in [0, 1], by free bubbles and adaptive bisection (DESIGN.md

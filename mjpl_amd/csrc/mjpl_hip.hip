@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <dlfcn.h>
 #include <cstdarg>
@@ -41,7 +42,9 @@
 #include "mjpl_jerk.h"
 #include "mjpl_shortcut.h"
 #include "mjpl_plan.h"
+#include "mjpl_roadmap.h"
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace {
@@ -57,6 +60,11 @@ constexpr size_t kToppChunkBytes = (size_t)512 << 20;
 constexpr size_t kShortcutChunkBytes = (size_t)256 << 20;
 // workspace of one chunk of problems of mjpl_plan_paths* (one problem may exceed it): the default of the option "plan_chunk_bytes"
 constexpr size_t kPlanChunkBytes = (size_t)256 << 20;
+// the edge batch of one launch of mjpl_roadmap_build*, and the distance workspace of one search launch of mjpl_roadmap_query*
+// whose graph does not fit in LDS: the default of the option "roadmap_chunk_bytes"
+constexpr size_t kRoadmapChunkBytes = (size_t)256 << 20;
+// the largest N whose distances mjpl_roadmap_query* keeps in LDS (144 KiB of the CU's 160): the default of "roadmap_lds_nodes"
+constexpr int kRoadmapLdsNodes = 18432;
 
 thread_local std::string g_err;
 
@@ -590,6 +598,20 @@ struct mjpl_engine {
   int64_t plan_chunk_bytes = (int64_t)kPlanChunkBytes;
   int64_t plan_last_chunks = 0, plan_last_rounds = 0, plan_last_edges = 0;
   double plan_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
+  // mjpl_roadmap_build* / mjpl_roadmap_query* (mjpl_roadmap.h): the configuration batch, the neighbour lists and the edge
+  // batch; the lists' indices, counts, flags and verdicts; the sort keys; the call's header; rocPRIM's sort and scan space.
+  // Nothing of a graph stays here between calls: the caller's arrays hold it.
+  DevBuf<double> d_rm_f64;
+  DevBuf<int> d_rm_i32;
+  DevBuf<unsigned long long> d_rm_u64, d_rm_head;
+  DevBuf<char> d_rm_tmp;
+  // options "roadmap_chunk_bytes" and "roadmap_lds_nodes" (more or fewer launches, no bit of any output); read-only: what
+  // the last call did and -- with "kernel_timer" & 1 -- spent per phase (build: nodes, neighbours, validate, graph;
+  // query: attach, validate, search with the walk)
+  int64_t roadmap_chunk_bytes = (int64_t)kRoadmapChunkBytes;
+  int64_t roadmap_lds_nodes = kRoadmapLdsNodes;
+  int64_t roadmap_last_edges = 0, roadmap_last_chunks = 0, roadmap_last_sweeps = 0;
+  double roadmap_last_ms[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -2274,6 +2296,16 @@ const EngineOption kEngineOptions[] = {
     {"plan_last_propose_ms", [](mjpl_engine *e) { return e->plan_last_ms[0]; }, nullptr},
     {"plan_last_validate_ms", [](mjpl_engine *e) { return e->plan_last_ms[1]; }, nullptr},
     {"plan_last_commit_ms", [](mjpl_engine *e) { return e->plan_last_ms[2]; }, nullptr},
+    // ---- roadmap planning (launch_roadmap_build, launch_roadmap_query; read at the next call: more or fewer launches, the same bits)
+    MJPL_OPT_INT("roadmap_chunk_bytes", roadmap_chunk_bytes, 1, 1ll << 40),
+    MJPL_OPT_INT("roadmap_lds_nodes", roadmap_lds_nodes, 0, kRoadmapLdsNodes),
+    {"roadmap_last_edges", [](mjpl_engine *e) { return (double)e->roadmap_last_edges; }, nullptr},
+    {"roadmap_last_chunks", [](mjpl_engine *e) { return (double)e->roadmap_last_chunks; }, nullptr},
+    {"roadmap_last_sweeps", [](mjpl_engine *e) { return (double)e->roadmap_last_sweeps; }, nullptr},
+    {"roadmap_last_phase0_ms", [](mjpl_engine *e) { return e->roadmap_last_ms[0]; }, nullptr},
+    {"roadmap_last_phase1_ms", [](mjpl_engine *e) { return e->roadmap_last_ms[1]; }, nullptr},
+    {"roadmap_last_phase2_ms", [](mjpl_engine *e) { return e->roadmap_last_ms[2]; }, nullptr},
+    {"roadmap_last_phase3_ms", [](mjpl_engine *e) { return e->roadmap_last_ms[3]; }, nullptr},
     {"kernel_timer", [](mjpl_engine *e) { return (double)e->kt_mode; },
      [](mjpl_engine *e, double v) {
        if (!(v >= 0 && v <= 3)) return false;
@@ -3410,6 +3442,281 @@ int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, cons
   return phase_sums(e, phases, e->plan_last_ms);
 }
 
+// ---- roadmap planning (mjpl_roadmap.h)
+constexpr int64_t kRoadmapMaxNodes = (int64_t)1 << 20, kRoadmapMaxProblems = (int64_t)1 << 24;
+
+int check_roadmap_common(const mjpl_engine *e, const void *d, double radius, double step_dist, int64_t N) {
+  if (!e) return fail(MJPL_E_ARG, "engine is NULL");
+  if (!d) return fail(MJPL_E_ARG, "mjpl_roadmap: NULL descriptor");
+  if (!(radius > 0.0) || !std::isfinite(radius)) return fail(MJPL_E_ARG, "`radius` must be > 0 and finite, got %g", radius);
+  if (!(step_dist > 0.0) || !std::isfinite(step_dist)) return fail(MJPL_E_ARG, "`step_dist` must be > 0 and finite, got %g", step_dist);
+  if (N < 0 || N > kRoadmapMaxNodes) return fail(MJPL_E_ARG, "mjpl_roadmap: %lld nodes (0..2^20 supported)", (long long)N);
+  if (rm_knn_lds((int)e->qidx.size()) > ((size_t)64 << 10))
+    return fail(MJPL_E_CAPACITY, "mjpl_roadmap: %zu planning columns do not fit the neighbour kernel's LDS", e->qidx.size());
+  return MJPL_OK;
+}
+
+int check_roadmap_build_args(const mjpl_engine *e, const mjpl_roadmap_desc *d, const void *Q, int64_t N, const void *node_valid,
+                             const void *row_off, const void *adj, const void *w) {
+  MJPL_TRY(check_roadmap_common(e, d, d ? d->radius : 1.0, d ? d->step_dist : 1.0, N));
+  if (d->k < 1 || d->k > kRmMaxK) return fail(MJPL_E_ARG, "`k` must be 1..%d, got %d", kRmMaxK, d->k);
+  if (N == 0) return MJPL_OK;
+  if (!Q || !node_valid || !row_off || !adj || !w) return fail(MJPL_E_ARG, "NULL batch pointer");
+  return MJPL_OK;
+}
+
+int check_roadmap_query_args(const mjpl_engine *e, const mjpl_roadmap_query_desc *d, const void *Q, int64_t N, const void *node_valid,
+                             const void *row_off, const void *adj, const void *w, const void *QI, const void *QG, int64_t B,
+                             const void *P, const void *n_out, const void *status) {
+  MJPL_TRY(check_roadmap_common(e, d, d ? d->radius : 1.0, d ? d->step_dist : 1.0, N));
+  if (d->connections < 1 || d->connections > kRmMaxK) return fail(MJPL_E_ARG, "`connections` must be 1..%d, got %d", kRmMaxK, d->connections);
+  if (d->max_rows < 2) return fail(MJPL_E_ARG, "`max_rows` must be at least 2, got %d", d->max_rows);
+  if (B < 0 || B > kRoadmapMaxProblems) return fail(MJPL_E_ARG, "mjpl_roadmap_query: batch size %lld out of range", (long long)B);
+  if (!row_off || (N > 0 && (!Q || !node_valid || !adj || !w))) return fail(MJPL_E_ARG, "NULL graph pointer");
+  if (B == 0) return MJPL_OK;
+  if (!QI || !QG || !P || !n_out || !status) return fail(MJPL_E_ARG, "NULL batch pointer");
+  return MJPL_OK;
+}
+
+// option "kernel_timer" & 1 around one phase of a roadmap call: its first and last event (launch_configs marks events of
+// its own between them), for the sums of the call
+struct RoadmapPhase {
+  mjpl_engine *e;
+  std::vector<std::array<int, 3>> &log;
+  int phase, at;
+  RoadmapPhase(mjpl_engine *e_, std::vector<std::array<int, 3>> &log_, int phase_) : e(e_), log(log_), phase(phase_), at(e_->kt_used[0]) {
+    kt_mark(e, 1, e->stream);
+  }
+  ~RoadmapPhase() {
+    const int before = e->kt_used[0];
+    kt_mark(e, 1, e->stream);
+    if (at < before && e->kt_used[0] == before + 1) log.push_back({phase, at, before});
+  }
+};
+
+int roadmap_sums(mjpl_engine *e, const std::vector<std::array<int, 3>> &phases) {
+  if (phases.empty()) return MJPL_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (const auto &ph : phases) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph[1]], e->kt_ev[0][(size_t)ph[2]]));
+    e->roadmap_last_ms[ph[0]] += ms;
+  }
+  return MJPL_OK;
+}
+
+void roadmap_reset(mjpl_engine *e) {
+  e->roadmap_last_edges = e->roadmap_last_chunks = e->roadmap_last_sweeps = 0;
+  for (double &ms : e->roadmap_last_ms) ms = 0.0;
+}
+
+inline unsigned rm_grid(size_t n) { return (unsigned)((n + kRmBlock - 1) / kRmBlock); }
+inline size_t rm_pad(size_t doubles) { return (doubles + 31) / 32 * 32; }  // (batches start on 256-byte boundaries)
+
+// rocPRIM's space for a radix sort of n keys (bits 0 .. 52: a node index is below 2^21) and a scan of n ints
+int roadmap_tmp(mjpl_engine *e, size_t n, size_t *bytes) {
+  size_t sort_bytes = 0, scan_bytes = 0;
+  if (rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0, 53, e->stream) != hipSuccess ||
+      rocprim::exclusive_scan(nullptr, scan_bytes, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), e->stream) != hipSuccess)
+    return fail(MJPL_E_HIP, "rocprim: no size for %zu keys", n);
+  *bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 1);
+  return e->d_rm_tmp.reserve(*bytes, 4096);  // (never null: a null space asks rocPRIM for the size)
+}
+
+int roadmap_knn(mjpl_engine *e, const RmKnn &a) {
+  if (a.M == 0) return MJPL_OK;
+  hipLaunchKernelGGL(k_rm_knn, dim3((unsigned)((a.M + kRmTile - 1) / kRmTile)), dim3(kRmTile), rm_knn_lds(a.d), e->stream, a);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+// mjpl_roadmap_build* on device arrays: k_rm_finite, ONE launch_configs, the neighbour lists, the candidate pairs by a
+// sort, one synchronisation (their number, then the longest edge of every launch), launch_edges per chunk of the option
+// "roadmap_chunk_bytes", the directed keys by a second sort, the CSR.
+int launch_roadmap_build(mjpl_engine *e, const mjpl_roadmap_desc &d, const double *dQ, int64_t N64, uint8_t *dnode_valid,
+                         int32_t *drow_off, int32_t *dadj, double *dw) {
+  roadmap_reset(e);
+  const hipStream_t st = e->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
+  const size_t np = e->qidx.size(), N = (size_t)N64, k = (size_t)d.k, M = N * k;
+  const unsigned long long none = (unsigned long long)N << 32;
+  // one launch's edges: two rows and a verdict each
+  const size_t chunk = std::min<size_t>(std::max<size_t>((size_t)e->roadmap_chunk_bytes / (2 * np * sizeof(double) + 1), 1), (size_t)1 << 30);
+  const size_t batch = std::min(chunk, M);
+  const size_t d2_at = rm_pad(N * np), qa_at = rm_pad(d2_at + M), qb_at = rm_pad(qa_at + batch * np);
+  MJPL_TRY(e->d_rm_f64.reserve(qb_at + batch * np));
+  MJPL_TRY(e->d_rm_i32.reserve(M + N + 2 * (M + 1) + (N + 3) / 4 + (M + 3) / 4));
+  MJPL_TRY(e->d_rm_u64.reserve(5 * M));
+  size_t tmp_bytes = 0;
+  MJPL_TRY(roadmap_tmp(e, 2 * M + 1, &tmp_bytes));
+  double *cfg = e->d_rm_f64.p, *nn_d2 = cfg + d2_at, *QA = cfg + qa_at, *QB = cfg + qb_at;
+  int *nn_j = e->d_rm_i32.p, *nn_cnt = nn_j + M, *flag = nn_cnt + N, *pos = flag + (M + 1);
+  uint8_t *fin = reinterpret_cast<uint8_t *>(pos + (M + 1)), *evalid = fin + (N + 3) / 4 * 4;
+  unsigned long long *ka = e->d_rm_u64.p, *kb = ka + 2 * M, *pairs = kb + 2 * M;
+  std::vector<std::array<int, 3>> phases;
+  {
+    RoadmapPhase ph(e, phases, 0);
+    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dQ, (const double *)nullptr, (int)N, (int)np, cfg, fin);
+    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_configs(e, cfg, (int64_t)N, MJPL_AOS, dnode_valid, nullptr));
+    hipLaunchKernelGGL(k_rm_mask, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dnode_valid, (const uint8_t *)fin, (int)N);
+    HIP_TRY(hipGetLastError());
+  }
+  int E32 = 0;
+  {
+    RoadmapPhase ph(e, phases, 1);
+    RmKnn a = {};
+    a.X = dQ; a.xok = dnode_valid; a.M = (int)N; a.Q = dQ; a.qok = dnode_valid; a.N = (int)N; a.d = (int)np; a.k = d.k;
+    a.r2 = d.radius * d.radius; a.lo2 = a.r2 * 0x1.0p-40; a.self = 1;
+    a.nn_j = nn_j; a.nn_d2 = nn_d2; a.nn_cnt = nn_cnt;
+    MJPL_TRY(roadmap_knn(e, a));
+    hipLaunchKernelGGL(k_rm_pair_keys, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const int32_t *)nn_j, (int64_t)M, d.k, none, ka);
+    HIP_TRY(hipGetLastError());
+    if (rocprim::radix_sort_keys(e->d_rm_tmp.p, tmp_bytes, ka, kb, M, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
+    hipLaunchKernelGGL(k_rm_unique, dim3(rm_grid(M + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)M, none, flag);
+    HIP_TRY(hipGetLastError());
+    if (rocprim::exclusive_scan(e->d_rm_tmp.p, tmp_bytes, flag, pos, 0, M + 1, rocprim::plus<int>(), st) != hipSuccess)
+      return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+    hipLaunchKernelGGL(k_rm_compact, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)M, (const int *)flag,
+                       (const int *)pos, pairs);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(&E32, pos + M, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const size_t E = (size_t)E32, nchunks = (E + chunk - 1) / chunk;
+  e->roadmap_last_edges = (int64_t)E;
+  if (E > 0) {
+    std::vector<unsigned long long> longest(nchunks);
+    {
+      RoadmapPhase ph(e, phases, 2);
+      MJPL_TRY(e->d_rm_head.reserve(nchunks, 64));
+      HIP_TRY(hipMemsetAsync(e->d_rm_head.p, 0, nchunks * sizeof(unsigned long long), st));
+      hipLaunchKernelGGL(k_rm_longest, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (int64_t)E, (int64_t)chunk, dQ,
+                         (int)np, e->d_rm_head.p);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(longest.data(), e->d_rm_head.p, nchunks * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t c = 0; c < nchunks; c++) {
+      const size_t e0 = c * chunk, ne = std::min(chunk, E - e0);
+      double len;
+      memcpy(&len, &longest[c], sizeof(double));
+      // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
+      const bool long_edges = ne <= 4096 && len > 64.0 * d.step_dist;
+      RoadmapPhase ph(e, phases, 2);
+      hipLaunchKernelGGL(k_rm_edge_rows, dim3(rm_grid(ne * np)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (int64_t)e0, (int64_t)ne, dQ,
+                         (int)np, QA, QB);
+      HIP_TRY(hipGetLastError());
+      MJPL_TRY(launch_edges(e, QA, QB, (int64_t)ne, d.step_dist, MJPL_AOS, 0, evalid + e0, nullptr, long_edges));
+      e->roadmap_last_chunks++;
+    }
+  }
+  {
+    RoadmapPhase ph(e, phases, 3);
+    if (E > 0) {
+      hipLaunchKernelGGL(k_rm_dir_keys, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (const uint8_t *)evalid, (int64_t)E,
+                         none, ka);
+      HIP_TRY(hipGetLastError());
+      if (rocprim::radix_sort_keys(e->d_rm_tmp.p, tmp_bytes, ka, kb, 2 * E, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
+    }
+    hipLaunchKernelGGL(k_rm_row_off, dim3(rm_grid(N + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)(2 * E), (int)N, drow_off);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rm_csr, dim3(rm_grid(2 * M)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)(2 * E), (int64_t)(2 * M), none, dQ,
+                       (int)np, dadj, dw);
+    HIP_TRY(hipGetLastError());
+  }
+  // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
+  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
+  return roadmap_sums(e, phases);
+}
+
+// mjpl_roadmap_query* on device arrays: k_rm_finite on the ends, ONE launch_configs, the attachments, one synchronisation
+// (the edge count and the longest edge), ONE launch_edges, then k_rm_search: one launch when the distances fit in LDS,
+// otherwise one per chunk of problems whose workspace fits the option "roadmap_chunk_bytes".
+int launch_roadmap_query(mjpl_engine *e, const mjpl_roadmap_query_desc &d, const double *dQ, int64_t N64, const uint8_t *dnode_valid,
+                         const int32_t *drow_off, const int32_t *dadj, const double *dw, const double *dQI, const double *dQG, int64_t B64,
+                         double *dP, int32_t *dn_out, int32_t *dstatus, double *dcost) {
+  roadmap_reset(e);
+  const hipStream_t st = e->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
+  const size_t np = e->qidx.size(), N = (size_t)N64, B = (size_t)B64, C = (size_t)d.connections, emax = B * (1 + 2 * C);
+  int lds_max = 0;
+  HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->device));
+  const bool in_lds = N <= (size_t)e->roadmap_lds_nodes && N * sizeof(double) <= (size_t)lds_max;
+  const size_t fit = in_lds ? B : std::min(B, std::max<size_t>((size_t)e->roadmap_chunk_bytes / std::max<size_t>(N * sizeof(double), 1), 1));
+  const size_t d2_at = rm_pad(2 * B * np), dist_at = rm_pad(d2_at + 2 * B * C), qa_at = rm_pad(dist_at + (in_lds ? 0 : fit * N)),
+               qb_at = rm_pad(qa_at + emax * np);
+  MJPL_TRY(e->d_rm_f64.reserve(qb_at + emax * np));
+  MJPL_TRY(e->d_rm_i32.reserve(2 * B * C + 2 * B + B + 2 * (B + 1) + (B + 3) / 4 + (2 * B + 3) / 4 + (emax + 3) / 4));
+  MJPL_TRY(e->d_rm_head.reserve(4, 64));
+  size_t tmp_bytes = 0;
+  MJPL_TRY(roadmap_tmp(e, B + 1, &tmp_bytes));
+  HIP_TRY(hipMemsetAsync(dP, 0, B * (size_t)d.max_rows * np * sizeof(double), st));
+  RmQuery a = {};
+  a.Q = dQ; a.row_off = drow_off; a.adj = dadj; a.w = dw;
+  a.N = (int)N; a.d = (int)np; a.C = d.connections; a.max_rows = d.max_rows;
+  a.QI = dQI; a.QG = dQG; a.B = (int)B;
+  double *cfg = e->d_rm_f64.p, *att_d2 = cfg + d2_at;
+  a.att_d2 = att_d2; a.dist = in_lds ? nullptr : cfg + dist_at; a.QA = cfg + qa_at; a.QB = cfg + qb_at;
+  int *att_j = e->d_rm_i32.p, *att_cnt = att_j + 2 * B * C;
+  a.att_j = att_j; a.att_cnt = att_cnt; a.state = att_cnt + 2 * B; a.cnt = a.state + B; a.off = a.cnt + (B + 1);
+  uint8_t *fin = reinterpret_cast<uint8_t *>(a.off + (B + 1)), *cvalid = fin + (B + 3) / 4 * 4, *evalid = cvalid + (2 * B + 3) / 4 * 4;
+  a.fin = fin; a.cvalid = cvalid; a.valid = evalid;
+  a.head = e->d_rm_head.p;
+  a.P = dP; a.n_out = dn_out; a.status = dstatus; a.cost = dcost;
+  std::vector<std::array<int, 3>> phases;
+  unsigned long long head[3] = {0, 0, 0};
+  {
+    RoadmapPhase ph(e, phases, 0);
+    HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
+    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(B)), dim3(kRmBlock), 0, st, dQI, dQG, (int)B, (int)np, cfg, fin);
+    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_configs(e, cfg, (int64_t)(2 * B), MJPL_AOS, cvalid, nullptr));
+    RmKnn q = {};
+    q.X = cfg; q.xok = nullptr; q.M = (int)(2 * B); q.Q = dQ; q.qok = dnode_valid; q.N = (int)N; q.d = (int)np; q.k = d.connections;
+    q.r2 = d.radius * d.radius; q.lo2 = 0.0; q.self = 0;
+    q.nn_j = att_j; q.nn_d2 = att_d2; q.nn_cnt = att_cnt;
+    MJPL_TRY(roadmap_knn(e, q));
+    hipLaunchKernelGGL(k_rm_q_count, dim3(rm_grid(B + 1)), dim3(kRmBlock), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (rocprim::exclusive_scan(e->d_rm_tmp.p, tmp_bytes, a.cnt, a.off, 0, B + 1, rocprim::plus<int>(), st) != hipSuccess)
+      return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+    hipLaunchKernelGGL(k_rm_q_gather, dim3((unsigned)((B + kRmBlock / 64 - 1) / (kRmBlock / 64))), dim3(kRmBlock), 0, st, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t E = (int64_t)head[1];
+  e->roadmap_last_edges = E;
+  if (E > 0) {
+    double longest;
+    memcpy(&longest, &head[0], sizeof(double));
+    // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
+    const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
+    RoadmapPhase ph(e, phases, 1);
+    MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, evalid, nullptr, long_edges));
+  }
+  // (a large graph: more waves per problem hide the adjacency's latency; a small one: more problems per CU)
+  const unsigned block = N >= 4096 ? 1024 : kRmBlock;
+  const size_t lds = in_lds ? std::max<size_t>(N * sizeof(double), 8) : 0;
+  if (lds > ((size_t)64 << 10))
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rm_search<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (size_t b0 = 0; b0 < B; b0 += fit) {
+    a.b0 = (int)b0; a.nb = (int)std::min(fit, B - b0);
+    RoadmapPhase ph(e, phases, 2);
+    if (in_lds) hipLaunchKernelGGL(k_rm_search<true>, dim3((unsigned)a.nb), dim3(block), lds, st, a);
+    else hipLaunchKernelGGL(k_rm_search<false>, dim3((unsigned)a.nb), dim3(block), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    e->roadmap_last_chunks++;
+  }
+  HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
+  // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
+  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
+  HIP_TRY(hipStreamSynchronize(st));
+  e->roadmap_last_sweeps = (int64_t)head[2];
+  return roadmap_sums(e, phases);
+}
+
 }  // namespace
 
 // ---- certified edge checks (mjpl_sweep.h)
@@ -4009,6 +4316,59 @@ int mjpl_plan_paths(mjpl_engine *e, const mjpl_plan_desc *d, const double *QI, c
   return staged(e, false, {{QI, qb}, {QG, qb}}, outs, [&](void **in, void **out) {
     return launch_plan(e, *d, (const double *)in[0], (const double *)in[1], B, lo, hi, (double *)out[0], (int32_t *)out[1],
                        (int32_t *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
+  });
+}
+
+// ---- roadmap planning (mjpl_roadmap.h)
+
+int mjpl_roadmap_build_dev(mjpl_engine *e, const mjpl_roadmap_desc *d, const double *dQ, int64_t N, uint8_t *dnode_valid, int32_t *drow_off,
+                           int32_t *dadj, double *dw) {
+  int rc = check_roadmap_build_args(e, d, dQ, N, dnode_valid, drow_off, dadj, dw);
+  if (rc == MJPL_OK && N == 0) roadmap_reset(e);
+  if (rc != MJPL_OK || N == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_roadmap_build(e, *d, dQ, N, dnode_valid, drow_off, dadj, dw);
+}
+
+int mjpl_roadmap_build(mjpl_engine *e, const mjpl_roadmap_desc *d, const double *Q, int64_t N, uint8_t *node_valid, int32_t *row_off,
+                       int32_t *adj, double *w) {
+  int rc = check_roadmap_build_args(e, d, Q, N, node_valid, row_off, adj, w);
+  if (rc == MJPL_OK && N == 0) roadmap_reset(e);
+  if (rc != MJPL_OK || N == 0) return rc;
+  const size_t n = (size_t)N, cap = 2 * n * (size_t)d->k;
+  const HostOut outs[] = {{node_valid, n}, {row_off, (n + 1) * sizeof(int32_t)}, {adj, cap * sizeof(int32_t)}, {w, cap * sizeof(double)}};
+  return staged(e, false, {{Q, n * e->qidx.size() * sizeof(double)}}, outs, [&](void **in, void **out) {
+    return launch_roadmap_build(e, *d, (const double *)in[0], N, (uint8_t *)out[0], (int32_t *)out[1], (int32_t *)out[2], (double *)out[3]);
+  });
+}
+
+int mjpl_roadmap_query_dev(mjpl_engine *e, const mjpl_roadmap_query_desc *d, const double *dQ, int64_t N, const uint8_t *dnode_valid,
+                           const int32_t *drow_off, const int32_t *dadj, const double *dw, const double *dQI, const double *dQG, int64_t B,
+                           double *dP, int32_t *dn_out, int32_t *dstatus, double *dcost) {
+  int rc = check_roadmap_query_args(e, d, dQ, N, dnode_valid, drow_off, dadj, dw, dQI, dQG, B, dP, dn_out, dstatus);
+  if (rc == MJPL_OK && B == 0) roadmap_reset(e);
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  return launch_roadmap_query(e, *d, dQ, N, dnode_valid, drow_off, dadj, dw, dQI, dQG, B, dP, dn_out, dstatus, dcost);
+}
+
+// (the graph is copied to the device with the ends: a caller with many query calls keeps it there and uses the _dev form)
+int mjpl_roadmap_query(mjpl_engine *e, const mjpl_roadmap_query_desc *d, const double *Q, int64_t N, const uint8_t *node_valid,
+                       const int32_t *row_off, const int32_t *adj, const double *w, const double *QI, const double *QG, int64_t B,
+                       double *P, int32_t *n_out, int32_t *status, double *cost) {
+  int rc = check_roadmap_query_args(e, d, Q, N, node_valid, row_off, adj, w, QI, QG, B, P, n_out, status);
+  if (rc == MJPL_OK && B == 0) roadmap_reset(e);
+  if (rc != MJPL_OK || B == 0) return rc;
+  const size_t n = (size_t)N, np = e->qidx.size(), qb = (size_t)B * np * sizeof(double), ib = (size_t)B * sizeof(int32_t);
+  // (the rows of the graph the search reads: row_off[N] of them; an array that is not a build's reads as an empty graph)
+  const size_t m = std::min<size_t>(row_off[n] > 0 ? (size_t)row_off[n] : 0, 2 * n * (size_t)kRmMaxK);
+  const HostOut outs[] = {{P, qb * (size_t)d->max_rows}, {n_out, ib}, {status, ib}, {cost, (size_t)B * sizeof(double)}};
+  return staged(e, false, {{Q, n * np * sizeof(double)}, {node_valid, n}, {row_off, (n + 1) * sizeof(int32_t)}, {adj, m * sizeof(int32_t)},
+                           {w, m * sizeof(double)}, {QI, qb}, {QG, qb}},
+                outs, [&](void **in, void **out) {
+    return launch_roadmap_query(e, *d, (const double *)in[0], N, (const uint8_t *)in[1], (const int32_t *)in[2], (const int32_t *)in[3],
+                                (const double *)in[4], (const double *)in[5], (const double *)in[6], B, (double *)out[0], (int32_t *)out[1],
+                                (int32_t *)out[2], (double *)out[3]);
   });
 }
 

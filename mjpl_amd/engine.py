@@ -28,6 +28,9 @@ TOPP_OK, TOPP_STALLED, TOPP_NONFINITE = 0, 1, 2
 SHORTCUT_CONVERGED, SHORTCUT_ROUNDS, SHORTCUT_NONFINITE = 0, 1, 2
 # mjpl_plan_paths* status values (include/mjpl_hip.h: MJPL_PLAN_*)
 PLAN_SOLVED, PLAN_ROUNDS, PLAN_NONFINITE, PLAN_INVALID_END, PLAN_NODES = 0, 1, 2, 3, 4
+# mjpl_roadmap_query* status values (include/mjpl_hip.h: MJPL_ROADMAP_*); the limits of both roadmap calls
+ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_NONFINITE, ROADMAP_INVALID_END, ROADMAP_LONG = 0, 1, 2, 3, 4
+ROADMAP_MAX_K, ROADMAP_MAX_NODES, ROADMAP_MAX_PROBLEMS = 32, 1 << 20, 1 << 24
 EDGE_INTERIOR_ONLY = 1
 
 _I32P = C.POINTER(C.c_int32)
@@ -120,6 +123,14 @@ class PlanDesc(C.Structure):
                 ("candidates", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RoadmapDesc(C.Structure):
+    _fields_ = [("radius", C.c_double), ("step_dist", C.c_double), ("k", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RoadmapQueryDesc(C.Structure):
+    _fields_ = [("radius", C.c_double), ("step_dist", C.c_double), ("connections", C.c_int32), ("max_rows", C.c_int32)]
+
+
 class SweepDesc(C.Structure):
     _fields_ = [("d_min", C.c_double), ("cap", C.c_double), ("max_depth", C.c_int32), ("lo", _F64P), ("hi", _F64P)]
 
@@ -197,6 +208,12 @@ ABI = {
     "mjpl_plan_paths": (C.c_int, [_VP, C.POINTER(PlanDesc), _F64P, _F64P, C.c_int64, _F64P, _F64P, _F64P, _I32P, _I32P, _I32P, _I32P,
                                   _I32P]),
     "mjpl_plan_paths_dev": (C.c_int, [_VP, C.POINTER(PlanDesc), _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_roadmap_build": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P]),
+    "mjpl_roadmap_build_dev": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _VP, C.c_int64, _VP, _VP, _VP, _VP]),
+    "mjpl_roadmap_query": (C.c_int, [_VP, C.POINTER(RoadmapQueryDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P, _F64P, _F64P, C.c_int64,
+                                     _F64P, _I32P, _I32P, _F64P]),
+    "mjpl_roadmap_query_dev": (C.c_int, [_VP, C.POINTER(RoadmapQueryDesc), _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP,
+                                         _VP, _VP]),
     "mjpl_sweep_levers": (C.c_int, [C.POINTER(_ModelDesc), _I32P, C.c_int32, _I32P, C.c_int32, _F64P, _F64P, _F64P, _F64P,
                                     C.c_int64]),
     "mjpl_sweep_bounds": (C.c_int, [_VP, _F64P, _F64P]),
@@ -981,6 +998,96 @@ class Engine:
         desc = self.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)
         self._ok(self.lib.mjpl_plan_paths_dev(self.h, C.byref(desc), dQI, dQG, int(B), lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P),
                                               dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes))
+
+    # -- roadmap planning: validate a scene's edges once, answer many queries (include/mjpl_hip.h, mjpl_roadmap_*)
+    @staticmethod
+    def _roadmap_lengths(radius, step_dist):
+        radius, step_dist = float(radius), float(step_dist)
+        if not (radius > 0.0 and np.isfinite(radius)):
+            raise ValueError(f"radius must be > 0 and finite, got {radius}")
+        if not (step_dist > 0.0 and np.isfinite(step_dist)):
+            raise ValueError(f"step_dist must be > 0 and finite, got {step_dist}")
+        return radius, step_dist
+
+    @staticmethod
+    def roadmap_desc(radius, step_dist, k=8):
+        """The mjpl_roadmap_desc of a build; ValueError for what the library would refuse as MJPL_E_ARG."""
+        radius, step_dist = Engine._roadmap_lengths(radius, step_dist)
+        k = int(k)
+        if not 1 <= k <= ROADMAP_MAX_K:
+            raise ValueError(f"k must be 1..{ROADMAP_MAX_K}, got {k}")
+        return RoadmapDesc(radius, step_dist, k, 0)
+
+    @staticmethod
+    def roadmap_query_desc(radius, step_dist, connections=8, max_rows=256):
+        """The mjpl_roadmap_query_desc of a query; ValueError for what the library would refuse as MJPL_E_ARG."""
+        radius, step_dist = Engine._roadmap_lengths(radius, step_dist)
+        connections, max_rows = int(connections), int(max_rows)
+        if not 1 <= connections <= ROADMAP_MAX_K:
+            raise ValueError(f"connections must be 1..{ROADMAP_MAX_K}, got {connections}")
+        if not 2 <= max_rows <= 2**31 - 1:
+            raise ValueError(f"max_rows must be at least 2, got {max_rows}")
+        return RoadmapQueryDesc(radius, step_dist, connections, max_rows)
+
+    def roadmap_build(self, Q, radius, step_dist, k=8):
+        """(node_valid uint8 [N], row_off int32 [N + 1], adj int32 [2 N k], w float64 [2 N k]): the roadmap over the rows
+        of Q [N, nplan].  A row is a node if it is finite and collision-free; every node is joined to its k nearest
+        nodes within `radius` (ties to the lowest index, nodes closer than 2^-20 radius left apart) where the edge
+        pipeline finds the edge valid at step_dist; the result is a symmetric CSR adjacency whose rows ascend, with
+        w = the edge's length, and adj = -1, w = 0 past row_off[N] (include/mjpl_hip.h states the algorithm)."""
+        Q = _f64(Q)
+        if Q.ndim != 2 or Q.shape[1] != self.nplan:
+            raise ValueError(f"Q must be [N, nplan] with nplan={self.nplan}, got {Q.shape}")
+        desc = self.roadmap_desc(radius, step_dist, k)
+        N = len(Q)
+        if N > ROADMAP_MAX_NODES:
+            raise ValueError(f"at most {ROADMAP_MAX_NODES} nodes, got {N}")
+        node_valid, row_off = np.zeros(N, np.uint8), np.zeros(N + 1, np.int32)
+        adj, w = np.full(2 * N * desc.k, -1, np.int32), np.zeros(2 * N * desc.k, np.float64)
+        self._ok(self.lib.mjpl_roadmap_build(self.h, C.byref(desc), Q.ctypes.data_as(_F64P), N, node_valid.ctypes.data_as(_U8P),
+                                             row_off.ctypes.data_as(_I32P), adj.ctypes.data_as(_I32P), w.ctypes.data_as(_F64P)))
+        return node_valid, row_off, adj, w
+
+    def roadmap_build_dev(self, dQ, N, radius, step_dist, dnode_valid, drow_off, dadj, dw, k=8):
+        """roadmap_build() on device pointers: dnode_valid N uint8, drow_off N + 1 int32, dadj 2 N k int32, dw 2 N k float64."""
+        desc = self.roadmap_desc(radius, step_dist, k)
+        self._ok(self.lib.mjpl_roadmap_build_dev(self.h, C.byref(desc), dQ, int(N), dnode_valid, drow_off, dadj, dw))
+
+    def roadmap_query(self, Q, node_valid, row_off, adj, w, QI, QG, radius, step_dist, connections=8, max_rows=256):
+        """(P float64 [B, max_rows, nplan], n_out, status int32 [B], cost float64 [B]) of the B problems QI[b] -> QG[b]
+        on the roadmap roadmap_build() returned for Q: each end is attached to its `connections` nearest nodes within
+        `radius`, ONE edge launch validates the direct edge and the attachments of every problem, and a shortest-path
+        search over the graph gives the path of least length.  Rows 0 .. n_out[b] - 1 of P[b] are the path of a problem
+        whose status is ROADMAP_SOLVED and cost[b] its length; the other statuses are ROADMAP_NO_PATH,
+        ROADMAP_NONFINITE, ROADMAP_INVALID_END and ROADMAP_LONG (more than max_rows rows)."""
+        Q, QI, QG = _f64(Q), _f64(QI), _f64(QG)
+        if Q.ndim != 2 or Q.shape[1] != self.nplan:
+            raise ValueError(f"Q must be [N, nplan] with nplan={self.nplan}, got {Q.shape}")
+        if QI.ndim != 2 or QI.shape[1] != self.nplan or QG.shape != QI.shape:
+            raise ValueError(f"QI and QG must both be [B, nplan] with nplan={self.nplan}, got {QI.shape} and {QG.shape}")
+        desc = self.roadmap_query_desc(radius, step_dist, connections, max_rows)
+        N, B = len(Q), len(QI)
+        node_valid = np.ascontiguousarray(node_valid, dtype=np.uint8)
+        row_off, adj = np.ascontiguousarray(row_off, dtype=np.int32), np.ascontiguousarray(adj, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if node_valid.shape != (N,) or row_off.shape != (N + 1,) or adj.ndim != 1 or w.shape != adj.shape:
+            raise ValueError("node_valid [N], row_off [N + 1], adj and w (one length) must be the arrays of roadmap_build()")
+        if N > ROADMAP_MAX_NODES or B > ROADMAP_MAX_PROBLEMS or len(adj) < row_off[N]:
+            raise ValueError(f"at most {ROADMAP_MAX_NODES} nodes and {ROADMAP_MAX_PROBLEMS} problems; adj must hold row_off[N] entries")
+        P = np.zeros((B, desc.max_rows, self.nplan), np.float64)
+        n_out, status, cost = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float64)
+        self._ok(self.lib.mjpl_roadmap_query(self.h, C.byref(desc), Q.ctypes.data_as(_F64P), N, node_valid.ctypes.data_as(_U8P),
+                                             row_off.ctypes.data_as(_I32P), adj.ctypes.data_as(_I32P), w.ctypes.data_as(_F64P),
+                                             QI.ctypes.data_as(_F64P), QG.ctypes.data_as(_F64P), B, P.ctypes.data_as(_F64P),
+                                             n_out.ctypes.data_as(_I32P), status.ctypes.data_as(_I32P), cost.ctypes.data_as(_F64P)))
+        return P, n_out, status, cost
+
+    def roadmap_query_dev(self, dQ, N, dnode_valid, drow_off, dadj, dw, dQI, dQG, B, radius, step_dist, dP, dn_out, dstatus, dcost=None,
+                          connections=8, max_rows=256):
+        """roadmap_query() on device pointers (dcost may be None): the graph stays on the device between calls."""
+        desc = self.roadmap_query_desc(radius, step_dist, connections, max_rows)
+        self._ok(self.lib.mjpl_roadmap_query_dev(self.h, C.byref(desc), dQ, int(N), dnode_valid, drow_off, dadj, dw, dQI, dQG, int(B), dP,
+                                                 dn_out, dstatus, dcost))
 
     # -- trajectories: jerk-limited parameterisation of a batch of paths (include/mjpl_hip.h, mjpl_jerk_*)
     @staticmethod

@@ -3,6 +3,7 @@ frontier-sharded bi-RRT (one batched launch per extension round), Cartesian path
 the path utilities."""
 from . import cartesian_planner as _cart
 from . import parallel_rrt as _prrt
+from . import roadmap as _roadmap
 from . import rrt as _rrt
 from . import tree as _tree
 from . import utils as _utils
@@ -15,6 +16,7 @@ cartesian_plan = _cart.cartesian_plan
 smooth_path, path_length = _utils.smooth_path, _utils.path_length
 smooth_paths = _utils.smooth_paths
 plan_paths = _utils.plan_paths
+Roadmap = _roadmap.Roadmap
 
 __all__ = ["RRT", "DeviceBiRRT", "ParallelBiRRT", "EdgeValidator", "HipEdgeValidator", "Node", "Tree", "cartesian_plan",
-           "smooth_path", "smooth_paths", "plan_paths", "path_length"]
+           "smooth_path", "smooth_paths", "plan_paths", "Roadmap", "path_length"]
