@@ -633,6 +633,86 @@ int mjpl_plan_paths_dev(mjpl_engine *e, const mjpl_plan_desc *desc, const double
                         const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
                         int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes);
 
+/* ---- planning under a PoseConstraint: many start/goal pairs in lockstep, every edge a projected step ----
+ * mjpl_plan_paths consults the collision check only, and joins its trees by one straight edge of any length --
+ * an edge whose interior leaves a constraint manifold.  These two calls plan under the PoseConstraint of a pose
+ * handle `p` (mjpl_pose_create), enforced by projection as the reference's CBiRRT does: every tree edge is ONE
+ * projected step of at most epsilon, and the trees are joined by a BRIDGE -- a chain of projected steps from the
+ * growing tree towards the other tree, closed by a straight edge of at most epsilon.  The engine is the handle's
+ * engine; QI, QG, lo, hi, the planning columns and the lockstep of the rounds are those of mjpl_plan_paths.
+ * Every number and decision below is stated in NumPy by tests/cplan_reference.py; the kernels
+ * (mjpl_amd/csrc/mjpl_cplan.h) match it bit for bit.
+ *
+ * d2, step(a, t) with epsilon, nearest, sm, the sample t of (seed, b, r, l) and the box lo, hi: as for
+ * mjpl_plan_paths.  New:
+ *   project(a, x) -> (y, ok), over planning rows: a and x are expanded to full qpos rows (qpos_base with the
+ *     planning columns replaced); the handle's PoseConstraint.apply runs on x with q_old = a -- the results of
+ *     mjpl_pose_apply on the same rows; ok = 0 if the projection reports failure (joint limits left, farther
+ *     than 2 q_step from q_old, the iteration bound reached), and also if any non-planning column of the
+ *     result differs in bits from qpos_base; y is the planning columns of the result.
+ *   cstep(a, t): x = step(a, t), (y, ok) = project(a, x).  Void if !ok, or sqrt(d2(a, y)) < 1e-8, or
+ *     d2(y, t) > d2(a, t) (the three termination rules of the reference's _constrained_extend); otherwise y.
+ *
+ * Ends.  1. A problem with a NaN or inf in either end gets status NONFINITE.  2. One configuration launch
+ * (mjpl_check_configs) and one mjpl_pose_valid launch cover all remaining ends; an end that fails either gives
+ * INVALID_END.  3. Every other problem starts with T0 = {QI[b]}, T1 = {QG[b]}, both of parent -1, gained = 0.
+ * There is no separate direct-edge stage: round 0's bridge covers it.
+ *
+ * Round r = 0 .. rounds - 1, for every live problem b (its index in the call):
+ *   1. Tree g = r & 1 grows, o = 1 - g is the other; n_g, n_o are their sizes at the start of the round.
+ *      n_g >= nodes: status NODES, rounds_used = r, retired.
+ *   2. Bridge target: for each p among the last max(1, gained) nodes of T_o, n = nearest(T_g, T_o[p]); the pair
+ *      of the least d2 wins, ties to the lowest p.  t = T_o[p], c_0 = T_g[n].
+ *   3. Bridge chain, s = 1 .. min(chain, nodes - n_g): if sqrt(d2(c_{s-1}, t)) <= epsilon the chain ends with
+ *      the CLOSING EDGE QA = c_{s-1}, QB = t.  Otherwise y = cstep(c_{s-1}, t); a void y ends the chain; else
+ *      c_s = y is a LINK with the edge QA = c_{s-1}, QB = c_s.  `links` is the number of links.  The chain is
+ *      generated before any verdict: a projection depends on the projected row before it, not on that row's
+ *      collision verdict.
+ *   4. Extension candidates l < min(candidates, nodes - n_g - links): t_l drawn as in mjpl_plan_paths,
+ *      k = nearest(T_g, t_l) over the tree as it stood at the start of the round, y = cstep(T_g[k], t_l).  A
+ *      void candidate sends no edge and is not counted; otherwise its edge is QA = T_g[k], QB = y.
+ *   5. ONE launch of the edge pipeline validates every edge of every problem (per problem: the links, the
+ *      closing edge if there is one, the non-void extensions in order of l), at step_dist, flags 0, exactly as
+ *      mjpl_plan_paths does: a refused edge counts as invalid.  A round in which no problem has an edge
+ *      launches nothing.
+ *   6. The leading valid links are appended to T_g: the first with parent n, each following one with the link
+ *      before it as parent.  If a closing edge exists, every link was valid and the closing edge is valid:
+ *      SOLVED, rounds_used = r + 1, the junctions are the last appended link (n when there is no link) and
+ *      T_o[p], this round's extensions dropped.  Otherwise the valid extensions are appended in order of l with
+ *      parent k.  In both cases gained = the number of nodes appended this round.
+ *   7. The path of a SOLVED problem is T0 from its root to its junction, then T1 from its junction to its root,
+ *      nothing de-duplicated.  A path of more than max_rows rows: status LONG, n_out = 0.
+ * Problems live after the last round get ROUNDS, rounds_used = rounds.  The state after `rounds` = R equals
+ * the state of a longer run after R rounds.
+ *
+ * P [B][max_rows][nplan], zeroed by the call: rows 0 .. n_out - 1 are the path of a SOLVED problem (first and
+ * last row bit-equal to the ends); n_out [B] (0 unless SOLVED); status [B]; and, each may be NULL,
+ * rounds_used [B], edges [B] (edges validated for the problem), tree_nodes [B][2] (0 0 for NONFINITE and
+ * INVALID_END).  Every row of a path is a projection's result or an end that passed mjpl_pose_valid; the
+ * interior of a step is sampled for collision only, as in the reference.
+ *
+ * MJPL_E_ARG: everything mjpl_plan_paths refuses, chain outside 1..32, max_rows < 2, a NULL handle, more
+ * planning columns than the projection's 16.  (The call knows the handle's engine only: a binding that takes an
+ * engine AND a handle refuses a handle of another engine itself, as mjpl_amd's does with a ValueError.)  The options "plan_chunk_bytes" (no bit of any
+ * output changes) and the read-only "plan_last_chunks", "plan_last_rounds", "plan_last_edges" serve these calls
+ * as they serve mjpl_plan_paths; with "kernel_timer" & 1, "plan_last_project_ms" is the projections' share.
+ * Choose epsilon < 2 q_step: at epsilon = 2 q_step the projection's "farther than 2 q_step" rule turns on
+ * roundings. */
+#define MJPL_PLAN_LONG        5
+typedef struct {
+  double epsilon, step_dist;
+  uint64_t seed;
+  int32_t rounds, candidates, nodes, chain, max_rows, reserved;
+} mjpl_cplan_desc;
+struct mjpl_pose; /* (mjpl_pose_create, below) */
+int mjpl_plan_paths_constrained(struct mjpl_pose *p, const mjpl_cplan_desc *desc, const double *QI, const double *QG,
+                                int64_t B, const double *lo, const double *hi, double *P, int32_t *n_out,
+                                int32_t *status, int32_t *rounds_used, int32_t *edges, int32_t *tree_nodes);
+int mjpl_plan_paths_constrained_dev(struct mjpl_pose *p, const mjpl_cplan_desc *desc, const double *dQI,
+                                    const double *dQG, int64_t B, const double *lo, const double *hi, double *dP,
+                                    int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
+                                    int32_t *dtree_nodes);
+
 /* ---- roadmap planning: validate a scene's edges once, answer many queries ------------------------
  * mjpl_plan_paths keeps nothing between calls: every call validates its edges again in the same static scene.
  * These two calls are the multi-query form (a probabilistic roadmap).  mjpl_roadmap_build turns N configurations

@@ -8,7 +8,7 @@ from .inverse_kinematics import HipIKSolver, IKSolver
 from .lie import SE3, SO3
 from .model import Model, ModelBuilder, load_mjcf, parse_mjcf
 from .planning import (RRT, DeviceBiRRT, EdgeValidator, HipEdgeValidator, Node, ParallelBiRRT, Roadmap, Tree,
-                       cartesian_plan, path_length, plan_paths, smooth_path, smooth_paths)
+                       cartesian_plan, path_length, plan_paths, plan_paths_constrained, smooth_path, smooth_paths)
 from .trajectory import (HipJerkTrajectoryGenerator, HipToppTrajectoryGenerator, Trajectory, TrajectoryGenerator,
                          generate_certified_trajectories, generate_certified_trajectory, generate_constrained_trajectories, generate_constrained_trajectory)
 from .utils import all_joints, qpos_idx, qvel_idx, random_config, site_pose
@@ -23,7 +23,7 @@ __all__ = (
     "CertifiedIntervals", "ClearanceConstraint", "CollisionConstraint", "CollisionRuleset", "Constraint", "JointLimitConstraint", "PoseConstraint",
     "SE3", "SO3", "site_pose", "HipIKSolver", "IKSolver", "cartesian_plan",
     "apply_constraints", "obeys_constraints", "Model", "ModelBuilder", "load_mjcf", "parse_mjcf",
-    "RRT", "Node", "Tree", "path_length", "smooth_path", "smooth_paths", "plan_paths", "Roadmap", "ParallelBiRRT", "DeviceBiRRT", "EdgeValidator", "HipEdgeValidator",
+    "RRT", "Node", "Tree", "path_length", "smooth_path", "smooth_paths", "plan_paths", "plan_paths_constrained", "Roadmap", "ParallelBiRRT", "DeviceBiRRT", "EdgeValidator", "HipEdgeValidator",
     "Trajectory", "TrajectoryGenerator", "HipToppTrajectoryGenerator", "HipJerkTrajectoryGenerator", "generate_constrained_trajectory",
     "generate_constrained_trajectories", "generate_certified_trajectory", "generate_certified_trajectories",
     "all_joints", "qpos_idx", "qvel_idx", "random_config", "comm_unique_id",

@@ -42,6 +42,7 @@
 #include "mjpl_jerk.h"
 #include "mjpl_shortcut.h"
 #include "mjpl_plan.h"
+#include "mjpl_cplan.h"
 #include "mjpl_roadmap.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -593,11 +594,12 @@ struct mjpl_engine {
   DevBuf<int> d_pl_i32;
   DevBuf<unsigned long long> d_pl_head;
   DevBuf<char> d_pl_tmp;
+  DevBuf<int> d_pl_q;  // mjpl_plan_paths_constrained* (mjpl_cplan.h): the planning columns and their inverse
   // option "plan_chunk_bytes": the workspace of one chunk of problems (more or fewer launches, no bit of any output);
   // read-only: "plan_last_chunks", and what the last call validated and -- with "kernel_timer" & 1 -- spent per phase
   int64_t plan_chunk_bytes = (int64_t)kPlanChunkBytes;
   int64_t plan_last_chunks = 0, plan_last_rounds = 0, plan_last_edges = 0;
-  double plan_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
+  double plan_last_ms[4] = {0, 0, 0, 0};  // propose (with scan and gather), validate, commit; constrained: project
   // mjpl_roadmap_build* / mjpl_roadmap_query* (mjpl_roadmap.h): the configuration batch, the neighbour lists and the edge
   // batch; the lists' indices, counts, flags and verdicts; the sort keys; the call's header; rocPRIM's sort and scan space.
   // Nothing of a graph stays here between calls: the caller's arrays hold it.
@@ -2296,6 +2298,7 @@ const EngineOption kEngineOptions[] = {
     {"plan_last_propose_ms", [](mjpl_engine *e) { return e->plan_last_ms[0]; }, nullptr},
     {"plan_last_validate_ms", [](mjpl_engine *e) { return e->plan_last_ms[1]; }, nullptr},
     {"plan_last_commit_ms", [](mjpl_engine *e) { return e->plan_last_ms[2]; }, nullptr},
+    {"plan_last_project_ms", [](mjpl_engine *e) { return e->plan_last_ms[3]; }, nullptr},
     // ---- roadmap planning (launch_roadmap_build, launch_roadmap_query; read at the next call: more or fewer launches, the same bits)
     MJPL_OPT_INT("roadmap_chunk_bytes", roadmap_chunk_bytes, 1, 1ll << 40),
     MJPL_OPT_INT("roadmap_lds_nodes", roadmap_lds_nodes, 0, kRoadmapLdsNodes),
@@ -3213,7 +3216,8 @@ struct ShortcutPhase {
 };
 
 // ... and the sums: device time per phase (propose with scan and gather, validate, commit)
-int phase_sums(mjpl_engine *e, const std::vector<std::pair<int, int>> &phases, double (&sums)[3]) {
+template <size_t NP>
+int phase_sums(mjpl_engine *e, const std::vector<std::pair<int, int>> &phases, double (&sums)[NP]) {
   if (phases.empty()) return MJPL_OK;
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (const auto &ph : phases) {
@@ -3352,7 +3356,7 @@ int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, cons
                 const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                 int32_t *dtree_nodes) {
   e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
-  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = 0.0;
+  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = e->plan_last_ms[3] = 0.0;
   const hipStream_t st = e->stream;
   HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
   const size_t np = e->qidx.size(), K = (size_t)d.candidates, N = (size_t)d.nodes, L64 = kPlanLanes;
@@ -4854,6 +4858,178 @@ int mjpl_pose_valid(mjpl_pose *p, const double *Q, int64_t N, uint8_t *valid, do
                   return mjpl_pose_valid_dev(p, (const double *)in[0], N, (uint8_t *)out[0], (double *)out[1],
                                              (double *)out[2]);
                 });
+}
+
+// ---- planning in lockstep under a PoseConstraint (mjpl_cplan.h)
+
+namespace {
+int check_cplan_args(const mjpl_pose *p, const mjpl_cplan_desc *d, const void *QI, const void *QG, int64_t B, const double *lo,
+                     const double *hi, const void *P, const void *n_out, const void *status) {
+  if (!p) return fail(MJPL_E_ARG, "pose handle is NULL");
+  if (!d) return fail(MJPL_E_ARG, "mjpl_plan: NULL descriptor");
+  const mjpl_plan_desc pd = {d->epsilon, d->step_dist, d->seed, d->rounds, d->candidates, d->nodes, 0};
+  if (d->chain < 1 || d->chain > kCplanMaxChain) return fail(MJPL_E_ARG, "`chain` must be 1..%d, got %d", kCplanMaxChain, d->chain);
+  if (d->max_rows < 2) return fail(MJPL_E_ARG, "`max_rows` must be >= 2, got %d", d->max_rows);
+  const size_t np = p->e->qidx.size();
+  if (np < 1 || np > (size_t)kRrtMaxPlan) return fail(MJPL_E_ARG, "%zu planning columns (1..%d supported under a projection)", np, kRrtMaxPlan);
+  return check_plan_args(p->e, &pd, QI, QG, B, lo, hi, P, n_out, status);
+}
+
+size_t cplan_lds(const mjpl_pose *p) { return pose_lds(p) + (size_t)kPoseBlock * sizeof(double) * ((size_t)p->nq + p->e->qidx.size()); }
+
+// mjpl_plan_paths_constrained* on device batches (lo, hi on the host).  Per chunk of problems whose workspace fits the
+// option "plan_chunk_bytes" (always at least one problem): k_cplan_init, ONE launch_configs and ONE k_pose_valid on the
+// ends, then per round propose, project, count -> one small copy and one synchronisation (the round's header) -> scan,
+// gather, ONE launch_edges -> commit, then k_cplan_finish.  A chunk whose problems are all retired ends its rounds; a
+// round without an edge launches no validation.
+int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, const double *dQG, int64_t B, const double *lo,
+                 const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
+                 int32_t *dtree_nodes) {
+  mjpl_engine *e = p->e;
+  e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = e->plan_last_ms[3] = 0.0;
+  if (cplan_lds(p) > 64 * 1024)
+    return fail(MJPL_E_CAPACITY, "constrained planning: %d qpos + %d chain joints exceed the LDS budget", p->nq, p->nj);
+  const hipStream_t st = e->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
+  const size_t np = e->qidx.size(), nq = (size_t)p->nq, K = (size_t)d.candidates, N = (size_t)d.nodes, S = (size_t)d.chain, L64 = kPlanLanes;
+  // the sampling box and the base configuration; the planning columns and their inverse
+  std::vector<int> qmap(np + nq, -1);
+  for (size_t c = 0; c < np; c++) {
+    qmap[c] = e->qidx[c];
+    qmap[np + (size_t)e->qidx[c]] = (int)c;
+  }
+  MJPL_TRY(e->d_pl_box.reserve(2 * np + nq, 64));
+  MJPL_TRY(e->d_pl_q.reserve(np + nq, 64));
+  MJPL_TRY(e->d_pl_head.reserve(4));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_box.p, lo, np * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_box.p + np, hi, np * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_box.p + 2 * np, e->qbase.data(), nq * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_pl_q.p, qmap.data(), (np + nq) * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (qmap is pageable and leaves scope with this call)
+  HIP_TRY(hipMemsetAsync(dP, 0, (size_t)B * (size_t)d.max_rows * np * sizeof(double), st));
+  // what one problem adds to a chunk: two trees with their parents, S + 1 + K edges (two rows and a verdict each), the
+  // round's targets, projected steps and links, the nodes they step from, its two ends (planning and full rows), its counters
+  const size_t per_problem = 2 * N * (np * sizeof(double) + sizeof(int)) + (S + 1 + K) * (2 * np * sizeof(double) + 1) +
+                             L64 * (2 * np * sizeof(double) + 2 * sizeof(int)) + S * np * sizeof(double) +
+                             2 * (np + nq) * sizeof(double) + 20 * sizeof(int);
+  const size_t fit = std::max<size_t>((size_t)e->plan_chunk_bytes / per_problem, 1);
+  const size_t chunk = std::min(fit, ((size_t)1 << 30) / (S + 1 + K));  // (edge offsets are ints)
+  std::vector<std::pair<int, int>> phases;
+  CplanBatch a = {};
+  a.QI = dQI; a.QG = dQG; a.box = e->d_pl_box.p; a.qbase = e->d_pl_box.p + 2 * np;
+  a.qidx = e->d_pl_q.p; a.qinv = e->d_pl_q.p + np; a.pi = p->d_pi; a.pd = p->d_pd; a.nq = p->nq;
+  a.d = (int)np; a.K = d.candidates; a.N = d.nodes; a.R = d.rounds; a.S = d.chain; a.max_rows = d.max_rows;
+  a.epsilon = d.epsilon;
+  a.seed_mixed = shortcut_mix(d.seed);
+  a.head = e->d_pl_head.p;
+  a.P = dP; a.n_out = dn_out; a.status = dstatus; a.rounds_used = drounds_used; a.edges = dedges; a.tree_nodes = dtree_nodes;
+  for (int64_t b0 = 0; b0 < B; b0 += (int64_t)chunk) {
+    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * (S + 1 + K);
+    // (the configuration and edge batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do)
+    const size_t ct_at = nb * 2 * N * np, cy_at = ct_at + nb * np * L64, cl_at = cy_at + nb * np * L64,
+                 cfg_at = (cl_at + nb * S * np + 31) / 32 * 32, cfq_at = (cfg_at + 2 * nb * np + 31) / 32 * 32,
+                 qa_at = (cfq_at + 2 * nb * nq + 31) / 32 * 32, qb_at = (qa_at + emax * np + 31) / 32 * 32;
+    MJPL_TRY(e->d_pl_f64.reserve(qb_at + emax * np));
+    const size_t ints = nb * 2 * N + 2 * nb * L64 + 2 * nb + 5 * nb + 3 * nb + 2 * nb + 2 * (nb + 1);
+    MJPL_TRY(e->d_pl_i32.reserve(ints + (std::max(emax, 4 * nb) + 3) / 4));
+    size_t tmp_bytes = 0;
+    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
+    MJPL_TRY(e->d_pl_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    a.b0 = (int)b0; a.nb = (int)nb;
+    a.T = e->d_pl_f64.p; a.ct = a.T + ct_at; a.cy = a.T + cy_at; a.cl = a.T + cl_at; a.cfg = a.T + cfg_at; a.cfq = a.T + cfq_at;
+    a.QA = a.T + qa_at; a.QB = a.T + qb_at;
+    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.cok = a.ck + nb * L64; a.n = a.cok + nb * L64; a.state = a.n + 2 * nb;
+    a.gained = a.state + nb; a.rused = a.gained + nb; a.nedges = a.rused + nb; a.nlinks = a.nedges + nb; a.conn = a.nlinks + nb;
+    a.jn = a.conn + 3 * nb; a.cnt = a.jn + 2 * nb; a.off = a.cnt + (nb + 1);
+    // the ends' verdicts first (configurations, then poses), every round's after
+    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.off + (nb + 1));
+    a.cvalid = dvalid; a.pvalid = dvalid + 2 * nb; a.valid = dvalid;
+    const dim3 grid((unsigned)((nb + kPlanWaves - 1) / kPlanWaves)), block(64 * kPlanWaves);
+    const int chain_blocks = (int)((nb + kPoseBlock - 1) / kPoseBlock);
+    const dim3 pgrid((unsigned)(chain_blocks + (nb * K + kPoseBlock - 1) / kPoseBlock));
+    hipLaunchKernelGGL(k_cplan_init, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, dvalid, nullptr));
+    MJPL_TRY(mjpl_pose_valid_dev(p, a.cfq, (int64_t)(2 * nb), dvalid + 2 * nb, nullptr, nullptr));
+    for (int r = 0; r < d.rounds; r++) {
+      a.round = r;
+      unsigned long long head[3] = {0, 0, 0};
+      {
+        ShortcutPhase ph(e, phases, 0);
+        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
+        hipLaunchKernelGGL(k_cplan_propose, grid, block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+      {
+        ShortcutPhase ph(e, phases, 3);
+        hipLaunchKernelGGL(k_cplan_project, pgrid, dim3(kPoseBlock), cplan_lds(p), st, a, chain_blocks);
+        HIP_TRY(hipGetLastError());
+      }
+      {
+        ShortcutPhase ph(e, phases, 0);
+        hipLaunchKernelGGL(k_cplan_count, grid, block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (head[2] == 0) break;  // every problem of the chunk is retired
+      e->plan_last_rounds++;
+      const int64_t E = (int64_t)head[1];
+      if (E > 0) {
+        {
+          ShortcutPhase ph(e, phases, 0);
+          if (rocprim::exclusive_scan(e->d_pl_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
+            return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+          hipLaunchKernelGGL(k_cplan_gather, grid, block, 0, st, a);
+          HIP_TRY(hipGetLastError());
+        }
+        double longest;
+        memcpy(&longest, &head[0], sizeof(double));
+        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
+        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
+        ShortcutPhase ph(e, phases, 1);
+        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
+        e->plan_last_edges += E;
+      }
+      ShortcutPhase ph(e, phases, 2);
+      hipLaunchKernelGGL(k_cplan_commit, grid, block, 0, st, a);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cplan_finish, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    e->plan_last_chunks++;
+  }
+  // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
+  HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
+  return phase_sums(e, phases, e->plan_last_ms);
+}
+}  // namespace
+
+int mjpl_plan_paths_constrained_dev(mjpl_pose *p, const mjpl_cplan_desc *d, const double *dQI, const double *dQG, int64_t B,
+                                    const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
+                                    int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes) {
+  int rc = check_cplan_args(p, d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
+  if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  HIP_TRY(hipSetDevice(p->e->device));
+  return launch_cplan(p, *d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
+}
+
+int mjpl_plan_paths_constrained(mjpl_pose *p, const mjpl_cplan_desc *d, const double *QI, const double *QG, int64_t B,
+                                const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status, int32_t *rounds_used,
+                                int32_t *edges, int32_t *tree_nodes) {
+  int rc = check_cplan_args(p, d, QI, QG, B, lo, hi, P, n_out, status);
+  if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
+  if (rc != MJPL_OK || B == 0) return rc;
+  mjpl_engine *e = p->e;
+  const size_t qb = (size_t)B * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
+  const HostOut outs[] = {{P, qb * (size_t)d->max_rows}, {n_out, ib}, {status, ib}, {rounds_used, ib}, {edges, ib}, {tree_nodes, 2 * ib}};
+  return staged(e, false, {{QI, qb}, {QG, qb}}, outs, [&](void **in, void **out) {
+    return launch_cplan(p, *d, (const double *)in[0], (const double *)in[1], B, lo, hi, (double *)out[0], (int32_t *)out[1],
+                        (int32_t *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
+  });
 }
 
 // ---- row f3: IK seeds ------------------------------------------------------------------------

@@ -28,6 +28,7 @@ TOPP_OK, TOPP_STALLED, TOPP_NONFINITE = 0, 1, 2
 SHORTCUT_CONVERGED, SHORTCUT_ROUNDS, SHORTCUT_NONFINITE = 0, 1, 2
 # mjpl_plan_paths* status values (include/mjpl_hip.h: MJPL_PLAN_*)
 PLAN_SOLVED, PLAN_ROUNDS, PLAN_NONFINITE, PLAN_INVALID_END, PLAN_NODES = 0, 1, 2, 3, 4
+PLAN_LONG = 5  # mjpl_plan_paths_constrained* only: a path of more than max_rows rows
 # mjpl_roadmap_query* status values (include/mjpl_hip.h: MJPL_ROADMAP_*); the limits of both roadmap calls
 ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_NONFINITE, ROADMAP_INVALID_END, ROADMAP_LONG = 0, 1, 2, 3, 4
 ROADMAP_MAX_K, ROADMAP_MAX_NODES, ROADMAP_MAX_PROBLEMS = 32, 1 << 20, 1 << 24
@@ -123,6 +124,11 @@ class PlanDesc(C.Structure):
                 ("candidates", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CplanDesc(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("step_dist", C.c_double), ("seed", C.c_uint64), ("rounds", C.c_int32),
+                ("candidates", C.c_int32), ("nodes", C.c_int32), ("chain", C.c_int32), ("max_rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RoadmapDesc(C.Structure):
     _fields_ = [("radius", C.c_double), ("step_dist", C.c_double), ("k", C.c_int32), ("reserved", C.c_int32)]
 
@@ -208,6 +214,10 @@ ABI = {
     "mjpl_plan_paths": (C.c_int, [_VP, C.POINTER(PlanDesc), _F64P, _F64P, C.c_int64, _F64P, _F64P, _F64P, _I32P, _I32P, _I32P, _I32P,
                                   _I32P]),
     "mjpl_plan_paths_dev": (C.c_int, [_VP, C.POINTER(PlanDesc), _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mjpl_plan_paths_constrained": (C.c_int, [_VP, C.POINTER(CplanDesc), _F64P, _F64P, C.c_int64, _F64P, _F64P, _F64P, _I32P, _I32P,
+                                              _I32P, _I32P, _I32P]),
+    "mjpl_plan_paths_constrained_dev": (C.c_int, [_VP, C.POINTER(CplanDesc), _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP, _VP, _VP, _VP,
+                                                  _VP]),
     "mjpl_roadmap_build": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P]),
     "mjpl_roadmap_build_dev": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_roadmap_query": (C.c_int, [_VP, C.POINTER(RoadmapQueryDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P, _F64P, _F64P, C.c_int64,
@@ -998,6 +1008,60 @@ class Engine:
         desc = self.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)
         self._ok(self.lib.mjpl_plan_paths_dev(self.h, C.byref(desc), dQI, dQG, int(B), lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P),
                                               dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes))
+
+    # -- planning under a PoseConstraint (include/mjpl_hip.h, mjpl_plan_paths_constrained*)
+    @staticmethod
+    def cplan_desc(step_dist, epsilon, rounds=64, candidates=16, nodes=1024, chain=8, max_rows=256, seed=0):
+        """The mjpl_cplan_desc of a call; ValueError for what the library would refuse as MJPL_E_ARG."""
+        base = Engine.plan_desc(step_dist, epsilon, rounds, candidates, nodes, seed)
+        chain, max_rows = int(chain), int(max_rows)
+        if not 1 <= chain <= 32:
+            raise ValueError(f"chain must be 1..32, got {chain}")
+        if not 2 <= max_rows < 2**31:
+            raise ValueError(f"max_rows must be >= 2, got {max_rows}")
+        return CplanDesc(base.epsilon, base.step_dist, base.seed, base.rounds, base.candidates, base.nodes, chain, max_rows, 0)
+
+    def _cplan_handle(self, pose):
+        """The mjpl_pose handle of a PoseConstraint or PoseProjector of THIS engine."""
+        proj = getattr(pose, "_proj", pose)
+        if getattr(proj, "eng", None) is not self:
+            raise ValueError("the pose constraint belongs to another engine")
+        if self.nplan > 16:
+            raise ValueError(f"at most 16 planning columns under a projection, got {self.nplan}")
+        return proj.h
+
+    def plan_paths_constrained(self, pose, QI, QG, lo, hi, step_dist, epsilon, rounds=64, candidates=16, nodes=1024, chain=8,
+                               max_rows=256, seed=0):
+        """plan_paths() under the PoseConstraint `pose` (a PoseConstraint or PoseProjector of this engine): every tree edge
+        is one projected step of at most `epsilon`, and the trees are joined by a bridge of up to `chain` such steps
+        (include/mjpl_hip.h states the algorithm).  -> (P float64 [B, max_rows, nplan], n_out, status, rounds_used, edges
+        int32 [B], tree_nodes int32 [B, 2]); the statuses are plan_paths' and PLAN_LONG (a path of more than max_rows rows)."""
+        h = self._cplan_handle(pose)
+        QI, QG = _f64(QI), _f64(QG)
+        if QI.ndim != 2 or QI.shape[1] != self.nplan or QG.shape != QI.shape:
+            raise ValueError(f"QI and QG must both be [B, nplan] with nplan={self.nplan}, got {QI.shape} and {QG.shape}")
+        lo, hi = self._plan_box(lo, hi)
+        desc = self.cplan_desc(step_dist, epsilon, rounds, candidates, nodes, chain, max_rows, seed)
+        B = len(QI)
+        P = np.zeros((B, desc.max_rows, self.nplan), np.float64)
+        n_out, status, rounds_used, edges = (np.zeros(B, np.int32) for _ in range(4))
+        tree_nodes = np.zeros((B, 2), np.int32)
+        self._ok(self.lib.mjpl_plan_paths_constrained(h, C.byref(desc), QI.ctypes.data_as(_F64P), QG.ctypes.data_as(_F64P), B,
+                                                      lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P), P.ctypes.data_as(_F64P),
+                                                      n_out.ctypes.data_as(_I32P), status.ctypes.data_as(_I32P),
+                                                      rounds_used.ctypes.data_as(_I32P), edges.ctypes.data_as(_I32P),
+                                                      tree_nodes.ctypes.data_as(_I32P)))
+        return P, n_out, status, rounds_used, edges, tree_nodes
+
+    def plan_paths_constrained_dev(self, pose, dQI, dQG, B, lo, hi, step_dist, epsilon, dP, dn_out, dstatus, drounds_used=None,
+                                   dedges=None, dtree_nodes=None, rounds=64, candidates=16, nodes=1024, chain=8, max_rows=256, seed=0):
+        """plan_paths_constrained() on device pointers (lo and hi stay host arrays; the last three outputs may be None)."""
+        h = self._cplan_handle(pose)
+        lo, hi = self._plan_box(lo, hi)
+        desc = self.cplan_desc(step_dist, epsilon, rounds, candidates, nodes, chain, max_rows, seed)
+        self._ok(self.lib.mjpl_plan_paths_constrained_dev(h, C.byref(desc), dQI, dQG, int(B), lo.ctypes.data_as(_F64P),
+                                                          hi.ctypes.data_as(_F64P), dP, dn_out, dstatus, drounds_used, dedges,
+                                                          dtree_nodes))
 
     # -- roadmap planning: validate a scene's edges once, answer many queries (include/mjpl_hip.h, mjpl_roadmap_*)
     @staticmethod

@@ -16,7 +16,8 @@ cartesian_plan = _cart.cartesian_plan
 smooth_path, path_length = _utils.smooth_path, _utils.path_length
 smooth_paths = _utils.smooth_paths
 plan_paths = _utils.plan_paths
+plan_paths_constrained = _utils.plan_paths_constrained
 Roadmap = _roadmap.Roadmap
 
 __all__ = ["RRT", "DeviceBiRRT", "ParallelBiRRT", "EdgeValidator", "HipEdgeValidator", "Node", "Tree", "cartesian_plan",
-           "smooth_path", "smooth_paths", "plan_paths", "Roadmap", "path_length"]
+           "smooth_path", "smooth_paths", "plan_paths", "plan_paths_constrained", "Roadmap", "path_length"]

@@ -286,3 +286,73 @@ def plan_paths(q_inits, q_goals, collision, step_dist: float, *, epsilon: float,
     info = [dict(status=names[int(status[b])], rounds_used=int(rounds_used[b]), edges=int(edges[b]),
                  nodes=(int(tree_nodes[b, 0]), int(tree_nodes[b, 1]))) for b in range(len(q_inits))]
     return paths, info
+
+
+def plan_paths_constrained(q_inits, q_goals, collision, pose, step_dist: float, *, epsilon: float, rounds: int = 64,
+                           candidates: int = 16, nodes: int = 1024, chain: int = 8, max_rows: int = 256, seed: int = 0,
+                           lo=None, hi=None, return_info: bool = False):
+    """:func:`plan_paths` under a projecting constraint: many start/goal pairs at once on the GPU, every waypoint on
+    the manifold of ``pose`` (a :class:`mjpl_amd.PoseConstraint` made with ``engine=collision.engine``).
+
+    This is the reference's CBiRRT taken in lockstep.  Every tree edge is ONE step of at most ``epsilon`` projected by
+    ``pose.apply`` (and kept only if it moved, came no farther from its target and stayed within ``2 * pose.q_step`` of
+    the node it left), so there is no straight connect edge of any length -- its interior would leave the manifold.
+    Instead each round a problem builds a *bridge*: a chain of up to ``chain`` (1..32) projected steps from the growing
+    tree towards the closest node the other tree gained, closed by one straight edge of at most ``epsilon``; beside it, up
+    to ``candidates`` projected extensions towards seeded uniform samples.  Links, closing edge and extensions of ALL
+    problems are validated by one edge launch of ``collision`` per round (waypoints ``step_dist`` apart; the interior of
+    a step is sampled for collision only, as in the reference).  ``include/mjpl_hip.h``
+    (``mjpl_plan_paths_constrained``) states the algorithm.
+
+    Choose ``epsilon < 2 * pose.q_step``: at ``epsilon == 2 * pose.q_step`` the projection's "farther than 2 q_step
+    from where it started" rule turns on roundings, and even a free straight line fails at random.
+
+    Returns what :func:`plan_paths` returns: per problem the path as a list of ``nq`` arrays, or ``None``.  A path has
+    at most ``max_rows`` waypoints; a longer one is reported, not cut: with ``return_info`` the status strings are those
+    of :func:`plan_paths` and ``"long"``.  Both ends must satisfy ``pose`` (``"invalid_end"`` otherwise).
+    :func:`smooth_paths` is unconstrained and would leave the manifold: hand the paths to
+    ``generate_constrained_trajectories`` as they are.
+
+    Raises ``ValueError`` if ``pose.engine is not collision.engine``, and for everything :func:`plan_paths` raises it for.
+    """
+    from .. import engine as _engine
+    model = collision.model
+    nq = model.nq
+    if getattr(pose, "engine", None) is not collision.engine:
+        raise ValueError("pose and collision must share one engine: PoseConstraint(..., engine=collision.engine)")
+    _engine.Engine.cplan_desc(step_dist, epsilon, rounds, candidates, nodes, chain, max_rows, seed)  # (ValueError for a bad parameter)
+    q_inits, q_goals = list(q_inits), list(q_goals)
+    if len(q_inits) != len(q_goals):
+        raise ValueError(f"{len(q_inits)} q_inits but {len(q_goals)} q_goals")
+    lo = np.asarray(model.jnt_range[:, 0] if lo is None else lo, dtype=np.float64)
+    hi = np.asarray(model.jnt_range[:, 1] if hi is None else hi, dtype=np.float64)
+    if lo.shape != (nq,) or hi.shape != (nq,):
+        raise ValueError(f"lo and hi must have {nq} entries, got {lo.shape} and {hi.shape}")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (lo > hi).any():
+        raise ValueError("lo and hi must be finite, with lo <= hi")
+    if not q_inits:
+        return ([], []) if return_info else []
+    QI, QG = np.asarray(q_inits, dtype=np.float64), np.asarray(q_goals, dtype=np.float64)
+    if QI.shape != (len(q_inits), nq) or QG.shape != QI.shape:
+        raise ValueError(f"q_inits and q_goals must be full configurations of {nq} entries, got {QI.shape} and {QG.shape}")
+    for name, Q in (("q_inits", QI), ("q_goals", QG)):
+        out = np.flatnonzero(((Q < lo) | (Q > hi)).any(axis=1))  # (NaN compares false: the library reports it)
+        if len(out):
+            raise ValueError(f"{name}[{out[0]}] lies outside [lo, hi]")
+    collision._ensure_full()
+    P, n_out, status, rounds_used, edges, tree_nodes = collision.engine.plan_paths_constrained(
+        pose, QI, QG, lo, hi, step_dist, epsilon, rounds=rounds, candidates=candidates, nodes=nodes, chain=chain, max_rows=max_rows,
+        seed=seed)
+    paths = []
+    for b in range(len(q_inits)):
+        if status[b] != _engine.PLAN_SOLVED:
+            paths.append(None)
+            continue
+        paths.append([q_inits[b]] + [P[b, k].copy() for k in range(1, n_out[b] - 1)] + [q_goals[b]])
+    if not return_info:
+        return paths
+    names = {_engine.PLAN_SOLVED: "solved", _engine.PLAN_ROUNDS: "rounds", _engine.PLAN_NONFINITE: "nonfinite",
+             _engine.PLAN_INVALID_END: "invalid_end", _engine.PLAN_NODES: "nodes", _engine.PLAN_LONG: "long"}
+    info = [dict(status=names[int(status[b])], rounds_used=int(rounds_used[b]), edges=int(edges[b]),
+                 nodes=(int(tree_nodes[b, 0]), int(tree_nodes[b, 1]))) for b in range(len(q_inits))]
+    return paths, info
