@@ -123,6 +123,27 @@ def box_box_overlap(c1, R1, h1, c2, R2, h2):
     return out
 
 
+def box_box_dist(c1, R1, h1, c2, R2, h2):
+    """Distance of two DISJOINT boxes from the same parts: every vertex of either box against the other box
+    (point_box_dist, 8 + 8) and every edge of one against every edge of the other (seg_seg_dist, 12 x 12).
+    Meaningless where the boxes overlap: box_box_overlap is the sign."""
+    n = len(c1)
+    sg = _SIGNS[None].astype(LD)
+    v1 = c1[:, None, :] + np.einsum("nij,nvj->nvi", R1, sg * h1[:, None, :])
+    v2 = c2[:, None, :] + np.einsum("nij,nvj->nvi", R2, sg * h2[:, None, :])
+    best = np.full(n, np.inf, LD)
+    for v in range(8):
+        best = np.minimum(best, np.minimum(point_box_dist(v1[:, v], c2, R2, h2), point_box_dist(v2[:, v], c1, R1, h1)))
+    ea = np.array([a for a, _ in _EDGES])
+    eb = np.array([b for _, b in _EDGES])
+    a1 = np.repeat(v1[:, ea], 12, axis=1).reshape(n * 144, 3)   # edge i of box 1 against ...
+    b1 = np.repeat(v1[:, eb], 12, axis=1).reshape(n * 144, 3)
+    a2 = np.tile(v2[:, ea], (1, 12, 1)).reshape(n * 144, 3)     # ... edge j of box 2
+    b2 = np.tile(v2[:, eb], (1, 12, 1)).reshape(n * 144, 3)
+    ee = seg_seg_dist(a1, b1, a2, b2).reshape(n, 144)
+    return np.minimum(best, ee.min(axis=1))
+
+
 def gap(t1, p1, R1, s1, t2, p2, R2, s2):
     """Signed surface distance where it exists (cores apart: distance of the cores minus the radii), and for
     box-box -- no radius to subtract -- +1 / -1 by the overlap predicate.  Contact iff gap <= 0.
