@@ -59,8 +59,10 @@ def main() -> bool:
 
     step = 0.01
     t0 = time.time()
+    # (extend=4: an extension is a chain of up to 4 projected steps -- the row of DESIGN.md 5.18 that solves the most pairs
+    # for its time at the other defaults)
     paths, info = mjpl.plan_paths_constrained(q_inits, q_goals, collision, pose, step, epsilon=q_step, seed=args.seed, lo=lo, hi=hi,
-                                              return_info=True)
+                                              return_info=True, extend=4)
     t_plan = time.time() - t0
     solved = [p for p in paths if p is not None]
     print(f"plan_paths_constrained: {len(solved)} of {len(paths)} solved in {t_plan:.3f}s, "

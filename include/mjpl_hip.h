@@ -713,6 +713,37 @@ int mjpl_plan_paths_constrained_dev(struct mjpl_pose *p, const mjpl_cplan_desc *
                                     int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                                     int32_t *dtree_nodes);
 
+/* ---- chained extensions: an extension candidate is a chain of up to `extend` projected steps ----
+ * In the rounds above an extension is ONE step of epsilon, so a tree's frontier moves by at most epsilon a round.
+ * The reference's _constrained_extend runs towards its target until it is stopped; these two calls take that
+ * loop inside one round and cut it at `extend` (X, 1..32) steps.  The descriptor and every other argument are
+ * those of mjpl_plan_paths_constrained*, which are these calls with extend = 1, bit for bit.
+ * tests/cplan_extend_reference.py is the NumPy statement.  The round stays as written except for steps 4 to 6:
+ *   4. The candidates are, as above, l < nc = min(candidates, nodes - n_g - links); t_l and k = nearest(T_g, t_l)
+ *      are taken, as above, over the tree as it stood at the start of the round.  Candidate l has an extension
+ *      chain: x_0 = T_g[k], and for s = 1 .. X, y = cstep(x_{s-1}, t_l).  A void y ends the chain; otherwise
+ *      x_s = y is an extension link with the edge QA = x_{s-1}, QB = x_s.  There is no rule for reaching the
+ *      target: at the target cstep moves less than 1e-8 and is void, which is how the reference's loop ends
+ *      too.  A chain with no link sends no edge.  As for the bridge, a chain is generated before any verdict.
+ *   5. The one edge launch takes, per problem, the bridge links, then the closing edge, then, for l ascending,
+ *      chain l's links for s ascending.
+ *   6. When the problem is not SOLVED the chains are appended for l ascending, and within a chain its leading
+ *      valid links in order of s: the first link's parent is k, each later link's the link before it.  A link
+ *      is appended only while the growing tree has fewer than `nodes` nodes; the first link of a chain that is
+ *      invalid, or that meets a full tree, ends that chain's appending.  gained = the nodes appended in the
+ *      round, bridge links included (at most chain + 64 X: the bridge target of step 2 is sought among them).
+ * With X = 1 this is the text above: nc <= nodes - n_g - links, so the cap never bites.  A chunk's workspace
+ * ("plan_chunk_bytes") holds chain + 1 + candidates X edges and 64 X chain rows per problem.
+ * MJPL_E_ARG: extend outside 1..32, checked before anything else (with B = 0 too); then as above. */
+int mjpl_plan_paths_constrained_ext(struct mjpl_pose *p, const mjpl_cplan_desc *desc, int32_t extend,
+                                    const double *QI, const double *QG, int64_t B, const double *lo,
+                                    const double *hi, double *P, int32_t *n_out, int32_t *status,
+                                    int32_t *rounds_used, int32_t *edges, int32_t *tree_nodes);
+int mjpl_plan_paths_constrained_ext_dev(struct mjpl_pose *p, const mjpl_cplan_desc *desc, int32_t extend,
+                                        const double *dQI, const double *dQG, int64_t B, const double *lo,
+                                        const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
+                                        int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes);
+
 /* ---- roadmap planning: validate a scene's edges once, answer many queries ------------------------
  * mjpl_plan_paths keeps nothing between calls: every call validates its edges again in the same static scene.
  * These two calls are the multi-query form (a probabilistic roadmap).  mjpl_roadmap_build turns N configurations

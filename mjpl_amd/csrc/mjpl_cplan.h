@@ -1,14 +1,16 @@
 // mjpl_cplan.h -- batched planning under a PoseConstraint (mjpl_plan_paths_constrained*, include/mjpl_hip.h).
 //
 // What it adds to mjpl_plan.h: every tree edge is ONE projected step of at most epsilon (cstep: step, the projection
-// pose_project_lane with q_old = the node stepped from, the three rules of the reference's _constrained_extend), and the
-// two trees are joined by a bridge -- a chain of up to `chain` projected steps from the growing tree towards the closest
+// pose_project_lane with q_old = the node stepped from, the three rules of the reference's _constrained_extend), an
+// extension candidate is a chain of up to `extend` such steps (mjpl_plan_paths_constrained_ext*; 1 = a single step), and
+// the two trees are joined by a bridge -- a chain of up to `chain` projected steps from the growing tree towards the closest
 // of the nodes the other tree gained, closed by one straight edge of at most epsilon -- instead of one straight connect
 // edge of any length, whose interior would leave the constraint manifold.  A chain is generated before any verdict is
 // known: a projected step depends on the projected row before it, not on that row's collision verdict (the argument of
 // k_rrt_gen_project, mjpl_project.h), so links, closing edge and extensions of every problem still go to ONE launch of
-// the edge pipeline per round.  tests/cplan_reference.py is the NumPy statement, operation for operation; DESIGN.md 5.18
-// has the reasoning.  All float64, -ffp-contract=off; integer atomics on the round's header only.
+// the edge pipeline per round.  tests/cplan_reference.py (extend = 1) and tests/cplan_extend_reference.py are the NumPy
+// statement, operation for operation; DESIGN.md 5.18 has the reasoning.  All float64, -ffp-contract=off; integer atomics
+// on the round's header only.
 //
 // Kernels, in launch order (one wave per problem unless said otherwise; no workgroup barrier anywhere):
 //   k_cplan_init     the NaN / inf scan, the roots, the ends as planning rows (configuration launch) and as full qpos
@@ -18,15 +20,18 @@
 //                    pair by a (d2, p) minimum over the wave; lane l draws extension target l and finds its nearest node.
 //   k_cplan_project  ONE LANE per row, 64 to a workgroup, LDS per lane qw[nq] | jst[6 njoint] | qo[nq] | t[nplan].  The
 //                    first ceil(nb / 64) workgroups take a problem's bridge chain per lane, its steps in sequence; the
-//                    others take one extension candidate per lane -- so up to 32 sequential projections never share a
-//                    wave with lanes that take one.  Links, projected candidates and their void flags.
-//   k_cplan_count    the problem's edges: links + closing edge + the non-void extensions that still fit; the header
+//                    others take one extension candidate per lane, up to `extend` steps in sequence -- so a wave's lanes
+//                    all run chains of one kind, and it leaves its loop when none of them is going.  Bridge links, the
+//                    extension chains' links and their counts.
+//   k_cplan_count    the problem's edges: links + closing edge + every link of the extension chains that still fit (an
+//                    integer prefix sum over the wave's per-lane link counts); the header
 //                    (edges: sum, longest edge: max of the bits of a non-negative double, problems at work: count).
 //   (rocprim::exclusive_scan of the per-problem counts)
-//   k_cplan_gather   the problem's edges into the AoS edge batch: links, closing edge, extensions by ballot prefix.
+//   k_cplan_gather   the problem's edges into the AoS edge batch: links, closing edge, chain l's links at the prefix of l.
 //   (launch_edges: the verdicts)
 //   k_cplan_commit   the leading valid links appended (a ballot); all links and the closing edge valid: SOLVED, the
-//                    junctions kept; otherwise the valid extensions appended by ballot prefix.
+//                    junctions kept; otherwise each chain's leading valid links appended at the prefix over the lanes
+//                    before it, cut where the tree is full.
 //   k_cplan_finish   the parent walks into P, LONG for a path of more than max_rows rows, status and counters.
 #pragma once
 
@@ -38,18 +43,20 @@ namespace mjpl {
 constexpr int kPlanLong = 5;         // MJPL_PLAN_LONG
 constexpr int kCplanMaxChain = 32;   // links of a bridge: a lane of the ballot each, the closing edge after them
 
+constexpr int kCplanMaxExtend = 32;  // links of an extension chain: K X <= 2048 edges beside the bridge's
+
 // PlanBatch's members keep their meaning (P has max_rows rows per problem, not R + 2); conn [nb][3] holds the bridge:
 // has a closing edge, its node p of the other tree, the node n of the growing tree the chain starts from.
 struct CplanBatch : PlanBatch {
-  int S, max_rows;  // chain, rows of P per problem
+  int S, X, max_rows;  // chain, extend, rows of P per problem
   // the projection: the handle's chain program, the planning columns and their inverse (-1: not a planning column)
   const int *pi;
   const double *pd;
   const int *qidx, *qinv;
   const double *qbase;
   int nq;
-  double *cy;      // [nb][d][64]: the projected steps of the round's extensions
-  int *cok;        // [nb][64]: 1 = not void
+  double *cy;      // [nb][X][d][64]: the links of the round's extension chains
+  int *cn;         // [nb][64]: the links of candidate l's chain (0: its first step was void)
   double *cl;      // [nb][S][d]: the round's links
   int *nlinks;     // [nb]
   double *cfq;     // [2 nb][nq]: the ends as full rows
@@ -110,6 +117,7 @@ __global__ void __launch_bounds__(64 * kPlanWaves) k_cplan_propose(CplanBatch a)
   const int d = a.d;
   const double *Tg = plan_tree(a, p, g), *To = plan_tree(a, p, o);
   // the bridge target: candidate q is the q-th of the last m nodes of the other tree; the least d2 wins, ties to the lowest q
+  // (m = the nodes that tree gained in its round, at most S + 64 X = 2080 and less than its size: the scan strides over them)
   const int gained = a.gained[p], m = gained > 1 ? gained : 1;
   double mb = 0.0;
   int mq = -1, mn = 0;
@@ -187,7 +195,8 @@ __device__ __forceinline__ bool cplan_cstep(const CplanBatch &a, double *qw, dou
 }
 
 // chain_blocks = ceil(nb / 64) workgroups of bridge chains (lane = problem, up to S steps in sequence), then
-// ceil(nb K / 64) of extension candidates (lane = candidate, one step): one loop, so the projection is inlined once
+// ceil(nb K / 64) of extension candidates (lane = candidate, up to X steps in sequence): one loop, left when no lane of
+// the wave is going, so the projection is inlined once
 __global__ void __launch_bounds__(kPoseBlock) k_cplan_project(CplanBatch a, int chain_blocks) {
   extern __shared__ double smem[];
   constexpr int B = kPoseBlock;
@@ -226,7 +235,10 @@ __global__ void __launch_bounds__(kPoseBlock) k_cplan_project(CplanBatch a, int 
     }
   }
   const bool mine = going;
-  const int steps = is_chain ? a.S : 1;
+  const int steps = is_chain ? a.S : a.X;
+  // where this lane's links go: a bridge's rows are contiguous, an extension chain's lane-minor
+  double *const out = is_chain ? a.cl + (int64_t)p * a.S * d : a.cy + (int64_t)p * a.X * d * 64 + l;
+  const int os = is_chain ? 1 : 64;
   int links = 0, closing = 0;
   for (int s = 0; s < steps && __ballot(going) != 0ull; s++) {
     if (going && is_chain) {
@@ -246,13 +258,9 @@ __global__ void __launch_bounds__(kPoseBlock) k_cplan_project(CplanBatch a, int 
     }
     const bool good = cplan_cstep(a, qw, jst, qo, tt, going);
     if (going) {
-      if (!is_chain) {
-        double *y = a.cy + (int64_t)p * d * 64 + l;
-        for (int c = 0; c < d; c++) y[c * 64] = qw[a.qidx[c] * B];
-        a.cok[p * 64 + l] = good ? 1 : 0;
-      } else if (good) {
-        double *y = a.cl + ((int64_t)p * a.S + links) * d;
-        for (int c = 0; c < d; c++) y[c] = qw[a.qidx[c] * B];
+      if (good) {  // a link; the next step is taken from it
+        double *y = out + (int64_t)links * d * os;
+        for (int c = 0; c < d; c++) y[c * os] = qw[a.qidx[c] * B];
         for (int k = 0; k < nq; k++) qo[k * B] = qw[k * B];
         links++;
       } else {
@@ -260,16 +268,42 @@ __global__ void __launch_bounds__(kPoseBlock) k_cplan_project(CplanBatch a, int 
       }
     }
   }
-  if (mine && is_chain) {
-    a.nlinks[p] = links;
-    a.conn[p * 3] = closing;
+  if (mine) {
+    if (is_chain) {
+      a.nlinks[p] = links;
+      a.conn[p * 3] = closing;
+    } else {
+      a.cn[p * 64 + l] = links;
+    }
   }
 }
 
-// the non-void extensions that still fit beside the round's links: lanes l < min(K, N - n_g - links)
-__device__ __forceinline__ bool cplan_ext(const CplanBatch &a, int p, int lane, int ng, int links) {
+// the links of lane l's extension chain, 0 for a chain that does not fit beside the round's links: lanes
+// l < min(K, N - n_g - links) count
+__device__ __forceinline__ int cplan_ext(const CplanBatch &a, int p, int lane, int ng, int links) {
   const int room = a.N - ng - links, next = a.K < room ? a.K : room;
-  return lane < next && a.cok[p * 64 + lane] != 0;
+  return lane < next ? a.cn[p * 64 + lane] : 0;
+}
+
+// plan_d2 of two lane-minor rows (both at a stride of 64)
+__device__ __forceinline__ double cplan_d2_lanes(const double *a, const double *t, int d) {
+  double s = 0.0;
+  for (int c = 0; c < d; c++) {
+    const double v = t[c * 64] - a[c * 64];
+    s += v * v;
+  }
+  return s;
+}
+
+// the sum of v over the lanes below this one, and over the wave (every lane of the wave calls it)
+__device__ __forceinline__ int cplan_prefix(int v, int lane, int *total) {
+  int incl = v;
+  for (int w = 1; w < 64; w <<= 1) {
+    const int below = __shfl_up(incl, w);
+    if (lane >= w) incl += below;
+  }
+  *total = __shfl(incl, 63);
+  return incl - v;
 }
 
 __global__ void __launch_bounds__(64 * kPlanWaves) k_cplan_count(CplanBatch a) {
@@ -283,17 +317,21 @@ __global__ void __launch_bounds__(64 * kPlanWaves) k_cplan_count(CplanBatch a) {
   const int links = a.nlinks[p], closing = a.conn[p * 3];
   const double *Tg = plan_tree(a, p, g), *cl = a.cl + (int64_t)p * a.S * d;
   const double *first = Tg + (int64_t)a.conn[p * 3 + 2] * d;
-  const bool ext = cplan_ext(a, p, lane, ng, links);
-  const int count = links + closing + __popcll(__ballot(ext));
-  // the longest edge: lane s < links holds link s, lane `links` the closing edge; every lane its extension
+  const int ext = cplan_ext(a, p, lane, ng, links);
+  int exts;
+  cplan_prefix(ext, lane, &exts);
+  const int count = links + closing + exts;
+  // the longest edge: lane s < links holds link s, lane `links` the closing edge; every lane the links of its chain
   double longest = 0.0;
   if (lane < links + closing) {
     const double *qa = lane == 0 ? first : cl + (int64_t)(lane - 1) * d;
     const double *qb = lane < links ? cl + (int64_t)lane * d : plan_tree(a, p, o) + (int64_t)a.conn[p * 3 + 1] * d;
     longest = sqrt(plan_d2(qa, qb, 1, d));
   }
-  if (ext) {
-    const double len = sqrt(plan_d2(Tg + (int64_t)a.ck[p * 64 + lane] * d, a.cy + (int64_t)p * d * 64 + lane, 64, d));
+  const double *cy = a.cy + (int64_t)p * a.X * d * 64 + lane;
+  for (int s = 0; s < ext; s++) {
+    const double *y = cy + (int64_t)s * d * 64;
+    const double len = s == 0 ? sqrt(plan_d2(Tg + (int64_t)a.ck[p * 64 + lane] * d, y, 64, d)) : sqrt(cplan_d2_lanes(y - (int64_t)d * 64, y, d));
     if (len > longest) longest = len;  // (NaN never compares greater)
   }
   for (int w = 32; w > 0; w >>= 1) {
@@ -318,19 +356,21 @@ __global__ void __launch_bounds__(64 * kPlanWaves) k_cplan_gather(CplanBatch a) 
   const int links = a.nlinks[p], closing = a.conn[p * 3];
   const double *Tg = plan_tree(a, p, g), *cl = a.cl + (int64_t)p * a.S * d;
   const double *first = Tg + (int64_t)a.conn[p * 3 + 2] * d, *target = plan_tree(a, p, o) + (int64_t)a.conn[p * 3 + 1] * d;
-  const int64_t e0 = (int64_t)a.off[p] * d;  // (off[p] + cnt <= nb (S + 1 + K): the batch is sized for that)
+  const int64_t e0 = (int64_t)a.off[p] * d;  // (off[p] + cnt <= nb (S + 1 + K X): the batch is sized for that)
   for (int i = lane; i < (links + closing) * d; i += 64) {
     const int j = i / d, c = i - j * d;
     a.QA[e0 + i] = j == 0 ? first[c] : cl[(int64_t)(j - 1) * d + c];
     a.QB[e0 + i] = j < links ? cl[(int64_t)j * d + c] : target[c];
   }
-  const bool ext = cplan_ext(a, p, lane, ng, links);
-  const unsigned long long mask = __ballot(ext);
-  if (ext) {
-    const int64_t e = e0 + (int64_t)(links + closing + __popcll(mask & shortcut_below(lane))) * d;
-    const double *from = Tg + (int64_t)a.ck[p * 64 + lane] * d, *y = a.cy + (int64_t)p * d * 64 + lane;
+  const int ext = cplan_ext(a, p, lane, ng, links);
+  int exts;
+  const int before = cplan_prefix(ext, lane, &exts);
+  const double *from = Tg + (int64_t)a.ck[p * 64 + lane] * d, *cy = a.cy + (int64_t)p * a.X * d * 64 + lane;
+  for (int s = 0; s < ext; s++) {  // chain `lane`: link s runs from link s - 1 (the nearest node for s = 0)
+    const int64_t e = e0 + (int64_t)(links + closing + before + s) * d;
+    const double *y = cy + (int64_t)s * d * 64;
     for (int c = 0; c < d; c++) {
-      a.QA[e + c] = from[c];
+      a.QA[e + c] = s == 0 ? from[c] : y[(c - d) * 64];
       a.QB[e + c] = y[c * 64];
     }
   }
@@ -363,19 +403,26 @@ __global__ void __launch_bounds__(64 * kPlanWaves) k_cplan_commit(CplanBatch a) 
     }
     return;
   }
-  const bool ext = cplan_ext(a, p, lane, ng, links);
-  const unsigned long long mask = __ballot(ext);
-  const bool ok = ext && a.valid[e0 + links + closing + __popcll(mask & shortcut_below(lane))] != 0;
-  const unsigned long long okmask = __ballot(ok);
-  if (ok) {
-    const int at = ng + lead + __popcll(okmask & shortcut_below(lane));  // (< N: extensions <= N - n_g - links)
-    const double *y = a.cy + (int64_t)p * d * 64 + lane;
-    for (int c = 0; c < d; c++) Tg[(int64_t)at * d + c] = y[c * 64];
-    par[at] = a.ck[p * 64 + lane];
+  // the extension chains: lane l's leading valid links, appended after those of the lanes below it, as many as fit
+  const int ext = cplan_ext(a, p, lane, ng, links);
+  int exts, oks;
+  const int64_t ve = e0 + links + closing + cplan_prefix(ext, lane, &exts);
+  int ok = 0;
+  while (ok < ext && a.valid[ve + ok] != 0) ok++;
+  const int below = cplan_prefix(ok, lane, &oks);
+  const int room = a.N - ng - lead;  // (>= 0: lead <= links <= N - n_g)
+  const int start = below < room ? below : room, take = ok < room - start ? ok : room - start;
+  const int at = ng + lead + start;  // (at + take <= N)
+  const double *cy = a.cy + (int64_t)p * a.X * d * 64 + lane;
+  for (int s = 0; s < take; s++) {
+    const double *y = cy + (int64_t)s * d * 64;
+    for (int c = 0; c < d; c++) Tg[(int64_t)(at + s) * d + c] = y[c * 64];
+    par[at + s] = s == 0 ? a.ck[p * 64 + lane] : at + s - 1;
   }
   if (lane == 0) {
-    a.n[p * 2 + g] = ng + lead + __popcll(okmask);
-    a.gained[p] = lead + __popcll(okmask);
+    const int got = oks < room ? oks : room;
+    a.n[p * 2 + g] = ng + lead + got;
+    a.gained[p] = lead + got;
   }
 }
 

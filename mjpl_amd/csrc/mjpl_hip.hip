@@ -4863,8 +4863,9 @@ int mjpl_pose_valid(mjpl_pose *p, const double *Q, int64_t N, uint8_t *valid, do
 // ---- planning in lockstep under a PoseConstraint (mjpl_cplan.h)
 
 namespace {
-int check_cplan_args(const mjpl_pose *p, const mjpl_cplan_desc *d, const void *QI, const void *QG, int64_t B, const double *lo,
-                     const double *hi, const void *P, const void *n_out, const void *status) {
+int check_cplan_args(const mjpl_pose *p, const mjpl_cplan_desc *d, int extend, const void *QI, const void *QG, int64_t B,
+                     const double *lo, const double *hi, const void *P, const void *n_out, const void *status) {
+  if (extend < 1 || extend > kCplanMaxExtend) return fail(MJPL_E_ARG, "`extend` must be 1..%d, got %d", kCplanMaxExtend, extend);
   if (!p) return fail(MJPL_E_ARG, "pose handle is NULL");
   if (!d) return fail(MJPL_E_ARG, "mjpl_plan: NULL descriptor");
   const mjpl_plan_desc pd = {d->epsilon, d->step_dist, d->seed, d->rounds, d->candidates, d->nodes, 0};
@@ -4877,13 +4878,14 @@ int check_cplan_args(const mjpl_pose *p, const mjpl_cplan_desc *d, const void *Q
 
 size_t cplan_lds(const mjpl_pose *p) { return pose_lds(p) + (size_t)kPoseBlock * sizeof(double) * ((size_t)p->nq + p->e->qidx.size()); }
 
-// mjpl_plan_paths_constrained* on device batches (lo, hi on the host).  Per chunk of problems whose workspace fits the
+// mjpl_plan_paths_constrained* on device batches (lo, hi on the host), an extension a chain of up to `extend` steps.
+// Per chunk of problems whose workspace fits the
 // option "plan_chunk_bytes" (always at least one problem): k_cplan_init, ONE launch_configs and ONE k_pose_valid on the
 // ends, then per round propose, project, count -> one small copy and one synchronisation (the round's header) -> scan,
 // gather, ONE launch_edges -> commit, then k_cplan_finish.  A chunk whose problems are all retired ends its rounds; a
 // round without an edge launches no validation.
-int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, const double *dQG, int64_t B, const double *lo,
-                 const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
+int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, int extend, const double *dQI, const double *dQG, int64_t B,
+                 const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                  int32_t *dtree_nodes) {
   mjpl_engine *e = p->e;
   e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
@@ -4892,7 +4894,9 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, cons
     return fail(MJPL_E_CAPACITY, "constrained planning: %d qpos + %d chain joints exceed the LDS budget", p->nq, p->nj);
   const hipStream_t st = e->stream;
   HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
-  const size_t np = e->qidx.size(), nq = (size_t)p->nq, K = (size_t)d.candidates, N = (size_t)d.nodes, S = (size_t)d.chain, L64 = kPlanLanes;
+  const size_t np = e->qidx.size(), nq = (size_t)p->nq, K = (size_t)d.candidates, N = (size_t)d.nodes, S = (size_t)d.chain,
+               X = (size_t)extend, L64 = kPlanLanes;
+  const size_t per_edges = S + 1 + K * X;  // a problem's edges in one round at most: the bridge, then K chains of X links
   // the sampling box and the base configuration; the planning columns and their inverse
   std::vector<int> qmap(np + nq, -1);
   for (size_t c = 0; c < np; c++) {
@@ -4908,26 +4912,27 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, cons
   HIP_TRY(hipMemcpyAsync(e->d_pl_q.p, qmap.data(), (np + nq) * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));  // (qmap is pageable and leaves scope with this call)
   HIP_TRY(hipMemsetAsync(dP, 0, (size_t)B * (size_t)d.max_rows * np * sizeof(double), st));
-  // what one problem adds to a chunk: two trees with their parents, S + 1 + K edges (two rows and a verdict each), the
-  // round's targets, projected steps and links, the nodes they step from, its two ends (planning and full rows), its counters
-  const size_t per_problem = 2 * N * (np * sizeof(double) + sizeof(int)) + (S + 1 + K) * (2 * np * sizeof(double) + 1) +
-                             L64 * (2 * np * sizeof(double) + 2 * sizeof(int)) + S * np * sizeof(double) +
+  // what one problem adds to a chunk: two trees with their parents, S + 1 + K X edges (two rows and a verdict each), the
+  // round's targets, the extension chains' links (X to a lane) and the bridge's, the nodes they step from, its two ends
+  // (planning and full rows), its counters
+  const size_t per_problem = 2 * N * (np * sizeof(double) + sizeof(int)) + per_edges * (2 * np * sizeof(double) + 1) +
+                             L64 * ((1 + X) * np * sizeof(double) + 2 * sizeof(int)) + S * np * sizeof(double) +
                              2 * (np + nq) * sizeof(double) + 20 * sizeof(int);
   const size_t fit = std::max<size_t>((size_t)e->plan_chunk_bytes / per_problem, 1);
-  const size_t chunk = std::min(fit, ((size_t)1 << 30) / (S + 1 + K));  // (edge offsets are ints)
+  const size_t chunk = std::min(fit, ((size_t)1 << 30) / per_edges);  // (edge offsets are ints)
   std::vector<std::pair<int, int>> phases;
   CplanBatch a = {};
   a.QI = dQI; a.QG = dQG; a.box = e->d_pl_box.p; a.qbase = e->d_pl_box.p + 2 * np;
   a.qidx = e->d_pl_q.p; a.qinv = e->d_pl_q.p + np; a.pi = p->d_pi; a.pd = p->d_pd; a.nq = p->nq;
-  a.d = (int)np; a.K = d.candidates; a.N = d.nodes; a.R = d.rounds; a.S = d.chain; a.max_rows = d.max_rows;
+  a.d = (int)np; a.K = d.candidates; a.N = d.nodes; a.R = d.rounds; a.S = d.chain; a.X = extend; a.max_rows = d.max_rows;
   a.epsilon = d.epsilon;
   a.seed_mixed = shortcut_mix(d.seed);
   a.head = e->d_pl_head.p;
   a.P = dP; a.n_out = dn_out; a.status = dstatus; a.rounds_used = drounds_used; a.edges = dedges; a.tree_nodes = dtree_nodes;
   for (int64_t b0 = 0; b0 < B; b0 += (int64_t)chunk) {
-    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * (S + 1 + K);
+    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * per_edges;
     // (the configuration and edge batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do)
-    const size_t ct_at = nb * 2 * N * np, cy_at = ct_at + nb * np * L64, cl_at = cy_at + nb * np * L64,
+    const size_t ct_at = nb * 2 * N * np, cy_at = ct_at + nb * np * L64, cl_at = cy_at + nb * X * np * L64,
                  cfg_at = (cl_at + nb * S * np + 31) / 32 * 32, cfq_at = (cfg_at + 2 * nb * np + 31) / 32 * 32,
                  qa_at = (cfq_at + 2 * nb * nq + 31) / 32 * 32, qb_at = (qa_at + emax * np + 31) / 32 * 32;
     MJPL_TRY(e->d_pl_f64.reserve(qb_at + emax * np));
@@ -4940,7 +4945,7 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, cons
     a.b0 = (int)b0; a.nb = (int)nb;
     a.T = e->d_pl_f64.p; a.ct = a.T + ct_at; a.cy = a.T + cy_at; a.cl = a.T + cl_at; a.cfg = a.T + cfg_at; a.cfq = a.T + cfq_at;
     a.QA = a.T + qa_at; a.QB = a.T + qb_at;
-    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.cok = a.ck + nb * L64; a.n = a.cok + nb * L64; a.state = a.n + 2 * nb;
+    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.cn = a.ck + nb * L64; a.n = a.cn + nb * L64; a.state = a.n + 2 * nb;
     a.gained = a.state + nb; a.rused = a.gained + nb; a.nedges = a.rused + nb; a.nlinks = a.nedges + nb; a.conn = a.nlinks + nb;
     a.jn = a.conn + 3 * nb; a.cnt = a.jn + 2 * nb; a.off = a.cnt + (nb + 1);
     // the ends' verdicts first (configurations, then poses), every round's after
@@ -5007,29 +5012,41 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, const double *dQI, cons
 }
 }  // namespace
 
-int mjpl_plan_paths_constrained_dev(mjpl_pose *p, const mjpl_cplan_desc *d, const double *dQI, const double *dQG, int64_t B,
-                                    const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
-                                    int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes) {
-  int rc = check_cplan_args(p, d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
+int mjpl_plan_paths_constrained_ext_dev(mjpl_pose *p, const mjpl_cplan_desc *d, int32_t extend, const double *dQI, const double *dQG,
+                                        int64_t B, const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
+                                        int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes) {
+  int rc = check_cplan_args(p, d, extend, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
   if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
   if (rc != MJPL_OK || B == 0) return rc;
   HIP_TRY(hipSetDevice(p->e->device));
-  return launch_cplan(p, *d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
+  return launch_cplan(p, *d, extend, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
 }
 
-int mjpl_plan_paths_constrained(mjpl_pose *p, const mjpl_cplan_desc *d, const double *QI, const double *QG, int64_t B,
-                                const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status, int32_t *rounds_used,
-                                int32_t *edges, int32_t *tree_nodes) {
-  int rc = check_cplan_args(p, d, QI, QG, B, lo, hi, P, n_out, status);
+int mjpl_plan_paths_constrained_ext(mjpl_pose *p, const mjpl_cplan_desc *d, int32_t extend, const double *QI, const double *QG,
+                                    int64_t B, const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status,
+                                    int32_t *rounds_used, int32_t *edges, int32_t *tree_nodes) {
+  int rc = check_cplan_args(p, d, extend, QI, QG, B, lo, hi, P, n_out, status);
   if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
   if (rc != MJPL_OK || B == 0) return rc;
   mjpl_engine *e = p->e;
   const size_t qb = (size_t)B * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
   const HostOut outs[] = {{P, qb * (size_t)d->max_rows}, {n_out, ib}, {status, ib}, {rounds_used, ib}, {edges, ib}, {tree_nodes, 2 * ib}};
   return staged(e, false, {{QI, qb}, {QG, qb}}, outs, [&](void **in, void **out) {
-    return launch_cplan(p, *d, (const double *)in[0], (const double *)in[1], B, lo, hi, (double *)out[0], (int32_t *)out[1],
-                        (int32_t *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
+    return launch_cplan(p, *d, extend, (const double *)in[0], (const double *)in[1], B, lo, hi, (double *)out[0],
+                        (int32_t *)out[1], (int32_t *)out[2], (int32_t *)out[3], (int32_t *)out[4], (int32_t *)out[5]);
   });
+}
+
+int mjpl_plan_paths_constrained_dev(mjpl_pose *p, const mjpl_cplan_desc *d, const double *dQI, const double *dQG, int64_t B,
+                                    const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
+                                    int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes) {
+  return mjpl_plan_paths_constrained_ext_dev(p, d, 1, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
+}
+
+int mjpl_plan_paths_constrained(mjpl_pose *p, const mjpl_cplan_desc *d, const double *QI, const double *QG, int64_t B,
+                                const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status, int32_t *rounds_used,
+                                int32_t *edges, int32_t *tree_nodes) {
+  return mjpl_plan_paths_constrained_ext(p, d, 1, QI, QG, B, lo, hi, P, n_out, status, rounds_used, edges, tree_nodes);
 }
 
 // ---- row f3: IK seeds ------------------------------------------------------------------------

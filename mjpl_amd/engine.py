@@ -218,6 +218,10 @@ ABI = {
                                               _I32P, _I32P, _I32P]),
     "mjpl_plan_paths_constrained_dev": (C.c_int, [_VP, C.POINTER(CplanDesc), _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP, _VP, _VP, _VP,
                                                   _VP]),
+    "mjpl_plan_paths_constrained_ext": (C.c_int, [_VP, C.POINTER(CplanDesc), C.c_int32, _F64P, _F64P, C.c_int64, _F64P, _F64P, _F64P, _I32P,
+                                                  _I32P, _I32P, _I32P, _I32P]),
+    "mjpl_plan_paths_constrained_ext_dev": (C.c_int, [_VP, C.POINTER(CplanDesc), C.c_int32, _VP, _VP, C.c_int64, _F64P, _F64P, _VP, _VP,
+                                                      _VP, _VP, _VP, _VP]),
     "mjpl_roadmap_build": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P]),
     "mjpl_roadmap_build_dev": (C.c_int, [_VP, C.POINTER(RoadmapDesc), _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "mjpl_roadmap_query": (C.c_int, [_VP, C.POINTER(RoadmapQueryDesc), _F64P, C.c_int64, _U8P, _I32P, _I32P, _F64P, _F64P, _F64P, C.c_int64,
@@ -1021,6 +1025,14 @@ class Engine:
             raise ValueError(f"max_rows must be >= 2, got {max_rows}")
         return CplanDesc(base.epsilon, base.step_dist, base.seed, base.rounds, base.candidates, base.nodes, chain, max_rows, 0)
 
+    @staticmethod
+    def _cplan_extend(extend):
+        """`extend` of mjpl_plan_paths_constrained_ext*; ValueError for what the library would refuse as MJPL_E_ARG."""
+        extend = int(extend)
+        if not 1 <= extend <= 32:
+            raise ValueError(f"extend must be 1..32, got {extend}")
+        return extend
+
     def _cplan_handle(self, pose):
         """The mjpl_pose handle of a PoseConstraint or PoseProjector of THIS engine."""
         proj = getattr(pose, "_proj", pose)
@@ -1031,11 +1043,14 @@ class Engine:
         return proj.h
 
     def plan_paths_constrained(self, pose, QI, QG, lo, hi, step_dist, epsilon, rounds=64, candidates=16, nodes=1024, chain=8,
-                               max_rows=256, seed=0):
+                               max_rows=256, seed=0, extend=1):
         """plan_paths() under the PoseConstraint `pose` (a PoseConstraint or PoseProjector of this engine): every tree edge
-        is one projected step of at most `epsilon`, and the trees are joined by a bridge of up to `chain` such steps
-        (include/mjpl_hip.h states the algorithm).  -> (P float64 [B, max_rows, nplan], n_out, status, rounds_used, edges
+        is one projected step of at most `epsilon`, the trees are joined by a bridge of up to `chain` such steps, and an
+        extension is a chain of up to `extend` (1..32) of them -- what the reference's _constrained_extend does until it
+        is stopped, taken inside one round and cut at `extend` (include/mjpl_hip.h states the algorithm;
+        mjpl_plan_paths_constrained_ext).  -> (P float64 [B, max_rows, nplan], n_out, status, rounds_used, edges
         int32 [B], tree_nodes int32 [B, 2]); the statuses are plan_paths' and PLAN_LONG (a path of more than max_rows rows)."""
+        extend = Engine._cplan_extend(extend)  # (before any engine work)
         h = self._cplan_handle(pose)
         QI, QG = _f64(QI), _f64(QG)
         if QI.ndim != 2 or QI.shape[1] != self.nplan or QG.shape != QI.shape:
@@ -1046,22 +1061,24 @@ class Engine:
         P = np.zeros((B, desc.max_rows, self.nplan), np.float64)
         n_out, status, rounds_used, edges = (np.zeros(B, np.int32) for _ in range(4))
         tree_nodes = np.zeros((B, 2), np.int32)
-        self._ok(self.lib.mjpl_plan_paths_constrained(h, C.byref(desc), QI.ctypes.data_as(_F64P), QG.ctypes.data_as(_F64P), B,
-                                                      lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P), P.ctypes.data_as(_F64P),
-                                                      n_out.ctypes.data_as(_I32P), status.ctypes.data_as(_I32P),
-                                                      rounds_used.ctypes.data_as(_I32P), edges.ctypes.data_as(_I32P),
-                                                      tree_nodes.ctypes.data_as(_I32P)))
+        self._ok(self.lib.mjpl_plan_paths_constrained_ext(h, C.byref(desc), extend, QI.ctypes.data_as(_F64P), QG.ctypes.data_as(_F64P), B,
+                                                          lo.ctypes.data_as(_F64P), hi.ctypes.data_as(_F64P), P.ctypes.data_as(_F64P),
+                                                          n_out.ctypes.data_as(_I32P), status.ctypes.data_as(_I32P),
+                                                          rounds_used.ctypes.data_as(_I32P), edges.ctypes.data_as(_I32P),
+                                                          tree_nodes.ctypes.data_as(_I32P)))
         return P, n_out, status, rounds_used, edges, tree_nodes
 
     def plan_paths_constrained_dev(self, pose, dQI, dQG, B, lo, hi, step_dist, epsilon, dP, dn_out, dstatus, drounds_used=None,
-                                   dedges=None, dtree_nodes=None, rounds=64, candidates=16, nodes=1024, chain=8, max_rows=256, seed=0):
+                                   dedges=None, dtree_nodes=None, rounds=64, candidates=16, nodes=1024, chain=8, max_rows=256, seed=0,
+                                   extend=1):
         """plan_paths_constrained() on device pointers (lo and hi stay host arrays; the last three outputs may be None)."""
+        extend = Engine._cplan_extend(extend)  # (before any engine work)
         h = self._cplan_handle(pose)
         lo, hi = self._plan_box(lo, hi)
         desc = self.cplan_desc(step_dist, epsilon, rounds, candidates, nodes, chain, max_rows, seed)
-        self._ok(self.lib.mjpl_plan_paths_constrained_dev(h, C.byref(desc), dQI, dQG, int(B), lo.ctypes.data_as(_F64P),
-                                                          hi.ctypes.data_as(_F64P), dP, dn_out, dstatus, drounds_used, dedges,
-                                                          dtree_nodes))
+        self._ok(self.lib.mjpl_plan_paths_constrained_ext_dev(h, C.byref(desc), extend, dQI, dQG, int(B), lo.ctypes.data_as(_F64P),
+                                                              hi.ctypes.data_as(_F64P), dP, dn_out, dstatus, drounds_used, dedges,
+                                                              dtree_nodes))
 
     # -- roadmap planning: validate a scene's edges once, answer many queries (include/mjpl_hip.h, mjpl_roadmap_*)
     @staticmethod

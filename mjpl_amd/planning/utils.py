@@ -290,7 +290,7 @@ def plan_paths(q_inits, q_goals, collision, step_dist: float, *, epsilon: float,
 
 def plan_paths_constrained(q_inits, q_goals, collision, pose, step_dist: float, *, epsilon: float, rounds: int = 64,
                            candidates: int = 16, nodes: int = 1024, chain: int = 8, max_rows: int = 256, seed: int = 0,
-                           lo=None, hi=None, return_info: bool = False):
+                           lo=None, hi=None, return_info: bool = False, extend: int = 1):
     """:func:`plan_paths` under a projecting constraint: many start/goal pairs at once on the GPU, every waypoint on
     the manifold of ``pose`` (a :class:`mjpl_amd.PoseConstraint` made with ``engine=collision.engine``).
 
@@ -299,7 +299,11 @@ def plan_paths_constrained(q_inits, q_goals, collision, pose, step_dist: float, 
     the node it left), so there is no straight connect edge of any length -- its interior would leave the manifold.
     Instead each round a problem builds a *bridge*: a chain of up to ``chain`` (1..32) projected steps from the growing
     tree towards the closest node the other tree gained, closed by one straight edge of at most ``epsilon``; beside it, up
-    to ``candidates`` projected extensions towards seeded uniform samples.  Links, closing edge and extensions of ALL
+    to ``candidates`` extensions towards seeded uniform samples.  An extension is a chain of up to ``extend`` (1..32)
+    projected steps from the nearest node, each from the one before it, cut at the first step that is refused: what the
+    reference's ``_constrained_extend`` does until it is stopped, taken inside one round and cut at ``extend``.  With the
+    default of 1 a tree's frontier moves by at most ``epsilon`` a round, which solves only pairs that are already
+    close on the manifold (DESIGN.md 5.18 has the measurements).  Links, closing edge and extensions of ALL
     problems are validated by one edge launch of ``collision`` per round (waypoints ``step_dist`` apart; the interior of
     a step is sampled for collision only, as in the reference).  ``include/mjpl_hip.h``
     (``mjpl_plan_paths_constrained``) states the algorithm.
@@ -321,6 +325,7 @@ def plan_paths_constrained(q_inits, q_goals, collision, pose, step_dist: float, 
     if getattr(pose, "engine", None) is not collision.engine:
         raise ValueError("pose and collision must share one engine: PoseConstraint(..., engine=collision.engine)")
     _engine.Engine.cplan_desc(step_dist, epsilon, rounds, candidates, nodes, chain, max_rows, seed)  # (ValueError for a bad parameter)
+    _engine.Engine._cplan_extend(extend)
     q_inits, q_goals = list(q_inits), list(q_goals)
     if len(q_inits) != len(q_goals):
         raise ValueError(f"{len(q_inits)} q_inits but {len(q_goals)} q_goals")
@@ -342,7 +347,7 @@ def plan_paths_constrained(q_inits, q_goals, collision, pose, step_dist: float, 
     collision._ensure_full()
     P, n_out, status, rounds_used, edges, tree_nodes = collision.engine.plan_paths_constrained(
         pose, QI, QG, lo, hi, step_dist, epsilon, rounds=rounds, candidates=candidates, nodes=nodes, chain=chain, max_rows=max_rows,
-        seed=seed)
+        seed=seed, extend=extend)
     paths = []
     for b in range(len(q_inits)):
         if status[b] != _engine.PLAN_SOLVED:

@@ -2,7 +2,8 @@
 
 The headline Franka scene over the 7 arm columns (fingers at home), the end effector's roll and pitch within 0.1 rad of
 the home pose; --problems seeded pairs ON that manifold (uniform draws in the arm's ranges projected with q_step = inf,
-kept where collision-valid and pose-valid), epsilon 0.05, q_step 0.05, step_dist 0.01, the defaults otherwise.
+kept where collision-valid and pose-valid), epsilon 0.05, q_step 0.05, step_dist 0.01, the defaults otherwise (--extend X:
+an extension is a chain of up to X projected steps; the default of 1 is a single step).
 Reported: the wall time of Engine.plan_paths_constrained (host form: copies in and out included; one warm-up call, then
 the median of --repeats calls and their spread), the share solved, the status counts, mean rounds and rows, the edges
 validated, and its phases from device events (option "kernel_timer": propose with count, scan and gather / project /
@@ -54,6 +55,7 @@ def main():
     ap.add_argument("--nodes", type=int, default=1024)
     ap.add_argument("--chain", type=int, default=8)
     ap.add_argument("--max-rows", type=int, default=256)
+    ap.add_argument("--extend", type=int, default=1, help="steps of an extension chain (1..32)")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -70,7 +72,7 @@ def main():
                       max_planning_time=a.serial_seconds, pose=pose)
     lo, hi = model.jnt_range[arm, 0].copy(), model.jnt_range[arm, 1].copy()
     QI, QG = manifold_ends(e, pose, arm, home, lo, hi, a.problems, a.seed)
-    kw = dict(rounds=a.rounds, candidates=a.candidates, nodes=a.nodes, chain=a.chain, max_rows=a.max_rows, seed=a.seed)
+    kw = dict(rounds=a.rounds, candidates=a.candidates, nodes=a.nodes, chain=a.chain, max_rows=a.max_rows, seed=a.seed, extend=a.extend)
 
     def call():
         return e.plan_paths_constrained(pose, QI, QG, lo, hi, a.step_dist, a.epsilon, **kw)
@@ -102,7 +104,7 @@ def main():
     per_pair = float(np.mean(serial_ms)) if ns else None
     print(json.dumps({
         "problems": a.problems, "step_dist": a.step_dist, "epsilon": a.epsilon, "q_step": a.q_step, "rounds": a.rounds,
-        "candidates": a.candidates, "nodes": a.nodes, "chain": a.chain, "max_rows": a.max_rows,
+        "candidates": a.candidates, "nodes": a.nodes, "chain": a.chain, "max_rows": a.max_rows, "extend": a.extend,
         "batched_wall_ms_median": float(np.median(wall)), "batched_wall_ms_min": float(np.min(wall)), "batched_wall_ms_max": float(np.max(wall)),
         "status_counts": np.bincount(status, minlength=6).tolist(), "solved_share": float(solved.mean()),
         "rounds_used_mean_solved": float(rounds_used[solved].mean()) if solved.any() else None,
