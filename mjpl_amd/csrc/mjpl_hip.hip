@@ -120,6 +120,18 @@ struct DevBuf {
   }
 };
 
+// An arena's spans, listed once: run without a base the listing gives the byte count, with it the pointers.
+struct Carver {
+  char *base;
+  size_t at = 0;
+  template <class T>
+  T *take(size_t count, size_t align = 256) {  // (the span's bytes rounded up to `align`)
+    T *span = base ? (T *)(base + at) : nullptr;
+    at += (count * sizeof(T) + align - 1) / align * align;
+    return span;
+  }
+};
+
 // What a nearest-neighbour look-up keeps between calls: its scratch, and what the last look-up ON THIS SCRATCH did.  The
 // engine has one; the planner a second for the look-ups on its second stream (mjpl_rrt.h), which go with the planner.
 struct NnScratch {
@@ -576,24 +588,22 @@ struct mjpl_engine {
   int64_t topp_chunk_bytes = (int64_t)kToppChunkBytes;
   int64_t topp_last_chunks = 0;
   // mjpl_shortcut_paths* (mjpl_shortcut.h): the call's offsets on the device, and per chunk of paths the live lists, arc
-  // lengths, candidates, the round's edge batch with its verdicts, the round's header and rocPRIM's scan space.
+  // lengths, candidates, the round's edge batch with its verdicts and rocPRIM's scan space (one arena: carve_shortcut),
+  // and the round's header.
   DevBuf<int64_t> d_sc_off;
-  DevBuf<double> d_sc_f64;
-  DevBuf<int> d_sc_i32;
+  DevBuf<char> d_sc_arena;
   DevBuf<unsigned long long> d_sc_head;
-  DevBuf<char> d_sc_tmp;
   // option "shortcut_chunk_bytes": the workspace of one chunk of paths (more or fewer launches, no bit of any output);
   // read-only: "shortcut_last_chunks", and what the last call validated and -- with "kernel_timer" & 1 -- spent per phase
   int64_t shortcut_chunk_bytes = (int64_t)kShortcutChunkBytes;
   int64_t shortcut_last_chunks = 0, shortcut_last_rounds = 0, shortcut_last_edges = 0;
   double shortcut_last_ms[3] = {0, 0, 0};  // propose (with scan and gather), validate, commit
   // mjpl_plan_paths* (mjpl_plan.h): the sampling box, and per chunk of problems the trees with their parents, the
-  // round's targets, the ends' batch, the round's edge batch with its verdicts, the round's header and rocPRIM's scan space.
+  // round's targets, the ends' batch, the round's edge batch with its verdicts and rocPRIM's scan space (one arena, which
+  // the constrained calls share: carve_plan, carve_cplan), and the round's header.
   DevBuf<double> d_pl_box;
-  DevBuf<double> d_pl_f64;
-  DevBuf<int> d_pl_i32;
+  DevBuf<char> d_pl_arena;
   DevBuf<unsigned long long> d_pl_head;
-  DevBuf<char> d_pl_tmp;
   DevBuf<int> d_pl_q;  // mjpl_plan_paths_constrained* (mjpl_cplan.h): the planning columns and their inverse
   // option "plan_chunk_bytes": the workspace of one chunk of problems (more or fewer launches, no bit of any output);
   // read-only: "plan_last_chunks", and what the last call validated and -- with "kernel_timer" & 1 -- spent per phase
@@ -601,12 +611,11 @@ struct mjpl_engine {
   int64_t plan_last_chunks = 0, plan_last_rounds = 0, plan_last_edges = 0;
   double plan_last_ms[4] = {0, 0, 0, 0};  // propose (with scan and gather), validate, commit; constrained: project
   // mjpl_roadmap_build* / mjpl_roadmap_query* (mjpl_roadmap.h): the configuration batch, the neighbour lists and the edge
-  // batch; the lists' indices, counts, flags and verdicts; the sort keys; the call's header; rocPRIM's sort and scan space.
-  // Nothing of a graph stays here between calls: the caller's arrays hold it.
-  DevBuf<double> d_rm_f64;
-  DevBuf<int> d_rm_i32;
-  DevBuf<unsigned long long> d_rm_u64, d_rm_head;
-  DevBuf<char> d_rm_tmp;
+  // batch; the lists' indices, counts, flags and verdicts; the sort keys; rocPRIM's sort and scan space (one arena:
+  // carve_roadmap_build, carve_roadmap_query); the call's header.  Nothing of a graph stays here between calls: the
+  // caller's arrays hold it.
+  DevBuf<char> d_rm_arena;
+  DevBuf<unsigned long long> d_rm_head;
   // options "roadmap_chunk_bytes" and "roadmap_lds_nodes" (more or fewer launches, no bit of any output); read-only: what
   // the last call did and -- with "kernel_timer" & 1 -- spent per phase (build: nodes, neighbours, validate, graph;
   // query: attach, validate, search with the walk)
@@ -2548,18 +2557,6 @@ int dispatch_nplan(int nplan, F &&f) {
   else return nplan == LO ? f(std::integral_constant<int, LO>{}) : dispatch_nplan<LO + 1, HI>(nplan, f);
 }
 
-// An arena's spans, listed once: run without a base the listing gives the byte count, with it the pointers.
-struct Carver {
-  char *base;
-  size_t at = 0;
-  template <class T>
-  T *take(size_t count, size_t align = 256) {  // (the span's bytes rounded up to `align`)
-    T *span = base ? (T *)(base + at) : nullptr;
-    at += (count * sizeof(T) + align - 1) / align * align;
-    return span;
-  }
-};
-
 // the partial rows: maxchunks of them and the seed row, distances then indices
 struct NnParts {
   double *pd2, *seed_d2;
@@ -3200,42 +3197,197 @@ int check_shortcut_args(const mjpl_engine *e, const mjpl_shortcut_desc *d, const
   return MJPL_OK;
 }
 
-// option "kernel_timer" & 1 around one phase of mjpl_shortcut_paths* or mjpl_plan_paths*: where its pair of events sits, for
-// the sums of the call
-struct ShortcutPhase {
+// ---- what mjpl_shortcut_paths*, mjpl_plan_paths*, mjpl_plan_paths_constrained* and the roadmap calls share on the host
+
+// option "kernel_timer" & 1 around one phase of such a call: its first and last event (launch_configs marks events of
+// its own between them), for the sums of the call.  A phase is logged only when both of its own events were recorded:
+// the pool stops at 4096 events, and later phases go untimed.
+using PhaseLog = std::vector<std::array<int, 3>>;
+
+struct PhaseScope {
   mjpl_engine *e;
-  std::vector<std::pair<int, int>> &log;
+  PhaseLog &log;
   int phase, at;
-  ShortcutPhase(mjpl_engine *e_, std::vector<std::pair<int, int>> &log_, int phase_) : e(e_), log(log_), phase(phase_), at(e_->kt_used[0]) {
+  PhaseScope(mjpl_engine *e_, PhaseLog &log_, int phase_) : e(e_), log(log_), phase(phase_), at(e_->kt_used[0]) {
     kt_mark(e, 1, e->stream);
   }
-  ~ShortcutPhase() {
+  ~PhaseScope() {
+    const int before = e->kt_used[0];
     kt_mark(e, 1, e->stream);
-    if (e->kt_used[0] == at + 2) log.emplace_back(phase, at);
+    if (at < before && e->kt_used[0] == before + 1) log.push_back({phase, at, before});
   }
 };
 
-// ... and the sums: device time per phase (propose with scan and gather, validate, commit)
-template <size_t NP>
-int phase_sums(mjpl_engine *e, const std::vector<std::pair<int, int>> &phases, double (&sums)[NP]) {
+// ... and the sums: device time per phase, added to the family's `*_last_ms`
+int phase_sums(mjpl_engine *e, const PhaseLog &phases, double *sums) {
   if (phases.empty()) return MJPL_OK;
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (const auto &ph : phases) {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph.second], e->kt_ev[0][(size_t)ph.second + 1]));
-    sums[ph.first] += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph[1]], e->kt_ev[0][(size_t)ph[2]]));
+    sums[ph[0]] += ms;
   }
   return MJPL_OK;
 }
 
+// every `*_last_*` value of a family, the times included: at the top of its launchers, and by its entry points on an
+// empty batch
+void shortcut_reset(mjpl_engine *e) {
+  e->shortcut_last_chunks = e->shortcut_last_rounds = e->shortcut_last_edges = 0;
+  for (double &ms : e->shortcut_last_ms) ms = 0.0;
+}
+
+void plan_reset(mjpl_engine *e) {
+  e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  for (double &ms : e->plan_last_ms) ms = 0.0;
+}
+
+void roadmap_reset(mjpl_engine *e) {
+  e->roadmap_last_edges = e->roadmap_last_chunks = e->roadmap_last_sweeps = 0;
+  for (double &ms : e->roadmap_last_ms) ms = 0.0;
+}
+
+// The header the kernels of a round (or of a roadmap query) leave for the host, three words: the bits of the longest edge
+// (a double), the edge count, and the problems still at work (the roadmap query: its sweeps).
+struct RoundHead {
+  double longest;
+  int64_t edges;
+  int64_t live;
+};
+
+inline double head_length(unsigned long long bits) {
+  double len;
+  memcpy(&len, &bits, sizeof(double));
+  return len;
+}
+
+inline RoundHead decode_head(const unsigned long long (&w)[3]) { return {head_length(w[0]), (int64_t)w[1], (int64_t)w[2]}; }
+
+// ... read: one small copy and one synchronisation of the engine's stream
+int read_head(mjpl_engine *e, const unsigned long long *dhead, RoundHead *h) {
+  unsigned long long w[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(w, dhead, sizeof(w), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  *h = decode_head(w);
+  return MJPL_OK;
+}
+
+// A handful of LONG edges (path shortcutting, smooth_path: planning/utils.py:9-87) is better served by the two
+// persistent kernels, which keep every 32nd exact waypoint as a checkpoint: the fused kernel rebuilds an undecided
+// waypoint by the recurrence from the start of its edge (measured: 64 edges of 2 400 waypoints 3.9 vs 7.6 ms).  Every
+// caller of launch_edges that knows its longest edge asks here, so the same edges take the same kernels whoever asks.
+constexpr int64_t kFewEdges = 4096;
+inline bool few_long_edges(int64_t E, double longest, double step_dist) { return E <= kFewEdges && longest > 64.0 * step_dist; }
+
+// rocPRIM's space for a scan of n ints (never 0 bytes: a span of the arena, and a null space asks rocPRIM for the size)
+int scan_space(hipStream_t st, size_t n, size_t *bytes) {
+  *bytes = 0;
+  if (rocprim::exclusive_scan(nullptr, *bytes, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), st) != hipSuccess)
+    return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", n);
+  *bytes = std::max<size_t>(*bytes, 1);
+  return MJPL_OK;
+}
+
+// An arena reserved for a listing of its spans (carve_shortcut and the like), then carved: the listing runs without a
+// base for the byte count and with it for the pointers.  An arena that is large enough is left as it is.
+template <class List>
+int carve_arena(DevBuf<char> &arena, List &&list) {
+  Carver size{nullptr};
+  list(size);
+  MJPL_TRY(arena.reserve(size.at));
+  Carver c{arena.p};
+  list(c);
+  return MJPL_OK;
+}
+
+// What the round loop itself touches of a chunk's workspace: the header, the edge counts [counts] and their offsets, the
+// scan's space, the round's edge batch and its verdicts.  (The kernels reach the same spans through their batch struct.)
+struct RoundSpans {
+  unsigned long long *head;
+  int *cnt, *off;
+  size_t counts;
+  void *scan;
+  size_t scan_bytes;
+  const double *QA, *QB;
+  uint8_t *valid;
+};
+
+// The rounds [first, last) of one chunk, for the three launchers in lockstep.  Per round: the header is zeroed and the
+// launcher proposes, propose(r), both in phase 0; project(r) is what a launcher's propose stage launches after that,
+// under phase scopes of its own (constrained planning: project and count) -- then the header is read (read_head).  No
+// problem at work ends the chunk's rounds.  A round with edges has them scanned and gathered (phase 0), validated by
+// ONE launch_edges (phase 1); commit(have_verdicts) runs in every round (phase 2).  A round before 0 (planning: the
+// direct edges) does not count in `rounds`.
+template <class Propose, class Project, class Gather, class Commit>
+int run_rounds(mjpl_engine *e, PhaseLog &phases, const RoundSpans &s, int first, int last, double step_dist, int64_t *rounds, int64_t *edges,
+               Propose &&propose, Project &&project, Gather &&gather, Commit &&commit) {
+  const hipStream_t st = e->stream;
+  size_t scan_bytes = s.scan_bytes;
+  for (int r = first; r < last; r++) {
+    {
+      PhaseScope ph(e, phases, 0);
+      HIP_TRY(hipMemsetAsync(s.head, 0, 3 * sizeof(unsigned long long), st));
+      MJPL_TRY(propose(r));
+    }
+    MJPL_TRY(project(r));
+    RoundHead h;
+    MJPL_TRY(read_head(e, s.head, &h));
+    if (h.live == 0) break;  // every problem of the chunk is retired
+    if (r >= 0) ++*rounds;
+    if (h.edges > 0) {
+      {
+        PhaseScope ph(e, phases, 0);
+        if (rocprim::exclusive_scan(s.scan, scan_bytes, s.cnt, s.off, 0, s.counts, rocprim::plus<int>(), st) != hipSuccess)
+          return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
+        MJPL_TRY(gather());
+      }
+      PhaseScope ph(e, phases, 1);
+      MJPL_TRY(launch_edges(e, s.QA, s.QB, h.edges, step_dist, MJPL_AOS, 0, s.valid, nullptr, few_long_edges(h.edges, h.longest, step_dist)));
+      *edges += h.edges;
+    }
+    PhaseScope ph(e, phases, 2);
+    MJPL_TRY(commit(h.edges > 0 ? 1 : 0));
+  }
+  return MJPL_OK;
+}
+
+// a kernel of these launchers on a stream, with the launch's error
+template <class K, class... A>
+int launch_checked(hipStream_t st, K kern, dim3 grid, dim3 block, size_t lds, const A &...args) {
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  HIP_TRY(hipGetLastError());
+  return MJPL_OK;
+}
+
+// The workspace of a chunk of `nb` paths with `rows` waypoints between them, K candidates a path.  (The edge batch starts
+// on a 256-byte boundary, as the staged batches of mjpl_check_edges do: every span does.)
+void carve_shortcut(Carver &c, size_t rows, size_t nb, size_t K, size_t np, size_t scan_bytes, ShortcutBatch *a, RoundSpans *s) {
+  const size_t L64 = kShortcutLanes, emax = nb * K;
+  a->L = c.take<double>(rows);
+  a->cs = c.take<double>(nb * L64);
+  a->QA = c.take<double>(emax * np);
+  a->QB = c.take<double>(emax * np);
+  a->live = c.take<int>(rows);
+  a->m = c.take<int>(nb);
+  a->state = c.take<int>(nb);
+  a->nprop = c.take<int>(nb);
+  a->nacc = c.take<int>(nb);
+  a->cnt = c.take<int>(nb + 1);
+  a->off = c.take<int>(nb + 1);
+  a->ci = c.take<int>(nb * L64);
+  a->cj = c.take<int>(nb * L64);
+  a->crank = c.take<int>(nb * L64);
+  uint8_t *valid = c.take<uint8_t>(emax);
+  a->valid = valid;
+  *s = {a->head, a->cnt, a->off, nb + 1, c.take<char>(scan_bytes), scan_bytes, a->QA, a->QB, valid};
+}
+
 // mjpl_shortcut_paths* on device batches (wp_off on the host).  Per chunk of paths whose workspace fits the option
-// "shortcut_chunk_bytes" (always at least one path): k_shortcut_init, then per round propose -> one small copy and one
-// synchronisation (the round's header) -> scan, gather, ONE launch_edges -> commit, then k_shortcut_finish.  A round
-// that proposed nothing launches no validation; a chunk whose paths are all retired ends its rounds.
+// "shortcut_chunk_bytes" (always at least one path): k_shortcut_init, the chunk's rounds (run_rounds), k_shortcut_finish.
+// A round that proposed nothing still commits, without verdicts.
 int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *dW, const int64_t *wp_off, int64_t B, uint8_t *dkeep,
                     int32_t *dn_out, double *dlength, int32_t *dstatus, int32_t *dproposed, int32_t *daccepted) {
-  e->shortcut_last_chunks = e->shortcut_last_rounds = e->shortcut_last_edges = 0;
-  e->shortcut_last_ms[0] = e->shortcut_last_ms[1] = e->shortcut_last_ms[2] = 0.0;
+  shortcut_reset(e);
   const hipStream_t st = e->stream;
   HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
   MJPL_TRY(e->d_sc_off.reserve((size_t)B + 1, 1024));
@@ -3245,7 +3397,7 @@ int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *d
   // what one path adds to a chunk: K edges (two rows and a verdict each), its candidates, its rows' live list and arc lengths
   const size_t per_path = K * (2 * np * sizeof(double) + 1) + L64 * (3 * sizeof(int) + sizeof(double)) + 6 * sizeof(int);
   const size_t per_row = sizeof(int) + sizeof(double), chunk_bytes = (size_t)e->shortcut_chunk_bytes;
-  std::vector<std::pair<int, int>> phases;
+  PhaseLog phases;
   ShortcutBatch a = {};
   a.W = dW; a.wp_off = e->d_sc_off.p; a.d = (int)np; a.K = d.candidates;
   a.min_saving = d.min_saving;
@@ -3261,62 +3413,31 @@ int launch_shortcut(mjpl_engine *e, const mjpl_shortcut_desc &d, const double *d
       bytes += more;
       b1++;
     }
-    const size_t nb = (size_t)(b1 - b0), rows = (size_t)(wp_off[b1] - wp_off[b0]), emax = nb * K;
-    // (the edge batch starts on a 256-byte boundary, as the staged batches of mjpl_check_edges do)
-    const size_t qa_at = (rows + nb * L64 + 31) / 32 * 32, qb_at = (qa_at + emax * np + 31) / 32 * 32;
-    MJPL_TRY(e->d_sc_f64.reserve(qb_at + emax * np));
-    MJPL_TRY(e->d_sc_i32.reserve(rows + 4 * nb + 2 * (nb + 1) + 3 * nb * L64 + (emax + 3) / 4));
-    size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
-    MJPL_TRY(e->d_sc_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    const size_t nb = (size_t)(b1 - b0), rows = (size_t)(wp_off[b1] - wp_off[b0]);
+    size_t scan_bytes = 0;
+    MJPL_TRY(scan_space(st, nb + 1, &scan_bytes));
+    RoundSpans s = {};
+    MJPL_TRY(carve_arena(e->d_sc_arena, [&](Carver &c) { carve_shortcut(c, rows, nb, K, np, scan_bytes, &a, &s); }));
     a.b0 = (int)b0; a.nb = (int)nb; a.row0 = wp_off[b0];
-    a.L = e->d_sc_f64.p; a.cs = a.L + rows; a.QA = a.L + qa_at; a.QB = a.L + qb_at;
-    a.live = e->d_sc_i32.p; a.m = a.live + rows; a.state = a.m + nb; a.nprop = a.state + nb; a.nacc = a.nprop + nb;
-    a.cnt = a.nacc + nb; a.off = a.cnt + (nb + 1); a.ci = a.off + (nb + 1); a.cj = a.ci + nb * L64; a.crank = a.cj + nb * L64;
-    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.crank + nb * L64);
-    a.valid = dvalid;
     const dim3 grid((unsigned)((nb + kShortcutWaves - 1) / kShortcutWaves)), block(64 * kShortcutWaves);
-    hipLaunchKernelGGL(k_shortcut_init, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    for (int r = 0; r < d.rounds; r++) {
-      a.round = r;
-      unsigned long long head[3] = {0, 0, 0};
-      {
-        ShortcutPhase ph(e, phases, 0);
-        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
-        hipLaunchKernelGGL(k_shortcut_propose, grid, block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-      }
-      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (head[2] == 0) break;  // every path of the chunk is retired
-      e->shortcut_last_rounds++;
-      const int64_t E = (int64_t)head[1];
-      a.have_verdicts = E > 0 ? 1 : 0;
-      if (E > 0) {
-        {
-          ShortcutPhase ph(e, phases, 0);
-          if (rocprim::exclusive_scan(e->d_sc_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-            return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
-          hipLaunchKernelGGL(k_shortcut_gather, grid, block, 0, st, a);
-          HIP_TRY(hipGetLastError());
-        }
-        double longest;
-        memcpy(&longest, &head[0], sizeof(double));
-        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
-        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
-        ShortcutPhase ph(e, phases, 1);
-        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
-        e->shortcut_last_edges += E;
-      }
-      ShortcutPhase ph(e, phases, 2);
-      hipLaunchKernelGGL(k_shortcut_commit, grid, block, 0, st, a);
-      HIP_TRY(hipGetLastError());
-    }
+    MJPL_TRY(launch_checked(st, k_shortcut_init, grid, block, 0, a));
+    MJPL_TRY(run_rounds(
+        e, phases, s, 0, d.rounds, d.step_dist, &e->shortcut_last_rounds, &e->shortcut_last_edges,
+        [&](int r) {
+          a.round = r;
+          return launch_checked(st, k_shortcut_propose, grid, block, 0, a);
+        },
+        [](int) { return MJPL_OK; },
+        [&] {
+          a.have_verdicts = 1;  // (a round that gathers has edges)
+          return launch_checked(st, k_shortcut_gather, grid, block, 0, a);
+        },
+        [&](int have_verdicts) {
+          a.have_verdicts = have_verdicts;
+          return launch_checked(st, k_shortcut_commit, grid, block, 0, a);
+        }));
     HIP_TRY(hipMemsetAsync(dkeep + wp_off[b0], 0, rows, st));
-    hipLaunchKernelGGL(k_shortcut_finish, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_checked(st, k_shortcut_finish, grid, block, 0, a));
     e->shortcut_last_chunks++;
     b0 = b1;
   }
@@ -3348,15 +3469,40 @@ int check_plan_args(const mjpl_engine *e, const mjpl_plan_desc *d, const void *Q
   return MJPL_OK;
 }
 
+// The workspace of a chunk of `nb` problems with trees of N nodes and `emax` edges a round at most.  The verdicts are one
+// span under two names: the ends' first (`end_verdicts` bytes), every round's after.  (The configuration and edge
+// batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do: every span does.)
+void carve_plan(Carver &c, size_t nb, size_t emax, size_t end_verdicts, size_t N, size_t np, size_t scan_bytes, PlanBatch *a, RoundSpans *s) {
+  const size_t L64 = kPlanLanes;
+  a->T = c.take<double>(nb * 2 * N * np);
+  a->ct = c.take<double>(nb * np * L64);
+  a->cfg = c.take<double>(2 * nb * np);
+  a->QA = c.take<double>(emax * np);
+  a->QB = c.take<double>(emax * np);
+  a->par = c.take<int>(nb * 2 * N);
+  a->ck = c.take<int>(nb * L64);
+  a->n = c.take<int>(2 * nb);
+  a->state = c.take<int>(nb);
+  a->gained = c.take<int>(nb);
+  a->rused = c.take<int>(nb);
+  a->nedges = c.take<int>(nb);
+  a->conn = c.take<int>(3 * nb);
+  a->jn = c.take<int>(2 * nb);
+  a->cnt = c.take<int>(nb + 1);
+  a->off = c.take<int>(nb + 1);
+  uint8_t *valid = c.take<uint8_t>(std::max(emax, end_verdicts));
+  a->cvalid = valid;
+  a->valid = valid;
+  *s = {a->head, a->cnt, a->off, nb + 1, c.take<char>(scan_bytes), scan_bytes, a->QA, a->QB, valid};
+}
+
 // mjpl_plan_paths* on device batches (lo, hi on the host).  Per chunk of problems whose workspace fits the option
-// "plan_chunk_bytes" (always at least one problem): k_plan_init, ONE launch_configs on the ends, then per round -- the
-// direct edges are round -1 -- propose -> one small copy and one synchronisation (the round's header) -> scan, gather,
-// ONE launch_edges -> commit, then k_plan_finish.  A chunk whose problems are all retired ends its rounds.
+// "plan_chunk_bytes" (always at least one problem): k_plan_init, ONE launch_configs on the ends, the chunk's rounds
+// (run_rounds) -- the direct edges are round -1 -- then k_plan_finish.
 int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, const double *dQG, int64_t B, const double *lo,
                 const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                 int32_t *dtree_nodes) {
-  e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
-  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = e->plan_last_ms[3] = 0.0;
+  plan_reset(e);
   const hipStream_t st = e->stream;
   HIP_TRY(hipStreamSynchronize(st));  // (an earlier call's launches read the same buffers)
   const size_t np = e->qidx.size(), K = (size_t)d.candidates, N = (size_t)d.nodes, L64 = kPlanLanes;
@@ -3372,7 +3518,7 @@ int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, cons
                              L64 * (np * sizeof(double) + sizeof(int)) + 2 * np * sizeof(double) + 16 * sizeof(int);
   const size_t fit = std::max<size_t>((size_t)e->plan_chunk_bytes / per_problem, 1);
   const size_t chunk = std::min(fit, ((size_t)1 << 30) / (K + 1));  // (edge offsets are ints)
-  std::vector<std::pair<int, int>> phases;
+  PhaseLog phases;
   PlanBatch a = {};
   a.QI = dQI; a.QG = dQG; a.box = e->d_pl_box.p;
   a.d = (int)np; a.K = d.candidates; a.N = d.nodes; a.R = d.rounds;
@@ -3381,64 +3527,26 @@ int launch_plan(mjpl_engine *e, const mjpl_plan_desc &d, const double *dQI, cons
   a.head = e->d_pl_head.p;
   a.P = dP; a.n_out = dn_out; a.status = dstatus; a.rounds_used = drounds_used; a.edges = dedges; a.tree_nodes = dtree_nodes;
   for (int64_t b0 = 0; b0 < B; b0 += (int64_t)chunk) {
-    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * (K + 1);
-    // (the configuration and edge batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do)
-    const size_t ct_at = nb * 2 * N * np, cfg_at = (ct_at + nb * np * L64 + 31) / 32 * 32, qa_at = (cfg_at + 2 * nb * np + 31) / 32 * 32,
-                 qb_at = (qa_at + emax * np + 31) / 32 * 32;
-    MJPL_TRY(e->d_pl_f64.reserve(qb_at + emax * np));
-    const size_t ints = nb * 2 * N + nb * L64 + 2 * nb + 4 * nb + 3 * nb + 2 * nb + 2 * (nb + 1);
-    MJPL_TRY(e->d_pl_i32.reserve(ints + (std::max(emax, 2 * nb) + 3) / 4));
-    size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
-    MJPL_TRY(e->d_pl_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    const size_t nb = std::min(chunk, (size_t)(B - b0));
+    size_t scan_bytes = 0;
+    MJPL_TRY(scan_space(st, nb + 1, &scan_bytes));
+    RoundSpans s = {};
+    MJPL_TRY(carve_arena(e->d_pl_arena, [&](Carver &c) { carve_plan(c, nb, nb * (K + 1), 2 * nb, N, np, scan_bytes, &a, &s); }));
     a.b0 = (int)b0; a.nb = (int)nb;
-    a.T = e->d_pl_f64.p; a.ct = a.T + ct_at; a.cfg = a.T + cfg_at; a.QA = a.T + qa_at; a.QB = a.T + qb_at;
-    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.n = a.ck + nb * L64; a.state = a.n + 2 * nb; a.gained = a.state + nb;
-    a.rused = a.gained + nb; a.nedges = a.rused + nb; a.conn = a.nedges + nb; a.jn = a.conn + 3 * nb; a.cnt = a.jn + 2 * nb;
-    a.off = a.cnt + (nb + 1);
-    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.off + (nb + 1));  // the ends' verdicts first, every round's after
-    a.cvalid = dvalid; a.valid = dvalid;
     const dim3 grid((unsigned)((nb + kPlanWaves - 1) / kPlanWaves)), block(64 * kPlanWaves);
-    hipLaunchKernelGGL(k_plan_init, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, dvalid, nullptr));
-    for (int r = -1; r < d.rounds; r++) {
-      a.round = r;
-      unsigned long long head[3] = {0, 0, 0};
-      {
-        ShortcutPhase ph(e, phases, 0);
-        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
-        hipLaunchKernelGGL(k_plan_propose, grid, block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-      }
-      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (head[2] == 0) break;  // every problem of the chunk is retired
-      if (r >= 0) e->plan_last_rounds++;
-      const int64_t E = (int64_t)head[1];  // (a problem at work has at least one edge)
-      {
-        ShortcutPhase ph(e, phases, 0);
-        if (rocprim::exclusive_scan(e->d_pl_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-          return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
-        hipLaunchKernelGGL(k_plan_gather, grid, block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-      }
-      {
-        double longest;
-        memcpy(&longest, &head[0], sizeof(double));
-        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
-        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
-        ShortcutPhase ph(e, phases, 1);
-        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
-        e->plan_last_edges += E;
-      }
-      ShortcutPhase ph(e, phases, 2);
-      hipLaunchKernelGGL(k_plan_commit, grid, block, 0, st, a);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_plan_finish, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_checked(st, k_plan_init, grid, block, 0, a));
+    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, s.valid, nullptr));
+    // (a problem at work has at least one edge: no round here goes without validation)
+    MJPL_TRY(run_rounds(
+        e, phases, s, -1, d.rounds, d.step_dist, &e->plan_last_rounds, &e->plan_last_edges,
+        [&](int r) {
+          a.round = r;
+          return launch_checked(st, k_plan_propose, grid, block, 0, a);
+        },
+        [](int) { return MJPL_OK; },
+        [&] { return launch_checked(st, k_plan_gather, grid, block, 0, a); },
+        [&](int) { return launch_checked(st, k_plan_commit, grid, block, 0, a); }));
+    MJPL_TRY(launch_checked(st, k_plan_finish, grid, block, 0, a));
     e->plan_last_chunks++;
   }
   // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
@@ -3482,49 +3590,71 @@ int check_roadmap_query_args(const mjpl_engine *e, const mjpl_roadmap_query_desc
   return MJPL_OK;
 }
 
-// option "kernel_timer" & 1 around one phase of a roadmap call: its first and last event (launch_configs marks events of
-// its own between them), for the sums of the call
-struct RoadmapPhase {
-  mjpl_engine *e;
-  std::vector<std::array<int, 3>> &log;
-  int phase, at;
-  RoadmapPhase(mjpl_engine *e_, std::vector<std::array<int, 3>> &log_, int phase_) : e(e_), log(log_), phase(phase_), at(e_->kt_used[0]) {
-    kt_mark(e, 1, e->stream);
-  }
-  ~RoadmapPhase() {
-    const int before = e->kt_used[0];
-    kt_mark(e, 1, e->stream);
-    if (at < before && e->kt_used[0] == before + 1) log.push_back({phase, at, before});
-  }
-};
+inline unsigned rm_grid(size_t n) { return (unsigned)((n + kRmBlock - 1) / kRmBlock); }
 
-int roadmap_sums(mjpl_engine *e, const std::vector<std::array<int, 3>> &phases) {
-  if (phases.empty()) return MJPL_OK;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (const auto &ph : phases) {
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->kt_ev[0][(size_t)ph[1]], e->kt_ev[0][(size_t)ph[2]]));
-    e->roadmap_last_ms[ph[0]] += ms;
-  }
+// rocPRIM's space for a radix sort of n keys (bits 0 .. 52: a node index is below 2^21) and a scan of n ints
+int roadmap_space(hipStream_t st, size_t n, size_t *bytes) {
+  size_t sort_bytes = 0, scan_bytes = 0;
+  if (rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0, 53, st) != hipSuccess)
+    return fail(MJPL_E_HIP, "rocprim: no size for %zu keys", n);
+  MJPL_TRY(scan_space(st, n, &scan_bytes));
+  *bytes = std::max(sort_bytes, scan_bytes);
   return MJPL_OK;
 }
 
-void roadmap_reset(mjpl_engine *e) {
-  e->roadmap_last_edges = e->roadmap_last_chunks = e->roadmap_last_sweeps = 0;
-  for (double &ms : e->roadmap_last_ms) ms = 0.0;
+// The workspace of a build of N nodes with M = N k neighbour slots, `batch` edges to a launch: the finite rows, the
+// neighbour lists, the edge batch; flags and their positions; the sort keys (in, out) and the candidate pairs; rocPRIM's space
+struct RmBuildSpans {
+  double *cfg, *nn_d2, *QA, *QB;
+  int *nn_j, *nn_cnt, *flag, *pos;
+  uint8_t *fin, *evalid;
+  unsigned long long *ka, *kb, *pairs;
+  void *tmp;
+};
+
+void carve_roadmap_build(Carver &c, size_t N, size_t M, size_t batch, size_t np, size_t tmp_bytes, RmBuildSpans *w) {
+  w->cfg = c.take<double>(N * np);
+  w->nn_d2 = c.take<double>(M);
+  w->QA = c.take<double>(batch * np);
+  w->QB = c.take<double>(batch * np);
+  w->nn_j = c.take<int>(M);
+  w->nn_cnt = c.take<int>(N);
+  w->flag = c.take<int>(M + 1);
+  w->pos = c.take<int>(M + 1);
+  w->fin = c.take<uint8_t>(N);
+  w->evalid = c.take<uint8_t>(M);
+  w->ka = c.take<unsigned long long>(2 * M);
+  w->kb = c.take<unsigned long long>(2 * M);
+  w->pairs = c.take<unsigned long long>(M);
+  w->tmp = c.take<char>(tmp_bytes);
 }
 
-inline unsigned rm_grid(size_t n) { return (unsigned)((n + kRmBlock - 1) / kRmBlock); }
-inline size_t rm_pad(size_t doubles) { return (doubles + 31) / 32 * 32; }  // (batches start on 256-byte boundaries)
+// The workspace of a query of B problems with C connections an end and `emax` edges at most; `dist`: distances of the
+// searches that do not keep theirs in LDS (0: none, the batch's pointer stays null).  What the host code writes through
+// and the kernels only read comes back in `w`.
+struct RmQuerySpans {
+  double *cfg;
+  uint8_t *fin, *cvalid, *evalid;
+  int *att_j, *att_cnt;
+  double *att_d2;
+  void *tmp;
+};
 
-// rocPRIM's space for a radix sort of n keys (bits 0 .. 52: a node index is below 2^21) and a scan of n ints
-int roadmap_tmp(mjpl_engine *e, size_t n, size_t *bytes) {
-  size_t sort_bytes = 0, scan_bytes = 0;
-  if (rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0, 53, e->stream) != hipSuccess ||
-      rocprim::exclusive_scan(nullptr, scan_bytes, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), e->stream) != hipSuccess)
-    return fail(MJPL_E_HIP, "rocprim: no size for %zu keys", n);
-  *bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 1);
-  return e->d_rm_tmp.reserve(*bytes, 4096);  // (never null: a null space asks rocPRIM for the size)
+void carve_roadmap_query(Carver &c, size_t B, size_t C, size_t emax, size_t dist, size_t np, size_t tmp_bytes, RmQuery *a, RmQuerySpans *w) {
+  w->cfg = c.take<double>(2 * B * np);
+  a->att_d2 = w->att_d2 = c.take<double>(2 * B * C);
+  a->dist = dist ? c.take<double>(dist) : nullptr;
+  a->QA = c.take<double>(emax * np);
+  a->QB = c.take<double>(emax * np);
+  a->att_j = w->att_j = c.take<int>(2 * B * C);
+  a->att_cnt = w->att_cnt = c.take<int>(2 * B);
+  a->state = c.take<int>(B);
+  a->cnt = c.take<int>(B + 1);
+  a->off = c.take<int>(B + 1);
+  a->fin = w->fin = c.take<uint8_t>(B);
+  a->cvalid = w->cvalid = c.take<uint8_t>(2 * B);
+  a->valid = w->evalid = c.take<uint8_t>(emax);
+  w->tmp = c.take<char>(tmp_bytes);
 }
 
 int roadmap_knn(mjpl_engine *e, const RmKnn &a) {
@@ -3546,56 +3676,49 @@ int launch_roadmap_build(mjpl_engine *e, const mjpl_roadmap_desc &d, const doubl
   const unsigned long long none = (unsigned long long)N << 32;
   // one launch's edges: two rows and a verdict each
   const size_t chunk = std::min<size_t>(std::max<size_t>((size_t)e->roadmap_chunk_bytes / (2 * np * sizeof(double) + 1), 1), (size_t)1 << 30);
-  const size_t batch = std::min(chunk, M);
-  const size_t d2_at = rm_pad(N * np), qa_at = rm_pad(d2_at + M), qb_at = rm_pad(qa_at + batch * np);
-  MJPL_TRY(e->d_rm_f64.reserve(qb_at + batch * np));
-  MJPL_TRY(e->d_rm_i32.reserve(M + N + 2 * (M + 1) + (N + 3) / 4 + (M + 3) / 4));
-  MJPL_TRY(e->d_rm_u64.reserve(5 * M));
   size_t tmp_bytes = 0;
-  MJPL_TRY(roadmap_tmp(e, 2 * M + 1, &tmp_bytes));
-  double *cfg = e->d_rm_f64.p, *nn_d2 = cfg + d2_at, *QA = cfg + qa_at, *QB = cfg + qb_at;
-  int *nn_j = e->d_rm_i32.p, *nn_cnt = nn_j + M, *flag = nn_cnt + N, *pos = flag + (M + 1);
-  uint8_t *fin = reinterpret_cast<uint8_t *>(pos + (M + 1)), *evalid = fin + (N + 3) / 4 * 4;
-  unsigned long long *ka = e->d_rm_u64.p, *kb = ka + 2 * M, *pairs = kb + 2 * M;
-  std::vector<std::array<int, 3>> phases;
+  MJPL_TRY(roadmap_space(st, 2 * M + 1, &tmp_bytes));
+  RmBuildSpans w = {};
+  MJPL_TRY(carve_arena(e->d_rm_arena, [&](Carver &c) { carve_roadmap_build(c, N, M, std::min(chunk, M), np, tmp_bytes, &w); }));
+  PhaseLog phases;
   {
-    RoadmapPhase ph(e, phases, 0);
-    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dQ, (const double *)nullptr, (int)N, (int)np, cfg, fin);
+    PhaseScope ph(e, phases, 0);
+    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dQ, (const double *)nullptr, (int)N, (int)np, w.cfg, w.fin);
     HIP_TRY(hipGetLastError());
-    MJPL_TRY(launch_configs(e, cfg, (int64_t)N, MJPL_AOS, dnode_valid, nullptr));
-    hipLaunchKernelGGL(k_rm_mask, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dnode_valid, (const uint8_t *)fin, (int)N);
+    MJPL_TRY(launch_configs(e, w.cfg, (int64_t)N, MJPL_AOS, dnode_valid, nullptr));
+    hipLaunchKernelGGL(k_rm_mask, dim3(rm_grid(N)), dim3(kRmBlock), 0, st, dnode_valid, (const uint8_t *)w.fin, (int)N);
     HIP_TRY(hipGetLastError());
   }
   int E32 = 0;
   {
-    RoadmapPhase ph(e, phases, 1);
+    PhaseScope ph(e, phases, 1);
     RmKnn a = {};
     a.X = dQ; a.xok = dnode_valid; a.M = (int)N; a.Q = dQ; a.qok = dnode_valid; a.N = (int)N; a.d = (int)np; a.k = d.k;
     a.r2 = d.radius * d.radius; a.lo2 = a.r2 * 0x1.0p-40; a.self = 1;
-    a.nn_j = nn_j; a.nn_d2 = nn_d2; a.nn_cnt = nn_cnt;
+    a.nn_j = w.nn_j; a.nn_d2 = w.nn_d2; a.nn_cnt = w.nn_cnt;
     MJPL_TRY(roadmap_knn(e, a));
-    hipLaunchKernelGGL(k_rm_pair_keys, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const int32_t *)nn_j, (int64_t)M, d.k, none, ka);
+    hipLaunchKernelGGL(k_rm_pair_keys, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const int32_t *)w.nn_j, (int64_t)M, d.k, none, w.ka);
     HIP_TRY(hipGetLastError());
-    if (rocprim::radix_sort_keys(e->d_rm_tmp.p, tmp_bytes, ka, kb, M, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
-    hipLaunchKernelGGL(k_rm_unique, dim3(rm_grid(M + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)M, none, flag);
+    if (rocprim::radix_sort_keys(w.tmp, tmp_bytes, w.ka, w.kb, M, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
+    hipLaunchKernelGGL(k_rm_unique, dim3(rm_grid(M + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.kb, (int64_t)M, none, w.flag);
     HIP_TRY(hipGetLastError());
-    if (rocprim::exclusive_scan(e->d_rm_tmp.p, tmp_bytes, flag, pos, 0, M + 1, rocprim::plus<int>(), st) != hipSuccess)
+    if (rocprim::exclusive_scan(w.tmp, tmp_bytes, w.flag, w.pos, 0, M + 1, rocprim::plus<int>(), st) != hipSuccess)
       return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
-    hipLaunchKernelGGL(k_rm_compact, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)M, (const int *)flag,
-                       (const int *)pos, pairs);
+    hipLaunchKernelGGL(k_rm_compact, dim3(rm_grid(M)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.kb, (int64_t)M, (const int *)w.flag,
+                       (const int *)w.pos, w.pairs);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(&E32, pos + M, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&E32, w.pos + M, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const size_t E = (size_t)E32, nchunks = (E + chunk - 1) / chunk;
   e->roadmap_last_edges = (int64_t)E;
   if (E > 0) {
     std::vector<unsigned long long> longest(nchunks);
     {
-      RoadmapPhase ph(e, phases, 2);
+      PhaseScope ph(e, phases, 2);
       MJPL_TRY(e->d_rm_head.reserve(nchunks, 64));
       HIP_TRY(hipMemsetAsync(e->d_rm_head.p, 0, nchunks * sizeof(unsigned long long), st));
-      hipLaunchKernelGGL(k_rm_longest, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (int64_t)E, (int64_t)chunk, dQ,
+      hipLaunchKernelGGL(k_rm_longest, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.pairs, (int64_t)E, (int64_t)chunk, dQ,
                          (int)np, e->d_rm_head.p);
       HIP_TRY(hipGetLastError());
     }
@@ -3603,35 +3726,32 @@ int launch_roadmap_build(mjpl_engine *e, const mjpl_roadmap_desc &d, const doubl
     HIP_TRY(hipStreamSynchronize(st));
     for (size_t c = 0; c < nchunks; c++) {
       const size_t e0 = c * chunk, ne = std::min(chunk, E - e0);
-      double len;
-      memcpy(&len, &longest[c], sizeof(double));
-      // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
-      const bool long_edges = ne <= 4096 && len > 64.0 * d.step_dist;
-      RoadmapPhase ph(e, phases, 2);
-      hipLaunchKernelGGL(k_rm_edge_rows, dim3(rm_grid(ne * np)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (int64_t)e0, (int64_t)ne, dQ,
-                         (int)np, QA, QB);
+      const bool long_edges = few_long_edges((int64_t)ne, head_length(longest[c]), d.step_dist);
+      PhaseScope ph(e, phases, 2);
+      hipLaunchKernelGGL(k_rm_edge_rows, dim3(rm_grid(ne * np)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.pairs, (int64_t)e0, (int64_t)ne, dQ,
+                         (int)np, w.QA, w.QB);
       HIP_TRY(hipGetLastError());
-      MJPL_TRY(launch_edges(e, QA, QB, (int64_t)ne, d.step_dist, MJPL_AOS, 0, evalid + e0, nullptr, long_edges));
+      MJPL_TRY(launch_edges(e, w.QA, w.QB, (int64_t)ne, d.step_dist, MJPL_AOS, 0, w.evalid + e0, nullptr, long_edges));
       e->roadmap_last_chunks++;
     }
   }
   {
-    RoadmapPhase ph(e, phases, 3);
+    PhaseScope ph(e, phases, 3);
     if (E > 0) {
-      hipLaunchKernelGGL(k_rm_dir_keys, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)pairs, (const uint8_t *)evalid, (int64_t)E,
-                         none, ka);
+      hipLaunchKernelGGL(k_rm_dir_keys, dim3(rm_grid(E)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.pairs, (const uint8_t *)w.evalid, (int64_t)E,
+                         none, w.ka);
       HIP_TRY(hipGetLastError());
-      if (rocprim::radix_sort_keys(e->d_rm_tmp.p, tmp_bytes, ka, kb, 2 * E, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
+      if (rocprim::radix_sort_keys(w.tmp, tmp_bytes, w.ka, w.kb, 2 * E, 0, 53, st) != hipSuccess) return fail(MJPL_E_HIP, "rocprim::radix_sort_keys failed");
     }
-    hipLaunchKernelGGL(k_rm_row_off, dim3(rm_grid(N + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)(2 * E), (int)N, drow_off);
+    hipLaunchKernelGGL(k_rm_row_off, dim3(rm_grid(N + 1)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.kb, (int64_t)(2 * E), (int)N, drow_off);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_rm_csr, dim3(rm_grid(2 * M)), dim3(kRmBlock), 0, st, (const unsigned long long *)kb, (int64_t)(2 * E), (int64_t)(2 * M), none, dQ,
+    hipLaunchKernelGGL(k_rm_csr, dim3(rm_grid(2 * M)), dim3(kRmBlock), 0, st, (const unsigned long long *)w.kb, (int64_t)(2 * E), (int64_t)(2 * M), none, dQ,
                        (int)np, dadj, dw);
     HIP_TRY(hipGetLastError());
   }
   // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
   HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
-  return roadmap_sums(e, phases);
+  return phase_sums(e, phases, e->roadmap_last_ms);
 }
 
 // mjpl_roadmap_query* on device arrays: k_rm_finite on the ends, ONE launch_configs, the attachments, one synchronisation
@@ -3648,57 +3768,44 @@ int launch_roadmap_query(mjpl_engine *e, const mjpl_roadmap_query_desc &d, const
   HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->device));
   const bool in_lds = N <= (size_t)e->roadmap_lds_nodes && N * sizeof(double) <= (size_t)lds_max;
   const size_t fit = in_lds ? B : std::min(B, std::max<size_t>((size_t)e->roadmap_chunk_bytes / std::max<size_t>(N * sizeof(double), 1), 1));
-  const size_t d2_at = rm_pad(2 * B * np), dist_at = rm_pad(d2_at + 2 * B * C), qa_at = rm_pad(dist_at + (in_lds ? 0 : fit * N)),
-               qb_at = rm_pad(qa_at + emax * np);
-  MJPL_TRY(e->d_rm_f64.reserve(qb_at + emax * np));
-  MJPL_TRY(e->d_rm_i32.reserve(2 * B * C + 2 * B + B + 2 * (B + 1) + (B + 3) / 4 + (2 * B + 3) / 4 + (emax + 3) / 4));
   MJPL_TRY(e->d_rm_head.reserve(4, 64));
   size_t tmp_bytes = 0;
-  MJPL_TRY(roadmap_tmp(e, B + 1, &tmp_bytes));
-  HIP_TRY(hipMemsetAsync(dP, 0, B * (size_t)d.max_rows * np * sizeof(double), st));
+  MJPL_TRY(roadmap_space(st, B + 1, &tmp_bytes));
   RmQuery a = {};
+  RmQuerySpans w = {};
+  MJPL_TRY(carve_arena(e->d_rm_arena, [&](Carver &c) { carve_roadmap_query(c, B, C, emax, in_lds ? 0 : fit * N, np, tmp_bytes, &a, &w); }));
+  HIP_TRY(hipMemsetAsync(dP, 0, B * (size_t)d.max_rows * np * sizeof(double), st));
   a.Q = dQ; a.row_off = drow_off; a.adj = dadj; a.w = dw;
   a.N = (int)N; a.d = (int)np; a.C = d.connections; a.max_rows = d.max_rows;
   a.QI = dQI; a.QG = dQG; a.B = (int)B;
-  double *cfg = e->d_rm_f64.p, *att_d2 = cfg + d2_at;
-  a.att_d2 = att_d2; a.dist = in_lds ? nullptr : cfg + dist_at; a.QA = cfg + qa_at; a.QB = cfg + qb_at;
-  int *att_j = e->d_rm_i32.p, *att_cnt = att_j + 2 * B * C;
-  a.att_j = att_j; a.att_cnt = att_cnt; a.state = att_cnt + 2 * B; a.cnt = a.state + B; a.off = a.cnt + (B + 1);
-  uint8_t *fin = reinterpret_cast<uint8_t *>(a.off + (B + 1)), *cvalid = fin + (B + 3) / 4 * 4, *evalid = cvalid + (2 * B + 3) / 4 * 4;
-  a.fin = fin; a.cvalid = cvalid; a.valid = evalid;
   a.head = e->d_rm_head.p;
   a.P = dP; a.n_out = dn_out; a.status = dstatus; a.cost = dcost;
-  std::vector<std::array<int, 3>> phases;
-  unsigned long long head[3] = {0, 0, 0};
+  PhaseLog phases;
   {
-    RoadmapPhase ph(e, phases, 0);
-    HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
-    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(B)), dim3(kRmBlock), 0, st, dQI, dQG, (int)B, (int)np, cfg, fin);
+    PhaseScope ph(e, phases, 0);
+    HIP_TRY(hipMemsetAsync(a.head, 0, 3 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_rm_finite, dim3(rm_grid(B)), dim3(kRmBlock), 0, st, dQI, dQG, (int)B, (int)np, w.cfg, w.fin);
     HIP_TRY(hipGetLastError());
-    MJPL_TRY(launch_configs(e, cfg, (int64_t)(2 * B), MJPL_AOS, cvalid, nullptr));
+    MJPL_TRY(launch_configs(e, w.cfg, (int64_t)(2 * B), MJPL_AOS, w.cvalid, nullptr));
     RmKnn q = {};
-    q.X = cfg; q.xok = nullptr; q.M = (int)(2 * B); q.Q = dQ; q.qok = dnode_valid; q.N = (int)N; q.d = (int)np; q.k = d.connections;
+    q.X = w.cfg; q.xok = nullptr; q.M = (int)(2 * B); q.Q = dQ; q.qok = dnode_valid; q.N = (int)N; q.d = (int)np; q.k = d.connections;
     q.r2 = d.radius * d.radius; q.lo2 = 0.0; q.self = 0;
-    q.nn_j = att_j; q.nn_d2 = att_d2; q.nn_cnt = att_cnt;
+    q.nn_j = w.att_j; q.nn_d2 = w.att_d2; q.nn_cnt = w.att_cnt;
     MJPL_TRY(roadmap_knn(e, q));
     hipLaunchKernelGGL(k_rm_q_count, dim3(rm_grid(B + 1)), dim3(kRmBlock), 0, st, a);
     HIP_TRY(hipGetLastError());
-    if (rocprim::exclusive_scan(e->d_rm_tmp.p, tmp_bytes, a.cnt, a.off, 0, B + 1, rocprim::plus<int>(), st) != hipSuccess)
+    if (rocprim::exclusive_scan(w.tmp, tmp_bytes, a.cnt, a.off, 0, B + 1, rocprim::plus<int>(), st) != hipSuccess)
       return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
     hipLaunchKernelGGL(k_rm_q_gather, dim3((unsigned)((B + kRmBlock / 64 - 1) / (kRmBlock / 64))), dim3(kRmBlock), 0, st, a);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int64_t E = (int64_t)head[1];
+  RoundHead h;
+  MJPL_TRY(read_head(e, a.head, &h));
+  const int64_t E = h.edges;
   e->roadmap_last_edges = E;
   if (E > 0) {
-    double longest;
-    memcpy(&longest, &head[0], sizeof(double));
-    // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
-    const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
-    RoadmapPhase ph(e, phases, 1);
-    MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, evalid, nullptr, long_edges));
+    PhaseScope ph(e, phases, 1);
+    MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, w.evalid, nullptr, few_long_edges(E, h.longest, d.step_dist)));
   }
   // (a large graph: more waves per problem hide the adjacency's latency; a small one: more problems per CU)
   const unsigned block = N >= 4096 ? 1024 : kRmBlock;
@@ -3707,18 +3814,21 @@ int launch_roadmap_query(mjpl_engine *e, const mjpl_roadmap_query_desc &d, const
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rm_search<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (size_t b0 = 0; b0 < B; b0 += fit) {
     a.b0 = (int)b0; a.nb = (int)std::min(fit, B - b0);
-    RoadmapPhase ph(e, phases, 2);
+    PhaseScope ph(e, phases, 2);
     if (in_lds) hipLaunchKernelGGL(k_rm_search<true>, dim3((unsigned)a.nb), dim3(block), lds, st, a);
     else hipLaunchKernelGGL(k_rm_search<false>, dim3((unsigned)a.nb), dim3(block), 0, st, a);
     HIP_TRY(hipGetLastError());
     e->roadmap_last_chunks++;
   }
+  // (the header once more, for the searches' sweeps.  Not read_head: that synchronises right after its copy, and here the
+  //  status word's reset goes between the copy and the one synchronisation both wait for)
+  unsigned long long head[3] = {0, 0, 0};
   HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
   // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
   HIP_TRY(hipMemsetAsync(e->d_status, 0, sizeof(int), st));
   HIP_TRY(hipStreamSynchronize(st));
-  e->roadmap_last_sweeps = (int64_t)head[2];
-  return roadmap_sums(e, phases);
+  e->roadmap_last_sweeps = decode_head(head).live;
+  return phase_sums(e, phases, e->roadmap_last_ms);
 }
 
 }  // namespace
@@ -3948,12 +4058,9 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
   if (E == 0) return MJPL_OK;
   if (!QB || !valid) return fail(MJPL_E_ARG, "NULL pointer");
   const size_t qb = (size_t)E * e->qidx.size() * sizeof(double);
-  // A handful of LONG edges (path shortcutting, smooth_path: planning/utils.py:9-87) is better served by the two
-  // persistent kernels, which keep every 32nd exact waypoint as a checkpoint: the fused kernel rebuilds an undecided
-  // waypoint by the recurrence from the start of its edge (measured: 64 edges of 2 400 waypoints 3.9 vs 7.6 ms).  The
-  // rows are in host memory here, so a small batch can simply be looked at.
+  // (few_long_edges) The rows are in host memory here, so a small batch can simply be looked at.
   bool long_edges = false;
-  if (E <= 4096) {
+  if (E <= kFewEdges) {
     const int64_t np = (int64_t)e->qidx.size();
     double longest2 = 0;
     for (int64_t i = 0; i < E; i++) {
@@ -3964,7 +4071,7 @@ int mjpl_check_edges(mjpl_engine *e, const double *QA, const double *QB, int64_t
       }
       if (s > longest2) longest2 = s;  // (a NaN never compares greater: such an edge is reported by the kernels)
     }
-    long_edges = std::sqrt(longest2) > 64.0 * step_dist;
+    long_edges = few_long_edges(E, std::sqrt(longest2), step_dist);
   }
   int status = 0;
   const HostOut outs[] = {{valid, (size_t)E}, {first_bad, (size_t)E * sizeof(int32_t)}, {&status, sizeof(int), e->d_status}};
@@ -4277,7 +4384,7 @@ int mjpl_shortcut_paths_dev(mjpl_engine *e, const mjpl_shortcut_desc *d, const d
                             uint8_t *dkeep, int32_t *dn_out, double *dlength, int32_t *dstatus, int32_t *dproposed,
                             int32_t *daccepted) {
   int rc = check_shortcut_args(e, d, dW, wp_off, B, dkeep, dn_out, dstatus);
-  if (rc == MJPL_OK && B == 0) e->shortcut_last_chunks = 0;
+  if (rc == MJPL_OK && B == 0) shortcut_reset(e);
   if (rc != MJPL_OK || B == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
   return launch_shortcut(e, *d, dW, wp_off, B, dkeep, dn_out, dlength, dstatus, dproposed, daccepted);
@@ -4286,7 +4393,7 @@ int mjpl_shortcut_paths_dev(mjpl_engine *e, const mjpl_shortcut_desc *d, const d
 int mjpl_shortcut_paths(mjpl_engine *e, const mjpl_shortcut_desc *d, const double *W, const int64_t *wp_off, int64_t B, uint8_t *keep,
                         int32_t *n_out, double *length, int32_t *status, int32_t *proposed, int32_t *accepted) {
   int rc = check_shortcut_args(e, d, W, wp_off, B, keep, n_out, status);
-  if (rc == MJPL_OK && B == 0) e->shortcut_last_chunks = 0;
+  if (rc == MJPL_OK && B == 0) shortcut_reset(e);
   if (rc != MJPL_OK || B == 0) return rc;
   const size_t wb = (size_t)wp_off[B] * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
   const HostOut outs[] = {{keep, (size_t)wp_off[B]}, {n_out, ib}, {length, (size_t)B * sizeof(double)}, {status, ib}, {proposed, ib},
@@ -4303,7 +4410,7 @@ int mjpl_plan_paths_dev(mjpl_engine *e, const mjpl_plan_desc *d, const double *d
                         const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                         int32_t *dtree_nodes) {
   int rc = check_plan_args(e, d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
-  if (rc == MJPL_OK && B == 0) e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  if (rc == MJPL_OK && B == 0) plan_reset(e);
   if (rc != MJPL_OK || B == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
   return launch_plan(e, *d, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
@@ -4313,7 +4420,7 @@ int mjpl_plan_paths(mjpl_engine *e, const mjpl_plan_desc *d, const double *QI, c
                     const double *hi, double *P, int32_t *n_out, int32_t *status, int32_t *rounds_used, int32_t *edges,
                     int32_t *tree_nodes) {
   int rc = check_plan_args(e, d, QI, QG, B, lo, hi, P, n_out, status);
-  if (rc == MJPL_OK && B == 0) e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
+  if (rc == MJPL_OK && B == 0) plan_reset(e);
   if (rc != MJPL_OK || B == 0) return rc;
   const size_t qb = (size_t)B * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
   const HostOut outs[] = {{P, qb * ((size_t)d->rounds + 2)}, {n_out, ib}, {status, ib}, {rounds_used, ib}, {edges, ib}, {tree_nodes, 2 * ib}};
@@ -4878,18 +4985,28 @@ int check_cplan_args(const mjpl_pose *p, const mjpl_cplan_desc *d, int extend, c
 
 size_t cplan_lds(const mjpl_pose *p) { return pose_lds(p) + (size_t)kPoseBlock * sizeof(double) * ((size_t)p->nq + p->e->qidx.size()); }
 
+// carve_plan, and what the projection adds: the extension chains' links (X to a lane) and their counts, the bridge's
+// links (S), the ends as full rows.  The ends' verdicts are 4 nb bytes: the launcher splits them.
+void carve_cplan(Carver &c, size_t nb, size_t emax, size_t X, size_t S, size_t N, size_t np, size_t nq, size_t scan_bytes, CplanBatch *a,
+                 RoundSpans *s) {
+  const size_t L64 = kPlanLanes;
+  carve_plan(c, nb, emax, 4 * nb, N, np, scan_bytes, a, s);
+  a->cy = c.take<double>(nb * X * np * L64);
+  a->cl = c.take<double>(nb * S * np);
+  a->cfq = c.take<double>(2 * nb * nq);
+  a->cn = c.take<int>(nb * L64);
+  a->nlinks = c.take<int>(nb);
+}
+
 // mjpl_plan_paths_constrained* on device batches (lo, hi on the host), an extension a chain of up to `extend` steps.
-// Per chunk of problems whose workspace fits the
-// option "plan_chunk_bytes" (always at least one problem): k_cplan_init, ONE launch_configs and ONE k_pose_valid on the
-// ends, then per round propose, project, count -> one small copy and one synchronisation (the round's header) -> scan,
-// gather, ONE launch_edges -> commit, then k_cplan_finish.  A chunk whose problems are all retired ends its rounds; a
-// round without an edge launches no validation.
+// Per chunk of problems whose workspace fits the option "plan_chunk_bytes" (always at least one problem): k_cplan_init,
+// ONE launch_configs and ONE k_pose_valid on the ends, the chunk's rounds (run_rounds) -- a round proposes, projects
+// and counts -- then k_cplan_finish.
 int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, int extend, const double *dQI, const double *dQG, int64_t B,
                  const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus, int32_t *drounds_used, int32_t *dedges,
                  int32_t *dtree_nodes) {
   mjpl_engine *e = p->e;
-  e->plan_last_chunks = e->plan_last_rounds = e->plan_last_edges = 0;
-  e->plan_last_ms[0] = e->plan_last_ms[1] = e->plan_last_ms[2] = e->plan_last_ms[3] = 0.0;
+  plan_reset(e);
   if (cplan_lds(p) > 64 * 1024)
     return fail(MJPL_E_CAPACITY, "constrained planning: %d qpos + %d chain joints exceed the LDS budget", p->nq, p->nj);
   const hipStream_t st = e->stream;
@@ -4920,7 +5037,7 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, int extend, const doubl
                              2 * (np + nq) * sizeof(double) + 20 * sizeof(int);
   const size_t fit = std::max<size_t>((size_t)e->plan_chunk_bytes / per_problem, 1);
   const size_t chunk = std::min(fit, ((size_t)1 << 30) / per_edges);  // (edge offsets are ints)
-  std::vector<std::pair<int, int>> phases;
+  PhaseLog phases;
   CplanBatch a = {};
   a.QI = dQI; a.QG = dQG; a.box = e->d_pl_box.p; a.qbase = e->d_pl_box.p + 2 * np;
   a.qidx = e->d_pl_q.p; a.qinv = e->d_pl_q.p + np; a.pi = p->d_pi; a.pd = p->d_pd; a.nq = p->nq;
@@ -4930,80 +5047,37 @@ int launch_cplan(mjpl_pose *p, const mjpl_cplan_desc &d, int extend, const doubl
   a.head = e->d_pl_head.p;
   a.P = dP; a.n_out = dn_out; a.status = dstatus; a.rounds_used = drounds_used; a.edges = dedges; a.tree_nodes = dtree_nodes;
   for (int64_t b0 = 0; b0 < B; b0 += (int64_t)chunk) {
-    const size_t nb = std::min(chunk, (size_t)(B - b0)), emax = nb * per_edges;
-    // (the configuration and edge batches start on 256-byte boundaries, as the staged batches of mjpl_check_edges do)
-    const size_t ct_at = nb * 2 * N * np, cy_at = ct_at + nb * np * L64, cl_at = cy_at + nb * X * np * L64,
-                 cfg_at = (cl_at + nb * S * np + 31) / 32 * 32, cfq_at = (cfg_at + 2 * nb * np + 31) / 32 * 32,
-                 qa_at = (cfq_at + 2 * nb * nq + 31) / 32 * 32, qb_at = (qa_at + emax * np + 31) / 32 * 32;
-    MJPL_TRY(e->d_pl_f64.reserve(qb_at + emax * np));
-    const size_t ints = nb * 2 * N + 2 * nb * L64 + 2 * nb + 5 * nb + 3 * nb + 2 * nb + 2 * (nb + 1);
-    MJPL_TRY(e->d_pl_i32.reserve(ints + (std::max(emax, 4 * nb) + 3) / 4));
-    size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-      return fail(MJPL_E_HIP, "rocprim::exclusive_scan: no size for %zu counts", nb + 1);
-    MJPL_TRY(e->d_pl_tmp.reserve(std::max<size_t>(tmp_bytes, 1), 4096));  // (never null: a null space asks rocPRIM for the size)
+    const size_t nb = std::min(chunk, (size_t)(B - b0));
+    size_t scan_bytes = 0;
+    MJPL_TRY(scan_space(st, nb + 1, &scan_bytes));
+    RoundSpans s = {};
+    MJPL_TRY(carve_arena(e->d_pl_arena, [&](Carver &c) { carve_cplan(c, nb, nb * per_edges, X, S, N, np, nq, scan_bytes, &a, &s); }));
     a.b0 = (int)b0; a.nb = (int)nb;
-    a.T = e->d_pl_f64.p; a.ct = a.T + ct_at; a.cy = a.T + cy_at; a.cl = a.T + cl_at; a.cfg = a.T + cfg_at; a.cfq = a.T + cfq_at;
-    a.QA = a.T + qa_at; a.QB = a.T + qb_at;
-    a.par = e->d_pl_i32.p; a.ck = a.par + nb * 2 * N; a.cn = a.ck + nb * L64; a.n = a.cn + nb * L64; a.state = a.n + 2 * nb;
-    a.gained = a.state + nb; a.rused = a.gained + nb; a.nedges = a.rused + nb; a.nlinks = a.nedges + nb; a.conn = a.nlinks + nb;
-    a.jn = a.conn + 3 * nb; a.cnt = a.jn + 2 * nb; a.off = a.cnt + (nb + 1);
-    // the ends' verdicts first (configurations, then poses), every round's after
-    uint8_t *dvalid = reinterpret_cast<uint8_t *>(a.off + (nb + 1));
-    a.cvalid = dvalid; a.pvalid = dvalid + 2 * nb; a.valid = dvalid;
+    uint8_t *const pose_valid = s.valid + 2 * nb;  // the ends' verdicts: the configurations' first, then the poses'
+    a.pvalid = pose_valid;
     const dim3 grid((unsigned)((nb + kPlanWaves - 1) / kPlanWaves)), block(64 * kPlanWaves);
     const int chain_blocks = (int)((nb + kPoseBlock - 1) / kPoseBlock);
     const dim3 pgrid((unsigned)(chain_blocks + (nb * K + kPoseBlock - 1) / kPoseBlock));
-    hipLaunchKernelGGL(k_cplan_init, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, dvalid, nullptr));
-    MJPL_TRY(mjpl_pose_valid_dev(p, a.cfq, (int64_t)(2 * nb), dvalid + 2 * nb, nullptr, nullptr));
-    for (int r = 0; r < d.rounds; r++) {
-      a.round = r;
-      unsigned long long head[3] = {0, 0, 0};
-      {
-        ShortcutPhase ph(e, phases, 0);
-        HIP_TRY(hipMemsetAsync(a.head, 0, sizeof(head), st));
-        hipLaunchKernelGGL(k_cplan_propose, grid, block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-      }
-      {
-        ShortcutPhase ph(e, phases, 3);
-        hipLaunchKernelGGL(k_cplan_project, pgrid, dim3(kPoseBlock), cplan_lds(p), st, a, chain_blocks);
-        HIP_TRY(hipGetLastError());
-      }
-      {
-        ShortcutPhase ph(e, phases, 0);
-        hipLaunchKernelGGL(k_cplan_count, grid, block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-      }
-      HIP_TRY(hipMemcpyAsync(head, a.head, sizeof(head), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (head[2] == 0) break;  // every problem of the chunk is retired
-      e->plan_last_rounds++;
-      const int64_t E = (int64_t)head[1];
-      if (E > 0) {
-        {
-          ShortcutPhase ph(e, phases, 0);
-          if (rocprim::exclusive_scan(e->d_pl_tmp.p, tmp_bytes, a.cnt, a.off, 0, nb + 1, rocprim::plus<int>(), st) != hipSuccess)
-            return fail(MJPL_E_HIP, "rocprim::exclusive_scan failed");
-          hipLaunchKernelGGL(k_cplan_gather, grid, block, 0, st, a);
-          HIP_TRY(hipGetLastError());
-        }
-        double longest;
-        memcpy(&longest, &head[0], sizeof(double));
-        // (the rule of mjpl_check_edges: a few long edges go to the kernels with checkpoints)
-        const bool long_edges = E <= 4096 && longest > 64.0 * d.step_dist;
-        ShortcutPhase ph(e, phases, 1);
-        MJPL_TRY(launch_edges(e, a.QA, a.QB, E, d.step_dist, MJPL_AOS, 0, dvalid, nullptr, long_edges));
-        e->plan_last_edges += E;
-      }
-      ShortcutPhase ph(e, phases, 2);
-      hipLaunchKernelGGL(k_cplan_commit, grid, block, 0, st, a);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_cplan_finish, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
+    MJPL_TRY(launch_checked(st, k_cplan_init, grid, block, 0, a));
+    MJPL_TRY(launch_configs(e, a.cfg, (int64_t)(2 * nb), MJPL_AOS, s.valid, nullptr));
+    MJPL_TRY(mjpl_pose_valid_dev(p, a.cfq, (int64_t)(2 * nb), pose_valid, nullptr, nullptr));
+    MJPL_TRY(run_rounds(
+        e, phases, s, 0, d.rounds, d.step_dist, &e->plan_last_rounds, &e->plan_last_edges,
+        [&](int r) {
+          a.round = r;
+          return launch_checked(st, k_cplan_propose, grid, block, 0, a);
+        },
+        [&](int) {
+          {
+            PhaseScope ph(e, phases, 3);
+            MJPL_TRY(launch_checked(st, k_cplan_project, pgrid, dim3(kPoseBlock), cplan_lds(p), a, chain_blocks));
+          }
+          PhaseScope ph(e, phases, 0);
+          return launch_checked(st, k_cplan_count, grid, block, 0, a);
+        },
+        [&] { return launch_checked(st, k_cplan_gather, grid, block, 0, a); },
+        [&](int) { return launch_checked(st, k_cplan_commit, grid, block, 0, a); }));
+    MJPL_TRY(launch_checked(st, k_cplan_finish, grid, block, 0, a));
     e->plan_last_chunks++;
   }
   // an edge the edge kernels refuse counts as invalid here: the pipeline's status word is not this call's to report
@@ -5016,7 +5090,7 @@ int mjpl_plan_paths_constrained_ext_dev(mjpl_pose *p, const mjpl_cplan_desc *d, 
                                         int64_t B, const double *lo, const double *hi, double *dP, int32_t *dn_out, int32_t *dstatus,
                                         int32_t *drounds_used, int32_t *dedges, int32_t *dtree_nodes) {
   int rc = check_cplan_args(p, d, extend, dQI, dQG, B, lo, hi, dP, dn_out, dstatus);
-  if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
+  if (rc == MJPL_OK && B == 0) plan_reset(p->e);
   if (rc != MJPL_OK || B == 0) return rc;
   HIP_TRY(hipSetDevice(p->e->device));
   return launch_cplan(p, *d, extend, dQI, dQG, B, lo, hi, dP, dn_out, dstatus, drounds_used, dedges, dtree_nodes);
@@ -5026,7 +5100,7 @@ int mjpl_plan_paths_constrained_ext(mjpl_pose *p, const mjpl_cplan_desc *d, int3
                                     int64_t B, const double *lo, const double *hi, double *P, int32_t *n_out, int32_t *status,
                                     int32_t *rounds_used, int32_t *edges, int32_t *tree_nodes) {
   int rc = check_cplan_args(p, d, extend, QI, QG, B, lo, hi, P, n_out, status);
-  if (rc == MJPL_OK && B == 0) p->e->plan_last_chunks = p->e->plan_last_rounds = p->e->plan_last_edges = 0;
+  if (rc == MJPL_OK && B == 0) plan_reset(p->e);
   if (rc != MJPL_OK || B == 0) return rc;
   mjpl_engine *e = p->e;
   const size_t qb = (size_t)B * e->qidx.size() * sizeof(double), ib = (size_t)B * sizeof(int32_t);
