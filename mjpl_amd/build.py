@@ -45,6 +45,11 @@ def hipcc_flags() -> list[str]:
 OVERLAY_HEADER = os.path.join(CSRC, "mjpl_overlay.h")
 
 
+# The fused binary32 pose helpers a generated translation unit includes (specialise.Options.pose_fma / .sincos): not
+# stamped either -- no layout, table or kernel of libmjpl_hip.so is in it.
+POSE_HEADER = os.path.join(CSRC, "mjpl_pose_f32.h")
+
+
 def overlay_flags() -> list[str]:
     return ["-include", OVERLAY_HEADER]
 
@@ -76,6 +81,27 @@ def hipcc() -> str:
     if not os.path.exists(exe):
         raise RuntimeError("hipcc not found: the gfx950 library cannot be built on this machine")
     return exe
+
+
+POSE_PROBE_LIB = os.path.join(CSRC, "libmjpl_pose_probe.so")
+POSE_PROBE_EXE = os.path.join(CSRC, "mjpl_pose_probe")
+
+
+def build_pose_probe(force: bool = False) -> tuple[str, str]:
+    """mjpl_pose_probe.hip twice, with the kernels' floating-point flags: the library (the binary32 pose helpers of
+    mjpl_pose_f32.h over arrays, host and device) and the host-only sweep program of sincos_half_f32 (tests only)."""
+    src = os.path.join(CSRC, "mjpl_pose_probe.hip")
+    for target, extra in ((POSE_PROBE_LIB, []), (POSE_PROBE_EXE, ["-DMJPL_PROBE_MAIN", "--offload-host-only", "-pthread"])):
+        if force or _stale(target):
+            flags = [f for f in hipcc_flags() if not (extra and f in ("-shared", "-fPIC"))]
+            tmp = f"{target}.tmp{os.getpid()}"
+            try:
+                subprocess.run([hipcc(), *flags, *extra, "-o", tmp, src], check=True)
+                os.replace(tmp, target)
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+    return POSE_PROBE_LIB, POSE_PROBE_EXE
 
 
 def build_hip(force: bool = False, lds_tables: bool = False, verbose: bool = False) -> str:

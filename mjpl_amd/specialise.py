@@ -49,6 +49,9 @@ SPEC_DIR = os.path.join(_build.CSRC, "spec")
 # under SPEC_DIR: a few libraries once more WITHOUT build.codegen_flags' option (build(uniform_regions=False)), compiled by
 # __graft_entry__.build() and compared bit for bit by tests/test_gpu_uniform_regions.py
 STRUCTURIZED_SUBDIR = "structurized"
+# ... and once more with the pose arithmetic as plain expressions and sincosf (build(opts=Options.for_build()._replace(
+# pose_fma=False, sincos=False))): the text without the helpers of mjpl_pose_f32.h, compared by tests/test_gpu_pose_fma.py
+UNFUSED_SUBDIR = "unfused"
 
 
 class ProgramInfo(C.Structure):
@@ -157,6 +160,39 @@ def quat_mul_const_right(a, b) -> list[str]:
             lin([(b[3], a[0]), (b[2], a[1]), (-b[1], a[2]), (b[0], a[3])])]
 
 
+def flin(terms, base: str | None = None) -> str:
+    """lin() with fused multiply-adds: the sum of coef * expr (onto `base`, if given) as one chain of __builtin_fmaf in the
+    order of `terms` -- the association of mjpl::pose_mul_quat and its kin (mjpl_pose_f32.h) -- with exact-zero terms
+    dropped and exact +-1 coefficients folded into an addition."""
+    acc = base
+    for c, e in terms:
+        c = float(np.float32(c))
+        if c == 0.0:
+            continue
+        if acc is None:
+            acc = e if c == 1.0 else (f"(-{e})" if c == -1.0 else f"({lit(c)} * {e})")
+        elif c == 1.0:
+            acc = f"({acc} + {e})"
+        elif c == -1.0:
+            acc = f"({acc} - {e})"
+        else:
+            acc = f"__builtin_fmaf({lit(c)}, {e}, {acc})"
+    return "0.0f" if acc is None else acc
+
+
+def _general(coefs) -> bool:
+    """No coefficient folds (none is an exact 0 or +-1 in binary32): the statement is a call of the header's helper."""
+    return all(float(np.float32(c)) not in (0.0, 1.0, -1.0) for c in coefs)
+
+
+def quat_mul_const_right_fused(a, b) -> list[str]:
+    """quat_mul_const_right as chains of fused multiply-adds: term for term mjpl::pose_mul_quat."""
+    return [flin([(b[0], a[0]), (-b[1], a[1]), (-b[2], a[2]), (-b[3], a[3])]),
+            flin([(b[1], a[0]), (b[0], a[1]), (b[3], a[2]), (-b[2], a[3])]),
+            flin([(b[2], a[0]), (-b[3], a[1]), (b[0], a[2]), (b[1], a[3])]),
+            flin([(b[3], a[0]), (b[2], a[1]), (-b[1], a[2]), (b[0], a[3])])]
+
+
 def quat_mul_np(a, b):
     return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
                      a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
@@ -196,17 +232,32 @@ class Options(NamedTuple):
     f64: bool = False          # MJPL_SPEC_F64=1: libraries carry the generated float64 check (generate_full_exact)
     f64_inline: bool = False   # MJPL_SPEC_F64_INLINE=1: ... inlined, for tools/f64_inline_probe.py
     mbox_waves: int = 2        # MJPL_SPEC_MBOX_WAVES: waves per SIMD the kernels of a model with moving boxes are built for (A/B builds)
+    # The two switches of the fused pose text (mjpl_pose_f32.h).  Off, the generator writes the plain expressions it always
+    # wrote -- the text tests/golden/generated_source_digests.json records; build() turns pose_fma on (for_build), so every
+    # library it compiles on its own carries the fused arithmetic; MJPL_SPEC_POSE_FMA=0 / MJPL_SPEC_SINCOS=1 there, or
+    # build(opts=...), give the comparison libraries of the A/B.
+    pose_fma: bool = False     # MJPL_SPEC_POSE_FMA: the pose arithmetic as calls of mjpl::pose_* (fused multiply-adds in a fixed order)
+    sincos: bool = False       # MJPL_SPEC_SINCOS: a hinge's half angle through mjpl::sincos_half_f32, not sincosf
 
     @classmethod
     def from_env(cls) -> "Options":
         e = os.environ.get
         return cls(e("MJPL_SPEC_CULL", "expanded"), e("MJPL_SPEC_CERT", "0") == "1", e("MJPL_SPEC_F64") == "1",
-                   e("MJPL_SPEC_F64_INLINE") == "1", max(1, min(3, int(e("MJPL_SPEC_MBOX_WAVES", "2")))))
+                   e("MJPL_SPEC_F64_INLINE") == "1", max(1, min(3, int(e("MJPL_SPEC_MBOX_WAVES", "2")))),
+                   e("MJPL_SPEC_POSE_FMA") == "1", e("MJPL_SPEC_SINCOS") == "1")
+
+    @classmethod
+    def for_build(cls) -> "Options":
+        """What build() generates with when its caller passes no switches: the environment's, with the fused pose arithmetic
+        on unless the environment says 0.  sincos stays an opt-in (MJPL_SPEC_SINCOS=1): measured alone it does not pay -- its
+        665 fewer vector instructions cost four more spilled registers (profiles/README.md, r12)."""
+        return cls.from_env()._replace(pose_fma=os.environ.get("MJPL_SPEC_POSE_FMA", "1") != "0")
 
 
 class _Gen:
-    def __init__(self):
+    def __init__(self, opts: Options = Options()):
         self.lines: list[str] = []
+        self.pose_fma, self.sincos = opts.pose_fma, opts.sincos
 
     def w(self, s="", ind=3):
         self.lines.append("  " * ind + s)
@@ -214,6 +265,18 @@ class _Gen:
     # rot_vec_quat(res, const vec, quat expr): v + 2 * cross(q_xyz, q_w v + cross(q_xyz, v))
     def rot_vec_quat(self, dst, vec, qn):
         v = [float(x) for x in vec]
+        if self.pose_fma and _general(v):
+            self.w(f"{{ const float v_[3] = {{{lit(v[0])}, {lit(v[1])}, {lit(v[2])}}}, q_[4] = {{{qn[0]}, {qn[1]}, {qn[2]}, {qn[3]}}};")
+            self.w(f"  float r_[3]; mjpl::pose_rot_vec(r_, v_, q_); {dst}0 = r_[0]; {dst}1 = r_[1]; {dst}2 = r_[2]; }}")
+            return
+        if self.pose_fma:  # (some component folds: the chains of mjpl::pose_rot_vec with those terms dropped)
+            self.w(f"{{ const float t0_ = {flin([(v[0], qn[0]), (v[2], qn[2]), (-v[1], qn[3])])};")
+            self.w(f"  const float t1_ = {flin([(v[1], qn[0]), (v[0], qn[3]), (-v[2], qn[1])])};")
+            self.w(f"  const float t2_ = {flin([(v[2], qn[0]), (v[1], qn[1]), (-v[0], qn[2])])};")
+            self.w(f"  {dst}0 = __builtin_fmaf(2.0f, __builtin_fmaf({qn[2]}, t2_, -({qn[3]} * t1_)), {lit(v[0])});")
+            self.w(f"  {dst}1 = __builtin_fmaf(2.0f, __builtin_fmaf({qn[3]}, t0_, -({qn[1]} * t2_)), {lit(v[1])});")
+            self.w(f"  {dst}2 = __builtin_fmaf(2.0f, __builtin_fmaf({qn[1]}, t1_, -({qn[2]} * t0_)), {lit(v[2])}); }}")
+            return
         self.w(f"{{ const float t0_ = {lin([(v[0], qn[0]), (v[2], qn[2]), (-v[1], qn[3])])};")
         self.w(f"  const float t1_ = {lin([(v[1], qn[0]), (v[0], qn[3]), (-v[2], qn[1])])};")
         self.w(f"  const float t2_ = {lin([(v[2], qn[0]), (v[1], qn[1]), (-v[0], qn[2])])};")
@@ -432,6 +495,31 @@ def _certificate(st: _Stage, dp, anc) -> tuple:
 
 
 # ----------------------------------------------------------------------------- emitters (text from analysed data)
+def _lin3(g: _Gen, base: str, c, r: int) -> str:
+    """base + c . (row r of the rotation matrix R0 .. R8), c literal: a body's origin, a geom's centre."""
+    terms = [(c[k], f"R{3 * r + k}") for k in range(3)]
+    if not g.pose_fma:
+        return f"{base} + {lin(terms)}"
+    if _general(c):
+        return f"mjpl::pose_lin3({base}, {', '.join(f'{lit(ck)}, {e}' for ck, e in terms)})"
+    left = [t for t in terms if float(np.float32(t[0])) != 0.0]
+    if len(left) <= 1:  # (one multiply-add onto the world coordinate: its one rounding at that magnitude)
+        return flin(left, base)
+    return f"({base} + {flin(left)})"  # (as pose_lin3: the products summed first, the world coordinate added once)
+
+
+def _emit_quat_mul_const(g: _Gen, typ: str, dst: str, b):
+    """`typ` {dst}0 .. {dst}3 = (q0, q1, q2, q3) (x) the literal quaternion b."""
+    qn = ["q0", "q1", "q2", "q3"]
+    if g.pose_fma and _general(b):
+        g.w(f"float {dst}0, {dst}1, {dst}2, {dst}3;")
+        g.w(f"{{ const float a_[4] = {{q0, q1, q2, q3}}, b_[4] = {{{', '.join(lit(x) for x in b)}}}; float r_[4];")
+        g.w(f"  mjpl::pose_mul_quat(r_, a_, b_); {dst}0 = r_[0]; {dst}1 = r_[1]; {dst}2 = r_[2]; {dst}3 = r_[3]; }}")
+        return
+    e = quat_mul_const_right_fused(qn, b) if g.pose_fma else quat_mul_const_right(qn, b)
+    g.w(f"{typ} {dst}0 = {e[0]}, {dst}1 = {e[1]}, {dst}2 = {e[2]}, {dst}3 = {e[3]};")
+
+
 def _emit_body_fk(g: _Gen, body, dp):
     """Forward kinematics of one body op: the parent's pose, the joints, normalisation, range check, save."""
     w = g.w
@@ -450,9 +538,8 @@ def _emit_body_fk(g: _Gen, body, dp):
             w("  MJPL_SPEC_QUAT2MAT(); }")
         bp, bq = bd[0:3], bd[3:7]
         for r in range(3):
-            w(f"float np{r} = p{r} + {lin([(bp[0], f'R{3 * r}'), (bp[1], f'R{3 * r + 1}'), (bp[2], f'R{3 * r + 2}')])};")
-        e = quat_mul_const_right(["q0", "q1", "q2", "q3"], bq)
-        w(f"float nq0 = {e[0]}, nq1 = {e[1]}, nq2 = {e[2]}, nq3 = {e[3]};")
+            w(f"float np{r} = {_lin3(g, f'p{r}', bp, r)};")
+        _emit_quat_mul_const(g, "float", "nq", bq)
     for jtype, qsrc, jflags, jdoff in body.joints:
         jd = dp[jdoff:]
         axis, jpos, qpos0, qconst = jd[0:3], jd[3:6], float(jd[6]), float(jd[7])
@@ -464,44 +551,71 @@ def _emit_body_fk(g: _Gen, body, dp):
         if jtype == JT_SLIDE:
             w("  float xa0, xa1, xa2;")
             g.rot_vec_quat("xa", axis, nqn)
-            w("  np0 += xa0 * dq; np1 += xa1 * dq; np2 += xa2 * dq; }")
+            if g.pose_fma:
+                w("  np0 = __builtin_fmaf(xa0, dq, np0); np1 = __builtin_fmaf(xa1, dq, np1); np2 = __builtin_fmaf(xa2, dq, np2); }")
+            else:
+                w("  np0 += xa0 * dq; np1 += xa1 * dq; np2 += xa2 * dq; }")
         else:
             if jflags & JF_POS_NONZERO:
                 w("  float an0, an1, an2;")
                 g.rot_vec_quat("an", jpos, nqn)
                 w("  an0 += np0; an1 += np1; an2 += np2;")
             w("  far = far || !(fabsf(dq) <= maxangle);  // binary32(q) is off by eps |q|")
-            w("  float sn, cs; sincosf(dq * 0.5f, &sn, &cs);")
+            w(f"  float sn, cs; {'mjpl::sincos_half_f32' if g.sincos else 'sincosf'}(dq * 0.5f, &sn, &cs);")
             # nq = nq (x) (cs, ax sn, ay sn, az sn)
             a = [float(np.float32(x)) for x in axis]
-            sx = [f"{lit(a[k])} * sn" if a[k] not in (0.0, 1.0, -1.0) else ("sn" if a[k] == 1.0 else ("(-sn)" if a[k] == -1.0 else None))
-                  for k in range(3)]
+            if g.pose_fma and _general(a):
+                w(f"  {{ const float ax_[3] = {{{lit(a[0])}, {lit(a[1])}, {lit(a[2])}}}; float h_[4] = {{nq0, nq1, nq2, nq3}};")
+                w("    mjpl::pose_hinge(h_, ax_, sn, cs); nq0 = h_[0]; nq1 = h_[1]; nq2 = h_[2]; nq3 = h_[3]; }")
+            elif g.pose_fma:  # (some component of the axis folds: the chains of mjpl::pose_hinge with those terms dropped)
+                sx = [None if a[k] == 0.0 else ("sn" if a[k] == 1.0 else ("(-sn)" if a[k] == -1.0 else f"({lit(a[k])} * sn)")) for k in range(3)]
+                rows = [[(1, "nq0", "cs"), (-1, "nq1", sx[0]), (-1, "nq2", sx[1]), (-1, "nq3", sx[2])],
+                        [(1, "nq0", sx[0]), (1, "nq1", "cs"), (1, "nq2", sx[2]), (-1, "nq3", sx[1])],
+                        [(1, "nq0", sx[1]), (-1, "nq1", sx[2]), (1, "nq2", "cs"), (1, "nq3", sx[0])],
+                        [(1, "nq0", sx[2]), (1, "nq1", sx[1]), (-1, "nq2", sx[0]), (1, "nq3", "cs")]]
+                exprs = []
+                for row in rows:
+                    acc = None
+                    for sign, left, right in row:
+                        if right is None:
+                            continue
+                        left = left if sign > 0 else f"-{left}"
+                        acc = f"{left} * {right}" if acc is None else f"__builtin_fmaf({left}, {right}, {acc})"
+                    exprs.append(acc)
+                w(f"  const float t0 = {exprs[0]}, t1 = {exprs[1]}, t2 = {exprs[2]}, t3 = {exprs[3]};")
+                w("  nq0 = t0; nq1 = t1; nq2 = t2; nq3 = t3;")
+            else:
+                sx = [f"{lit(a[k])} * sn" if a[k] not in (0.0, 1.0, -1.0) else ("sn" if a[k] == 1.0 else ("(-sn)" if a[k] == -1.0 else None))
+                      for k in range(3)]
 
-            def term(sign, left, right):
-                return None if right is None else (sign, f"{left} * {right}")
+                def term(sign, left, right):
+                    return None if right is None else (sign, f"{left} * {right}")
 
-            comps = [
-                [("+", "nq0 * cs"), term("-", "nq1", sx[0]), term("-", "nq2", sx[1]), term("-", "nq3", sx[2])],
-                [term("+", "nq0", sx[0]), ("+", "nq1 * cs"), term("+", "nq2", sx[2]), term("-", "nq3", sx[1])],
-                [term("+", "nq0", sx[1]), term("-", "nq1", sx[2]), ("+", "nq2 * cs"), term("+", "nq3", sx[0])],
-                [term("+", "nq0", sx[2]), term("+", "nq1", sx[1]), term("-", "nq2", sx[0]), ("+", "nq3 * cs")],
-            ]
-            exprs = []
-            for comp in comps:
-                ts = [t for t in comp if t is not None]
-                out = ("-" if ts[0][0] == "-" else "") + ts[0][1]
-                for sgn, ex in ts[1:]:
-                    out += f" {sgn} {ex}"
-                exprs.append(out)
-            w(f"  const float t0 = {exprs[0]}, t1 = {exprs[1]}, t2 = {exprs[2]}, t3 = {exprs[3]};")
-            w("  nq0 = t0; nq1 = t1; nq2 = t2; nq3 = t3;")
+                comps = [
+                    [("+", "nq0 * cs"), term("-", "nq1", sx[0]), term("-", "nq2", sx[1]), term("-", "nq3", sx[2])],
+                    [term("+", "nq0", sx[0]), ("+", "nq1 * cs"), term("+", "nq2", sx[2]), term("-", "nq3", sx[1])],
+                    [term("+", "nq0", sx[1]), term("-", "nq1", sx[2]), ("+", "nq2 * cs"), term("+", "nq3", sx[0])],
+                    [term("+", "nq0", sx[2]), term("+", "nq1", sx[1]), term("-", "nq2", sx[0]), ("+", "nq3 * cs")],
+                ]
+                exprs = []
+                for comp in comps:
+                    ts = [t for t in comp if t is not None]
+                    out = ("-" if ts[0][0] == "-" else "") + ts[0][1]
+                    for sgn, ex in ts[1:]:
+                        out += f" {sgn} {ex}"
+                    exprs.append(out)
+                w(f"  const float t0 = {exprs[0]}, t1 = {exprs[1]}, t2 = {exprs[2]}, t3 = {exprs[3]};")
+                w("  nq0 = t0; nq1 = t1; nq2 = t2; nq3 = t3;")
             if jflags & JF_POS_NONZERO:
                 w("  float vv0, vv1, vv2;")
                 g.rot_vec_quat("vv", jpos, nqn)
                 w("  np0 = an0 - vv0; np1 = an1 - vv1; np2 = an2 - vv2;")
             w("}")
     # ---- normalise, rotation matrix, range check, save
-    w("{ const float inv = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(nq0 * nq0 + nq1 * nq1 + nq2 * nq2 + nq3 * nq3));")
+    if g.pose_fma:
+        w("{ const float inv = mjpl::pose_inv_norm(nq0, nq1, nq2, nq3);")
+    else:
+        w("{ const float inv = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(nq0 * nq0 + nq1 * nq1 + nq2 * nq2 + nq3 * nq3));")
     w("  q0 = nq0 * inv; q1 = nq1 * inv; q2 = nq2 * inv; q3 = nq3 * inv; }")
     w("p0 = np0; p1 = np1; p2 = np2;")
     w("MJPL_SPEC_QUAT2MAT();")
@@ -521,17 +635,23 @@ def _emit_geom_pose(g: _Gen, st: _Stage, dp):
         w("cx = p0; cy = p1; cz = p2;")
     else:
         for r, nm in enumerate(("cx", "cy", "cz")):
-            w(f"{nm} = p{r} + {lin([(lpos[0], f'R{3 * r}'), (lpos[1], f'R{3 * r + 1}'), (lpos[2], f'R{3 * r + 2}')])};")
+            w(f"{nm} = {_lin3(g, f'p{r}', lpos, r)};")
     if st.geom.flags & GF_SAMEROT:
         w("zx = R2; zy = R5; zz = R8;")
         if st.curbox:
             w("xx = R0; xy = R3; xz = R6; yx = R1; yy = R4; yz = R7;")
     else:
-        e = quat_mul_const_right(["q0", "q1", "q2", "q3"], lquat)
-        w(f"{{ const float g0 = {e[0]}, g1 = {e[1]}, g2 = {e[2]}, g3 = {e[3]};")
+        if g.pose_fma:
+            w("{")
+            _emit_quat_mul_const(g, "const float", "g", lquat)
+        else:
+            e = quat_mul_const_right(["q0", "q1", "q2", "q3"], lquat)
+            w(f"{{ const float g0 = {e[0]}, g1 = {e[1]}, g2 = {e[2]}, g3 = {e[3]};")
         if st.curbox:  # the whole frame, by the interpreter's own routine (same binary32 values)
             w("  const float gq_[4] = {g0, g1, g2, g3}; float mm_[9]; mjpl::quat2mat(mm_, gq_);")
             w("  zx = mm_[2]; zy = mm_[5]; zz = mm_[8]; xx = mm_[0]; xy = mm_[3]; xz = mm_[6]; yx = mm_[1]; yy = mm_[4]; yz = mm_[7]; }")
+        elif g.pose_fma:
+            w("  float z_[3]; mjpl::pose_quat2zaxis(z_, g0, g1, g2, g3); zx = z_[0]; zy = z_[1]; zz = z_[2]; }")
         else:
             w("  zx = 2.0f * (g1 * g3 + g0 * g2); zy = 2.0f * (g2 * g3 - g0 * g1); zz = g0 * g0 - g1 * g1 - g2 * g2 + g3 * g3; }")
 
@@ -577,12 +697,17 @@ def _emit_culls(g: _Gen, st: _Stage, prog, fp, cull_form: str, generic: bool, ce
 
 
 # the fixed macros of every generated check
-_MACROS = r"""#define MJPL_SPEC_QUAT2MAT() \
+_QUAT2MAT = r"""#define MJPL_SPEC_QUAT2MAT() \
+  do { float m_[9]; mjpl::pose_quat2mat(m_, q0, q1, q2, q3); R0 = m_[0]; R1 = m_[1]; R2 = m_[2]; R3 = m_[3]; R4 = m_[4]; \
+       R5 = m_[5]; R6 = m_[6]; R7 = m_[7]; R8 = m_[8]; } while (0)
+"""
+_QUAT2MAT_PLAIN = r"""#define MJPL_SPEC_QUAT2MAT() \
   do { R0 = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; R4 = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3; \
        R8 = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3; R1 = 2.0f * (q1 * q2 - q0 * q3); R2 = 2.0f * (q1 * q3 + q0 * q2); \
        R3 = 2.0f * (q1 * q2 + q0 * q3); R5 = 2.0f * (q2 * q3 - q0 * q1); R6 = 2.0f * (q1 * q3 - q0 * q2); \
        R7 = 2.0f * (q2 * q3 + q0 * q1); } while (0)
-typedef float spec_v2f __attribute__((ext_vector_type(2)));
+"""
+_MACROS = r"""typedef float spec_v2f __attribute__((ext_vector_type(2)));
 // (a scalar branch around the two v_writelane -- most culls pass for no lane of the wave -- measured
 //  3 % SLOWER than parking unconditionally: 213 more branches per configuration)
 #define MJPL_SPEC_HIT(k, pass) \
@@ -661,7 +786,7 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
     # emitted), the geom's pose, its culls
     text, nbody_done = [], 0
     for st, (_, cert_lines, _) in zip(stages, cert):
-        g = _Gen()
+        g = _Gen(opts)
         for body in prog.bodies[nbody_done: st.geom.body + 1]:
             g.lines.append("{")
             _emit_body_fk(g, body, dp)
@@ -670,7 +795,7 @@ def _generate(ip, fp, dp, info, cull_form: str | None = None, generic: bool = Fa
         _emit_geom_pose(g, st, dp)
         _emit_culls(g, st, prog, fp, cull_form, generic, cert_lines if cert_ok else None)
         text.append(g.lines)
-    return _emit_spec(prog, fp, info, stages, text, generic, cert_ok)
+    return _emit_spec(prog, fp, info, stages, text, generic, cert_ok, opts.pose_fma)
 
 
 def _emit_scene_rows(o):
@@ -725,7 +850,7 @@ def _emit_scene_rows(o):
     o("      }")
 
 
-def _emit_spec(prog, fp, info, stages, text, generic: bool, cert_ok: bool) -> str:
+def _emit_spec(prog, fp, info, stages, text, generic: bool, cert_ok: bool, pose_fma: bool = False) -> str:
     """The library's float32 check: the fixed macros, the descriptor table, `struct Spec` with the loop around the stages."""
     mbox, maxs, nstage = bool(info.mbox), int(info.maxs), len(stages)
     desc = [st.desc for st in stages]
@@ -734,7 +859,7 @@ def _emit_spec(prog, fp, info, stages, text, generic: bool, cert_ok: bool) -> st
     o("// GENERATED by mjpl_amd/specialise.py -- straight-line per-configuration check of ONE compiled program.")
     o(f"// program hash {info.hash:016x}, {len(prog.bodies)} moving bodies, {nstage} moving geoms, "
       f"{sum(1 for d in desc for x in d if x)} literal pairs{' (static partners: scene table)' if generic else ''}, slot file width {maxs}")
-    o(_MACROS)
+    o((_QUAT2MAT if pose_fma else _QUAT2MAT_PLAIN) + _MACROS)
     o("")
     o(f"__constant__ int kSpecDesc[{nstage} * 64] = {{")
     for d in desc:
@@ -1140,7 +1265,7 @@ _TU = """// GENERATED translation unit: the float32 filter kernels of mjpl_filte
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
-%(waves_define)s#include "mjpl_filter.h"
+%(waves_define)s%(pose_include)s#include "mjpl_filter.h"
 #include "mjpl_project.h"
 
 namespace {
@@ -1417,6 +1542,9 @@ int mjpl_spec_launch_fused_f64(hipStream_t st, int nwaves, size_t lds, FusedArgs
 }"""
 
 
+_POSE_INCLUDE = '#include "mjpl_pose_f32.h"\n'  # (a unit whose generated check calls the fused helpers)
+
+
 def translation_unit(spec: str, exact: str, key: int, info, generic_word: int = 0, pose: str | None = None, exact_full: str | None = None,
                      opts: Options | None = None) -> str:
     """The source of a library: the kernels of mjpl_filter.h / mjpl_fused.h instantiated around `spec` / `exact`,
@@ -1433,7 +1561,9 @@ def translation_unit(spec: str, exact: str, key: int, info, generic_word: int = 
                       # two waves per SIMD (256 VGPRs), eight waves per workgroup of the fused kernel -- at three the kernels
                       # spill 60 .. 90 registers and the fused kernel's LDS no longer fits: 0.56 against 0.42 ms on Franka-P
                       # with the ten pad boxes (profiles/r04_pads.json)
-                      fwaves=(4 * opts.mbox_waves) if mbox else 12, waves_define=f"#define MJPL_SPEC_WAVES {opts.mbox_waves}\n" if mbox else "",
+                      fwaves=(4 * opts.mbox_waves) if mbox else 12,
+                      waves_define=f"#define MJPL_SPEC_WAVES {opts.mbox_waves}\n" if mbox else "",
+                      pose_include=_POSE_INCLUDE if (opts.pose_fma or opts.sincos) else "",
                       generic=generic_word)
 
 
@@ -1469,7 +1599,7 @@ def library_source(model, allowed_collision_bodies=(), qidx=None, qpos_base=None
 
 def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_tol: float = 0.0, force: bool = False,
           keep_source: bool = True, extra_flags=(), output: str | None = None, generic: bool = False, prune_contacts: int = 1,
-          overlay: bool = True, uniform_regions: bool = True) -> str | None:
+          overlay: bool = True, uniform_regions: bool = True, opts: Options | None = None) -> str | None:
     """Generate and compile the specialised library of (model, planning set, tolerance).  Returns the
     path of the library, or None if the model cannot be specialised (immediate interpreter).
     generic: the ROBOT's scene-generic library instead (named by the robot hash): built from any scene that
@@ -1479,14 +1609,18 @@ def build(model, allowed_collision_bodies=(), qidx=None, qpos_base=None, filter_
     overlay: False leaves mjpl_overlay.h (build.overlay_flags) off the compiler's line: the same text, the same hash, the
     same values from the plain templates of mjpl_device.h -- the comparison build of tests/test_gpu_overlay.py.
     uniform_regions: False leaves build.codegen_flags' option off the line in the same way: the compiler's default control
-    flow, the same values -- the comparison build of tests/test_gpu_uniform_regions.py."""
-    made = library_source(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, generic, prune_contacts)
+    flow, the same values -- the comparison build of tests/test_gpu_uniform_regions.py.
+    opts: the generation switches (None: Options.for_build() -- the environment's, the fused pose arithmetic on).
+    Options.for_build()._replace(pose_fma=False, sincos=False) writes the pose arithmetic as plain expressions and calls
+    sincosf: the same program hash, so give such a library an `output` outside SPEC_DIR's top level, where no engine looks
+    on its own -- the comparison build of tests/test_gpu_pose_fma.py."""
+    made = library_source(model, allowed_collision_bodies, qidx, qpos_base, filter_tol, generic, prune_contacts, opts or Options.for_build())
     if made is None:
         return None
     key, src = made
     os.makedirs(SPEC_DIR, exist_ok=True)
     target = output or spec_path(key, generic)  # (output, extra_flags: timing-only variants, tools/time_variants.sh)
-    deps = [os.path.join(_build.CSRC, f) for f in _build.STAMPED_HEADERS] + [_build.OVERLAY_HEADER] + list(GENERATOR_SOURCES)
+    deps = [os.path.join(_build.CSRC, f) for f in _build.STAMPED_HEADERS] + [_build.OVERLAY_HEADER, _build.POSE_HEADER] + list(GENERATOR_SOURCES)
     if not force and os.path.exists(target) and all(os.path.getmtime(d) <= os.path.getmtime(target) for d in deps):
         return target
     return _compile(src, os.path.join(SPEC_DIR, f"spec{'g' if generic else ''}_{key:016x}.hip"), target, keep_source, extra_flags, overlay, uniform_regions)

@@ -1,5 +1,8 @@
 """tests/golden/generated_source_digests.json: sha256 of every text mjpl_amd/specialise.py generates for the models of
-tests/spec_models.py, and of the translation units build() composes for the libraries __graft_entry__.build() compiles.
+tests/spec_models.py, and of the translation units library_source() composes, under the generator's own default switches
+-- since the fused pose helpers (mjpl_pose_f32.h) that is the text WITHOUT them, which __graft_entry__.build() compiles
+under spec/unfused/ only.  tests/golden/generated_source_digests_build.json (compute_build, below) holds the same for
+Options.for_build(): the texts and translation units of the libraries build() compiles and engines load.
 The generator is host Python over the program tables and deterministic, so a change that is meant to leave the generated
 code alone is proved by these digests (tests/test_generated_source.py).  The sha256 of ip / fp / dp and the program
 hash are recorded beside them: where THEY differ the compiler's tables changed and the file is to be recorded again;
@@ -23,6 +26,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from mjpl_amd import specialise as sp  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "generated_source_digests.json")
+# ... and of what specialise.build() hands the compiler when its caller passes no switches (Options.for_build(): the fused
+# pose arithmetic of mjpl_pose_f32.h) -- the texts of the libraries __graft_entry__.build() compiles; GOLDEN above holds
+# the generator's own default, the text without the helpers (tests/test_generated_source_unfused.py compares both)
+BUILD_GOLDEN = os.path.join(ROOT, "tests", "golden", "generated_source_digests_build.json")
 
 
 def sha(x):
@@ -120,12 +127,45 @@ def compute(env):
     return {"models": {e[0]: model_digests(e, env) for e in entries}, "translation units": unit_digests(entries, env)}
 
 
+def compute_build(env):
+    """compute()'s counterpart for Options.for_build(): per model the generated check as build() generates it ("spec",
+    "spec, generic") and with the sincos switch on as well ("spec, sincos"); the translation units of unit_digests()."""
+    from spec_models import generic_robots, spec_models
+    for name in [n for n in os.environ if n.startswith(("MJPL_SPEC_", "MJPL_GEN_"))]:
+        env.delenv(name)
+    entries = spec_models()
+    models = {}
+    for name, model, allowed, qidx, base in entries:
+        ip, fp, dp, info = sp.dump_program(model, allowed, qidx, base)
+        never = sp.dump_never_touch(model, allowed, qidx, base)[0]
+        opts = sp.Options.for_build()
+        out = {"hash": f"{int(info.hash):016x}", "spec": sha(sp.generate(ip, fp, dp, info, never_touch=never, opts=opts)),
+               "spec, sincos": sha(sp.generate(ip, fp, dp, info, never_touch=never, opts=opts._replace(sincos=True)))}
+        if info.scene_ok:
+            out["spec, generic"] = sha(sp.generate(ip, fp, dp, info, generic=True, opts=opts))
+        models[name] = out
+
+    def unit(args, **kw):
+        return sha(sp.library_source(*args, opts=sp.Options.for_build(), **kw)[1])
+
+    bench = entries[0][1:]
+    units = {"bench": unit(bench), "bench, prune_contacts=0": unit(bench, prune_contacts=0)}
+    for var in ("MJPL_SPEC_CERT", "MJPL_SPEC_F64"):
+        env.setenv(var, "1")
+        units[f"bench, {var}=1"] = unit(bench)
+        env.delenv(var)
+    for k, robot in enumerate(generic_robots()):
+        units[f"generic robot {k}"] = unit(robot, generic=True)
+    units["pad boxes"] = unit(next(e for e in entries if "pad boxes" in e[0])[1:])
+    return {"models": models, "translation units": units}
+
+
 def main():
-    out = compute(ProcessEnv)
-    with open(GOLDEN, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
-    print(json.dumps({k: len(v) for k, v in out.items()}))
+    for path, out in ((GOLDEN, compute(ProcessEnv)), (BUILD_GOLDEN, compute_build(ProcessEnv))):
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: len(v) for k, v in out.items()}))
 
 
 if __name__ == "__main__":
